@@ -11,6 +11,14 @@ shapes, fp16 weights, 4k context, a 32-token prompt (BOS + LCG ids) hydrated fir
 offline): generated on the device from include/xalm_synth.h; the CPU baseline builds the
 bit-identical host copy and runs the C oracle (the reference's CPU algorithm restated).
 
+A plain run (`--gpus 1 --steps N --warmup W`) does what the headline figure needs: set-up,
+warm-up, the N timed steps, the result line (tok/s, ms_per_step, and hbm_step = the timed
+steps' algorithmic bytes against the HBM peak).  `--dump-outputs DIR` adds the last timed
+step's outputs as DIR/<name>.npy.  `--full` adds the measurements that take runs of their own:
+each graph kernel timed alone and the W1/W3 roofline, the prompt-pass timings, and the CPU
+baseline with its parity block (the `roofline`, `kernels`, `prefill` and `cpu_baseline` fields,
+null in a plain run).
+
 Multi-GPU: the path does not shard -> N independent replicas, one process per
 GPU, no collective on the data path; value = total tokens of all ranks / max rank time.
 """
@@ -337,12 +345,34 @@ def cpu_baseline(w, c, prompt, gpu_logits0, gpu_tokens, n_decode, one_thread_tok
                         "greedy_tokens_agree": f"{agree}/{n_decode}", "disagreements": disagree[:16]})
 
 
+def dump_outputs(out_dir, model, st, toks):
+    """--dump-outputs: what the timed decode_greedy call left for its caller, as <name>.npy.
+    tokens: the greedy token of every timed step (float64, exact for token ids); logits: the
+    logits of the last timed forward, still on the device when the call returns (float32
+    [vocab], the values the next token would be sampled from).  Weights, K/V history and
+    prompt are seeded, so the same arguments give the same inputs on every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    model.get_logits(st)
+    np.save(os.path.join(out_dir, "tokens.npy"), np.asarray(toks, dtype=np.float64))
+    np.save(os.path.join(out_dir, "logits.npy"), st.logits().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--workload", default="mistral-7b-f16", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="beside the decode figure: each graph kernel timed on its own and the W1/W3 roofline, "
+                         "the prompt-pass (prefill / perplexity) timings, and the CPU baseline with its parity "
+                         "block.  Without it the run sets up, warms up, times --steps decode tokens and prints "
+                         "the result line; --cpu-tokens, --no-cpu-baseline, --kernel-iters, --prefill-mode and "
+                         "--prefill-tokens act under --full only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left for the caller as "
+                         "DIR/<name>.npy: tokens (the greedy tokens of the timed steps) and logits (the logits "
+                         "the last timed forward produced)")
     ap.add_argument("--cpu-tokens", type=int, default=128,
                     help="CPU baseline decode tokens (-m completion -n N; 32k workload: min(N, 32))")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -360,16 +390,21 @@ def main():
                          "hydrated at pos0 (e.g. 3808: the timed tokens end at kv_len 4096, the worst token of "
                          "the 4k context, SURVEY 8d)")
     args = ap.parse_args()
+    if not args.full:  # the plain run: the decode figure only
+        args.no_cpu_baseline, args.prefill_tokens = True, 0
 
-    world = int(os.environ.get("WORLD_SIZE", "1"))
+    world =int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     dist = None
     torch_mod = None
-    try:
-        import torch as torch_mod  # noqa: F811  (plumbing: barrier + device sync only)
-    except ImportError:
-        torch_mod = None
+    # a plain single-process run needs no torch: decode_greedy returns after its stream has
+    # drained (the tokens are on the host), so the timed region is bracketed already
+    if world > 1 or args.full:
+        try:
+            import torch as torch_mod  # noqa: F811  (plumbing: barrier + device sync only)
+        except ImportError:
+            torch_mod = None
     if world > 1:
         import torch.distributed as dist
         dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -412,6 +447,8 @@ def main():
 
     toks, elapsed = timed_region(dist, torch_mod, lambda: model.decode_greedy(pos, args.steps))
     assert len(toks) == args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, st, toks)
     # the CPU baseline's teacher-forcing tokens beyond the timed ones (-n 128 whatever --steps is):
     # the same greedy sequence continued on the device, untimed
     cpu_n = 0
@@ -426,17 +463,19 @@ def main():
     step_bytes = sum(model.active_bytes(p) for p in range(pos, pos + args.steps))
     step_gbps = step_bytes / elapsed / 1e9
 
-    # graph engine's kernels, each timed on its own (HIP events on the context stream)
-    kv_len_now = min(c.max_seq_len, pos + args.steps)
-    k_us = model.time_kernel(0, args.kernel_iters)
-    k_bytes = model.kernel_bytes(0, kv_len_now)
-    k_gbps = k_bytes / (k_us * 1e-6) / 1e9
-    extra_kernels = {"gemv_w13": {"avg_us": round(k_us, 2), "GBps": round(k_gbps, 1)}}
-    timed = [(1, "gemv_qkv"), (2, "gemv_wo"), (3, "gemv_w2"), (4, "gemv_lm_head"), (5, "attention")]
-    for which, name in timed:
-        us = model.time_kernel(which, max(20, args.kernel_iters // 4))
-        b = model.kernel_bytes(which, kv_len_now)
-        extra_kernels[name] = {"avg_us": round(us, 2), "GBps": round(b / (us * 1e-6) / 1e9, 1)}
+    # --full: graph engine's kernels, each timed on its own (HIP events on the context stream)
+    extra_kernels = roofline = None
+    if args.full:
+        kv_len_now = min(c.max_seq_len, pos + args.steps)
+        k_us = model.time_kernel(0, args.kernel_iters)
+        k_bytes = model.kernel_bytes(0, kv_len_now)
+        k_gbps = k_bytes / (k_us * 1e-6) / 1e9
+        extra_kernels = {"gemv_w13": {"avg_us": round(k_us, 2), "GBps": round(k_gbps, 1)}}
+        timed = [(1, "gemv_qkv"), (2, "gemv_wo"), (3, "gemv_w2"), (4, "gemv_lm_head"), (5, "attention")]
+        for which, name in timed:
+            us = model.time_kernel(which, max(20, args.kernel_iters // 4))
+            b = model.kernel_bytes(which, kv_len_now)
+            extra_kernels[name] = {"avg_us": round(us, 2), "GBps": round(b / (us * 1e-6) / 1e9, 1)}
 
     # prompt processing, reported beside the decode metric: xh_prefill of a
     # synthetic prompt at positions 0.. (overwrites the ring rows the decode used; timed last)
@@ -522,13 +561,14 @@ def main():
 
     # the W1/W3 launch's instantiation (the pipelined PF shape, PIPE = 2; the name's prefix, so
     # the trailing GemvShape parameters added since round 6 still match)
-    traffic, src = pmc_traffic("void xalm::gemv_kernel<%d, 1, 3, xalm::GemvShape<512, 2, %d, true, 4, true, 2, 2"
-                               % (w["wdt"], 2 if w["wdt"] == L.Q4_0 else 4))
-    roofline = {"bound": "hbm", "achieved": round(k_gbps, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": round(k_gbps / HBM_PEAK_GBPS, 4), "traffic": traffic,
-                "traffic_source": src,
-                "kernel": "gemv_kernel<PRO_RMSNORM,EPI_GLU> (fused W1/W3 + rmsnorm + silu*up), layers rotating",
-                "bytes_per_launch": k_bytes, "avg_launch_us": round(k_us, 2)}
+    if args.full:
+        traffic, src = pmc_traffic("void xalm::gemv_kernel<%d, 1, 3, xalm::GemvShape<512, 2, %d, true, 4, true, 2, 2"
+                                   % (w["wdt"], 2 if w["wdt"] == L.Q4_0 else 4))
+        roofline = {"bound": "hbm", "achieved": round(k_gbps, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": round(k_gbps / HBM_PEAK_GBPS, 4), "traffic": traffic,
+                    "traffic_source": src,
+                    "kernel": "gemv_kernel<PRO_RMSNORM,EPI_GLU> (fused W1/W3 + rmsnorm + silu*up), layers rotating",
+                    "bytes_per_launch": k_bytes, "avg_launch_us": round(k_us, 2)}
     value = job_value(world, args.steps, elapsed)
     if rank == 0:
         out = {
@@ -541,6 +581,7 @@ def main():
             "ms_per_step": round(1000 * elapsed / args.steps, 4),
             "higher_is_better": True,
             "scaling": "weak",
+            "full": args.full,
             "vs_baseline": None,
             "dtype": w["dtype"],
             "data": "synthetic (deterministic xalm_synth weights of the named shapes; no checkpoint offline)",

@@ -53,6 +53,30 @@ def test_timed_region_max_over_two_gloo_ranks():
     assert res[0][3] == pytest.approx(2 * 64 / e0)  # weak scaling: both replicas' tokens
 
 
+def test_dump_outputs_writes_tokens_and_last_logits(tmp_path):
+    """--dump-outputs: the timed steps' tokens and the device's logits after the last one, as
+    float64 / float32 .npy files (a stub stands in for the device)."""
+    import numpy as np
+
+    class State:
+        def __init__(self):
+            self._l = np.zeros(5, dtype=np.float32)
+
+        def logits(self):
+            return self._l
+
+    class StubModel:
+        def get_logits(self, s):
+            s.logits()[:] = [0.5, -1.0, 2.0, 0.0, 3.5]
+
+    out = tmp_path / "dump" / "nested"
+    bench.dump_outputs(str(out), StubModel(), State(), [4, 2, 4])
+    assert sorted(p.name for p in out.iterdir()) == ["logits.npy", "tokens.npy"]
+    toks, logits = np.load(out / "tokens.npy"), np.load(out / "logits.npy")
+    assert toks.dtype == np.float64 and toks.tolist() == [4.0, 2.0, 4.0]
+    assert logits.dtype == np.float32 and logits.tolist() == [0.5, -1.0, 2.0, 0.0, 3.5]
+
+
 def test_timed_region_single_process():
     out, elapsed = bench.timed_region(None, None, lambda: 7)
     assert out == 7 and 0 <= elapsed < 1.0

@@ -12,7 +12,7 @@ STEPS=${STEPS:-256}
 for r in $(seq 1 "$ROUNDS"); do
   for w in $WL; do
     for v in $LIBS; do
-      XALM_HIP_LIB=xalm_amd/lib/var_$v.so timeout -k 10 200 python3 bench.py --workload "$w" --steps "$STEPS" \
+      XALM_HIP_LIB=xalm_amd/lib/var_$v.so timeout -k 10 200 python3 bench.py --full --workload "$w" --steps "$STEPS" \
         --no-cpu-baseline --prefill-tokens 0 --kernel-iters 20 ${ARGS:-} > gpurun_out/abn.json 2> gpurun_out/abn.err || {
         echo "FAILED $w $v rc=$?"; tail -5 gpurun_out/abn.err; exit 1; }
       python3 - "$w" "$v" <<'EOF'

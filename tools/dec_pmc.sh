@@ -13,7 +13,7 @@ for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE
     i=$((i+1))
     echo "== pass $i: $set"
     timeout -s KILL 120 rocprofv3 --pmc $set --kernel-trace -d "$OUT/p$i" -o run --output-format csv -- \
-        python3 bench.py --workload $WL --steps 8 --warmup 2 --no-cpu-baseline --kernel-iters 5 --prefill-tokens 0 > "$OUT/p$i.log" 2>&1
+        python3 bench.py --full --workload $WL --steps 8 --warmup 2 --no-cpu-baseline --kernel-iters 5 --prefill-tokens 0 > "$OUT/p$i.log" 2>&1
     rc=$?
     echo "rc=$rc"
     if [ $rc -ne 0 ]; then tail -3 "$OUT/p$i.log"; exit $rc; fi

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
     echo "== pass $c $(date +%T)"
     timeout -k 10 600 rocprofv3 --pmc $c --kernel-trace -d "$OUT/$c" -o run --output-format csv -- \
-        python bench.py --steps 16 --warmup 2 --no-cpu-baseline --kernel-iters 10 > "$OUT/$c.log" 2>&1
+        python bench.py --full --steps 16 --warmup 2 --no-cpu-baseline --kernel-iters 10 > "$OUT/$c.log" 2>&1
     rc=$?
     echo "== pass $c rc=$rc"
     [ $rc -ne 0 ] && { tail -5 "$OUT/$c.log"; exit $rc; }

@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp XALM_BENCH_DEVICE=0
 N=${N:-2}
 timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-    --master-port 29517 bench.py --gpus $N --steps 32 --warmup 4 --kernel-iters 5 --prefill-tokens 256 \
+    --master-port 29517 bench.py --full --gpus $N --steps 32 --warmup 4 --kernel-iters 5 --prefill-tokens 256 \
     > gpurun_out/rehearse_$N.log 2>&1
 rc=$?
 tail -2 gpurun_out/rehearse_$N.log | cut -c1-600
