@@ -11,8 +11,7 @@ HOSTFLAGS := -O2 -std=c++17 -fPIC -Wall -Wextra
 
 LIB := xalm_amd/lib
 BIN := xalm_amd/bin
-HIP_SRC := xalm_amd/csrc/xalm_hip.hip
-HIP_HDR := $(wildcard xalm_amd/csrc/*.h) include/xalm_hip.h
+HIP_UNITS := xalm_hip launch decode prefill prefill_blas upload ops
 HOST_SRC := $(wildcard xalm_amd/host/*.cpp)
 HOST_HDR := $(wildcard xalm_amd/host/*.h) include/xalm_hip.h include/xalm_host.h
 
@@ -26,19 +25,22 @@ endif
 oracle:
 	$(MAKE) -C oracle
 
-# the fused attention + Wo kernel is instantiated per Wo dtype in its own objects (parallel build)
+# one object per host unit; the fused attention + Wo kernel (dt_launch.hip) once per Wo dtype.
+# Every object depends on the headers it includes (-MMD).
 OBJ := xalm_amd/build
 PK_DTS := 1 2 3 6 7 9
-PK_OBJS := $(patsubst %,$(OBJ)/dt_launch_dt%.o,$(PK_DTS))
-$(OBJ)/xalm_hip.o: $(HIP_SRC) $(HIP_HDR)
+HIP_OBJS := $(patsubst %,$(OBJ)/%.o,$(HIP_UNITS)) $(patsubst %,$(OBJ)/dt_launch_dt%.o,$(PK_DTS))
+$(OBJ)/%.o: xalm_amd/csrc/%.hip
 	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $(HIP_SRC)
-$(OBJ)/dt_launch_dt%.o: xalm_amd/csrc/dt_launch.hip $(HIP_HDR)
+	$(HIPCC) $(HIPFLAGS) -MMD -MP -c -o $@ $<
+$(OBJ)/dt_launch_dt%.o: xalm_amd/csrc/dt_launch.hip
 	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -DPK_DT=$* -c -o $@ $<
-$(LIB)/libxalm_hip.so: $(OBJ)/xalm_hip.o $(PK_OBJS)
+	$(HIPCC) $(HIPFLAGS) -MMD -MP -DPK_DT=$* -c -o $@ $<
+$(LIB)/libxalm_hip.so: $(HIP_OBJS)
 	@mkdir -p $(LIB)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $^
+$(HIP_OBJS:.o=.d): ;
+-include $(HIP_OBJS:.o=.d)
 
 HOST_LIB_SRC := $(filter-out xalm_amd/host/main.cpp,$(HOST_SRC))
 $(LIB)/libxalm_host.so: $(HOST_LIB_SRC) $(HOST_HDR) $(LIB)/libxalm_hip.so

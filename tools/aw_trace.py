@@ -53,7 +53,7 @@ def main():
     us = lambda v: (v - t0) / 100.0  # noqa: E731
     nsplit = None
     # attention workgroups: stamp 1 = done (0 if it exited as an inactive split: then = start)
-    nsplit = max(1, min(256 // nkv, 128, (c.max_seq_len + 255) // 256))  # attn_nsplit (xalm_hip.hip)
+    nsplit = max(1, min(256 // nkv, 128, (c.max_seq_len + 255) // 256))  # attn_nsplit (launch.hip)
     # Wo workgroups (AwShape: 16 waves x 2 rows, one round of <= 4096 waves): ceil(dim / 32)
     rows_per_wg = 2 * args.aw_threads // 64
     nb_wo = (c.dim + rows_per_wg - 1) // rows_per_wg

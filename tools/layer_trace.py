@@ -12,7 +12,7 @@ import bench  # noqa: E402
 from xalm_amd import _lib as L  # noqa: E402
 from xalm_amd.model import InferenceState, Model  # noqa: E402
 
-# (name, first word, words, words per workgroup): xalm_hip.hip LT_* regions
+# (name, first word, words, words per workgroup): ctx.h LT_* regions
 REGIONS = [("qkv", 0, 8192, 4), ("attn+wo", 8192, 8192, 8), ("w1/w3", 16384, 4096, 4), ("w2", 20480, 4096, 4),
            ("lm_head", 24576, 4096, 4)]
 

@@ -1,0 +1,224 @@
+// ctx.h — the device context and what the host translation units share (internal, not installed).
+// Functions that cross units live in namespace xalm; each is defined in the unit named above it.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "attention.h"
+#include "gemv.h"
+
+namespace xalm {
+
+inline size_t dtype_size(int dt) {
+    switch (dt) {
+        case XH_F32: return 4;
+        case XH_F16: case XH_BF16: return 2;
+        case XH_F8_E4M3: case XH_F8_E5M2: case XH_Q8: case XH_U8: return 1;
+        default: return 0;
+    }
+}
+inline bool matrix_dtype_ok(int dt) {
+    return dt == XH_F32 || dt == XH_F16 || dt == XH_BF16 || dt == XH_F8_E4M3 || dt == XH_F8_E5M2 || dt == XH_Q8 ||
+           gq_dt(dt);
+}
+// bytes of one [n]-element row: in the device layout (gguf blocks: planar, gq_pitch) and in
+// the .xalm file / host upload (gguf blocks: n/32 blocks of gq_block_bytes)
+inline size_t dev_row_bytes(int dt, size_t n) { return gq_dt(dt) ? gq_pitch(dt, n) : n * dtype_size(dt); }
+inline size_t file_row_bytes(int dt, size_t n) { return gq_dt(dt) ? n / 32 * gq_block_bytes(dt) : n * dtype_size(dt); }
+inline int elems_per_16b(int dt) { return 16 / (int)dtype_size(dt); }
+// the kernel's decode form for a matrix: fp8 with NaN/Inf codes -> the exact bit decoder
+inline int kdt(int dt, bool special) {
+    if (!special) return dt;
+    return dt == XH_F8_E4M3 ? XH_F8_E4M3_EXACT : dt == XH_F8_E5M2 ? XH_F8_E5M2_EXACT : dt;
+}
+
+struct LayerW {
+    void* wqkv = nullptr; int qkv_dt = 0; unsigned qkv_have = 0;  // bit0 q, bit1 k, bit2 v
+    void* w13 = nullptr; int w13_dt = 0; unsigned w13_have = 0;   // bit0 w1, bit1 w3
+    void* wo = nullptr; int wo_dt = 0;
+    void* w2 = nullptr; int w2_dt = 0;
+    // fp8 matrices holding NaN/Inf codes (decoded with the exact bit form, no fused kernels)
+    bool qkv_x = false, w13_x = false, wo_x = false, w2_x = false;
+    void* attn_norm = nullptr; int an_dt = 0;
+    void* ffn_norm = nullptr; int fn_dt = 0;
+};
+
+struct BlasState;  // hipBLASLt handle, workspace, plans (prefill_blas.hip)
+
+constexpr int ARGMAX_CANDS = 1024;  // the lm_head workgroups' argmax keys (argmax_embed_kernel's block size)
+
+}  // namespace xalm
+
+struct xh_ctx {
+    xh_config c{};
+    int dev = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+    std::vector<xalm::LayerW> L;
+    void* embed = nullptr; int embed_dt = 0;
+    void* final_norm = nullptr; int final_norm_dt = 0;
+    void* wcls = nullptr; int wcls_dt = 0; bool wcls_x = false;
+    int* scan_flag = nullptr;  // device word for the fp8 special-code scan
+    int q_dim = 0, kv_dim = 0, qpk = 0;
+    uint16_t* kv = nullptr;  // [n_layers][2][max_seq_len][kv_dim]
+    float *x = nullptr, *q = nullptr, *attn_out = nullptr, *hb = nullptr, *logits = nullptr;
+    float *part_o = nullptr, *part_ml = nullptr;
+    int* attn_cnt = nullptr;        // [n_kv_heads] split arrival tickets
+    float *rope_freq = nullptr, *sink_cos = nullptr, *sink_sin = nullptr;
+    float* rope_cs = nullptr;  // [head_dim]: this step's rotations (rope_table, gemv.h)
+    xalm::StepParams* sp = nullptr;       // device
+    xalm::StepParams* sp_host = nullptr;  // pinned
+    int* dec_tokens = nullptr;      // device, decode loop output
+    unsigned long long* cand = nullptr;  // device [ARGMAX_CANDS]: lm_head workgroups' argmax keys
+    bool cand_valid = false;        // cand describes the logits on the device
+    int dec_cap = 0;
+    int nsplit = 1, t_max = 16;
+    // fused attention + Wo launch (attn_wo.h): per-layer hand-off words [n_layers][4]
+    bool fuse_attn_wo = true;
+    unsigned* aw_sync = nullptr;
+    // batched prefill (prefill.h), buffers allocated on first use
+    bool prefill_batched = true;
+    // XH_OPT_PREFILL: 1 = the LDS-tiled f16 MFMA GEMM (gemm16.h) for f16 / e4m3 / e5m2 weights (fp8
+    // as an exact f16 image), f32 MFMA otherwise; 2 = split-f16 register-streaming MFMA wherever the
+    // weights convert exactly; 3 = f32 MFMA only; 4 = as 1 with hipBLASLt in place of gemm16.h
+    int prefill_gemm = 1;
+    int pf_pass = 0;                             // tokens per pass of the current prefill
+    int pf_cap = 0;                              // tokens the pass buffers hold (pf_alloc)
+    bool pf_scaled = false;                      // the last pf_gemm's partials carry 1 / s_t (pf_xs)
+    int mm_ok = 0;                               // 0 unchecked, 1 every pass GEMM fits gemm16.h, -1 not
+    xalm::BlasState* blas = nullptr;             // XH_OPT_PREFILL 4, created on the first prompt that uses it
+    uint16_t* pf_wdq = nullptr;                  // f16 image of one fp8 matrix for the f16 GEMMs (pf_prepare)
+    size_t pf_wdq_elems = 0;
+    bool pf_split_ready = false;                 // pf_norm left the next GEMM's split input
+    bool pf_resid_norm = true;                   // residual + rmsnorm split in one launch (XH_OPT_PREFILL_GLU_SPLIT 0: off)
+    bool pf_glu_split = true;                    // XH_OPT_PREFILL_GLU_SPLIT: fused GLU -> split input
+    int pf_fa_split = 1;                         // XH_OPT_PREFILL_ATTN_SPLIT: history splits for short passes
+    int pf_attn_mode = 1;                        // XH_OPT_PREFILL_ATTN: 1 shared-tile MFMA (v1 for head_dim != 128),
+                                                 // 2 per-wave MFMA tiles, 0 per-token split kernel
+    // T = pf_cap tokens (the pass length in use; pf_alloc)
+    uint16_t* pf_xh = nullptr;                   // [2T][max K] f16 halves of a GEMM input (pf_alloc)
+    uint16_t* pf_xl = nullptr;                   // [PF_TOK][max K] the split kernel's lo fragments
+    float* pf_xs = nullptr;                      // [T] 1 / row scale
+    int* pf_tok = nullptr;                       // [T]
+    float *pf_x = nullptr, *pf_xn = nullptr;     // [T][dim]
+    float *pf_q = nullptr, *pf_att = nullptr;    // [T][q_dim]
+    float* pf_h = nullptr;                       // [T][hidden]
+    float* pf_part = nullptr;                    // split-K partials [ks][n][rows] (pf_part_floats)
+    xalm::StepParams* pf_sp = nullptr;           // [T] per-token attention scalars
+    // the per-token split attention (XH_OPT_PREFILL_ATTN 0 only, allocated on its first use):
+    float *pf_po = nullptr, *pf_pml = nullptr;   // [T][nsplit][q_dim], [T][nsplit][n_heads][2]
+    int* pf_cnt = nullptr;                       // [T][n_kv_heads] split tickets
+    int pf_po_cap = 0;                           // tokens those hold
+    // xh_perplexity: per-token logits of a pass, targets, probabilities (allocated on first use)
+    float* pf_logits = nullptr;                  // [T][vocab]
+    int* pf_tgt = nullptr;                       // [T]
+    int* ppl_tgt = nullptr;                      // [ppl_cap] targets (per-token path)
+    float* ppl_prob = nullptr;                   // [ppl_cap]
+    int ppl_cap = 0;
+    int t_max_aw = 16;
+    bool use_graphs = true;
+    hipGraphExec_t g_logits = nullptr, g_hydrate = nullptr, g_decode = nullptr;
+    int max_gemv_waves = 4096;  // 16 waves per CU
+    // the qkv launch: its whole matrix is one round at 16 waves per CU (every wave one group,
+    // requested at once); at 8 waves per CU each wave streams two groups back to back
+    // (tools/gemv_bench GB_T1K: 10.95 -> 10.12 us f16, 7.93 -> 7.34 us fp8)
+    int qkv_waves = 2048;
+    int n_cu = 0;
+    // debug timelines (xh_debug_trace): device-clock stamps per workgroup
+    unsigned long long* aw_trace = nullptr;
+    size_t aw_trace_len = 0;
+    bool aw_trace_on = false;   // attn_wo launches ([workgroup][8])
+    bool w13_trace_on = false;  // plain W1/W3 launches ([workgroup][4]: tools/balance_trace.py)
+    // the last layer's launches and the lm_head each write their own region (LT_*): the step's
+    // timeline, kernel boundaries included (tools/layer_trace.py)
+    bool layer_trace_on = false;
+    uint16_t* kcache(int l) { return kv + (size_t)l * 2 * c.max_seq_len * kv_dim; }
+    uint16_t* vcache(int l) { return kcache(l) + (size_t)c.max_seq_len * kv_dim; }
+};
+
+namespace xalm {
+
+// xalm_hip.hip: the message goes to ctx, or to the creating thread when there is none
+int set_err(xh_ctx* ctx, int code, const char* fmt, ...);
+
+#define HIP_TRY(ctx, expr)                                                                     \
+    do {                                                                                       \
+        hipError_t _e = (expr);                                                                \
+        if (_e != hipSuccess)                                                                  \
+            return xalm::set_err((ctx), XH_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), \
+                                 __FILE__, __LINE__);                                          \
+    } while (0)
+
+// Host <-> device copies and fills go on ctx->stream and wait for it.  ctx->stream is
+// non-blocking, so null-stream work (hipMemcpy, hipMemset, hipMemcpy2D) is not ordered with
+// its kernels: a fill can land after a kernel wrote the buffer, and a pageable upload can
+// return before its DMA does.
+inline hipError_t copy_sync(xh_ctx* ctx, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, ctx->stream);
+    return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream);
+}
+inline hipError_t copy2d_sync(xh_ctx* ctx, void* dst, size_t dpitch, const void* src, size_t spitch, size_t width,
+                              size_t height) {
+    const hipError_t e = hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, hipMemcpyHostToDevice, ctx->stream);
+    return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream);
+}
+inline hipError_t fill_sync(xh_ctx* ctx, void* dst, int value, size_t bytes) {
+    const hipError_t e = hipMemsetAsync(dst, value, bytes, ctx->stream);
+    return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream);
+}
+template <typename T>
+int dmalloc(xh_ctx* ctx, T** p, size_t n) {
+    HIP_TRY(ctx, hipMalloc((void**)p, n ? n * sizeof(T) : 16));
+    HIP_TRY(ctx, fill_sync(ctx, *p, 0, n ? n * sizeof(T) : 16));
+    return 0;
+}
+
+// debug layer timeline: regions of aw_trace (words) per launch of the traced (last) layer
+constexpr size_t LT_QKV = 0, LT_AW = 8192, LT_W13 = 16384, LT_W2 = 20480, LT_CLS = 24576, LT_WORDS = 28672;
+
+// launch.hip: the only unit that instantiates gemv_kernel and attn_split_kernel.  A role is one
+// (prologue, epilogue) pair of gemv.h; false = no instantiation for the dtype / head shape.
+enum GemvRole { GEMV_QKV, GEMV_GLU, GEMV_RESID, GEMV_LOGITS, GEMV_STORE };
+bool launch_gemv(GemvRole role, int dt, const GemvArgs& a, hipStream_t s, int max_waves);
+bool launch_attn(const AttnArgs& a, int hd, int qpk, int n_kv_heads, int t_max, hipStream_t s);
+int attn_nsplit(int n_kv_heads, int max_seq_len);
+// The dynamic-LDS limit of a kernel above 64 KiB (up to the CU's 160 KiB), set once per (kernel,
+// device); false when it could not be set.
+bool ensure_lds(const void* fn, int bytes = 160 * 1024);
+
+// decode.hip
+GemvArgs qkv_args(xh_ctx* ctx, int l);
+GemvArgs wo_args(xh_ctx* ctx, int l);
+GemvArgs w13_args(xh_ctx* ctx, int l);
+GemvArgs w2_args(xh_ctx* ctx, int l);
+GemvArgs cls_args(xh_ctx* ctx);
+AttnArgs attn_args(xh_ctx* ctx, int l);
+int qkv_launch_waves(const xh_ctx* ctx, int l);
+int check_ready(xh_ctx* ctx);
+int check_aw(xh_ctx* ctx);
+void drop_graphs(xh_ctx* ctx);
+int host_step_params(xh_ctx* ctx, int token, int pos);
+int run_step(xh_ctx* ctx, bool with_logits);
+
+// prefill.hip: the pass buffers, and gemm16.h for xh_op_prompt_gemm (device pointers).  mm_op_ks:
+// *ks = 0 picks the K slicing; 0, 1 when K is no multiple of MM_KMULT, 2 when *ks slices do not divide it
+void pf_free(xh_ctx* ctx);
+int mm_op_ks(int rows, int K, int n, int* ks);
+void mm_op_launch(const uint16_t* w, const uint16_t* xh, const uint16_t* xl, float* out, int rows, int K, int n, int ks,
+                  int n_cu);
+
+// prefill_blas.hip (XH_OPT_PREFILL 4).  blas_ok: 0 unprobed, 1 every GEMM shape of the model has
+// an f16 plan, -1 not.  blas_has_plan: *have = hipBLASLt has an algorithm for the shape.
+int blas_ok(const xh_ctx* ctx);
+void blas_set_ok(xh_ctx* ctx, int ok);
+int blas_has_plan(xh_ctx* ctx, int rows, int K, int n, bool* have);
+int blas_gemm(xh_ctx* ctx, const void* w, int K, int rows, const uint16_t* x, int n, float* y);
+void blas_free(xh_ctx* ctx);
+
+// upload.hip
+void gq_repack(int dt, const uint8_t* src, size_t rows, size_t cols, uint8_t* dst);
+
+}  // namespace xalm

@@ -1,0 +1,419 @@
+// decode.hip — the per-token step: argument builders, the fused attention + Wo launch, graph
+// capture and replay, and the ABI entries that run it (xh_forward, xh_decode_greedy, xh_get_logits).
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <vector>
+
+#include "ctx.h"
+#include "dt_launch.h"
+
+using namespace xalm;
+
+// The step's own kernels.  Non-template kernels are defined in one translation unit: this one.
+namespace xalm {
+
+// Model::_copy_embedding (src/infer.cpp:553-602): x = dec(embed[token, :])
+__global__ void embed_kernel(const void* emb, int dtype, int dim, float* x, const StepParams* sp,
+                             const float* rope_freq, float* rope_cs, int half) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < dim) x[i] = dec_row(dtype, emb, (size_t)sp->token, dim, i);
+    if (blockIdx.x == 0) rope_table(rope_cs, rope_freq, half, sp->pos, threadIdx.x);
+}
+
+// Greedy decode step head: argmax over the lm_head workgroups' candidates (Sampler::
+// sample_argmax, src/sampler.cpp:19-30: the first maximum among logits > FLT_MIN, else token
+// 0), the decode-loop bookkeeping of argmax_advance (tokens[step], step, token, positions,
+// src/infer.cpp:611-613) and x = embed[token] (Model::_copy_embedding,
+// src/infer.cpp:553-602), in one 1024-thread workgroup.
+__global__ __launch_bounds__(1024) void argmax_embed_kernel(const unsigned long long* cand, StepParams* sp,
+                                                            int* tokens, int cap, const void* emb, int dtype,
+                                                            int dim, float* x, const float* rope_freq,
+                                                            float* rope_cs, int half) {
+    __shared__ unsigned long long kb[16];
+    __shared__ int tok_s, pos_s;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    unsigned long long best = cand[tid];  // ARGMAX_CANDS == blockDim.x
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(best, o, 64);
+        best = other > best ? other : best;
+    }
+    if (lane == 0) kb[wid] = best;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long bb = 0;
+#pragma unroll
+        for (int w = 0; w < 16; w++) bb = kb[w] > bb ? kb[w] : bb;
+        const int tok = argmax_key_index(bb);
+        if (sp->step < cap) tokens[sp->step] = tok;
+        sp->step += 1;
+        sp->token = tok;
+        step_positions(sp, sp->pos_next);
+        sp->pos_next += 1;
+        tok_s = tok;
+        pos_s = sp->pos;
+    }
+    __syncthreads();
+    rope_table(rope_cs, rope_freq, half, pos_s, tid);
+    for (int i = tid; i < dim; i += 1024) x[i] = dec_row(dtype, emb, (size_t)tok_s, dim, i);
+}
+
+// Candidates from logits already on the device (the first greedy step after logits that no
+// EPI_LOGITS launch produced): cand[0] = best key, the rest 0.
+__global__ __launch_bounds__(1024) void logits_cand_kernel(const float* logits, int vocab, unsigned long long* cand) {
+    __shared__ unsigned long long kb[16];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    unsigned long long best = 0;
+    for (int i = tid; i < vocab; i += 1024) {
+        const float v = logits[i];
+        if (v > FLT_MIN) {
+            const unsigned long long k = argmax_key(v, i);
+            best = k > best ? k : best;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(best, o, 64);
+        best = other > best ? other : best;
+    }
+    if (lane == 0) kb[wid] = best;
+    __syncthreads();
+    unsigned long long bb = 0;
+#pragma unroll
+    for (int w = 0; w < 16; w++) bb = kb[w] > bb ? kb[w] : bb;
+    cand[tid] = tid == 0 ? bb : 0ull;
+}
+
+}  // namespace xalm
+
+namespace {
+
+// ---------------------------------------------------------------------------------------
+// the per-token step, enqueued on a stream (eager or under graph capture)
+// ---------------------------------------------------------------------------------------
+bool layer_traced(const xh_ctx* ctx, int l) { return ctx->layer_trace_on && l == ctx->c.n_layers - 1; }
+
+__global__ void argmax_advance_kernel(const float* logits, int vocab, StepParams* sp, int* tokens, int cap) {
+    // Sampler::sample_argmax (src/sampler.cpp:19-30): max starts at FLT_MIN, strict '>',
+    // so the first index of the maximum wins and all-tiny logits give token 0.
+    __shared__ float bv[1024];
+    __shared__ int bi[1024];
+    const int tid = threadIdx.x;
+    float best = FLT_MIN;
+    int idx = 0;
+    for (int i = tid; i < vocab; i += blockDim.x)
+        if (logits[i] > best) { best = logits[i]; idx = i; }
+    bv[tid] = best;
+    bi[tid] = idx;
+    __syncthreads();
+    for (int o = blockDim.x / 2; o > 0; o >>= 1) {
+        if (tid < o) {
+            const float v2 = bv[tid + o];
+            const int i2 = bi[tid + o];
+            if (v2 > bv[tid] || (v2 == bv[tid] && i2 < bi[tid])) { bv[tid] = v2; bi[tid] = i2; }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const int tok = bi[0];
+        if (sp->step < cap) tokens[sp->step] = tok;
+        sp->step += 1;
+        sp->token = tok;
+        step_positions(sp, sp->pos_next);
+        sp->pos_next += 1;
+    }
+}
+
+bool use_attn_wo(const xh_ctx* ctx, int l) {
+    const int dt = ctx->L[l].wo_dt;
+    if (ctx->L[l].wo_x) return false;  // exact fp8 decode: the separate launches
+    return ctx->fuse_attn_wo && aw_instantiated(ctx->c.head_dim, ctx->qpk) &&
+           (dt == XH_F32 || dt == XH_F16 || dt == XH_BF16 || dt == XH_F8_E4M3 || dt == XH_F8_E5M2 || dt == XH_Q8);
+}
+
+int launch_attn_wo(xh_ctx* ctx, int l, hipStream_t s) {
+    const AttnArgs aa = attn_args(ctx, l);
+    const GemvArgs ga = wo_args(ctx, l);
+    unsigned* sync = ctx->aw_sync + (size_t)AW_SYNC_WORDS * l;
+    const int hd = ctx->c.head_dim, qpk = ctx->qpk, nkv = ctx->c.n_kv_heads, tm = ctx->t_max_aw;
+    const int mw = ctx->max_gemv_waves;
+    unsigned long long* tr = ctx->aw_trace_on ? ctx->aw_trace : layer_traced(ctx, l) ? ctx->aw_trace + LT_AW : nullptr;
+    switch (ctx->L[l].wo_dt) {
+        case XH_F32: return aw_launch_dt1(aa, ga, hd, qpk, nkv, tm, sync, mw, s, tr);
+        case XH_F16: return aw_launch_dt2(aa, ga, hd, qpk, nkv, tm, sync, mw, s, tr);
+        case XH_BF16: return aw_launch_dt3(aa, ga, hd, qpk, nkv, tm, sync, mw, s, tr);
+        case XH_F8_E4M3: return aw_launch_dt6(aa, ga, hd, qpk, nkv, tm, sync, mw, s, tr);
+        case XH_F8_E5M2: return aw_launch_dt7(aa, ga, hd, qpk, nkv, tm, sync, mw, s, tr);
+        case XH_Q8: return aw_launch_dt9(aa, ga, hd, qpk, nkv, tm, sync, mw, s, tr);
+        default: return XH_E_INVALID;
+    }
+}
+
+// greedy: the token is the argmax of the previous step's logits (argmax_embed_kernel)
+int enqueue_step(xh_ctx* ctx, hipStream_t s, bool with_logits, bool greedy = false) {
+    const xh_config& c = ctx->c;
+    const int mb = ctx->max_gemv_waves;
+    if (greedy)
+        hipLaunchKernelGGL(argmax_embed_kernel, dim3(1), dim3(ARGMAX_CANDS), 0, s, (const unsigned long long*)ctx->cand,
+                           ctx->sp, ctx->dec_tokens, ctx->dec_cap, (const void*)ctx->embed, ctx->embed_dt, c.dim,
+                           ctx->x, (const float*)ctx->rope_freq, ctx->rope_cs, c.head_dim / 2);
+    else
+        hipLaunchKernelGGL(embed_kernel, dim3((c.dim + 255) / 256), dim3(256), 0, s, (const void*)ctx->embed,
+                           ctx->embed_dt, c.dim, ctx->x, (const StepParams*)ctx->sp, (const float*)ctx->rope_freq,
+                           ctx->rope_cs, c.head_dim / 2);
+    for (int l = 0; l < c.n_layers; l++) {
+        const LayerW& w = ctx->L[l];
+        if (!launch_gemv(GEMV_QKV, kdt(w.qkv_dt, w.qkv_x), qkv_args(ctx, l), s, qkv_launch_waves(ctx, l)))
+            return set_err(ctx, XH_E_INVALID, "layer %d: unsupported qkv dtype %d", l, w.qkv_dt);
+        GemvArgs a13 = w13_args(ctx, l);
+        if (use_attn_wo(ctx, l)) {
+            const int rc = launch_attn_wo(ctx, l, s);
+            if (rc) return set_err(ctx, rc, "layer %d: fused attention + Wo launch failed", l);
+            // W1/W3 right behind it zeroes its hand-off words for the next step
+            a13.aw_reset = ctx->aw_sync + (size_t)AW_SYNC_WORDS * l;
+        } else {
+            if (!launch_attn(attn_args(ctx, l), c.head_dim, ctx->qpk, c.n_kv_heads, ctx->t_max, s))
+                return set_err(ctx, XH_E_INVALID, "unsupported head_dim %d / q-per-kv %d", c.head_dim, ctx->qpk);
+            if (!launch_gemv(GEMV_RESID, kdt(w.wo_dt, w.wo_x), wo_args(ctx, l), s, mb))
+                return set_err(ctx, XH_E_INVALID, "layer %d: unsupported wo dtype", l);
+        }
+        if (!launch_gemv(GEMV_GLU, kdt(w.w13_dt, w.w13_x), a13, s, mb))
+            return set_err(ctx, XH_E_INVALID, "layer %d: unsupported w1/w3 dtype", l);
+        if (!launch_gemv(GEMV_RESID, kdt(w.w2_dt, w.w2_x), w2_args(ctx, l), s, mb))
+            return set_err(ctx, XH_E_INVALID, "layer %d: unsupported w2 dtype", l);
+    }
+    if (with_logits) {
+        if (!launch_gemv(GEMV_LOGITS, kdt(ctx->wcls_dt, ctx->wcls_x), cls_args(ctx), s, mb))
+            return set_err(ctx, XH_E_INVALID, "unsupported wcls dtype");
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+int capture(xh_ctx* ctx, int kind, hipGraphExec_t* out) {
+    hipGraph_t g = nullptr;
+    HIP_TRY(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
+    const int rc = enqueue_step(ctx, ctx->stream, kind != 1, kind == 2);
+    hipError_t e = hipStreamEndCapture(ctx->stream, &g);
+    if (rc) { if (g) hipGraphDestroy(g); return rc; }
+    if (e != hipSuccess) return set_err(ctx, XH_E_HIP, "graph capture failed: %s", hipGetErrorString(e));
+    e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
+    hipGraphDestroy(g);
+    if (e != hipSuccess) return set_err(ctx, XH_E_HIP, "graph instantiate failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+// an eager step that failed part-way: the attention + Wo hand-off words may hold arrivals that
+// the layer's W1/W3 launch never zeroed
+int eager_step(xh_ctx* ctx, bool with_logits, bool greedy) {
+    const int rc = enqueue_step(ctx, ctx->stream, with_logits, greedy);
+    if (rc) hipMemsetAsync(ctx->aw_sync, 0, (size_t)ctx->c.n_layers * AW_SYNC_WORDS * 4, ctx->stream);
+    return rc;
+}
+}  // namespace
+
+GemvArgs xalm::qkv_args(xh_ctx* ctx, int l) {
+    const LayerW& w = ctx->L[l];
+    GemvArgs a{};
+    a.w = w.wqkv; a.row_bytes = dev_row_bytes(w.qkv_dt, ctx->c.dim);
+    a.n = ctx->c.dim; a.rows = ctx->q_dim + 2 * ctx->kv_dim; a.x = ctx->x;
+    a.norm_w = w.attn_norm; a.norm_dtype = w.an_dt; a.eps = ctx->c.norm_eps;
+    a.q = ctx->q; a.kcache = ctx->kcache(l); a.vcache = ctx->vcache(l);
+    a.q_dim = ctx->q_dim; a.kv_dim = ctx->kv_dim; a.head_dim = ctx->c.head_dim;
+    a.rope_freq = ctx->rope_freq; a.rope_cs = ctx->rope_cs; a.sink_cos = ctx->sink_cos; a.sink_sin = ctx->sink_sin;
+    a.qkv_clip = ctx->c.qkv_clip; a.sp = ctx->sp;
+    if (layer_traced(ctx, l)) a.trace = ctx->aw_trace + LT_QKV;
+    return a;
+}
+GemvArgs xalm::wo_args(xh_ctx* ctx, int l) {
+    const LayerW& w = ctx->L[l];
+    GemvArgs a{};
+    a.w = w.wo; a.row_bytes = dev_row_bytes(w.wo_dt, ctx->q_dim);
+    a.n = ctx->q_dim; a.rows = ctx->c.dim; a.x = ctx->attn_out; a.out = ctx->x; a.sp = ctx->sp;
+    return a;
+}
+GemvArgs xalm::w13_args(xh_ctx* ctx, int l) {
+    const LayerW& w = ctx->L[l];
+    GemvArgs a{};
+    a.w = w.w13; a.row_bytes = dev_row_bytes(w.w13_dt, ctx->c.dim);
+    a.n = ctx->c.dim; a.rows = 2 * ctx->c.hidden_dim; a.x = ctx->x;
+    a.norm_w = w.ffn_norm; a.norm_dtype = w.fn_dt; a.eps = ctx->c.norm_eps;
+    a.out = ctx->hb; a.act = ctx->c.act; a.sp = ctx->sp;
+    if (ctx->w13_trace_on) a.trace = ctx->aw_trace;
+    if (layer_traced(ctx, l)) a.trace = ctx->aw_trace + LT_W13;
+    return a;
+}
+GemvArgs xalm::w2_args(xh_ctx* ctx, int l) {
+    const LayerW& w = ctx->L[l];
+    GemvArgs a{};
+    a.w = w.w2; a.row_bytes = dev_row_bytes(w.w2_dt, ctx->c.hidden_dim);
+    a.n = ctx->c.hidden_dim; a.rows = ctx->c.dim; a.x = ctx->hb; a.out = ctx->x; a.sp = ctx->sp;
+    if (layer_traced(ctx, l)) a.trace = ctx->aw_trace + LT_W2;
+    return a;
+}
+GemvArgs xalm::cls_args(xh_ctx* ctx) {
+    GemvArgs a{};
+    a.w = ctx->wcls; a.row_bytes = dev_row_bytes(ctx->wcls_dt, ctx->c.dim);
+    a.n = ctx->c.dim; a.rows = ctx->c.vocab_size; a.x = ctx->x;
+    a.norm_w = ctx->final_norm; a.norm_dtype = ctx->final_norm_dt; a.eps = ctx->c.norm_eps;
+    a.out = ctx->logits; a.sp = ctx->sp; a.cand = ctx->cand;
+    if (ctx->layer_trace_on) a.trace = ctx->aw_trace + LT_CLS;
+    return a;
+}
+AttnArgs xalm::attn_args(xh_ctx* ctx, int l) {
+    AttnArgs a{};
+    a.q = ctx->q; a.kc = ctx->kcache(l); a.vc = ctx->vcache(l); a.kv_dim = ctx->kv_dim;
+    a.n_heads = ctx->c.n_heads; a.nsplit = ctx->nsplit; a.out = ctx->attn_out;
+    a.part_o = ctx->part_o; a.part_ml = ctx->part_ml; a.counters = ctx->attn_cnt; a.sp = ctx->sp;
+    return a;
+}
+// wave cap of layer l's qkv launch: ctx->qkv_waves for the pipelined shape; gguf blocks take the
+// unpipelined staged shape, every wave one group at 16 waves per CU
+int xalm::qkv_launch_waves(const xh_ctx* ctx, int l) {
+    return gq_dt(ctx->L[l].qkv_dt) ? ctx->max_gemv_waves : ctx->qkv_waves;
+}
+
+// a fused hand-off that timed out leaves its sticky flag: report it (after the stream sync)
+int xalm::check_aw(xh_ctx* ctx) {
+    if (!ctx->fuse_attn_wo) return 0;
+    std::vector<unsigned> h((size_t)ctx->c.n_layers * AW_SYNC_WORDS);
+    HIP_TRY(ctx, copy_sync(ctx, h.data(), ctx->aw_sync, h.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    for (int l = 0; l < ctx->c.n_layers; l++)
+        if (h[(size_t)AW_SYNC_WORDS * l + 2]) {
+            // reported once: the sticky words are cleared so the context can be reset and reused
+            HIP_TRY(ctx, fill_sync(ctx, ctx->aw_sync, 0, h.size() * sizeof(unsigned)));
+            return set_err(ctx, XH_E_HIP, "layer %d: attention -> Wo hand-off timed out", l);
+        }
+    return 0;
+}
+
+int xalm::check_ready(xh_ctx* ctx) {
+    if (!ctx->embed) return set_err(ctx, XH_E_STATE, "embed.weight not uploaded");
+    if (!ctx->final_norm) return set_err(ctx, XH_E_STATE, "output.norm.weight not uploaded");
+    if (!ctx->wcls) {
+        if (ctx->c.tie_word_embeddings) { ctx->wcls = ctx->embed; ctx->wcls_dt = ctx->embed_dt; }
+        else return set_err(ctx, XH_E_STATE, "output.weight not uploaded");
+    }
+    for (int l = 0; l < ctx->c.n_layers; l++) {
+        const LayerW& w = ctx->L[l];
+        if (w.qkv_have != 7 || w.w13_have != 3 || !w.wo || !w.w2 || !w.attn_norm || !w.ffn_norm)
+            return set_err(ctx, XH_E_STATE, "layer %d: weights incomplete", l);
+    }
+    return 0;
+}
+
+void xalm::drop_graphs(xh_ctx* ctx) {
+    if (ctx->g_logits) hipGraphExecDestroy(ctx->g_logits);
+    if (ctx->g_hydrate) hipGraphExecDestroy(ctx->g_hydrate);
+    if (ctx->g_decode) hipGraphExecDestroy(ctx->g_decode);
+    ctx->g_logits = ctx->g_hydrate = ctx->g_decode = nullptr;
+}
+
+
+// the step at host_step_params' position
+int xalm::run_step(xh_ctx* ctx, bool with_logits) {
+    if (with_logits) ctx->cand_valid = true;  // the lm_head launch writes candidates
+    if (!ctx->use_graphs) return eager_step(ctx, with_logits, false);
+    hipGraphExec_t* ge = with_logits ? &ctx->g_logits : &ctx->g_hydrate;
+    if (!*ge) {
+        int rc = capture(ctx, with_logits ? 0 : 1, ge);
+        if (rc) return rc;
+    }
+    HIP_TRY(ctx, hipGraphLaunch(*ge, ctx->stream));
+    return 0;
+}
+
+int xalm::host_step_params(xh_ctx* ctx, int token, int pos) {
+    StepParams* h = ctx->sp_host;
+    const int msl = ctx->c.max_seq_len;
+    h->token = token;
+    h->pos = pos;
+    h->kv_sink = pos >= msl ? 2 : 0;
+    h->kv_pos = h->kv_sink + (pos - h->kv_sink) % (msl - h->kv_sink);
+    h->kv_len = pos >= msl ? msl : pos + 1;
+    h->step = 0;
+    h->pos_next = pos + 1;
+    h->max_seq_len = msl;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->sp, h, sizeof(StepParams), hipMemcpyHostToDevice, ctx->stream));
+    return 0;
+}
+
+extern "C" {
+
+int xh_forward(xh_ctx* ctx, int token, int pos, int mode, float* logits_out) {
+    if (!ctx) return XH_E_INVALID;
+    if (token < 0 || token >= ctx->c.vocab_size) return set_err(ctx, XH_E_INVALID, "token %d out of range", token);
+    if (pos < 0) return set_err(ctx, XH_E_INVALID, "negative pos");
+    if (mode != XH_HYDRATE_KV_CACHE && mode != XH_OUTPUT_LOGITS) return set_err(ctx, XH_E_INVALID, "bad mode");
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    int rc = check_ready(ctx);
+    if (rc) return rc;
+    rc = host_step_params(ctx, token, pos);
+    if (!rc) rc = run_step(ctx, mode == XH_OUTPUT_LOGITS);
+    if (rc) return rc;
+    if (logits_out && mode == XH_OUTPUT_LOGITS)
+        HIP_TRY(ctx, hipMemcpyAsync(logits_out, ctx->logits, (size_t)ctx->c.vocab_size * 4, hipMemcpyDeviceToHost,
+                                    ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return check_aw(ctx);
+}
+
+int xh_decode_greedy(xh_ctx* ctx, int pos, int n_steps, int stop_a, int stop_b, int* tokens_out, int* n_done) {
+    if (!ctx || n_steps < 0) return XH_E_INVALID;
+    if (n_done) *n_done = 0;
+    if (n_steps > ctx->dec_cap) return set_err(ctx, XH_E_INVALID, "n_steps > %d", ctx->dec_cap);
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    int rc = check_ready(ctx);
+    if (rc) return rc;
+    // step counter 0, next position `pos`; token/pos fields are set by argmax_advance_kernel
+    StepParams* h = ctx->sp_host;
+    h->step = 0;
+    h->pos_next = pos;
+    h->max_seq_len = ctx->c.max_seq_len;
+    HIP_TRY(ctx, hipMemcpyAsync(&ctx->sp->step, &h->step, 3 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    if (ctx->use_graphs && n_steps > 0 && !ctx->g_decode) {
+        rc = capture(ctx, 2, &ctx->g_decode);
+        if (rc) return rc;
+    }
+    // the first token is the argmax of the logits on the device: candidates from them if the
+    // launch that produced them left none (nothing yet)
+    if (!ctx->cand_valid)
+        hipLaunchKernelGGL(logits_cand_kernel, dim3(1), dim3(ARGMAX_CANDS), 0, ctx->stream, (const float*)ctx->logits,
+                           ctx->c.vocab_size, ctx->cand);
+    ctx->cand_valid = true;
+    const bool stops = stop_a >= 0 || stop_b >= 0;
+    int done = 0;
+    for (int i = 0; i < n_steps; i++) {
+        if (ctx->use_graphs) {
+            HIP_TRY(ctx, hipGraphLaunch(ctx->g_decode, ctx->stream));
+        } else {
+            rc = eager_step(ctx, true, true);
+            if (rc) return rc;
+        }
+        done = i + 1;
+        if (stops) {
+            int tok = -1;
+            HIP_TRY(ctx, hipMemcpyAsync(&tok, ctx->dec_tokens + i, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (tok == stop_a || tok == stop_b) break;
+        }
+    }
+    if (tokens_out && done)
+        HIP_TRY(ctx, hipMemcpyAsync(tokens_out, ctx->dec_tokens, (size_t)done * sizeof(int), hipMemcpyDeviceToHost,
+                                    ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_done) *n_done = done;
+    return check_aw(ctx);
+}
+
+int xh_get_logits(xh_ctx* ctx, float* logits_out) {
+    if (!ctx || !logits_out) return XH_E_INVALID;
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    HIP_TRY(ctx, hipMemcpyAsync(logits_out, ctx->logits, (size_t)ctx->c.vocab_size * 4, hipMemcpyDeviceToHost,
+                                ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // dt_launch.h — launchers of the fused attention + Wo kernel (attn_wo.h), one translation unit
 // per Wo dtype (dt_launch.hip compiled with -DPK_DT=<id>), so the instantiations build in
-// parallel.
+// parallel.  decode.hip picks the launcher by Wo dtype (launch_attn_wo).
 #pragma once
 
 #include <stddef.h>

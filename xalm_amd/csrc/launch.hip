@@ -1,0 +1,214 @@
+// launch.hip — launch dispatch of the decode kernels: every gemv_kernel (gemv.h) and
+// attn_split_kernel (attention.h) instantiation lives in this translation unit.
+#include <hip/hip_runtime.h>
+
+#include <mutex>
+#include <set>
+
+#include "ctx.h"
+
+using namespace xalm;
+
+// the attribute belongs to the device current at the call; a failure is not recorded, so the
+// next launch tries again
+bool xalm::ensure_lds(const void* fn, const int bytes) {
+    static std::mutex mu;
+    static std::set<std::pair<const void*, int>> done;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return false;
+    std::lock_guard<std::mutex> g(mu);
+    if (done.count({fn, dev})) return true;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
+    done.insert({fn, dev});
+    return true;
+}
+
+namespace {
+
+constexpr int ROWS = 2;  // rows per wave (even: rope pairs, gate/up pairs)
+constexpr int UNROLL = 4;
+
+// ---------------------------------------------------------------------------------------
+// gemv launch dispatch
+// ---------------------------------------------------------------------------------------
+// Shapes, chosen with tools/gemv_bench.hip and tools/chain_bench.hip on MI355X
+// (profiles/r01_gemv_bench.txt, profiles/r01_chain_bench.txt): 512-thread blocks (8 waves share
+// one x image), 2 rows x 4 chunks in flight per wave, non-temporal weight loads, 16 waves per
+// CU.  PF shapes hold x in registers (XN float4 per thread) and request the first weight chunks
+// inside the prologue (-5.7 % per decode layer); the plain shape covers every other n.
+using ShapeShort = GemvShape<512, ROWS, UNROLL, true, 4, false>;
+using ShapeLong = GemvShape<512, ROWS, UNROLL, true, 4, false>;
+using ShapePF2 = GemvShape<512, ROWS, UNROLL, true, 4, true, 2>;  // n <= 4096
+using ShapePF8 = GemvShape<512, ROWS, UNROLL, true, 4, true, 8>;  // n <= 16384 (W2 / Wo inputs)
+
+template <int DT, int PRO, int EPI, class S>
+void launch_gemv_s(const GemvArgs& a, hipStream_t s, int max_waves) {
+    const size_t smem = gemv_smem_bytes<DT, S>(a.n);
+    const int blocks = gemv_blocks<S>(a.rows, max_waves / S::WAVES);
+    auto k = gemv_kernel<DT, PRO, EPI, S>;
+    if (smem > 64 * 1024) ensure_lds((const void*)k);
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(S::THREADS), smem, s, a);
+}
+
+// pipelined PF shape (gemv_rows_pipe: the next row step requested before the current one is
+// multiplied, across row groups too) for the qkv and W1/W3 launches: fp8 Mistral-7B decode
+// 568 -> 584 tok/s (their 4 KiB rows are one step per group, so a wave drained to zero at
+// every group), f16 unchanged (383 / 383); W2, Wo and lm_head unchanged either way
+using ShapePF2P = GemvShape<512, ROWS, UNROLL, true, 4, true, 2, 2>;  // n <= 4096
+// qkv with 2-byte weights (QKV_T384): 384-thread workgroups, two per CU, every wave ONE row group
+// at 3072 waves (tools/gemv_bench GB_BAL: 10.29 -> 9.95 us f16; fp8 rows are one step: no gain)
+using ShapeQ384 = GemvShape<384, ROWS, UNROLL, true, 3, true, 3, 2>;  // n <= 4608
+#ifndef QKV_T384
+#define QKV_T384 1
+#endif
+// W2-long rows of one-byte weights (W2_T1024): one 1024-thread workgroup per CU, one row per
+// wave, hb in 4 float4 per thread (tools/gemv_bench GB_W2, fp8 Mistral W2: 12.58 -> 11.99 us;
+// f16 no gain)
+using ShapeW2K = GemvShape<1024, 1, UNROLL, true, 4, true, 4, 1>;  // n <= 16384
+#ifndef W2_T1024
+#define W2_T1024 1
+#endif
+#ifndef GEMV_BAL_GQ_GLU
+#define GEMV_BAL_GQ_GLU 1
+#endif
+#ifndef GEMV_BAL_FP8_QKV
+#define GEMV_BAL_FP8_QKV 1
+#endif
+
+
+template <int DT, int PRO, int EPI>
+void launch_gemv_t(const GemvArgs& a, hipStream_t s, int max_waves) {
+    constexpr int E = WDec<DT>::E;
+    // gguf blocks take the staged shapes below (4 rows per wave measured slower: Q8_0 442 ->
+    // 303 tok/s, Q4_0 560 -> 506)
+    // PF needs whole first chunks (n >= 64 E U) and x in XN float4 per thread
+    const bool pf = !gq_dt(DT) && a.n % 4 == 0 && a.n >= 64 * E * UNROLL;
+    if constexpr ((EPI == EPI_QKV || EPI == EPI_GLU) && !gq_dt(DT)) {
+        if constexpr (EPI == EPI_QKV && E <= 8 && QKV_T384) {
+            if (pf && a.n / 4 <= 3 * 384 && a.n % (64 * E * UNROLL) == 0)
+                return launch_gemv_s<DT, PRO, EPI, ShapeQ384>(a, s, 3 * (max_waves / 2));
+        }
+        if constexpr (EPI == EPI_QKV && E >= 16 && GEMV_BAL_FP8_QKV) {
+            // one-byte qkv rows: 3072 one-step groups, 512 workgroups of 6 busy waves (fp8 qkv
+            // 7.3 -> 7.1 us, decode +0.5 %, profiles/r06_decode_ab.txt ab9)
+            using ShapePF2PB = GemvShape<512, ROWS, UNROLL, true, 4, true, 2, 2, true>;
+            if (pf && a.n / 4 <= 2 * 512 && a.n % (64 * E * UNROLL) == 0)
+                return launch_gemv_s<DT, PRO, EPI, ShapePF2PB>(a, s, max_waves);
+        }
+        if (pf && a.n / 4 <= 2 * 512 && a.n % (64 * E * UNROLL) == 0)
+            return launch_gemv_s<DT, PRO, EPI, ShapePF2P>(a, s, max_waves);
+    }
+    if constexpr (gq_dt(DT)) {
+        // gguf blocks: the pipelined PF shapes with the block scales loaded beside the codes.
+        // Q4_0 rows of a 4096-wide input are 2 chunks, so 2 chunks per step; W2-long inputs
+        // (14336: 14 / 7 chunks per row) step by 2 (Q8_0) / 1 (Q4_0) chunks
+        constexpr int UG = DT == XH_Q4_0 ? 2 : UNROLL;
+        // W1/W3 (GEMV_BAL_GQ_GLU): balanced grid, Q4_0 15.0 -> 14.0 us (profiles/r06_decode_ab.txt ab8)
+        using ShapeGQ = GemvShape<512, ROWS, UG, true, 4, true, 2, 2, EPI == EPI_GLU && GEMV_BAL_GQ_GLU>;
+        if (a.n % 4 == 0 && a.n / 4 <= 2 * 512 && a.n % (64 * E * UG) == 0)
+            return launch_gemv_s<DT, PRO, EPI, ShapeGQ>(a, s, max_waves);
+        if constexpr (PRO == PRO_PLAIN) {
+            constexpr int UL = DT == XH_Q4_0 ? 1 : 2;
+            using ShapeGQL = GemvShape<512, ROWS, UL, true, 4, true, 8, 2>;
+            if (a.n % 4 == 0 && a.n / 4 <= 8 * 512 && a.n % (64 * E * UL) == 0)
+                return launch_gemv_s<DT, PRO, EPI, ShapeGQL>(a, s, max_waves);
+        }
+    }
+    if (pf && a.n / 4 <= 2 * 512) launch_gemv_s<DT, PRO, EPI, ShapePF2>(a, s, max_waves);
+    else if constexpr (PRO == PRO_PLAIN && EPI == EPI_RESID && E >= 16 && W2_T1024) {
+        if (pf && a.n / 4 <= 4 * 1024) launch_gemv_s<DT, PRO, EPI, ShapeW2K>(a, s, max_waves);
+        else launch_gemv_s<DT, PRO, EPI, ShapeLong>(a, s, max_waves);
+    } else if constexpr (PRO == PRO_PLAIN) {
+        if (pf && a.n / 4 <= 8 * 512) launch_gemv_s<DT, PRO, EPI, ShapePF8>(a, s, max_waves);
+        else launch_gemv_s<DT, PRO, EPI, ShapeLong>(a, s, max_waves);
+    } else if (gemv_smem_bytes<DT, ShapeShort>(a.n) <= 40 * 1024) {
+        launch_gemv_s<DT, PRO, EPI, ShapeShort>(a, s, max_waves);
+    } else {
+        launch_gemv_s<DT, PRO, EPI, ShapeLong>(a, s, max_waves);
+    }
+}
+
+template <int PRO, int EPI>
+bool launch_gemv_dt(int dt, const GemvArgs& a, hipStream_t s, int max_blocks) {
+    switch (dt) {
+        case XH_F32: launch_gemv_t<XH_F32, PRO, EPI>(a, s, max_blocks); return true;
+        case XH_F16: launch_gemv_t<XH_F16, PRO, EPI>(a, s, max_blocks); return true;
+        case XH_BF16: launch_gemv_t<XH_BF16, PRO, EPI>(a, s, max_blocks); return true;
+        case XH_F8_E4M3: launch_gemv_t<XH_F8_E4M3, PRO, EPI>(a, s, max_blocks); return true;
+        case XH_F8_E5M2: launch_gemv_t<XH_F8_E5M2, PRO, EPI>(a, s, max_blocks); return true;
+        case XH_Q8: launch_gemv_t<XH_Q8, PRO, EPI>(a, s, max_blocks); return true;
+        case XH_F8_E4M3_EXACT: launch_gemv_t<XH_F8_E4M3_EXACT, PRO, EPI>(a, s, max_blocks); return true;
+        case XH_F8_E5M2_EXACT: launch_gemv_t<XH_F8_E5M2_EXACT, PRO, EPI>(a, s, max_blocks); return true;
+        case XH_Q8_0: launch_gemv_t<XH_Q8_0, PRO, EPI>(a, s, max_blocks); return true;
+        case XH_Q4_0: launch_gemv_t<XH_Q4_0, PRO, EPI>(a, s, max_blocks); return true;
+        default: return false;
+    }
+}
+
+}  // namespace
+
+bool xalm::launch_gemv(GemvRole role, int dt, const GemvArgs& a, hipStream_t s, int max_waves) {
+    switch (role) {
+        case GEMV_QKV: return launch_gemv_dt<PRO_RMSNORM, EPI_QKV>(dt, a, s, max_waves);
+        case GEMV_GLU: return launch_gemv_dt<PRO_RMSNORM, EPI_GLU>(dt, a, s, max_waves);
+        case GEMV_RESID: return launch_gemv_dt<PRO_PLAIN, EPI_RESID>(dt, a, s, max_waves);
+        case GEMV_LOGITS: return launch_gemv_dt<PRO_RMSNORM, EPI_LOGITS>(dt, a, s, max_waves);
+        case GEMV_STORE: return launch_gemv_dt<PRO_PLAIN, EPI_STORE>(dt, a, s, max_waves);
+    }
+    return false;
+}
+
+namespace {
+
+// ---------------------------------------------------------------------------------------
+// attention launch dispatch
+// ---------------------------------------------------------------------------------------
+template <int HD, int QPK>
+void launch_attn_t(const AttnArgs& a, int n_kv_heads, int t_max, hipStream_t s) {
+    const size_t smem = attn_smem_bytes(HD, QPK, t_max, a.nsplit);
+    auto k = attn_split_kernel<HD, QPK>;
+    if (smem > 64 * 1024) ensure_lds((const void*)k);
+    hipLaunchKernelGGL(k, dim3(n_kv_heads, a.nsplit), dim3(ATTN_THREADS), smem, s, a);
+}
+
+template <int HD>
+bool launch_attn_hd(const AttnArgs& a, int qpk, int n_kv_heads, int t_max, hipStream_t s) {
+    switch (qpk) {
+        case 1: launch_attn_t<HD, 1>(a, n_kv_heads, t_max, s); return true;
+        case 2: launch_attn_t<HD, 2>(a, n_kv_heads, t_max, s); return true;
+        case 4: launch_attn_t<HD, 4>(a, n_kv_heads, t_max, s); return true;
+        case 8: launch_attn_t<HD, 8>(a, n_kv_heads, t_max, s); return true;
+        default: return false;
+    }
+}
+
+}  // namespace
+
+bool xalm::launch_attn(const AttnArgs& a, int hd, int qpk, int n_kv_heads, int t_max, hipStream_t s) {
+    bool ok = false;
+    switch (hd) {
+        case 16: ok = launch_attn_hd<16>(a, qpk, n_kv_heads, t_max, s); break;
+        case 32: ok = launch_attn_hd<32>(a, qpk, n_kv_heads, t_max, s); break;
+        case 64: ok = launch_attn_hd<64>(a, qpk, n_kv_heads, t_max, s); break;
+        case 128: ok = launch_attn_hd<128>(a, qpk, n_kv_heads, t_max, s); break;
+        case 256: ok = launch_attn_hd<256>(a, qpk, n_kv_heads, t_max, s); break;
+        default: return false;
+    }
+    return ok;
+}
+
+int xalm::attn_nsplit(int n_kv_heads, int max_seq_len) {
+    // one split workgroup per CU at the longest context (tools/attn_bench.hip, 32k: 32 splits
+    // per KV head 34.9 us vs 64 splits 39.0 us)
+#ifndef ATTN_SPLIT_WGS
+#define ATTN_SPLIT_WGS 256
+#endif
+    int ns = ATTN_SPLIT_WGS / n_kv_heads;
+    if (ns > 128) ns = 128;  // the merge holds <= 2 partials per lane
+#ifndef ATTN_CAP_T
+#define ATTN_CAP_T ATTN_MIN_T
+#endif
+    const int cap = (max_seq_len + ATTN_CAP_T - 1) / ATTN_CAP_T;
+    if (ns > cap) ns = cap;
+    return ns < 1 ? 1 : ns;
+}

@@ -1,0 +1,708 @@
+// prefill.hip — batched prompt passes: pass buffers, the GEMM and attention dispatch of prefill.h
+// and gemm16.h (this unit alone includes them: they define non-template kernels), and the ABI
+// entries xh_prefill and xh_perplexity.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "ctx.h"
+#include "prefill.h"
+
+using namespace xalm;
+
+namespace {
+
+// ---------------------------------------------------------------------------------------
+// batched prefill (prefill.h)
+// ---------------------------------------------------------------------------------------
+constexpr int PF_WAVE_TARGET = 1024;  // 1 wave per SIMD (RT=2: 2048 -16 %, 512 -38 %; fewer, longer K slices)
+constexpr int PF_RT = 2;                // 32-row tiles per GEMM wave (1: -11 %, 4: -9 %)
+constexpr int PF_RT16 = 4;              // 32-row tiles per split-f16 GEMM wave
+constexpr size_t PF_PART_ROWS = 32 * PF_RT16 * PF_WAVE_TARGET;  // >= ks * rows (ks * ceil(rows/(32 RT)) <= target)
+
+constexpr int PF_CLS_CHUNK = (int)(PF_PART_ROWS / 4);  // lm_head rows per GEMM (ks <= 4 fits the partials)
+
+// partials buffer: the register-streaming MFMA kernels' K slices of 64 tokens, or up to 2 T
+// token rows of partials over the widest matrix (gemm16.h K slices: ks * n <= 2 T; hipBLASLt: the
+// hi and lo halves)
+size_t pf_part_floats(const xh_ctx* ctx, const int T) {
+    const xh_config& c = ctx->c;
+    const int rows = std::max({ctx->q_dim + 2 * ctx->kv_dim, 2 * c.hidden_dim, c.dim, std::min(c.vocab_size, PF_CLS_CHUNK)});
+    return std::max(PF_PART_ROWS * PF_TOK, (size_t)2 * T * rows);
+}
+
+}  // namespace
+
+void xalm::pf_free(xh_ctx* ctx) {
+    for (void* p : {(void*)ctx->pf_tok, (void*)ctx->pf_x, (void*)ctx->pf_xn, (void*)ctx->pf_q, (void*)ctx->pf_att,
+                    (void*)ctx->pf_h, (void*)ctx->pf_part, (void*)ctx->pf_sp, (void*)ctx->pf_xh, (void*)ctx->pf_xl,
+                    (void*)ctx->pf_xs, (void*)ctx->pf_logits, (void*)ctx->pf_tgt, (void*)ctx->pf_po,
+                    (void*)ctx->pf_pml, (void*)ctx->pf_cnt})
+        hipFree(p);
+    ctx->pf_tok = nullptr; ctx->pf_x = ctx->pf_xn = ctx->pf_q = ctx->pf_att = ctx->pf_h = ctx->pf_part = nullptr;
+    ctx->pf_sp = nullptr; ctx->pf_xh = ctx->pf_xl = nullptr; ctx->pf_xs = nullptr; ctx->pf_logits = nullptr;
+    ctx->pf_tgt = nullptr; ctx->pf_po = ctx->pf_pml = nullptr; ctx->pf_cnt = nullptr;
+    ctx->pf_cap = ctx->pf_po_cap = 0;
+}
+
+namespace {
+
+// pass buffers for T tokens (kept while later passes fit; a longer pass length reallocates)
+int pf_alloc(xh_ctx* ctx, const int T) {
+    if (ctx->pf_cap >= T) return 0;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    pf_free(ctx);
+    const xh_config& c = ctx->c;
+    const size_t t = (size_t)T;
+    int rc;
+    if ((rc = dmalloc(ctx, &ctx->pf_tok, t)) || (rc = dmalloc(ctx, &ctx->pf_x, t * c.dim)) ||
+        (rc = dmalloc(ctx, &ctx->pf_xn, t * c.dim)) || (rc = dmalloc(ctx, &ctx->pf_q, t * ctx->q_dim)) ||
+        (rc = dmalloc(ctx, &ctx->pf_att, t * ctx->q_dim)) || (rc = dmalloc(ctx, &ctx->pf_h, t * c.hidden_dim)) ||
+        (rc = dmalloc(ctx, &ctx->pf_part, pf_part_floats(ctx, T))) || (rc = dmalloc(ctx, &ctx->pf_sp, t)))
+        return rc;
+    // pf_xh: the split-kernel fragments of <= 64 tokens, or hi rows then lo rows of a row-major
+    // pass input (gemm16.h / hipBLASLt); pf_xl: the split kernel's lo fragments
+    const size_t kmax = std::max({(size_t)c.dim, (size_t)c.hidden_dim, (size_t)ctx->q_dim});
+    if ((rc = dmalloc(ctx, &ctx->pf_xh, 2 * std::max(t, (size_t)PF_TOK) * kmax)) ||
+        (rc = dmalloc(ctx, &ctx->pf_xl, PF_TOK * kmax)) || (rc = dmalloc(ctx, &ctx->pf_xs, std::max(t, (size_t)PF_TOK))))
+        return rc;
+    ctx->pf_cap = T;
+    return 0;
+}
+
+// the per-token split attention's partials (XH_OPT_PREFILL_ATTN 0), sized for the pass
+int pf_alloc_split_attn(xh_ctx* ctx) {
+    if (ctx->pf_po_cap >= ctx->pf_cap) return 0;
+    hipFree(ctx->pf_po); hipFree(ctx->pf_pml); hipFree(ctx->pf_cnt);
+    ctx->pf_po = ctx->pf_pml = nullptr; ctx->pf_cnt = nullptr; ctx->pf_po_cap = 0;
+    const size_t t = (size_t)ctx->pf_cap;
+    int rc;
+    if ((rc = dmalloc(ctx, &ctx->pf_po, t * ctx->nsplit * ctx->q_dim)) ||
+        (rc = dmalloc(ctx, &ctx->pf_pml, t * ctx->nsplit * ctx->c.n_heads * 2)) ||
+        (rc = dmalloc(ctx, &ctx->pf_cnt, t * ctx->c.n_kv_heads)))
+        return rc;
+    ctx->pf_po_cap = ctx->pf_cap;
+    return 0;
+}
+
+// K slices for a GEMM of `rows` outputs: about PF_WAVE_TARGET waves, K divisible into whole
+// chunk pairs
+int pf_ks(int rows, int K, int E) {
+    const int n_rt = (rows + 32 * PF_RT - 1) / (32 * PF_RT);
+    int ks = 1;
+    // slices stay whole multiples of 4 chunk pairs (the pipelined kernel) where K allows
+    const int unit = K % (8 * E) == 0 ? 8 * E : 2 * E;
+    while (ks < 64 && (size_t)2 * ks * n_rt <= PF_WAVE_TARGET && K % (2 * ks * unit) == 0) ks *= 2;
+    return ks;
+}
+
+template <int DT>
+void pf_gemm_t(const PfGemmArgs& a, hipStream_t s) {
+    const int waves = (a.rows + 32 * PF_RT - 1) / (32 * PF_RT) * a.ks;
+    constexpr int E = WDec<DT>::E;
+    const dim3 grid((waves + PF_WAVES - 1) / PF_WAVES);
+    if ((a.K / a.ks) % (8 * E) == 0)
+        hipLaunchKernelGGL((prefill_gemm_kernel<DT, true, PF_RT>), grid, dim3(PF_THREADS), 0, s, a);
+    else
+        hipLaunchKernelGGL((prefill_gemm_kernel<DT, false, PF_RT>), grid, dim3(PF_THREADS), 0, s, a);
+}
+// split-f16 GEMM: K slices of whole 4-stage rings (8E), about PF_WAVE_TARGET waves, partials fit
+int pf_ks16(int rows, int K, int E) {
+    if (K % (8 * E)) return 0;
+    const int n_rt = (rows + 32 * PF_RT16 - 1) / (32 * PF_RT16);
+    int ks = 1;
+    while (ks < 64 && (size_t)2 * ks * n_rt <= PF_WAVE_TARGET && K % (2 * ks * 8 * E) == 0) ks *= 2;
+    while (ks > 1 && (size_t)ks * rows > PF_PART_ROWS) ks /= 2;
+    return (size_t)ks * rows <= PF_PART_ROWS ? ks : 0;
+}
+template <int DT>
+void pf_gemm16_t(const PfGemm16Args& a, hipStream_t s) {
+    const int waves = (a.rows + 32 * PF_RT16 - 1) / (32 * PF_RT16) * a.ks;
+    hipLaunchKernelGGL((prefill_gemm16_kernel<DT, PF_RT16>), dim3((waves + PF_WAVES - 1) / PF_WAVES), dim3(PF_THREADS),
+                       0, s, a);
+}
+// weights per 16-byte chunk of the f32-input MFMA kernel's decoders (WDec<DT>::E)
+int pf_elems(int dt) {
+    if (dt == XH_F8_E4M3_EXACT || dt == XH_F8_E5M2_EXACT || dt == XH_Q8_0) return 16;
+    return dt == XH_Q4_0 ? 32 : elems_per_16b(dt);
+}
+// weights the f16 GEMMs take: f16 as stored, e4m3 / e5m2 through their exact f16 image (kdt
+// keeps the _EXACT dtypes, whose NaN / Inf codes the reference decodes to finite values, off it)
+bool pf_f8(int dt) { return dt == XH_F8_E4M3 || dt == XH_F8_E5M2; }
+bool pf_f16w(int dt) { return dt == XH_F16 || pf_f8(dt); }
+// Does the GEMM over W (dtype dt, K columns) run on the row-major split input: gemm16.h
+// (XH_OPT_PREFILL 1: K in whole 64-deep steps) or hipBLASLt (4: a plan for every shape)?
+bool pf_lay0(const xh_ctx* ctx, int dt, int K) {
+    // gguf blocks: their exact f16 hi + lo images through gemm16.h (XH_OPT_PREFILL 1)
+    if (gq_dt(dt)) return ctx->prefill_gemm == 1 && K % MM_KMULT == 0;
+    if (!pf_f16w(dt)) return false;
+    if (ctx->prefill_gemm == 1) return K % MM_KMULT == 0;
+    if (ctx->prefill_gemm == 4) return blas_ok(ctx) > 0;
+    return false;
+}
+// Once per prefill: (XH_OPT_PREFILL 4, once per context) does hipBLASLt have an f16 plan for every
+// full-pass GEMM of the model (if not, every dtype keeps the MFMA kernels); and the f16 image
+// buffer of the largest fp8 matrix that goes to the f16 GEMMs.
+int pf_prepare(xh_ctx* ctx) {
+    const xh_config& c = ctx->c;
+    struct G { int dt, rows, K; };
+    std::vector<G> gs;
+    for (const LayerW& w : ctx->L) {
+        gs.push_back({kdt(w.qkv_dt, w.qkv_x), ctx->q_dim + 2 * ctx->kv_dim, c.dim});
+        gs.push_back({kdt(w.wo_dt, w.wo_x), c.dim, ctx->q_dim});
+        gs.push_back({kdt(w.w13_dt, w.w13_x), 2 * c.hidden_dim, c.dim});
+        gs.push_back({kdt(w.w2_dt, w.w2_x), c.dim, c.hidden_dim});
+    }
+    gs.push_back({kdt(ctx->wcls_dt, ctx->wcls_x), std::min(PF_CLS_CHUNK, c.vocab_size), c.dim});
+    if (ctx->prefill_gemm == 4 && !blas_ok(ctx)) {
+        int ok = 1;
+        for (const G& g : gs) {
+            if (!pf_f16w(g.dt)) continue;
+            bool have = false;
+            int rc = blas_has_plan(ctx, g.rows, g.K, 2 * PF_TOK_BLAS, &have);
+            if (rc) return rc;
+            if (!have) ok = -1;
+        }
+        blas_set_ok(ctx, ok);
+    }
+    size_t wdq = 0;  // fp8: one f16 image; gguf blocks: hi and lo images
+    for (const G& g : gs)
+        if ((pf_f8(g.dt) || gq_dt(g.dt)) && pf_lay0(ctx, g.dt, g.K))
+            wdq = std::max(wdq, (size_t)g.rows * g.K * (gq_dt(g.dt) ? 2 : 1));
+    if (wdq > ctx->pf_wdq_elems) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        hipFree(ctx->pf_wdq);
+        ctx->pf_wdq = nullptr;
+        ctx->pf_wdq_elems = 0;
+        int rc = dmalloc(ctx, &ctx->pf_wdq, wdq);
+        if (rc) return rc;
+        ctx->pf_wdq_elems = wdq;
+    }
+    return 0;
+}
+// Layout of the split-f16 input of the GEMM over W (dtype dt, [rows][K]): 0 = row-major (gemm16.h
+// or hipBLASLt), E > 0 = the split-f16 register-streaming kernel's fragments, -1 = no split
+// (f32-input MFMA).  XH_OPT_PREFILL 1 / 4: row-major for f16 / e4m3 / e5m2 where the GEMM fits,
+// else the split kernel for fp8; 2: the split kernel for f16 and fp8; 3: never split.  The split
+// kernel also needs a K slicing.
+int pf_layout(const xh_ctx* ctx, int dt, int K, int rows) {
+    if (pf_lay0(ctx, dt, K)) return 0;
+    const bool f8 = pf_f8(dt);
+    const int m = ctx->prefill_gemm;
+    if (!(m == 2 || ((m == 1 || m == 4) && f8))) return -1;
+    if (dt != XH_F16 && !f8) return -1;
+    const int E = elems_per_16b(dt);
+    return pf_ks16(rows, K, E) ? E : -1;
+}
+// split-f16 halves of a pass's rows: hi into pf_xh; lo into pf_xl (fragments) or right after
+// the hi rows (row-major)
+uint16_t* pf_lo(xh_ctx* ctx, int layout, int n, int K) {
+    return layout ? ctx->pf_xl : ctx->pf_xh + (size_t)n * K;
+}
+// grid of the split kernels: one workgroup per token row, fragments padded to 32-token tiles
+int pf_split_grid(int layout, int n) { return layout ? 32 * ((n + 31) / 32) : n; }
+// Tokens per pass: PF_TOK_MM (gemm16.h) / PF_TOK_BLAS (hipBLASLt) when every layer GEMM takes the
+// row-major input (the lm_head of a perplexity pass aside: it runs on 64-token slices when it
+// cannot), else 64 (the register-streaming MFMA kernels' two token tiles)
+int pf_pass_tokens(const xh_ctx* ctx) {
+    const xh_config& c = ctx->c;
+    for (const LayerW& w : ctx->L)
+        if (!pf_lay0(ctx, kdt(w.qkv_dt, w.qkv_x), c.dim) || !pf_lay0(ctx, kdt(w.wo_dt, w.wo_x), ctx->q_dim) ||
+            !pf_lay0(ctx, kdt(w.w13_dt, w.w13_x), c.dim) || !pf_lay0(ctx, kdt(w.w2_dt, w.w2_x), c.hidden_dim))
+            return PF_TOK;
+    return ctx->prefill_gemm == 4 ? PF_TOK_BLAS : PF_TOK_MM;
+}
+// rmsnorm of the pass's rows (pf_x) as the input of the GEMM over W (dt, [rows][dim]): written
+// straight into the split-f16 halves when that GEMM takes a split input (one launch)
+void pf_norm(xh_ctx* ctx, const void* nw, int ndt, int m, int dt, int rows) {
+    const xh_config& c = ctx->c;
+    const int lay = pf_layout(ctx, dt, c.dim, rows);
+    if (lay >= 0) {
+        hipLaunchKernelGGL(prefill_rmsnorm_split_kernel, dim3(pf_split_grid(lay, m)), dim3(256), 0, ctx->stream,
+                           (const float*)ctx->pf_x, c.dim, nw, ndt, c.norm_eps, m, lay, ctx->pf_xh,
+                           pf_lo(ctx, lay, m, c.dim), ctx->pf_xs);
+        ctx->pf_split_ready = true;
+    } else {
+        hipLaunchKernelGGL(prefill_rmsnorm_kernel, dim3(m), dim3(256), 0, ctx->stream, (const float*)ctx->pf_x, c.dim,
+                           nw, ndt, c.norm_eps, ctx->pf_xn);
+    }
+}
+// one prompt GEMM launch (gemm16.h): the 4-wave instantiation when the launch has at least
+// MM_W4_PER_CU workgroups per CU, else the default
+void mm_launch(const MmArgs& a, int n_cu, hipStream_t s) {
+    const int grid = a.n_rt * a.n_tt * a.ks;
+    if (grid >= MM_W4_PER_CU * n_cu) {
+        ensure_lds((const void*)mm_f16_kernel_w4, MM_LDS_W4);
+        hipLaunchKernelGGL(mm_f16_kernel_w4, dim3(grid), dim3(MM_THREADS_W4), MM_LDS_W4, s, a);
+    } else {
+        ensure_lds((const void*)mm_f16_kernel, MM_LDS);
+        hipLaunchKernelGGL(mm_f16_kernel, dim3(grid), dim3(MM_THREADS), MM_LDS, s, a);
+    }
+}
+// Y partials of W[rows][K] . X[n][K] into pf_part ([ks][n][rows]).  Split-f16 paths convert x
+// first unless pf_norm / the fused GLU already left its halves.  0 or an error code.
+int pf_gemm(xh_ctx* ctx, const char* what, int dt, const void* w, int K, int rows, const float* x, int n, int& ks) {
+    const int lay = pf_layout(ctx, dt, K, rows);
+    ctx->pf_scaled = false;
+    if (lay >= 0) {
+        if (ctx->pf_split_ready)
+            ctx->pf_split_ready = false;
+        else
+            hipLaunchKernelGGL(prefill_split_kernel, dim3(pf_split_grid(lay, n)), dim3(256), 0, ctx->stream, x, K, n,
+                               lay, ctx->pf_xh, pf_lo(ctx, lay, n, K), ctx->pf_xs);
+    }
+    if (lay == 0) {
+        // row-major hi rows then lo rows; partials unscaled, the epilogue multiplies by 1 / s_t
+        if (pf_f8(dt)) {
+            // the matrix's exact f16 image first (one streaming pass: 1 B read, 2 B written per weight)
+            const size_t n16 = (size_t)rows * K / 16;
+            if ((size_t)rows * K > ctx->pf_wdq_elems || K % 16)
+                return set_err(ctx, XH_E_INVALID, "prefill: %s fp8 image does not fit", what);
+            const int grid = (int)std::min<size_t>((n16 + 255) / 256, 8192);
+            if (dt == XH_F8_E4M3)
+                hipLaunchKernelGGL(pf_dequant_f16_kernel<XH_F8_E4M3>, dim3(grid), dim3(256), 0, ctx->stream,
+                                   (const u32x4*)w, n16, (u32x4*)ctx->pf_wdq);
+            else
+                hipLaunchKernelGGL(pf_dequant_f16_kernel<XH_F8_E5M2>, dim3(grid), dim3(256), 0, ctx->stream,
+                                   (const u32x4*)w, n16, (u32x4*)ctx->pf_wdq);
+            w = ctx->pf_wdq;
+        }
+        const uint16_t* w_lo = nullptr;  // gguf blocks: the lo image, a second GEMM into more partials
+        if (gq_dt(dt)) {
+            if ((size_t)2 * rows * K > ctx->pf_wdq_elems || K % 32)
+                return set_err(ctx, XH_E_INVALID, "prefill: %s block image does not fit", what);
+            const size_t chunks = (size_t)rows * K / 8;
+            const int grid = (int)std::min<size_t>((chunks + 255) / 256, 8192);
+            uint16_t* hi = ctx->pf_wdq;
+            uint16_t* lo = ctx->pf_wdq + (size_t)rows * K;
+            if (dt == XH_Q8_0)
+                hipLaunchKernelGGL(pf_dequant_gq_kernel<XH_Q8_0>, dim3(grid), dim3(256), 0, ctx->stream,
+                                   (const uint8_t*)w, rows, K, hi, lo);
+            else
+                hipLaunchKernelGGL(pf_dequant_gq_kernel<XH_Q4_0>, dim3(grid), dim3(256), 0, ctx->stream,
+                                   (const uint8_t*)w, rows, K, hi, lo);
+            w = hi;
+            w_lo = lo;
+        }
+        ctx->pf_scaled = true;
+        if (ctx->prefill_gemm == 4) {
+            // hi and lo rows as one B operand of 2n columns: partials [2][n][rows]; a pass length
+            // hipBLASLt has no algorithm for runs on gemm16.h instead (same layout, same bound)
+            bool have = false;
+            int rc = blas_has_plan(ctx, rows, K, 2 * n, &have);
+            if (rc) return rc;
+            if (have || K % MM_KMULT) {
+                rc = blas_gemm(ctx, w, K, rows, ctx->pf_xh, 2 * n, ctx->pf_part);
+                if (rc) return rc;
+                ks = 2;
+                return 0;
+            }
+        }
+        const int images = w_lo ? 2 : 1;
+        const size_t cap = pf_part_floats(ctx, ctx->pf_cap);
+        MmArgs a{};
+        a.w = (const uint16_t*)w; a.xh = ctx->pf_xh; a.xl = ctx->pf_xh + (size_t)n * K; a.out = ctx->pf_part;
+        a.rows = rows; a.K = K; a.n = n; a.ks = mm_pick_ks(rows, K, n, cap / images, ctx->n_cu);
+        a.n_rt = mm_row_tiles(rows); a.n_tt = mm_tok_tiles(n);
+        if (a.ks <= 0 || (size_t)images * a.ks * n * rows > cap)
+            return set_err(ctx, XH_E_INVALID, "prefill: %s GEMM %d x %d over %d tokens does not fit", what, rows, K, n);
+        mm_launch(a, ctx->n_cu, ctx->stream);
+        if (w_lo) {  // partials [ks, 2 ks): W_lo . X, summed after W_hi's by the epilogue
+            a.w = w_lo;
+            a.out = ctx->pf_part + (size_t)a.ks * n * rows;
+            mm_launch(a, ctx->n_cu, ctx->stream);
+        }
+        ks = images * a.ks;
+        return 0;
+    }
+    if (lay > 0) {
+        PfGemm16Args a{};
+        a.w = w; a.row_bytes = (size_t)K * (16 / lay); a.K = K; a.rows = rows;
+        a.xh = ctx->pf_xh; a.xl = ctx->pf_xl; a.inv_s = ctx->pf_xs; a.n = n; a.ks = pf_ks16(rows, K, lay);
+        a.part = ctx->pf_part;
+        switch (dt) {
+            case XH_F16: pf_gemm16_t<XH_F16>(a, ctx->stream); break;
+            case XH_F8_E4M3: pf_gemm16_t<XH_F8_E4M3>(a, ctx->stream); break;
+            default: pf_gemm16_t<XH_F8_E5M2>(a, ctx->stream); break;
+        }
+        ks = a.ks;
+        return 0;
+    }
+    const int E = pf_elems(dt);
+    if (K % (2 * E) || n > PF_TOK) return set_err(ctx, XH_E_INVALID, "prefill: %s shape not supported", what);
+    PfGemmArgs a{};
+    a.w = w; a.K = K; a.rows = rows; a.x = x; a.n = n; a.part = ctx->pf_part;
+    a.row_bytes = gq_dt(dt) ? gq_pitch(dt, K) : (size_t)K * (16 / E);
+    a.ks = pf_ks(rows, K, E);
+    if ((size_t)a.ks * rows > PF_PART_ROWS) return set_err(ctx, XH_E_INVALID, "prefill: %s shape not supported", what);
+    hipStream_t s = ctx->stream;
+    switch (dt) {
+        case XH_F32: pf_gemm_t<XH_F32>(a, s); break;
+        case XH_F16: pf_gemm_t<XH_F16>(a, s); break;
+        case XH_BF16: pf_gemm_t<XH_BF16>(a, s); break;
+        case XH_F8_E4M3: pf_gemm_t<XH_F8_E4M3>(a, s); break;
+        case XH_F8_E5M2: pf_gemm_t<XH_F8_E5M2>(a, s); break;
+        case XH_Q8: pf_gemm_t<XH_Q8>(a, s); break;
+        case XH_Q8_0: pf_gemm_t<XH_Q8_0>(a, s); break;
+        case XH_Q4_0: pf_gemm_t<XH_Q4_0>(a, s); break;
+        case XH_F8_E4M3_EXACT: pf_gemm_t<XH_F8_E4M3_EXACT>(a, s); break;
+        case XH_F8_E5M2_EXACT: pf_gemm_t<XH_F8_E5M2_EXACT>(a, s); break;
+        default: return set_err(ctx, XH_E_INVALID, "prefill: %s dtype %d not supported", what, dt);
+    }
+    ks = a.ks;
+    return 0;
+}
+void pf_epi(xh_ctx* ctx, PfEpiArgs e) {
+    e.part = ctx->pf_part;
+    e.part_s = ctx->pf_scaled ? ctx->pf_xs : nullptr;
+    const int threads = e.n * ((e.rows + 1) / 2);
+    hipLaunchKernelGGL(prefill_epi_kernel, dim3((threads + 255) / 256), dim3(256), 0, ctx->stream, e);
+}
+// x += the last GEMM's partials (EPI_RESID), then the rmsnorm of the updated rows as the input of
+// the GEMM over W (dt, [rows][dim]): one launch when that GEMM takes the split input and the
+// rows fit the LDS, else pf_epi + pf_norm (the same bits either way)
+int pf_resid_norm(xh_ctx* ctx, int ks, const void* nw, int ndt, int m, int dt, int rows) {
+    const xh_config& c = ctx->c;
+    const int lay = pf_layout(ctx, dt, c.dim, rows);
+    const size_t lds = (size_t)c.dim * sizeof(float);  // + the kernel's static red[4]
+    if (lay >= 0 && ctx->pf_resid_norm && c.dim % 8 == 0 && lds + 4 * sizeof(float) <= 64 * 1024) {
+        HIP_TRY(ctx, hipGetLastError());  // an earlier launch's error is reported as such
+        hipLaunchKernelGGL(prefill_resid_norm_split_kernel, dim3(pf_split_grid(lay, m)), dim3(256), lds, ctx->stream,
+                           (const float*)ctx->pf_part, ks, (const float*)(ctx->pf_scaled ? ctx->pf_xs : nullptr),
+                           ctx->pf_x, c.dim, nw, ndt, c.norm_eps, m, lay, ctx->pf_xh, pf_lo(ctx, lay, m, c.dim),
+                           ctx->pf_xs);
+        HIP_TRY(ctx, hipGetLastError());
+        ctx->pf_split_ready = true;
+        return 0;
+    }
+    PfEpiArgs e{};
+    e.ks = ks; e.n = m; e.rows = c.dim; e.epi = EPI_RESID; e.out = ctx->pf_x;
+    pf_epi(ctx, e);
+    pf_norm(ctx, nw, ndt, m, dt, rows);
+    return 0;
+}
+template <int HD, int QPK>
+void pf_attn_t(xh_ctx* ctx, const AttnArgs& a, int n) {
+    const size_t smem = attn_smem_bytes(HD, QPK, ctx->t_max, a.nsplit);
+    auto k = prefill_attn_kernel<HD, QPK>;
+    if (smem > 64 * 1024) ensure_lds((const void*)k);
+    hipLaunchKernelGGL(k, dim3(ctx->c.n_kv_heads, a.nsplit, n), dim3(ATTN_THREADS), smem, ctx->stream, a,
+                       (const StepParams*)ctx->pf_sp, ctx->q_dim, ctx->c.n_kv_heads);
+}
+// History splits of the shared-tile prompt attention: a pass whose (KV head, query tile)
+// workgroups cannot fill two per CU (a short pass: 8 workgroups for <= 32 tokens at 8 KV heads)
+// walks its history in up to that many splits of >= FA_MIN_SPLIT_STAGES ring stages each (the
+// split partials live in pf_part, free between the qkv epilogue and the Wo GEMM).
+constexpr int FA_MIN_SPLIT_STAGES = 4;
+int pf_fa_nsplit(const xh_ctx* ctx, int nqt, int n, int pos0) {
+    if (!ctx->pf_fa_split) return 1;
+    const int wg = ctx->c.n_kv_heads * nqt;
+    int ns = std::min((2 * ctx->n_cu + wg - 1) / wg, pos0 / (32 * FA_TPS) / FA_MIN_SPLIT_STAGES);
+    const size_t per = (size_t)n * (ctx->q_dim + 2 * ctx->c.n_heads);
+    ns = (int)std::min<size_t>((size_t)ns, pf_part_floats(ctx, ctx->pf_cap) / per);
+    return std::max(ns, 1);
+}
+template <int HD, int QPK>
+void pf_fa_t(xh_ctx* ctx, const AttnArgs& a, int n, int pos0) {
+    constexpr int TPW = 32 / QPK;
+    if constexpr (HD == 128) {
+        if (ctx->pf_attn_mode == 1) {
+            constexpr int NW = PF_FA_WAVES;
+            auto k = prefill_fa2_kernel<QPK, NW>;
+            ensure_lds((const void*)k);
+            const int nqt = (n + NW * TPW - 1) / (NW * TPW);
+            const int nsplit = pf_fa_nsplit(ctx, nqt, n, pos0);
+            float* po = nsplit > 1 ? ctx->pf_part : nullptr;
+            float2* pml = nsplit > 1 ? (float2*)(ctx->pf_part + (size_t)nsplit * n * ctx->q_dim) : nullptr;
+            hipLaunchKernelGGL(k, dim3(ctx->c.n_kv_heads, nqt, nsplit), dim3(64 * NW), fa_lds_bytes(), ctx->stream, a.q,
+                               a.kc, a.vc, a.out, n, pos0, ctx->q_dim, ctx->kv_dim, po, pml);
+            if (nsplit > 1)
+                hipLaunchKernelGGL(prefill_fa_merge_kernel, dim3(ctx->c.n_heads, n), dim3(256), 0, ctx->stream, (const float*)po,
+                                   (const float2*)pml, a.out, n, nsplit, ctx->q_dim);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((prefill_fa_kernel<HD, QPK>), dim3(ctx->c.n_kv_heads, (n + TPW - 1) / TPW), dim3(64), 0,
+                       ctx->stream, a.q, a.kc, a.vc, a.out, n, pos0, ctx->q_dim, ctx->kv_dim);
+}
+// head shapes of the batched path's attention: head_dim 128 / 64 with 1, 2, 4 or 8 q heads per KV
+// head (MHA through GQA), and the test fixtures' head_dim 16 x 2
+bool pf_attn_shape(int hd, int qpk) {
+    return ((hd == 128 || hd == 64) && (qpk == 1 || qpk == 2 || qpk == 4 || qpk == 8)) || (hd == 16 && qpk == 2);
+}
+template <int HD>
+bool pf_attn_hd(xh_ctx* ctx, const AttnArgs& a, int n, int pos0, int qpk) {
+    if (ctx->pf_attn_mode != 0) {
+        switch (qpk) {
+            case 1: pf_fa_t<HD, 1>(ctx, a, n, pos0); return true;
+            case 2: pf_fa_t<HD, 2>(ctx, a, n, pos0); return true;
+            case 4: pf_fa_t<HD, 4>(ctx, a, n, pos0); return true;
+            case 8: pf_fa_t<HD, 8>(ctx, a, n, pos0); return true;
+            default: return false;
+        }
+    }
+    switch (qpk) {
+        case 1: pf_attn_t<HD, 1>(ctx, a, n); return true;
+        case 2: pf_attn_t<HD, 2>(ctx, a, n); return true;
+        case 4: pf_attn_t<HD, 4>(ctx, a, n); return true;
+        case 8: pf_attn_t<HD, 8>(ctx, a, n); return true;
+        default: return false;
+    }
+}
+// 0, XH_E_INVALID for a head shape with no prompt attention, or the split buffers' allocation error
+int pf_attn(xh_ctx* ctx, const AttnArgs& a, int n, int pos0) {
+    const int hd = ctx->c.head_dim, qpk = ctx->qpk;
+    if (!pf_attn_shape(hd, qpk)) return set_err(ctx, XH_E_INVALID, "prefill: head shape not instantiated");
+    AttnArgs b = a;
+    if (ctx->pf_attn_mode == 0) {
+        const int rc = pf_alloc_split_attn(ctx);  // keeps dmalloc's code and message
+        if (rc) return rc;
+        b.part_o = ctx->pf_po; b.part_ml = ctx->pf_pml; b.counters = ctx->pf_cnt;
+    }
+    bool ok = true;
+    if (hd == 128) ok = pf_attn_hd<128>(ctx, b, n, pos0, qpk);
+    else if (hd == 64) ok = pf_attn_hd<64>(ctx, b, n, pos0, qpk);
+    else if (ctx->pf_attn_mode != 0) pf_fa_t<16, 2>(ctx, b, n, pos0);
+    else pf_attn_t<16, 2>(ctx, b, n);
+    return ok ? 0 : set_err(ctx, XH_E_INVALID, "prefill: head shape not instantiated");
+}
+
+// Whether the batched path covers this prompt (else the per-token loop): no ring wrap inside
+// the prompt, an instantiated head shape, K multiples of the chunk pair (always, for K % 32).
+bool pf_supported(const xh_ctx* ctx, int n, int pos0) {
+    const xh_config& c = ctx->c;
+    if (!ctx->prefill_batched || pos0 + n > c.max_seq_len) return false;
+    const int hd = c.head_dim, qpk = ctx->qpk;
+    if (!pf_attn_shape(hd, qpk)) return false;
+    // every GEMM's K in whole chunk pairs of its decoder (f32-input kernel; the others need less)
+    auto ok = [](int dt, int K) { return K % (2 * pf_elems(dt)) == 0; };
+    for (const LayerW& w : ctx->L)
+        if (!ok(w.qkv_dt, c.dim) || !ok(w.wo_dt, ctx->q_dim) || !ok(w.w13_dt, c.dim) || !ok(w.w2_dt, c.hidden_dim))
+            return false;
+    return ok(ctx->wcls_dt, c.dim) && c.dim % 32 == 0 && c.hidden_dim % 32 == 0 && ctx->q_dim % 32 == 0;
+}
+
+// tokens[0..n) at positions pos0..: HYDRATE for every token, then the last token's logits.
+// probs (device, n floats) != nullptr: also every token's logits (final rmsnorm + lm_head as
+// one GEMM per pass) and probs[i] = sample_prob(targets[i]) (targets: host, n ints).
+int prefill_batched(xh_ctx* ctx, const int* tokens, int n, int pos0, int want_logits, const int* targets = nullptr,
+                    float* probs = nullptr) {
+    const xh_config& c = ctx->c;
+    int rc = pf_prepare(ctx);
+    if (rc) return rc;
+    const int pass = ctx->pf_pass = pf_pass_tokens(ctx);
+    if ((rc = pf_alloc(ctx, std::min(pass, std::max(n, PF_TOK))))) return rc;
+    ctx->pf_split_ready = false;
+    if (probs && !ctx->pf_logits &&
+        ((rc = dmalloc(ctx, &ctx->pf_logits, (size_t)ctx->pf_cap * c.vocab_size)) ||
+         (rc = dmalloc(ctx, &ctx->pf_tgt, (size_t)ctx->pf_cap))))
+        return rc;
+    std::vector<StepParams> sps(pass);
+    for (int off = 0; off < n; off += pass) {
+        const int m = std::min(n - off, pass);
+        const int p0 = pos0 + off;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->pf_tok, tokens + off, (size_t)m * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        for (int t = 0; t < m; t++) {
+            StepParams& h = sps[t];
+            h = StepParams{};
+            h.token = tokens[off + t];
+            h.pos = p0 + t;
+            h.kv_sink = 0;
+            h.kv_pos = p0 + t;
+            h.kv_len = p0 + t + 1;
+            h.max_seq_len = c.max_seq_len;
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->pf_sp, sps.data(), (size_t)m * sizeof(StepParams), hipMemcpyHostToDevice,
+                                    ctx->stream));
+        hipLaunchKernelGGL(prefill_embed_kernel, dim3(m), dim3(256), 0, ctx->stream, (const int*)ctx->pf_tok,
+                           (const void*)ctx->embed, ctx->embed_dt, c.dim, ctx->pf_x);
+        for (int l = 0; l < c.n_layers; l++) {
+            const LayerW& w = ctx->L[l];
+            // attention block (src/infer.cpp:380-452)
+            const int qkv_rows = ctx->q_dim + 2 * ctx->kv_dim;
+            int ks = 0;
+            // layers after the first: the previous W2 residual and this rmsnorm ran as one launch
+            if (l == 0) pf_norm(ctx, w.attn_norm, w.an_dt, m, kdt(w.qkv_dt, w.qkv_x), qkv_rows);
+            if ((rc = pf_gemm(ctx, "qkv", kdt(w.qkv_dt, w.qkv_x), w.wqkv, c.dim, qkv_rows, ctx->pf_xn, m, ks))) return rc;
+            PfEpiArgs e{};
+            e.ks = ks; e.n = m; e.rows = qkv_rows; e.epi = EPI_QKV; e.q = ctx->pf_q;
+            e.kcache = ctx->kcache(l); e.vcache = ctx->vcache(l); e.q_dim = ctx->q_dim; e.kv_dim = ctx->kv_dim;
+            e.head_dim = c.head_dim; e.rope_freq = ctx->rope_freq; e.qkv_clip = c.qkv_clip; e.pos0 = p0; e.act = c.act;
+            pf_epi(ctx, e);
+            AttnArgs aa = attn_args(ctx, l);
+            aa.q = ctx->pf_q; aa.out = ctx->pf_att;
+            // splits for this pass's longest row (attn_block: >= ATTN_MIN_T slots per split)
+            aa.nsplit = std::min(ctx->nsplit, std::max(1, (p0 + m + ATTN_MIN_T - 1) / ATTN_MIN_T));
+            if ((rc = pf_attn(ctx, aa, m, p0))) return rc;
+            if ((rc = pf_gemm(ctx, "wo", kdt(w.wo_dt, w.wo_x), w.wo, ctx->q_dim, c.dim, ctx->pf_att, m, ks))) return rc;
+            // residual, then the feed-forward block's rmsnorm (src/infer.cpp:449-452, 455-494)
+            if ((rc = pf_resid_norm(ctx, ks, w.ffn_norm, w.fn_dt, m, kdt(w.w13_dt, w.w13_x), 2 * c.hidden_dim))) return rc;
+            if ((rc = pf_gemm(ctx, "w1/w3", kdt(w.w13_dt, w.w13_x), w.w13, c.dim, 2 * c.hidden_dim, ctx->pf_xn, m, ks)))
+                return rc;
+            const int lay2 = pf_layout(ctx, kdt(w.w2_dt, w.w2_x), c.hidden_dim, c.dim);
+            // dynamic LDS = one f32 row of h; the kernel adds a static 16-float reduction array
+            const size_t glu_lds = (size_t)c.hidden_dim * sizeof(float);
+            bool glu_fused = false;
+            if (lay2 >= 0 && ctx->pf_glu_split && glu_lds + 16 * sizeof(float) <= 64 * 1024) {
+                // GLU epilogue straight into the W2 GEMM's split-f16 input (one launch); the size
+                // check above is the launch's only precondition, so any error here is real.
+                // part_s and inv_s are both pf_xs: a workgroup reads its token's factor before
+                // the barrier and writes the new one after it.
+                HIP_TRY(ctx, hipGetLastError());  // an earlier launch's error is reported as such
+                hipLaunchKernelGGL(prefill_glu_split_kernel, dim3(pf_split_grid(lay2, m)), dim3(1024), glu_lds,
+                                   ctx->stream, (const float*)ctx->pf_part, ks, m, c.hidden_dim, c.act, lay2,
+                                   ctx->pf_xh, pf_lo(ctx, lay2, m, c.hidden_dim), ctx->pf_xs,
+                                   (const float*)(ctx->pf_scaled ? ctx->pf_xs : nullptr));
+                HIP_TRY(ctx, hipGetLastError());
+                glu_fused = true;
+                ctx->pf_split_ready = true;
+            }
+            if (!glu_fused) {
+                e = PfEpiArgs{};
+                e.ks = ks; e.n = m; e.rows = 2 * c.hidden_dim; e.epi = EPI_GLU; e.out = ctx->pf_h; e.act = c.act;
+                pf_epi(ctx, e);
+            }
+            if ((rc = pf_gemm(ctx, "w2", kdt(w.w2_dt, w.w2_x), w.w2, c.hidden_dim, c.dim, ctx->pf_h, m, ks))) return rc;
+            if (l + 1 < c.n_layers) {
+                // residual, then the next layer's attention rmsnorm (src/infer.cpp:491-494, 380)
+                const LayerW& wn = ctx->L[l + 1];
+                if ((rc = pf_resid_norm(ctx, ks, wn.attn_norm, wn.an_dt, m, kdt(wn.qkv_dt, wn.qkv_x), qkv_rows))) return rc;
+            } else {
+                e = PfEpiArgs{};
+                e.ks = ks; e.n = m; e.rows = c.dim; e.epi = EPI_RESID; e.out = ctx->pf_x;
+                pf_epi(ctx, e);
+            }
+        }
+        if (probs) {
+            // Model::forward's OUTPUT_LOGITS tail (src/infer.cpp:620-637) for every token of the
+            // pass, then Sampler::sample_prob of each token's target
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->pf_tgt, targets + off, (size_t)m * sizeof(int), hipMemcpyHostToDevice,
+                                        ctx->stream));
+            hipLaunchKernelGGL(prefill_rmsnorm_kernel, dim3(m), dim3(256), 0, ctx->stream, (const float*)ctx->pf_x, c.dim,
+                               (const void*)ctx->final_norm, ctx->final_norm_dt, c.norm_eps, ctx->pf_xn);
+            const size_t cls_rb = dev_row_bytes(ctx->wcls_dt, c.dim);
+            const int cls_dt = kdt(ctx->wcls_dt, ctx->wcls_x);
+            // lm_head weights off the hipBLASLt path (bf16 on the fp8 checkpoints): 64-token slices
+            const int tstep = pf_lay0(ctx, cls_dt, c.dim) ? m : PF_TOK;
+            for (int r0 = 0; r0 < c.vocab_size; r0 += PF_CLS_CHUNK) {
+                const int rows = std::min(PF_CLS_CHUNK, c.vocab_size - r0);
+                for (int t0 = 0; t0 < m; t0 += tstep) {
+                    const int mt = std::min(tstep, m - t0);
+                    int ks = 0;
+                    if ((rc = pf_gemm(ctx, "lm_head", cls_dt, (const char*)ctx->wcls + (size_t)r0 * cls_rb, c.dim, rows,
+                                      ctx->pf_xn + (size_t)t0 * c.dim, mt, ks)))
+                        return rc;
+                    PfEpiArgs e{};
+                    e.ks = ks; e.n = mt; e.rows = rows; e.epi = EPI_STORE;
+                    e.out = ctx->pf_logits + (size_t)t0 * c.vocab_size + r0;
+                    e.out_stride = (size_t)c.vocab_size;
+                    pf_epi(ctx, e);
+                }
+            }
+            hipLaunchKernelGGL(token_prob_kernel, dim3(m), dim3(1024), 0, ctx->stream, (const float*)ctx->pf_logits,
+                               c.vocab_size, (size_t)c.vocab_size, (const int*)ctx->pf_tgt, probs + off);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+        if (off + m == n) {
+            // the last token's residual stream is the decode path's x
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->x, ctx->pf_x + (size_t)(m - 1) * c.dim, (size_t)c.dim * 4,
+                                        hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // sps / token staging reused by the next pass
+    }
+    // step parameters of the last prompt token (as the per-token loop leaves them)
+    rc = host_step_params(ctx, tokens[n - 1], pos0 + n - 1);
+    if (rc) return rc;
+    if (want_logits) {
+        if (!launch_gemv(GEMV_LOGITS, kdt(ctx->wcls_dt, ctx->wcls_x), cls_args(ctx), ctx->stream, ctx->max_gemv_waves))
+            return set_err(ctx, XH_E_INVALID, "unsupported wcls dtype");
+        ctx->cand_valid = true;
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
+int xalm::mm_op_ks(int rows, int K, int n, int* ks) {
+    if (K % MM_KMULT) return 1;
+    if (*ks == 0) *ks = mm_pick_ks(rows, K, n, (size_t)8 * n * rows);
+    return *ks <= 0 || K % (*ks * MM_KMULT) ? 2 : 0;
+}
+void xalm::mm_op_launch(const uint16_t* w, const uint16_t* xh, const uint16_t* xl, float* out, int rows, int K, int n,
+                        int ks, int n_cu) {
+    MmArgs a{};
+    a.w = w; a.xh = xh; a.xl = xl; a.out = out;
+    a.rows = rows; a.K = K; a.n = n; a.ks = ks; a.n_rt = mm_row_tiles(rows); a.n_tt = mm_tok_tiles(n);
+    mm_launch(a, n_cu, nullptr);
+}
+
+extern "C" {
+
+int xh_prefill(xh_ctx* ctx, const int* tokens, int n, int pos0, int want_logits, float* logits_out) {
+    if (!ctx || !tokens || n <= 0 || pos0 < 0) return set_err(ctx, XH_E_INVALID, "bad prefill arguments");
+    for (int i = 0; i < n; i++)
+        if (tokens[i] < 0 || tokens[i] >= ctx->c.vocab_size) return set_err(ctx, XH_E_INVALID, "token out of range");
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    int rc = check_ready(ctx);
+    if (rc) return rc;
+    // a one-token prompt runs the decode step (one graph replay of the matvecs) rather than a
+    // pass of GEMMs over one token: 3.3 vs 7.3 ms at the end of a 32k ring (tools/short_pass.py)
+    if (n >= 2 && pf_supported(ctx, n, pos0)) {
+        rc = prefill_batched(ctx, tokens, n, pos0, want_logits);
+    } else {
+        for (int i = 0; i < n && !rc; i++) {
+            rc = host_step_params(ctx, tokens[i], pos0 + i);
+            if (!rc) rc = run_step(ctx, i == n - 1 && want_logits);
+            // the step parameters are copied from one pinned host slot: drain before reuse
+            if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess)
+                rc = set_err(ctx, XH_E_HIP, "hipStreamSynchronize failed");
+        }
+    }
+    if (rc) return rc;
+    if (logits_out && want_logits)
+        HIP_TRY(ctx, hipMemcpyAsync(logits_out, ctx->logits, (size_t)ctx->c.vocab_size * 4, hipMemcpyDeviceToHost,
+                                    ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return check_aw(ctx);
+}
+
+// The perplexity loop of run_perplexity (src/main.cpp:243-254): forward tokens[0..n-1) at
+// positions pos0.. with logits, probs_out[i] = Sampler::sample_prob(tokens[i + 1]) after token
+// i (src/sampler.cpp:3-17).  The logits never leave the device; batched passes where the
+// prompt path allows, else token by token.
+int xh_perplexity(xh_ctx* ctx, const int* tokens, int n, int pos0, float* probs_out) {
+    if (!ctx || !tokens || !probs_out || n < 2 || pos0 < 0) return set_err(ctx, XH_E_INVALID, "bad perplexity arguments");
+    for (int i = 0; i < n; i++)
+        if (tokens[i] < 0 || tokens[i] >= ctx->c.vocab_size) return set_err(ctx, XH_E_INVALID, "token out of range");
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    int rc = check_ready(ctx);
+    if (rc) return rc;
+    const int m = n - 1, V = ctx->c.vocab_size;
+    if (ctx->ppl_cap < m) {
+        hipFree(ctx->ppl_tgt); hipFree(ctx->ppl_prob);
+        ctx->ppl_tgt = nullptr; ctx->ppl_prob = nullptr; ctx->ppl_cap = 0;
+        if ((rc = dmalloc(ctx, &ctx->ppl_tgt, (size_t)m)) || (rc = dmalloc(ctx, &ctx->ppl_prob, (size_t)m))) return rc;
+        ctx->ppl_cap = m;
+    }
+    if (pf_supported(ctx, m, pos0)) {
+        rc = prefill_batched(ctx, tokens, m, pos0, 0, tokens + 1, ctx->ppl_prob);
+    } else {
+        HIP_TRY(ctx, copy_sync(ctx, ctx->ppl_tgt, tokens + 1, (size_t)m * sizeof(int), hipMemcpyHostToDevice));
+        for (int i = 0; i < m && !rc; i++) {
+            rc = host_step_params(ctx, tokens[i], pos0 + i);
+            if (!rc) rc = run_step(ctx, true);
+            if (rc) break;
+            hipLaunchKernelGGL(token_prob_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const float*)ctx->logits, V,
+                               (size_t)V, (const int*)ctx->ppl_tgt + i, ctx->ppl_prob + i);
+            // the step parameters are copied from one pinned host slot: drain before reuse
+            if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = set_err(ctx, XH_E_HIP, "hipStreamSynchronize failed");
+        }
+    }
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(probs_out, ctx->ppl_prob, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return check_aw(ctx);
+}
+}  // extern "C"

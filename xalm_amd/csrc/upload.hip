@@ -1,0 +1,349 @@
+// upload.hip — weights and KV rows onto the device: the device layout of each tensor, host,
+// file and synthetic uploads, the fp8 special-code scan (xh_upload*, xh_kv_*).
+#include <hip/hip_runtime.h>
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <cerrno>
+#include <cstring>
+#include <thread>
+#include <vector>
+
+#include "../../include/xalm_synth.h"
+#include "ctx.h"
+
+using namespace xalm;
+
+namespace {
+
+// Destination of one logical tensor [rows][cols] inside the device layout: the buffer
+// (allocated on first use), the byte offset of row 0 and the byte pitch between rows.
+struct Slot {
+    char* base = nullptr;
+    size_t pitch = 0;
+    size_t rows = 0, cols = 0;
+};
+
+int tensor_slot(xh_ctx* ctx, int kind, int layer, int dtype, Slot* out) {
+    const xh_config& c = ctx->c;
+    const bool per_layer = !(kind == XH_EMBED || kind == XH_FINAL_NORM || kind == XH_WCLS);
+    if (per_layer && (layer < 0 || layer >= c.n_layers))
+        return set_err(ctx, XH_E_INVALID, "layer %d out of range", layer);
+    size_t rows = 0, cols = 0;
+    bool is_norm = false;
+    switch (kind) {
+        case XH_EMBED: case XH_WCLS: rows = c.vocab_size; cols = c.dim; break;
+        case XH_ATTN_NORM: case XH_FFN_NORM: case XH_FINAL_NORM: rows = 1; cols = c.dim; is_norm = true; break;
+        case XH_WQ: rows = ctx->q_dim; cols = c.dim; break;
+        case XH_WK: case XH_WV: rows = ctx->kv_dim; cols = c.dim; break;
+        case XH_WO: rows = c.dim; cols = ctx->q_dim; break;
+        case XH_W1: case XH_W3: rows = c.hidden_dim; cols = c.dim; break;
+        case XH_W2: rows = c.dim; cols = c.hidden_dim; break;
+        default: return set_err(ctx, XH_E_INVALID, "unknown tensor kind %d", kind);
+    }
+    if (is_norm ? !(dtype == XH_F32 || dtype == XH_BF16) : !matrix_dtype_ok(dtype))
+        return set_err(ctx, XH_E_INVALID, "tensor kind %d: unsupported dtype %d", kind, dtype);
+    if (gq_dt(dtype) && cols % 32) return set_err(ctx, XH_E_INVALID, "tensor kind %d: %zu columns, not whole 32-element blocks", kind, cols);
+    const size_t rb = dev_row_bytes(dtype, cols);
+    out->rows = rows;
+    out->cols = cols;
+    out->pitch = rb;
+    drop_graphs(ctx);
+    auto plain = [&](void** dst, int* dst_dt, bool* special = nullptr) -> int {
+        if (special) *special = false;  // a whole-buffer upload: rescanned after the copy
+        if (*dst && *dst_dt != dtype) {
+            if (*dst == ctx->wcls && *dst != ctx->embed) ctx->wcls = nullptr;
+            hipFree(*dst);
+            *dst = nullptr;
+        }
+        if (!*dst) HIP_TRY(ctx, hipMalloc(dst, rows * rb));
+        *dst_dt = dtype;
+        out->base = (char*)*dst;
+        return 0;
+    };
+    if (kind == XH_EMBED) {
+        const bool alias = ctx->wcls != nullptr && ctx->wcls == ctx->embed;
+        if (alias) ctx->wcls = nullptr;
+        int rc = plain(&ctx->embed, &ctx->embed_dt);
+        if (alias) { ctx->wcls = ctx->embed; ctx->wcls_dt = ctx->embed_dt; }
+        return rc;
+    }
+    if (kind == XH_FINAL_NORM) return plain(&ctx->final_norm, &ctx->final_norm_dt);
+    if (kind == XH_WCLS) {
+        if (ctx->wcls == ctx->embed) ctx->wcls = nullptr;
+        return plain(&ctx->wcls, &ctx->wcls_dt, &ctx->wcls_x);
+    }
+    LayerW& w = ctx->L[layer];
+    switch (kind) {
+        case XH_ATTN_NORM: return plain(&w.attn_norm, &w.an_dt);
+        case XH_FFN_NORM: return plain(&w.ffn_norm, &w.fn_dt);
+        case XH_WO: return plain(&w.wo, &w.wo_dt, &w.wo_x);
+        case XH_W2: return plain(&w.w2, &w.w2_dt, &w.w2_x);
+        case XH_WQ: case XH_WK: case XH_WV: {
+            // fused [Wq; Wk; Wv] rows, one dtype
+            if (w.wqkv && w.qkv_dt != dtype) {
+                if (w.qkv_have & ~(1u << (kind - XH_WQ)))
+                    return set_err(ctx, XH_E_INVALID, "layer %d: q/k/v must share one dtype", layer);
+                hipFree(w.wqkv); w.wqkv = nullptr; w.qkv_have = 0;
+            }
+            if (!(w.qkv_have & ~(1u << (kind - XH_WQ)))) w.qkv_x = false;  // no other part holds codes
+            if (!w.wqkv) HIP_TRY(ctx, hipMalloc(&w.wqkv, (size_t)(ctx->q_dim + 2 * ctx->kv_dim) * rb));
+            w.qkv_dt = dtype;
+            const size_t row0 = kind == XH_WQ ? 0 : kind == XH_WK ? ctx->q_dim : ctx->q_dim + ctx->kv_dim;
+            out->base = (char*)w.wqkv + row0 * rb;
+            w.qkv_have |= 1u << (kind - XH_WQ);
+            return 0;
+        }
+        case XH_W1: case XH_W3: {
+            // fused gate/up, rows interleaved: row 2i = W1[i], row 2i+1 = W3[i]
+            const unsigned bit = kind == XH_W1 ? 1u : 2u;
+            if (w.w13 && w.w13_dt != dtype) {
+                if (w.w13_have & ~bit) return set_err(ctx, XH_E_INVALID, "layer %d: w1/w3 must share one dtype", layer);
+                hipFree(w.w13); w.w13 = nullptr; w.w13_have = 0;
+            }
+            if (!(w.w13_have & ~bit)) w.w13_x = false;
+            if (!w.w13) HIP_TRY(ctx, hipMalloc(&w.w13, (size_t)2 * c.hidden_dim * rb));
+            w.w13_dt = dtype;
+            out->base = (char*)w.w13 + (kind == XH_W3 ? rb : 0);
+            out->pitch = 2 * rb;
+            w.w13_have |= bit;
+            return 0;
+        }
+    }
+    return set_err(ctx, XH_E_INVALID, "unhandled kind");
+}
+
+// any NaN/Inf fp8 code (f8_special) in a [rows][cols] byte matrix of row pitch `pitch`
+__global__ void f8_special_scan_kernel(const uint8_t* base, size_t pitch, size_t rows, size_t cols, int e5m2, int* flag) {
+    int hit = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows * cols; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / cols;
+        hit |= f8_special(base[r * pitch + (i - r * cols)], e5m2 != 0);
+    }
+    if (hit) *flag = 1;
+}
+
+// after an upload into slot s: record whether the fp8 matrix holds NaN/Inf codes
+int scan_f8(xh_ctx* ctx, int kind, int layer, int dtype, const Slot& s) {
+    if (dtype != XH_F8_E4M3 && dtype != XH_F8_E5M2) return 0;
+    if (kind == XH_EMBED || kind == XH_ATTN_NORM || kind == XH_FFN_NORM || kind == XH_FINAL_NORM) return 0;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->scan_flag, 0, sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(f8_special_scan_kernel, dim3(2048), dim3(256), 0, ctx->stream, (const uint8_t*)s.base, s.pitch,
+                       s.rows, s.cols, (int)(dtype == XH_F8_E5M2), ctx->scan_flag);
+    int hit = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&hit, ctx->scan_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (!hit) return 0;
+    drop_graphs(ctx);
+    if (kind == XH_WCLS) { ctx->wcls_x = true; return 0; }
+    LayerW& w = ctx->L[layer];
+    switch (kind) {
+        case XH_WQ: case XH_WK: case XH_WV: w.qkv_x = true; break;
+        case XH_W1: case XH_W3: w.w13_x = true; break;
+        case XH_WO: w.wo_x = true; break;
+        case XH_W2: w.w2_x = true; break;
+    }
+    return 0;
+}
+
+__global__ void synth_fill_kernel(char* base, size_t pitch, size_t rows, size_t cols, int dtype, uint64_t seed,
+                                  float mean, float std) {
+    const size_t n = rows * cols;
+    const size_t esz = dtype == XH_F32 ? 4 : (dtype == XH_F16 || dtype == XH_BF16) ? 2 : 1;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / cols, cidx = i - r * cols;
+        xs_store(base + r * pitch, cidx, dtype, xs_value(seed, i, mean, std));
+        (void)esz;
+    }
+}
+
+}  // namespace
+
+// gguf blocks: file layout ([rows][cols/32 blocks: f16 d, codes]) -> planar device rows
+// ([codes][d per block][zero pad], pitch gq_pitch), on the host, split over threads
+void xalm::gq_repack(int dt, const uint8_t* src, size_t rows, size_t cols, uint8_t* dst) {
+    const size_t nb = cols / 32, bs = gq_block_bytes(dt), qb = bs - 2;
+    const size_t pitch = gq_pitch(dt, cols), qbytes = gq_qbytes(dt, cols);
+    auto part = [&](size_t r0, size_t r1) {
+        for (size_t r = r0; r < r1; r++) {
+            const uint8_t* in = src + r * nb * bs;
+            uint8_t* out = dst + r * pitch;
+            for (size_t b = 0; b < nb; b++) {
+                memcpy(out + b * qb, in + b * bs + 2, qb);
+                memcpy(out + qbytes + 2 * b, in + b * bs, 2);
+            }
+            memset(out + qbytes + 2 * nb, 0, pitch - qbytes - 2 * nb);
+        }
+    };
+    const size_t nt = std::min<size_t>(16, std::max<size_t>(1, rows / 256));
+    std::vector<std::thread> th;
+    for (size_t t = 1; t < nt; t++) th.emplace_back(part, rows * t / nt, rows * (t + 1) / nt);
+    part(0, rows / nt);
+    for (auto& x : th) x.join();
+}
+
+namespace {
+
+// synthetic gguf blocks: one thread per block, the values and quantizer of xalm_synth.h
+// (xs_block: the oracle's bytes exactly), written straight into the planar rows of the slot
+__global__ void synth_gq_kernel(char* base, size_t pitch, size_t rows, size_t cols, int dtype, uint64_t seed, float mean,
+                                float std) {
+    const size_t nb = cols / 32, qb = gq_block_bytes(dtype) - 2, qbytes = gq_qbytes(dtype, cols);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows * nb; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / nb, b = i - r * nb;
+        uint8_t blk[34];
+        xs_block(blk, dtype, seed, r, cols, b, mean, std);
+        char* row = base + r * pitch;
+        for (size_t k = 0; k < qb; k++) row[b * qb + k] = (char)blk[2 + k];
+        row[qbytes + 2 * b] = (char)blk[0];
+        row[qbytes + 2 * b + 1] = (char)blk[1];
+    }
+}
+
+// the byte count of a tensor upload against the config (load_tensor's checks,
+// src/model.cpp:62-76), before the device layout is touched
+int check_bytes(xh_ctx* ctx, int kind, int dtype, size_t bytes) {
+    const xh_config& c = ctx->c;
+    size_t rows = 0, cols = 0;
+    switch (kind) {
+        case XH_EMBED: case XH_WCLS: rows = c.vocab_size; cols = c.dim; break;
+        case XH_ATTN_NORM: case XH_FFN_NORM: case XH_FINAL_NORM: rows = 1; cols = c.dim; break;
+        case XH_WQ: rows = ctx->q_dim; cols = c.dim; break;
+        case XH_WK: case XH_WV: rows = ctx->kv_dim; cols = c.dim; break;
+        case XH_WO: rows = c.dim; cols = ctx->q_dim; break;
+        case XH_W1: case XH_W3: rows = c.hidden_dim; cols = c.dim; break;
+        case XH_W2: rows = c.dim; cols = c.hidden_dim; break;
+        default: return set_err(ctx, XH_E_INVALID, "unknown tensor kind %d", kind);
+    }
+    const size_t rb = file_row_bytes(dtype, cols);
+    if (rb == 0 || (gq_dt(dtype) && cols % 32) || bytes != rows * rb)
+        return set_err(ctx, XH_E_INVALID, "tensor kind %d: %zu bytes, expected %zu ([%zu,%zu] of dtype %d)", kind,
+                       bytes, rows * rb, rows, cols, dtype);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int xh_upload(xh_ctx* ctx, int kind, int layer, int dtype, const void* host, size_t bytes) {
+    if (!ctx || !host) return set_err(ctx, XH_E_INVALID, "null argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    Slot s;
+    int rc = check_bytes(ctx, kind, dtype, bytes);
+    if (!rc) rc = tensor_slot(ctx, kind, layer, dtype, &s);
+    if (rc) return rc;
+    if (gq_dt(dtype)) {
+        const size_t rb = dev_row_bytes(dtype, s.cols);
+        std::vector<uint8_t> tmp(s.rows * rb);
+        gq_repack(dtype, (const uint8_t*)host, s.rows, s.cols, tmp.data());
+        HIP_TRY(ctx, copy2d_sync(ctx, s.base, s.pitch, tmp.data(), rb, rb, s.rows));
+        return 0;
+    }
+    HIP_TRY(ctx, copy2d_sync(ctx, s.base, s.pitch, host, s.cols * dtype_size(dtype), s.cols * dtype_size(dtype),
+                                 s.rows));
+    return scan_f8(ctx, kind, layer, dtype, s);
+}
+
+// Tensor bytes straight from a file (the .xalm layout: tensor data at an absolute, 32-B
+// aligned offset, convert.py:248-321) into the device slot.  The range is mapped with
+// MAP_POPULATE (read ahead in one pass), registered with the runtime for the duration of
+// the copy and moved by one DMA: no host copy of the tensor.  Measured on MI355X with the
+// file in the page cache (tools/load_bench.py): 45 GB/s, against 16 GB/s for pread into
+// two pinned staging buffers and 33 GB/s for a pageable copy of the mapping.
+int xh_upload_file(xh_ctx* ctx, int kind, int layer, int dtype, const char* path, uint64_t offset, size_t bytes) {
+    if (!ctx || !path) return set_err(ctx, XH_E_INVALID, "null argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    int rc = check_bytes(ctx, kind, dtype, bytes);
+    if (rc) return rc;
+    const int fd = open(path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) return set_err(ctx, XH_E_INVALID, "%s: %s", path, strerror(errno));
+    struct stat st;
+    if (fstat(fd, &st) != 0 || offset > (uint64_t)st.st_size || bytes > (uint64_t)st.st_size - offset) {
+        close(fd);
+        return set_err(ctx, XH_E_INVALID, "%s: %zu bytes at offset %llu run past the end of the file", path, bytes,
+                       (unsigned long long)offset);
+    }
+    const uint64_t a0 = offset & ~(uint64_t)(sysconf(_SC_PAGESIZE) - 1);
+    const size_t len = bytes + (size_t)(offset - a0);
+    void* map = mmap(nullptr, len, PROT_READ, MAP_SHARED | MAP_POPULATE, fd, (off_t)a0);
+    const int map_errno = errno;
+    close(fd);
+    if (map == MAP_FAILED) return set_err(ctx, XH_E_INVALID, "%s: mmap: %s", path, strerror(map_errno));
+    Slot s;
+    rc = tensor_slot(ctx, kind, layer, dtype, &s);
+    if (!rc && gq_dt(dtype)) {
+        // gguf blocks: repacked on the host from the mapping (planar device rows)
+        const size_t rb = dev_row_bytes(dtype, s.cols);
+        std::vector<uint8_t> tmp(s.rows * rb);
+        gq_repack(dtype, (const uint8_t*)map + (offset - a0), s.rows, s.cols, tmp.data());
+        const hipError_t e = copy2d_sync(ctx, s.base, s.pitch, tmp.data(), rb, rb, s.rows);
+        if (e != hipSuccess) rc = set_err(ctx, XH_E_HIP, "%s: copy to the device: %s", path, hipGetErrorString(e));
+    } else if (!rc) {
+        const size_t row_bytes = s.cols * dtype_size(dtype);
+        // unregistered (e.g. a mapping the driver cannot pin) the same copy runs pageable
+        const bool reg = hipHostRegister(map, len, hipHostRegisterReadOnly) == hipSuccess;
+        const hipError_t e = copy2d_sync(ctx, s.base, s.pitch, (const char*)map + (offset - a0), row_bytes,
+                                         row_bytes, s.rows);
+        if (reg) hipHostUnregister(map);
+        if (e != hipSuccess) rc = set_err(ctx, XH_E_HIP, "%s: copy to the device: %s", path, hipGetErrorString(e));
+    }
+    munmap(map, len);
+    return rc ? rc : scan_f8(ctx, kind, layer, dtype, s);
+}
+
+int xh_upload_synthetic(xh_ctx* ctx, int kind, int layer, int dtype, uint64_t seed, float mean, float std) {
+    if (!ctx) return XH_E_INVALID;
+    if (dtype == XH_Q8) return set_err(ctx, XH_E_INVALID, "no synthetic Q8");
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    Slot s;
+    int rc = tensor_slot(ctx, kind, layer, dtype, &s);
+    if (rc) return rc;
+    if (gq_dt(dtype))
+        hipLaunchKernelGGL(synth_gq_kernel, dim3(4096), dim3(256), 0, ctx->stream, s.base, s.pitch, s.rows, s.cols, dtype,
+                           seed, mean, std);
+    else
+        hipLaunchKernelGGL(synth_fill_kernel, dim3(4096), dim3(256), 0, ctx->stream, s.base, s.pitch, s.rows, s.cols,
+                           dtype, seed, mean, std);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return scan_f8(ctx, kind, layer, dtype, s);
+}
+
+int xh_kv_fill_synthetic(xh_ctx* ctx, int layer, int which, int slot0, int n_slots, uint64_t seed, float std) {
+    if (!ctx || layer < 0 || layer >= ctx->c.n_layers || (which != 0 && which != 1) || slot0 < 0 || n_slots < 0 ||
+        slot0 + n_slots > ctx->c.max_seq_len)
+        return set_err(ctx, XH_E_INVALID, "bad kv_fill_synthetic arguments");
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    char* base = (char*)((which ? ctx->vcache(layer) : ctx->kcache(layer)) + (size_t)slot0 * ctx->kv_dim);
+    hipLaunchKernelGGL(synth_fill_kernel, dim3(2048), dim3(256), 0, ctx->stream, base, (size_t)ctx->kv_dim * 2,
+                       (size_t)n_slots, (size_t)ctx->kv_dim, (int)XH_F16, seed, 0.0f, std);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int xh_kv_write(xh_ctx* ctx, int layer, int which, int slot0, int n_slots, const uint16_t* host) {
+    if (!ctx || !host || layer < 0 || layer >= ctx->c.n_layers || (which != 0 && which != 1) || slot0 < 0 ||
+        n_slots < 0 || slot0 + n_slots > ctx->c.max_seq_len)
+        return set_err(ctx, XH_E_INVALID, "bad kv_write arguments");
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    uint16_t* base = (which ? ctx->vcache(layer) : ctx->kcache(layer)) + (size_t)slot0 * ctx->kv_dim;
+    HIP_TRY(ctx, copy_sync(ctx, base, host, (size_t)n_slots * ctx->kv_dim * 2, hipMemcpyHostToDevice));
+    return 0;
+}
+
+int xh_kv_read(xh_ctx* ctx, int layer, int which, int slot0, int n_slots, uint16_t* host) {
+    if (!ctx || !host || layer < 0 || layer >= ctx->c.n_layers || (which != 0 && which != 1) || slot0 < 0 ||
+        n_slots < 0 || slot0 + n_slots > ctx->c.max_seq_len)
+        return set_err(ctx, XH_E_INVALID, "bad kv_read arguments");
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const uint16_t* base = (which ? ctx->vcache(layer) : ctx->kcache(layer)) + (size_t)slot0 * ctx->kv_dim;
+    HIP_TRY(ctx, copy_sync(ctx, host, base, (size_t)n_slots * ctx->kv_dim * 2, hipMemcpyDeviceToHost));
+    return 0;
+}
+}  // extern "C"
