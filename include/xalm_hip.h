@@ -43,9 +43,20 @@ enum xh_dtype {
      * int8, value d*q.  Q4_0 (quants.py:281-311): 18 B = d + 16 bytes, byte j holding element
      * j (low nibble) and j+16 (high nibble), value d*(nibble-8).  Tensors are uploaded in that
      * file layout ([rows][cols/32 blocks], header shape = bytes per row); the reference C++
-     * runtime cannot parse them (src/types.h:468-499), so the ids are this build's. */
+     * runtime cannot parse them (src/types.h:468-499), so the ids are this build's.
+     * The affine and 5-bit blocks (`--type q4_1 / q5_0 / q5_1`), nibbles as Q4_0, bit j of the
+     * little-endian u32 qh the fifth bit of element j, every value ONE f32 rounding
+     * fmaf(d, q, m) (quants.py evaluates (d*q) + m in float32 and d*q is exact):
+     *   Q4_1 (quants.py:316-350): 20 B = d, f16 m, 16 bytes;          value d*q + m, q = 0..15
+     *   Q5_0 (quants.py:353-393): 22 B = d, u32 qh, 16 bytes;         value d*(q-16), q = 0..31
+     *   Q5_1 (quants.py:396-438): 24 B = d, f16 m, u32 qh, 16 bytes;  value d*q + m, q = 0..31
+     * XH_OPT_FUSE_ATTN_WO 1: the fused attention + Wo kernel has no block instantiation; a
+     * layer whose Wo is any of the five block types takes the two-launch route. */
     XH_Q8_0 = 20,
-    XH_Q4_0 = 21
+    XH_Q4_0 = 21,
+    XH_Q4_1 = 22,
+    XH_Q5_0 = 23,
+    XH_Q5_1 = 24
 };
 
 /* ---- tensor kinds (names as in .xalm, src/model.cpp:83-114) ------------------------ */
@@ -123,6 +134,11 @@ int xh_upload_file(xh_ctx* ctx, int tensor_kind, int layer, int dtype, const cha
  * tensor = xs_value(seed, i, mean, std) rounded to `dtype`).  The CPU baseline builds the
  * bit-identical host copy from the same header.  Q8 is not supported. */
 int xh_upload_synthetic(xh_ctx* ctx, int tensor_kind, int layer, int dtype, uint64_t seed, float mean, float std);
+/* The converter's block quantizer on the host (no context, no device): n_blocks * 32 floats ->
+ * n_blocks blocks of `dtype` (any of the five XH_Q*_* block types) in the file layout, the bytes
+ * quants.py `quantize` writes.  It is the quantizer of the synthetic weights
+ * (include/xalm_synth.h).  XH_E_INVALID for another dtype or a null pointer. */
+int xh_quantize_blocks(int dtype, const float* values, size_t n_blocks, void* out);
 /* Fill KV ring rows [slot0, slot0+n_slots) of one layer with synthetic fp16 N(0, std)-like values. */
 int xh_kv_fill_synthetic(xh_ctx* ctx, int layer, int which, int slot0, int n_slots, uint64_t seed, float std);
 
@@ -185,7 +201,11 @@ int xh_set_graphs(xh_ctx* ctx, int enable);
  * GEMM (gemm16.h) in passes of up to PF_TOK_MM = 2048 tokens (fp8 matrices through their exact f16 image),
  * activations as exact f16 hi + lo pairs under a power-of-two row scale (|x - (hi + lo) / s| <=
  * 2^-22 |x|, a 22-bit mantissa where the reference's f32 has 24), products exact, f32
- * accumulation in an order fixed by the tiling (the same bits on every run); other weight dtypes
+ * accumulation in an order fixed by the tiling (the same bits on every run); Q8_0 / Q4_0 / Q5_0
+ * blocks likewise through their exact f16 hi + lo images (d*q has at most 19 significant bits);
+ * the affine blocks Q4_1 / Q5_1, whose fmaf(d, q, m) is a general f32 with no exact f16 pair, take
+ * the f32-input MFMA kernel under every value >= 1 (lm_head of xh_perplexity included), as bf16
+ * and f32 weights do; other weight dtypes
  * on the f32-input MFMA kernel (activations exactly as the reference) in passes of 64 tokens;
  * 2 = the split-f16 register-streaming MFMA kernel wherever the weights convert exactly to f16
  * (f16, fp8), passes of 64 tokens; 3 = f32-input MFMA only; 4 = as 1 with vendor hipBLASLt in place

@@ -134,12 +134,98 @@ XS_FN void xs_quant_q4_0(const float* v, uint8_t* out) {
     out[1] = (uint8_t)(dh >> 8);
     for (int j = 0; j < 16; j++) out[2 + j] = (uint8_t)(q[j] | (q[j + 16] << 4));
 }
+/* ---- affine and 5-bit blocks (XH_Q4_1 / XH_Q5_0 / XH_Q5_1; quants.py Q4_1 :316-335, Q5_0
+ * :353-374, Q5_1 :396-417).  numpy rounds `(v - min) * id` to float32 before it adds 0.5: the
+ * product is formed in double (exact: 24 x 24 bits) and rounded once, and the sum likewise (a
+ * double sum of two floats rounds to float as the float sum does), so no compiler can contract
+ * the two into one fma. */
+XS_FN float xs_mul_add_half(float a, float b) {
+    const float p = (float)((double)a * (double)b);
+    return (float)((double)p + 0.5);
+}
+XS_FN void xs_put_f16(uint8_t* out, float v) {
+    const uint16_t h = xs_to_f16(v);
+    out[0] = (uint8_t)(h & 0xFFu);
+    out[1] = (uint8_t)(h >> 8);
+}
+/* codes q[32] (0..31) -> 16 bytes of nibbles (byte j = q[j] & 15 | q[j+16] << 4) and, when
+ * qh != NULL, the 4 little-endian bytes of the fifth bits (bit j = q[j] >> 4) */
+XS_FN void xs_pack_codes(const uint8_t* q, uint8_t* qh, uint8_t* qs) {
+    for (int j = 0; j < 16; j++) qs[j] = (uint8_t)((q[j] & 15u) | ((q[j + 16] & 15u) << 4));
+    if (qh) {
+        uint32_t h = 0;
+        for (int j = 0; j < 32; j++) h |= (uint32_t)(q[j] >> 4) << j;
+        for (int k = 0; k < 4; k++) qh[k] = (uint8_t)(h >> (8 * k));
+    }
+}
+/* min / max form, `levels` = 15 (Q4_1) or 31 (Q5_1): d = (max - min) / levels, m = min,
+ * q = trunc((v - min) * id + 0.5) in float32, id = 0 when d == 0 */
+XS_FN void xs_quant_affine(const float* v, int levels, float* d_out, float* m_out, uint8_t* q) {
+    float mx = v[0], mn = v[0];
+    for (int k = 1; k < 32; k++) { mx = fmaxf(mx, v[k]); mn = fminf(mn, v[k]); }
+    const float d = (mx - mn) / (float)levels;
+    const float id = d == 0.0f ? 0.0f : 1.0f / d;
+    for (int k = 0; k < 32; k++) {
+        const float t = truncf(xs_mul_add_half(v[k] - mn, id));
+        q[k] = (uint8_t)(t < 0.0f ? 0.0f : (t > (float)levels ? (float)levels : t));
+    }
+    *d_out = d;
+    *m_out = mn;
+}
+/* out: 20 bytes, f16 d, f16 m, 16 bytes of nibbles; value d*q + m */
+XS_FN void xs_quant_q4_1(const float* v, uint8_t* out) {
+    float d, m;
+    uint8_t q[32];
+    xs_quant_affine(v, 15, &d, &m, q);
+    xs_put_f16(out, d);
+    xs_put_f16(out + 2, m);
+    xs_pack_codes(q, (uint8_t*)0, out + 4);
+}
+/* out: 22 bytes, f16 d, u32 qh (little endian), 16 bytes of nibbles; value d*(q - 16).
+ * `trunc(float64(x) * float64(id) + 16.5)` cast to float32, as Q4_0's 8.5 */
+XS_FN void xs_quant_q5_0(const float* v, uint8_t* out) {
+    int imax = 0;
+    float amax = fabsf(v[0]);
+    for (int k = 1; k < 32; k++)
+        if (fabsf(v[k]) > amax) { amax = fabsf(v[k]); imax = k; }  /* argmax: the first maximum */
+    const float d = v[imax] / -16.0f;
+    const float id = d == 0.0f ? 0.0f : 1.0f / d;
+    uint8_t q[32];
+    for (int k = 0; k < 32; k++) {
+        const float t = truncf((float)((double)v[k] * (double)id + 16.5));
+        q[k] = (uint8_t)(t < 0.0f ? 0.0f : (t > 31.0f ? 31.0f : t));
+    }
+    xs_put_f16(out, d);
+    xs_pack_codes(q, out + 2, out + 6);
+}
+/* out: 24 bytes, f16 d, f16 m, u32 qh, 16 bytes of nibbles; value d*q + m, q = 0..31 */
+XS_FN void xs_quant_q5_1(const float* v, uint8_t* out) {
+    float d, m;
+    uint8_t q[32];
+    xs_quant_affine(v, 31, &d, &m, q);
+    xs_put_f16(out, d);
+    xs_put_f16(out + 2, m);
+    xs_pack_codes(q, out + 4, out + 8);
+}
+/* one block of `dtype` (20 Q8_0, 21 Q4_0, 22 Q4_1, 23 Q5_0, 24 Q5_1) from 32 floats; returns the
+ * block's bytes, 0 for another dtype */
+XS_FN int xs_quant_block(int dtype, const float* v, uint8_t* out) {
+    switch (dtype) {
+        case 20: xs_quant_q8_0(v, out); return 34;
+        case 21: xs_quant_q4_0(v, out); return 18;
+        case 22: xs_quant_q4_1(v, out); return 20;
+        case 23: xs_quant_q5_0(v, out); return 22;
+        case 24: xs_quant_q5_1(v, out); return 24;
+        default: return 0;
+    }
+}
 /* synthetic block b of row r of a [rows][cols] tensor: the 32 values xs_value gives elements
- * r*cols + 32b .. +31, quantized (dtype 20 Q8_0 / 21 Q4_0) */
+ * r*cols + 32b .. +31, quantized (dtype 20 Q8_0 / 21 Q4_0 / 22 Q4_1 / 23 Q5_0 / 24 Q5_1) */
 XS_FN void xs_block(uint8_t* out, int dtype, uint64_t seed, uint64_t r, uint64_t cols, uint64_t b, float mean, float std) {
     float v[32];
     for (int k = 0; k < 32; k++) v[k] = xs_value(seed, r * cols + 32 * b + k, mean, std);
     if (dtype == 20) xs_quant_q8_0(v, out);
+    else if (dtype >= 22 && dtype <= 24) xs_quant_block(dtype, v, out);
     else xs_quant_q4_0(v, out);
 }
 

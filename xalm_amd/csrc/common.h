@@ -142,15 +142,54 @@ template <> struct WDec<XH_Q8> {
 // so a 16-B load is 16 int8 (Q8_0, half a block) or 32 nibbles (Q4_0, one block) and the
 // scales of a wave's chunks are one coalesced read.  WDec decodes the codes (q, q - 8); the
 // matvec multiplies each chunk's partial dot product by its block's d.
-__host__ __device__ constexpr bool gq_dt(const int dt) { return dt == XH_Q8_0 || dt == XH_Q4_0; }
+//
+// The affine and 5-bit blocks (XH_Q4_1 / XH_Q5_0 / XH_Q5_1; quants.py :316-438) keep the planar
+// idea, two properties deciding the planes of a row:
+//   [nibbles: n/2 B][qh: 4 B per block, gq_has_qh][d: 2 B per block][m: 2 B per block, gq_has_m]
+// so a 16-B load is still one whole block of nibbles, and qh, d and m of a wave's chunks are
+// coalesced reads.  A weight's value is fmaf(d, q, m) (one f32 rounding, m = 0 without the plane).
+__host__ __device__ constexpr bool gq_has_qh(const int dt) { return dt == XH_Q5_0 || dt == XH_Q5_1; }  // fifth-bit plane
+__host__ __device__ constexpr bool gq_has_m(const int dt) { return dt == XH_Q4_1 || dt == XH_Q5_1; }   // affine: d*q + m
+__host__ __device__ constexpr bool gq_ext(const int dt) { return gq_has_qh(dt) || gq_has_m(dt); }
+__host__ __device__ constexpr bool gq_dt(const int dt) { return dt == XH_Q8_0 || dt == XH_Q4_0 || gq_ext(dt); }
+// the code the scale multiplies is q - gq_bias (Q8_0: the int8 itself)
+__host__ __device__ constexpr int gq_bias(const int dt) { return dt == XH_Q4_0 ? 8 : dt == XH_Q5_0 ? 16 : 0; }
 __host__ __device__ constexpr size_t gq_qbytes(const int dt, const size_t n) { return dt == XH_Q8_0 ? n : n / 2; }
-__host__ __device__ constexpr size_t gq_pitch(const int dt, const size_t n) {
-    return (gq_qbytes(dt, n) + n / 16 + 15) & ~(size_t)15;
+// byte offsets of the planes behind the codes
+__host__ __device__ constexpr size_t gq_d_off(const int dt, const size_t n) {
+    return gq_qbytes(dt, n) + (gq_has_qh(dt) ? n / 8 : 0);
 }
-__host__ __device__ constexpr size_t gq_block_bytes(const int dt) { return dt == XH_Q8_0 ? 34 : 18; }
-template <int DT> struct WScale { static constexpr int BLOCK = 0; };  // elements per scale (0: none)
-template <> struct WScale<XH_Q8_0> { static constexpr int BLOCK = 32; };
-template <> struct WScale<XH_Q4_0> { static constexpr int BLOCK = 32; };
+__host__ __device__ constexpr size_t gq_m_off(const int dt, const size_t n) { return gq_d_off(dt, n) + n / 16; }
+__host__ __device__ constexpr size_t gq_pitch(const int dt, const size_t n) {
+    return (gq_d_off(dt, n) + (gq_has_m(dt) ? n / 8 : n / 16) + 15) & ~(size_t)15;
+}
+// bytes of one block in the file: d, m, qh, codes
+__host__ __device__ constexpr size_t gq_block_bytes(const int dt) {
+    return dt == XH_Q8_0 ? 34 : 18 + (gq_has_qh(dt) ? 4 : 0) + (gq_has_m(dt) ? 2 : 0);
+}
+// every block dtype carries one scale set per 32 elements (BLOCK: elements per scale, 0: none)
+template <int DT> struct WScale { static constexpr int BLOCK = gq_dt(DT) ? 32 : 0; };
+// What the matvec holds per chunk beside the codes: the block's d, and for the affine / 5-bit
+// blocks m and qh too (a field the dtype lacks is never read and costs no register)
+struct GqScX { float d, m; uint32_t qh; };
+template <int DT, bool X = gq_ext(DT)> struct GqSc { typedef float T; };
+template <int DT> struct GqSc<DT, true> { typedef GqScX T; };
+// ... read from a row's planes (tail: the row's first byte behind the codes, qbytes: the codes'
+// bytes, n / 2 for the nibble types, so a row has qbytes / 16 blocks)
+template <int DT>
+__device__ __forceinline__ typename GqSc<DT>::T gq_ld_sc(const char* tail, const size_t qbytes, const int blk) {
+    if constexpr (gq_ext(DT)) {
+        const size_t nb = qbytes / 16;
+        const char* dp = tail + (gq_has_qh(DT) ? 4 * nb : 0);
+        GqScX s;
+        s.d = (float)__builtin_bit_cast(_Float16, *(const uint16_t*)(dp + blk * 2));
+        s.m = gq_has_m(DT) ? (float)__builtin_bit_cast(_Float16, *(const uint16_t*)(dp + 2 * nb + blk * 2)) : 0.f;
+        s.qh = gq_has_qh(DT) ? *(const uint32_t*)(tail + blk * 4) : 0u;
+        return s;
+    } else {
+        return (float)__builtin_bit_cast(_Float16, *(const uint16_t*)(tail + blk * 2));
+    }
+}
 
 template <> struct WDec<XH_Q8_0> {
     static constexpr int E = 16;
@@ -177,6 +216,42 @@ template <> struct WDec<XH_Q4_0> {
     }
 };
 
+// The affine / 5-bit blocks' 16 B of nibbles: dec gives the plain nibbles (0..15; the fifth
+// bits live in the qh plane), gq_vals the 32 weights of the block, fmaf(d, q - bias, m) with
+// q = nibble | bit j of qh << 4 (quants.py dequantize_blocks; d*(q - bias) is exact).
+template <int DT> struct WDecNib {
+    static constexpr int E = 32;
+    __device__ __forceinline__ static void dec(const u32x4 v, float* f) {
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const uint32_t b = (w[i] >> (8 * k)) & 0xffu;
+                f[4 * i + k] = (float)(b & 15u);
+                f[16 + 4 * i + k] = (float)(b >> 4);
+            }
+    }
+};
+template <> struct WDec<XH_Q4_1> : WDecNib<XH_Q4_1> {};
+template <> struct WDec<XH_Q5_0> : WDecNib<XH_Q5_0> {};
+template <> struct WDec<XH_Q5_1> : WDecNib<XH_Q5_1> {};
+// the weights of one chunk of a block dtype from its codes and scale set (sc: GqSc<DT>::T)
+template <int DT, class SC>
+__device__ __forceinline__ void gq_vals(const u32x4 v, const SC& sc, float* f) {
+    WDec<DT>::dec(v, f);
+    if constexpr (gq_ext(DT)) {
+#pragma unroll
+        for (int e = 0; e < 32; e++) {
+            const float q = f[e] + (float)(int)((gq_has_qh(DT) ? ((sc.qh >> e) & 1u) * 16u : 0u)) - (float)gq_bias(DT);
+            f[e] = fmaf(sc.d, q, sc.m);
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < WDec<DT>::E; e++) f[e] *= sc;
+    }
+}
+
 // single-element decode (embedding gather, norm weights)
 __device__ __forceinline__ float dec1(const int dtype, const void* p, const size_t i) {
     switch (dtype) {
@@ -200,10 +275,15 @@ __device__ __forceinline__ float dec1(const int dtype, const void* p, const size
 __device__ __forceinline__ float dec_row(const int dtype, const void* p, const size_t row, const int n, const int i) {
     if (!gq_dt(dtype)) return dec1(dtype, p, row * (size_t)n + i);
     const uint8_t* r = (const uint8_t*)p + row * gq_pitch(dtype, n);
-    const float d = (float)__builtin_bit_cast(_Float16, *(const uint16_t*)(r + gq_qbytes(dtype, n) + (i >> 5) * 2));
+    const float d = (float)__builtin_bit_cast(_Float16, *(const uint16_t*)(r + gq_d_off(dtype, n) + (i >> 5) * 2));
     if (dtype == XH_Q8_0) return d * (float)(int8_t)r[i];
     const uint8_t b = r[(i >> 5) * 16 + (i & 15)];
-    return d * (float)((int)((i & 16) ? (b >> 4) : (b & 15u)) - 8);
+    if (dtype == XH_Q4_0) return d * (float)((int)((i & 16) ? (b >> 4) : (b & 15u)) - 8);
+    // affine / 5-bit blocks: the planes behind the nibbles; exactly fmaf(d, q - bias, m)
+    int q = (int)((i & 16) ? (b >> 4) : (b & 15u)) - gq_bias(dtype);
+    if (gq_has_qh(dtype)) q += (int)((*(const uint32_t*)(r + gq_qbytes(dtype, n) + (i >> 5) * 4) >> (i & 31)) & 1u) << 4;
+    const float m = gq_has_m(dtype) ? (float)__builtin_bit_cast(_Float16, *(const uint16_t*)(r + gq_m_off(dtype, n) + (i >> 5) * 2)) : 0.f;
+    return fmaf(d, (float)q, m);
 }
 
 __device__ __forceinline__ uint16_t f32_to_f16_bits(const float f) {

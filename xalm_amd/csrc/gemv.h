@@ -185,8 +185,13 @@ __device__ __forceinline__ float4 load_norm4_nb(const void* w, const int dtype, 
 
 // Q4_0 staging (the denormal form of gq_dot): the image holds x / 16 for elements 16..31 of each
 // 32-element block and, after the n_it * 64 * E floats of the image, -8 sum(x) of every block
+// The affine / 5-bit blocks (Q4_1 / Q5_0 / Q5_1) share the image; what follows it is the block's
+// sum(x) times the factor their form needs: -8 (Q4_0), -16 (Q5_0: d * sum((q - 16) x)), 1 (affine:
+// the m * sum(x) term).  gq4_image: 0 = no such image, else the dtype (the factor's selector).
 template <int DT>
-__device__ __host__ constexpr bool gq4_image() { return DT == XH_Q4_0; }
+__device__ __host__ constexpr int gq4_image() { return gq_dt(DT) && DT != XH_Q8_0 ? DT : 0; }
+template <int GQ4>
+__device__ __host__ constexpr float gq4_factor() { return GQ4 == XH_Q4_0 ? -8.f : GQ4 == XH_Q5_0 ? -16.f : 1.f; }
 __device__ __forceinline__ const float* gq4_nxs(const float4* xs4, const int n) {
     constexpr int E = 32;
     return (const float*)xs4 + (size_t)((n + 64 * E - 1) / (64 * E)) * 64 * E;
@@ -194,9 +199,10 @@ __device__ __forceinline__ const float* gq4_nxs(const float4* xs4, const int n) 
 // one float4 v = x[4 i .. 4 i + 3] into the image slot of a Q4_0 block (lanes 8 k .. 8 k + 7 hold
 // the 8 float4 of block k, i % 8 == lane % 8): the sum over the block in a fixed shuffle tree, the
 // block's -8 sum(x) stored by its first lane; valid: i < n / 4 (the 8 lanes agree)
+template <int GQ4>
 __device__ __forceinline__ float4 gq4_stage(float4 v, const int i, const bool valid, float4* xs4, const int n) {
     const float t = group_reduce<8>((v.x + v.y) + (v.z + v.w));  // DPP: no LDS round trips
-    if (valid && (i & 7) == 0) ((float*)gq4_nxs(xs4, n))[i >> 3] = -8.f * t;
+    if (valid && (i & 7) == 0) ((float*)gq4_nxs(xs4, n))[i >> 3] = gq4_factor<GQ4>() * t;
     const float f = (i & 4) ? 0.0625f : 1.f;  // elements 16..31 of the block: x / 16 (exact)
     v.x *= f; v.y *= f; v.z *= f; v.w *= f;
     return v;
@@ -205,7 +211,7 @@ __device__ __forceinline__ float4 gq4_stage(float4 v, const int i, const bool va
 // x (optionally rms-normalised and weighted) -> LDS image xs4, permuted so that lane l at
 // chunk `it` finds the E/4 float4 it multiplies at xs4[(it*E/4 + q)*64 + l].
 // SC1: x was published inside the running launch (write-through): read it with sc1 loads.
-template <int E, int PRO, int THREADS, bool SC1 = false, bool GQ4 = false>
+template <int E, int PRO, int THREADS, bool SC1 = false, int GQ4 = 0>
 __device__ __forceinline__ void stage_x(const GemvArgs& a, float4* xs4, float* red) {
     const int n = a.n;
     float scale = 1.f;
@@ -226,7 +232,7 @@ __device__ __forceinline__ void stage_x(const GemvArgs& a, float4* xs4, float* r
             v.z = v.z * scale * w.z;
             v.w = v.w * scale * w.w;
         }
-        if constexpr (GQ4) v = gq4_stage(v, i, true, xs4, n);
+        if constexpr (GQ4 != 0) v = gq4_stage<GQ4>(v, i, true, xs4, n);
         const int c = i << 2;
         const int it = c / (64 * E);
         const int rem = c - it * 64 * E;
@@ -434,8 +440,9 @@ __device__ __forceinline__ uint32_t gq_pair(const uint32_t b, const uint32_t sel
     const uint32_t p = __builtin_amdgcn_perm(0x64646464u, b, sel);
     return __builtin_bit_cast(uint32_t, __builtin_bit_cast(h2_t, p) + c);
 }
+// Q5_0 / Q5_1: qh = the block's 32 fifth bits (bit j: element j); see the nibble form below
 template <int DT>
-__device__ __forceinline__ float gq_dot(const u32x4 w, const float4* xv) {
+__device__ __forceinline__ float gq_dot(const u32x4 w, const float4* xv, const uint32_t qh = 0u) {
     const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
     float s = 0.f;
     if constexpr (DT == XH_Q8_0) {
@@ -460,8 +467,25 @@ __device__ __forceinline__ float gq_dot(const u32x4 w, const float4* xv) {
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const uint32_t w8 = ww[i] >> 8;
-            const uint32_t a = ww[i] & 0x000F000Fu, b = w8 & 0x000F000Fu;
-            const uint32_t c = ww[i] & 0x00F000F0u, d = w8 & 0x00F000F0u;
+            uint32_t a = ww[i] & 0x000F000Fu, b = w8 & 0x000F000Fu;
+            uint32_t c = ww[i] & 0x00F000F0u, d = w8 & 0x00F000F0u;
+            if constexpr (gq_has_qh(DT)) {
+                // The fifth bits join the same denormal operands: word i holds elements 4i..4i+3
+                // (low nibbles, qh bits 4i..) and 16+4i..16+4i+3 (high nibbles, qh bits 16+4i..).
+                // Each group of four bits e0..e3 is copied twice by one multiply (e at bits
+                // 4..7 and 18..21; for the high nibbles, 16 times larger, at 8..11 and 22..25), and
+                // one v_and_or_b32 per operand drops (e0, e2) / after a shift (e1, e3) onto mantissa
+                // bit 4 (bit 8) of the two halves: q * 2^-24 and 16 q * 2^-24 with q = 0..31, still
+                // exact.  2 extracts + 2 multiplies + 2 shifts + 4 and-or = 10 VALU ops per 8
+                // elements on top of the 13 of the 4-bit form: 2.9 per element, no per-element
+                // integer extract.
+                const uint32_t ml = ((qh >> (4 * i)) & 0xFu) * 0x40010u;
+                const uint32_t mh = ((qh >> (16 + 4 * i)) & 0xFu) * 0x400100u;
+                a |= ml & 0x00100010u;
+                b |= (ml >> 1) & 0x00100010u;
+                c |= mh & 0x01000100u;
+                d |= (mh >> 1) & 0x01000100u;
+            }
             s = fma_mix_lo(a, xv[i].x, s);
             s = fma_mix_lo(b, xv[i].y, s);
             s = fma_mix_hi(a, xv[i].z, s);
@@ -475,13 +499,21 @@ __device__ __forceinline__ float gq_dot(const u32x4 w, const float4* xv) {
     return s;
 }
 
-// acc[r] += d[r] * sum(q * x) for the ROWS rows of one chunk (Q4_0: nx = -8 sum(x) of the block)
+// acc[r] += d[r] * sum(q * x) for the ROWS rows of one chunk (Q4_0: nx = -8 sum(x) of the block).
+// Q5_0: d * (sum(q x) - 16 sum(x)), nx = -16 sum(x).  Affine (Q4_1 / Q5_1): the block's
+// sum((d q + m) x) as d * sum(q x) + m * sum(x), nx = sum(x): two products per block instead of a
+// fused multiply-add per element; each rounds relative to its own term, |d| sum|q x| and
+// |m| sum|x| (the tests' magnitude), not to their possibly cancelling sum.
 template <int DT, int ROWS>
-__device__ __forceinline__ void gq_rows(const u32x4 (&w)[ROWS], const float (&d)[ROWS], const float4* xv, float* acc,
-                                        const float nx) {
+__device__ __forceinline__ void gq_rows(const u32x4 (&w)[ROWS], const typename GqSc<DT>::T (&d)[ROWS], const float4* xv,
+                                        float* acc, const float nx) {
 #pragma unroll
     for (int r = 0; r < ROWS; r++) {
-        if constexpr (DT == XH_Q4_0) acc[r] = fmaf(d[r], fmaf(gq_dot<DT>(w[r], xv), 0x1p24f, nx), acc[r]);
+        if constexpr (gq_has_m(DT))
+            acc[r] = fmaf(d[r].d, gq_dot<DT>(w[r], xv, d[r].qh) * 0x1p24f, fmaf(d[r].m, nx, acc[r]));
+        else if constexpr (DT == XH_Q5_0)
+            acc[r] = fmaf(d[r].d, fmaf(gq_dot<DT>(w[r], xv, d[r].qh), 0x1p24f, nx), acc[r]);
+        else if constexpr (DT == XH_Q4_0) acc[r] = fmaf(d[r], fmaf(gq_dot<DT>(w[r], xv), 0x1p24f, nx), acc[r]);
         else acc[r] = fmaf(d[r], gq_dot<DT>(w[r], xv), acc[r]);
     }
 }
@@ -498,14 +530,14 @@ __device__ __forceinline__ void gemv_chunk_gq(const char* wrow, const size_t row
     constexpr int QN = E / 4;
     u32x4 wv[U][ROWS];
     gemv_load<ROWS, U, NT>(wv, wrow, row_bytes, it);
-    float d[U][ROWS];
+    typename GqSc<DT>::T d[U][ROWS];
     const char* rb = wrow - lane * 16 + qbytes;
 #pragma unroll
     for (int u = 0; u < U; u++)
 #pragma unroll
         for (int r = 0; r < ROWS; r++) {
             const int blk = (((it + u) * 64 + lane) * E) / WScale<DT>::BLOCK;
-            d[u][r] = (float)__builtin_bit_cast(_Float16, *(const uint16_t*)(rb + (size_t)r * row_bytes + blk * 2));
+            d[u][r] = gq_ld_sc<DT>(rb + (size_t)r * row_bytes, qbytes, blk);
         }
 #pragma unroll
     for (int u = 0; u < U; u++) {
@@ -519,7 +551,7 @@ __device__ __forceinline__ void gemv_chunk_gq(const char* wrow, const size_t row
 // gguf blocks, split in two for the pipelined stream: the f16 block scale d of each of the
 // chunks [it, it+U) of a row group (wrow: this lane's pointer into the group's first row)...
 template <int DT, int ROWS, int U>
-__device__ __forceinline__ void gq_load_scales(float (&d)[U][ROWS], const char* wrow, const size_t row_bytes,
+__device__ __forceinline__ void gq_load_scales(typename GqSc<DT>::T (&d)[U][ROWS], const char* wrow, const size_t row_bytes,
                                                const size_t qbytes, const int it, const int lane) {
     constexpr int E = WDec<DT>::E;
     const char* rb = wrow - lane * 16 + qbytes;
@@ -528,12 +560,12 @@ __device__ __forceinline__ void gq_load_scales(float (&d)[U][ROWS], const char* 
 #pragma unroll
         for (int r = 0; r < ROWS; r++) {
             const int blk = (((it + u) * 64 + lane) * E) / WScale<DT>::BLOCK;
-            d[u][r] = (float)__builtin_bit_cast(_Float16, *(const uint16_t*)(rb + (size_t)r * row_bytes + blk * 2));
+            d[u][r] = gq_ld_sc<DT>(rb + (size_t)r * row_bytes, qbytes, blk);
         }
 }
 // ...and the scaled chunk sums against the staged x, as gemv_chunk_gq
 template <int DT, int ROWS, int U>
-__device__ __forceinline__ void gq_compute(const u32x4 (&wv)[U][ROWS], const float (&d)[U][ROWS], const float4* xs4,
+__device__ __forceinline__ void gq_compute(const u32x4 (&wv)[U][ROWS], const typename GqSc<DT>::T (&d)[U][ROWS], const float4* xs4,
                                            const int it, const int lane, float* acc, const float* nxs) {
     constexpr int QN = WDec<DT>::E / 4;
 #pragma unroll
@@ -641,7 +673,7 @@ template <int DT, int EPI, class S, bool FIRST, bool SC1 = false>
 __device__ __forceinline__ void gemv_rows_pipe(const GemvArgs& a, const int g0, const int total_waves, const int lane,
                                                const float4* xs4, const u32x4 (&pre)[S::U][S::ROWS],
                                                unsigned long long* best = nullptr,
-                                               const float (*pre_d)[S::ROWS] = nullptr) {
+                                               const typename GqSc<DT>::T (*pre_d)[S::ROWS] = nullptr) {
     constexpr int ROWS = S::ROWS, U = S::U;
     constexpr int E = WDec<DT>::E;
     constexpr bool GQ = WScale<DT>::BLOCK > 0;
@@ -663,7 +695,8 @@ __device__ __forceinline__ void gemv_rows_pipe(const GemvArgs& a, const int g0, 
     // QKV: the rotation (cos, sin) of each row pair of the step's group; RESID: its residual rows
     constexpr bool RES = EPI == EPI_RESID && !SC1;
     float fa[ROWS], fb[ROWS];
-    auto load = [&](u32x4 (&w)[U][ROWS], float (&d)[U][ROWS], float (&f)[ROWS], const int k) {
+    typedef typename GqSc<DT>::T Sc;  // the chunk's block scale(s)
+    auto load = [&](u32x4 (&w)[U][ROWS], Sc (&d)[U][ROWS], float (&f)[ROWS], const int k) {
         const int q = k / steps;
         size_t rs;
         const char* wrow = gemv_row_ptr<ROWS>(a, g0 + q * total_waves, lane, rs);
@@ -688,7 +721,7 @@ __device__ __forceinline__ void gemv_rows_pipe(const GemvArgs& a, const int g0, 
 #pragma unroll
     for (int r = 0; r < ROWS; r++) acc[r] = 0.f;
     // multiply step k's chunks; after a group's last step, its reduction and epilogue
-    auto step = [&](const u32x4 (&w)[U][ROWS], const float (&d)[U][ROWS], const float (&f)[ROWS], const int k) {
+    auto step = [&](const u32x4 (&w)[U][ROWS], const Sc (&d)[U][ROWS], const float (&f)[ROWS], const int k) {
         const int q = k / steps;
         const int it = (k - q * steps) * U;
         if constexpr (GQ) gq_compute<DT, ROWS, U>(w, d, xs4, it, lane, acc, gq4_image<DT>() ? gq4_nxs(xs4, a.n) : nullptr);
@@ -708,7 +741,7 @@ __device__ __forceinline__ void gemv_rows_pipe(const GemvArgs& a, const int g0, 
         }
     };
     u32x4 wa[U][ROWS], wb[U][ROWS];
-    float da[U][ROWS], db[U][ROWS];  // GQ only (otherwise unused)
+    Sc da[U][ROWS], db[U][ROWS];  // GQ only (otherwise unused)
     if constexpr (FIRST) {
 #pragma unroll
         for (int u = 0; u < U; u++)
@@ -770,7 +803,7 @@ __device__ __forceinline__ void stage_x_issue(const GemvArgs& a, float4 (&xv)[S:
 // the same value) and the permuted LDS image.  Branch-free like part 1 (a branch would let the
 // compiler sink a load to its use and wait for the weights too): clamped duplicates are
 // masked out of the sum and store the same value to the same slot.
-template <int E, int PRO, class S, bool GQ4 = false>
+template <int E, int PRO, class S, int GQ4 = 0>
 __device__ __forceinline__ void stage_x_finish(const GemvArgs& a, const float4 (&xv)[S::XN], const float4 (&nw)[S::XN],
                                                float4* xs4, float* red) {
     const int n4 = a.n >> 2;
@@ -812,7 +845,7 @@ __device__ __forceinline__ void stage_x_finish(const GemvArgs& a, const float4 (
             v.z = v.z * scale * nw[j].z;
             v.w = v.w * scale * nw[j].w;
         }
-        if constexpr (GQ4) v = gq4_stage(v, i, (int)threadIdx.x + j * S::THREADS < n4, xs4, a.n);
+        if constexpr (GQ4 != 0) v = gq4_stage<GQ4>(v, i, (int)threadIdx.x + j * S::THREADS < n4, xs4, a.n);
         const int c = i << 2;
         const int it = c / (64 * E);
         const int rem = c - it * 64 * E;
@@ -858,7 +891,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, const int block, co
         const int n_groups = gemv_groups<S>(a);
         const bool prefetched = g < n_groups;
         u32x4 pre[S::U][S::ROWS];
-        float pre_d[S::U][S::ROWS];
+        typename GqSc<DT>::T pre_d[S::U][S::ROWS];
         gemv_prefetch<S>(a, min(g, n_groups - 1), lane, pre);
         if constexpr (WScale<DT>::BLOCK > 0) {
             size_t rs;
@@ -916,7 +949,7 @@ template <int DT, class S>
 inline size_t gemv_smem_bytes(const int n) {
     constexpr int E = WDec<DT>::E;
     const int n_it = (n + 64 * E - 1) / (64 * E);
-    // Q4_0: -8 sum(x) per 32-element block after the image (gq4_nxs)
+    // nibble blocks: the factor times sum(x) per 32-element block after the image (gq4_nxs)
     return LDS_HEAD_BYTES + (size_t)n_it * 64 * E * sizeof(float) + (gq4_image<DT>() ? (size_t)n_it * 64 * sizeof(float) : 0);
 }
 // balanced rounds: at most max_blocks * WAVES waves, each with the same group count

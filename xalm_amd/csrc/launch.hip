@@ -102,13 +102,13 @@ void launch_gemv_t(const GemvArgs& a, hipStream_t s, int max_waves) {
         // gguf blocks: the pipelined PF shapes with the block scales loaded beside the codes.
         // Q4_0 rows of a 4096-wide input are 2 chunks, so 2 chunks per step; W2-long inputs
         // (14336: 14 / 7 chunks per row) step by 2 (Q8_0) / 1 (Q4_0) chunks
-        constexpr int UG = DT == XH_Q4_0 ? 2 : UNROLL;
+        constexpr int UG = E == 32 ? 2 : UNROLL;  // the nibble types (Q4_0, Q4_1, Q5_0, Q5_1): 32 elements per chunk
         // W1/W3 (GEMV_BAL_GQ_GLU): balanced grid, Q4_0 15.0 -> 14.0 us (profiles/r06_decode_ab.txt ab8)
         using ShapeGQ = GemvShape<512, ROWS, UG, true, 4, true, 2, 2, EPI == EPI_GLU && GEMV_BAL_GQ_GLU>;
         if (a.n % 4 == 0 && a.n / 4 <= 2 * 512 && a.n % (64 * E * UG) == 0)
             return launch_gemv_s<DT, PRO, EPI, ShapeGQ>(a, s, max_waves);
         if constexpr (PRO == PRO_PLAIN) {
-            constexpr int UL = DT == XH_Q4_0 ? 1 : 2;
+            constexpr int UL = E == 32 ? 1 : 2;
             using ShapeGQL = GemvShape<512, ROWS, UL, true, 4, true, 8, 2>;
             if (a.n % 4 == 0 && a.n / 4 <= 8 * 512 && a.n % (64 * E * UL) == 0)
                 return launch_gemv_s<DT, PRO, EPI, ShapeGQL>(a, s, max_waves);
@@ -141,6 +141,9 @@ bool launch_gemv_dt(int dt, const GemvArgs& a, hipStream_t s, int max_blocks) {
         case XH_F8_E5M2_EXACT: launch_gemv_t<XH_F8_E5M2_EXACT, PRO, EPI>(a, s, max_blocks); return true;
         case XH_Q8_0: launch_gemv_t<XH_Q8_0, PRO, EPI>(a, s, max_blocks); return true;
         case XH_Q4_0: launch_gemv_t<XH_Q4_0, PRO, EPI>(a, s, max_blocks); return true;
+        case XH_Q4_1: launch_gemv_t<XH_Q4_1, PRO, EPI>(a, s, max_blocks); return true;
+        case XH_Q5_0: launch_gemv_t<XH_Q5_0, PRO, EPI>(a, s, max_blocks); return true;
+        case XH_Q5_1: launch_gemv_t<XH_Q5_1, PRO, EPI>(a, s, max_blocks); return true;
         default: return false;
     }
 }

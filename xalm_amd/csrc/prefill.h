@@ -50,7 +50,9 @@ struct PfGemmArgs {
 // tiles per wave; each X operand load feeds RT x 2 accumulator tiles.
 // gguf blocks (Q8_0 / Q4_0): each lane's 16-B chunk lies in one 32-element block; its f16 d
 // (the planar row's scale area) multiplies the decoded codes, w = q * d exact in f32 as
-// quants.py's dequantize (oracle xo_gq_elem), before the MFMA.
+// quants.py's dequantize (oracle xo_gq_elem), before the MFMA.  The affine / 5-bit blocks (Q4_1 /
+// Q5_0 / Q5_1) bring m and qh from their planes too: w = fmaf(d, q, m), the converter's one
+// rounding (gq_vals, common.h).
 template <int DT, bool PIPE, int RT>
 __global__ __launch_bounds__(PF_THREADS) void prefill_gemm_kernel(const PfGemmArgs a) {
     constexpr int E = WDec<DT>::E;
@@ -78,7 +80,7 @@ __global__ __launch_bounds__(PF_THREADS) void prefill_gemm_kernel(const PfGemmAr
     // one's 2 E RT MFMAs run (weights come from HBM, X from L2)
     struct Stage {
         u32x4 w[RT];
-        float d[RT];
+        typename GqSc<DT>::T d[RT];
         float4 x0[E / 4], x1[E / 4];
     };
     const size_t qb = GQ ? gq_qbytes(DT, (size_t)a.K) : 0;
@@ -87,7 +89,7 @@ __global__ __launch_bounds__(PF_THREADS) void prefill_gemm_kernel(const PfGemmAr
 #pragma unroll
         for (int i = 0; i < RT; i++) {
             st.w[i] = *(const u32x4*)(wrow[i] + (size_t)k * 16 / E);
-            if constexpr (GQ) st.d[i] = f16_bits_to_f32(*(const uint16_t*)(wrow[i] + qb + (size_t)(k >> 5) * 2));
+            if constexpr (GQ) st.d[i] = gq_ld_sc<DT>(wrow[i] + qb, qb, k >> 5);
         }
 #pragma unroll
         for (int q = 0; q < E / 4; q++) st.x0[q] = *(const float4*)(x0 + k + 4 * q);
@@ -100,11 +102,8 @@ __global__ __launch_bounds__(PF_THREADS) void prefill_gemm_kernel(const PfGemmAr
 #pragma unroll
         for (int i = 0; i < RT; i++) {
             float wf[E];
-            WDec<DT>::dec(st.w[i], wf);
-            if constexpr (GQ) {
-#pragma unroll
-                for (int e = 0; e < E; e++) wf[e] *= st.d[i];
-            }
+            if constexpr (GQ) gq_vals<DT>(st.w[i], st.d[i], wf);
+            else WDec<DT>::dec(st.w[i], wf);
 #pragma unroll
             for (int q = 0; q < E / 4; q++) {
                 acc0[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(st.x0[q].x, wf[4 * q + 0], acc0[i], 0, 0, 0);
@@ -1146,7 +1145,8 @@ __global__ __launch_bounds__(256) void pf_dequant_f16_kernel(const u32x4* w, con
     }
 }
 
-// gguf blocks (Q8_0 / Q4_0, planar device rows: codes, then one f16 scale d per 32 elements) ->
+// gguf blocks (Q8_0 / Q4_0 / Q5_0, planar device rows: codes, [Q5_0: the fifth bits,] then one
+// f16 scale d per 32 elements; Q5_0's d * (q - 16) has at most 16 significant bits) ->
 // the exact f16 hi + lo of every weight for the f16 GEMMs of a prompt pass.  The converter's
 // value d * q (quants.py: Q8_0 :448-454, Q4_0 :302-311) is exact in f32 (11-bit d times a 4- or
 // 8-bit q) and splits exactly into hi = f16(v) and lo = f16(v - hi) (at most 19 significant bits,
@@ -1162,7 +1162,7 @@ __global__ __launch_bounds__(256) void pf_dequant_gq_kernel(const uint8_t* w, co
         const int k = (int)(i - r * per_row) * 8;  // 8 elements k .. k+7 of one block
         const uint8_t* row = w + r * pitch;
         const int b = k >> 5, j0 = k & 31;
-        const float d = f16_bits_to_f32(*(const uint16_t*)(row + qbytes + 2 * b));
+        const float d = f16_bits_to_f32(*(const uint16_t*)(row + gq_d_off(DT, (size_t)K) + 2 * b));
         int q[8];
         if constexpr (DT == XH_Q8_0) {
             const uint2 u = *(const uint2*)(row + k);
@@ -1174,7 +1174,12 @@ __global__ __launch_bounds__(256) void pf_dequant_gq_kernel(const uint8_t* w, co
 #pragma unroll
             for (int e = 0; e < 8; e++) {
                 const uint32_t byte = ((e < 4 ? u.x : u.y) >> (8 * (e & 3))) & 0xffu;
-                q[e] = (int)(j0 < 16 ? (byte & 15u) : (byte >> 4)) - 8;
+                q[e] = (int)(j0 < 16 ? (byte & 15u) : (byte >> 4)) - gq_bias(DT);
+            }
+            if constexpr (gq_has_qh(DT)) {
+                const uint32_t qh = *(const uint32_t*)(row + qbytes + 4 * b) >> j0;  // bit e: element j0 + e
+#pragma unroll
+                for (int e = 0; e < 8; e++) q[e] += (int)((qh >> e) & 1u) << 4;
             }
         }
         uint32_t h[4], l[4];

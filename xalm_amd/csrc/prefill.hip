@@ -125,7 +125,7 @@ void pf_gemm16_t(const PfGemm16Args& a, hipStream_t s) {
 // weights per 16-byte chunk of the f32-input MFMA kernel's decoders (WDec<DT>::E)
 int pf_elems(int dt) {
     if (dt == XH_F8_E4M3_EXACT || dt == XH_F8_E5M2_EXACT || dt == XH_Q8_0) return 16;
-    return dt == XH_Q4_0 ? 32 : elems_per_16b(dt);
+    return gq_dt(dt) ? 32 : elems_per_16b(dt);  // the nibble blocks (Q8_0 above)
 }
 // weights the f16 GEMMs take: f16 as stored, e4m3 / e5m2 through their exact f16 image (kdt
 // keeps the _EXACT dtypes, whose NaN / Inf codes the reference decodes to finite values, off it)
@@ -134,7 +134,9 @@ bool pf_f16w(int dt) { return dt == XH_F16 || pf_f8(dt); }
 // Does the GEMM over W (dtype dt, K columns) run on the row-major split input: gemm16.h
 // (XH_OPT_PREFILL 1: K in whole 64-deep steps) or hipBLASLt (4: a plan for every shape)?
 bool pf_lay0(const xh_ctx* ctx, int dt, int K) {
-    // gguf blocks: their exact f16 hi + lo images through gemm16.h (XH_OPT_PREFILL 1)
+    // gguf blocks: their exact f16 hi + lo images through gemm16.h (XH_OPT_PREFILL 1); the affine
+    // blocks (fmaf(d, q, m): no exact f16 pair) always take the f32-input MFMA kernel
+    if (gq_has_m(dt)) return false;
     if (gq_dt(dt)) return ctx->prefill_gemm == 1 && K % MM_KMULT == 0;
     if (!pf_f16w(dt)) return false;
     if (ctx->prefill_gemm == 1) return K % MM_KMULT == 0;
@@ -279,6 +281,9 @@ int pf_gemm(xh_ctx* ctx, const char* what, int dt, const void* w, int K, int row
             if (dt == XH_Q8_0)
                 hipLaunchKernelGGL(pf_dequant_gq_kernel<XH_Q8_0>, dim3(grid), dim3(256), 0, ctx->stream,
                                    (const uint8_t*)w, rows, K, hi, lo);
+            else if (dt == XH_Q5_0)
+                hipLaunchKernelGGL(pf_dequant_gq_kernel<XH_Q5_0>, dim3(grid), dim3(256), 0, ctx->stream,
+                                   (const uint8_t*)w, rows, K, hi, lo);
             else
                 hipLaunchKernelGGL(pf_dequant_gq_kernel<XH_Q4_0>, dim3(grid), dim3(256), 0, ctx->stream,
                                    (const uint8_t*)w, rows, K, hi, lo);
@@ -346,6 +351,9 @@ int pf_gemm(xh_ctx* ctx, const char* what, int dt, const void* w, int K, int row
         case XH_Q8: pf_gemm_t<XH_Q8>(a, s); break;
         case XH_Q8_0: pf_gemm_t<XH_Q8_0>(a, s); break;
         case XH_Q4_0: pf_gemm_t<XH_Q4_0>(a, s); break;
+        case XH_Q4_1: pf_gemm_t<XH_Q4_1>(a, s); break;
+        case XH_Q5_0: pf_gemm_t<XH_Q5_0>(a, s); break;
+        case XH_Q5_1: pf_gemm_t<XH_Q5_1>(a, s); break;
         case XH_F8_E4M3_EXACT: pf_gemm_t<XH_F8_E4M3_EXACT>(a, s); break;
         case XH_F8_E5M2_EXACT: pf_gemm_t<XH_F8_E5M2_EXACT>(a, s); break;
         default: return set_err(ctx, XH_E_INVALID, "prefill: %s dtype %d not supported", what, dt);

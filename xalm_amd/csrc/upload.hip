@@ -162,20 +162,26 @@ __global__ void synth_fill_kernel(char* base, size_t pitch, size_t rows, size_t 
 
 }  // namespace
 
-// gguf blocks: file layout ([rows][cols/32 blocks: f16 d, codes]) -> planar device rows
-// ([codes][d per block][zero pad], pitch gq_pitch), on the host, split over threads
+// gguf blocks: file layout ([rows][cols/32 blocks: f16 d, f16 m (affine), u32 qh (5-bit), codes])
+// -> planar device rows ([codes][qh per block][d per block][m per block][zero pad], pitch
+// gq_pitch; common.h), on the host, split over threads
 void xalm::gq_repack(int dt, const uint8_t* src, size_t rows, size_t cols, uint8_t* dst) {
-    const size_t nb = cols / 32, bs = gq_block_bytes(dt), qb = bs - 2;
+    const size_t nb = cols / 32, bs = gq_block_bytes(dt);
+    const size_t hm = gq_has_m(dt) ? 2 : 0, hq = gq_has_qh(dt) ? 4 : 0;  // header bytes behind d
+    const size_t qb = bs - 2 - hm - hq;
     const size_t pitch = gq_pitch(dt, cols), qbytes = gq_qbytes(dt, cols);
+    const size_t d_off = gq_d_off(dt, cols), m_off = gq_m_off(dt, cols), end = m_off + hm * nb;
     auto part = [&](size_t r0, size_t r1) {
         for (size_t r = r0; r < r1; r++) {
             const uint8_t* in = src + r * nb * bs;
             uint8_t* out = dst + r * pitch;
             for (size_t b = 0; b < nb; b++) {
-                memcpy(out + b * qb, in + b * bs + 2, qb);
-                memcpy(out + qbytes + 2 * b, in + b * bs, 2);
+                memcpy(out + b * qb, in + b * bs + 2 + hm + hq, qb);
+                memcpy(out + d_off + 2 * b, in + b * bs, 2);
+                if (hm) memcpy(out + m_off + 2 * b, in + b * bs + 2, 2);
+                if (hq) memcpy(out + qbytes + 4 * b, in + b * bs + 2 + hm, 4);
             }
-            memset(out + qbytes + 2 * nb, 0, pitch - qbytes - 2 * nb);
+            memset(out + end, 0, pitch - end);
         }
     };
     const size_t nt = std::min<size_t>(16, std::max<size_t>(1, rows / 256));
@@ -191,15 +197,20 @@ namespace {
 // (xs_block: the oracle's bytes exactly), written straight into the planar rows of the slot
 __global__ void synth_gq_kernel(char* base, size_t pitch, size_t rows, size_t cols, int dtype, uint64_t seed, float mean,
                                 float std) {
-    const size_t nb = cols / 32, qb = gq_block_bytes(dtype) - 2, qbytes = gq_qbytes(dtype, cols);
+    const size_t nb = cols / 32, qbytes = gq_qbytes(dtype, cols);
+    const size_t hm = gq_has_m(dtype) ? 2 : 0, hq = gq_has_qh(dtype) ? 4 : 0;  // header bytes behind d
+    const size_t qb = gq_block_bytes(dtype) - 2 - hm - hq;
+    const size_t d_off = gq_d_off(dtype, cols), m_off = gq_m_off(dtype, cols);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows * nb; i += (size_t)gridDim.x * blockDim.x) {
         const size_t r = i / nb, b = i - r * nb;
         uint8_t blk[34];
         xs_block(blk, dtype, seed, r, cols, b, mean, std);
         char* row = base + r * pitch;
-        for (size_t k = 0; k < qb; k++) row[b * qb + k] = (char)blk[2 + k];
-        row[qbytes + 2 * b] = (char)blk[0];
-        row[qbytes + 2 * b + 1] = (char)blk[1];
+        for (size_t k = 0; k < qb; k++) row[b * qb + k] = (char)blk[2 + hm + hq + k];
+        row[d_off + 2 * b] = (char)blk[0];
+        row[d_off + 2 * b + 1] = (char)blk[1];
+        for (size_t k = 0; k < hm; k++) row[m_off + 2 * b + k] = (char)blk[2 + k];
+        for (size_t k = 0; k < hq; k++) row[qbytes + 4 * b + k] = (char)blk[2 + hm + k];
     }
 }
 
@@ -311,6 +322,13 @@ int xh_upload_synthetic(xh_ctx* ctx, int kind, int layer, int dtype, uint64_t se
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return scan_f8(ctx, kind, layer, dtype, s);
+}
+
+int xh_quantize_blocks(int dtype, const float* values, size_t n_blocks, void* out) {
+    if (!gq_dt(dtype) || !values || !out) return set_err(nullptr, XH_E_INVALID, "quantize_blocks: dtype %d is no block type, or a null pointer", dtype);
+    const size_t bs = gq_block_bytes(dtype);
+    for (size_t b = 0; b < n_blocks; b++) xs_quant_block(dtype, values + 32 * b, (uint8_t*)out + b * bs);
+    return 0;
 }
 
 int xh_kv_fill_synthetic(xh_ctx* ctx, int layer, int which, int slot0, int n_slots, uint64_t seed, float std) {

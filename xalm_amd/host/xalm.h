@@ -50,6 +50,9 @@ struct XalmFile {
 
 int parse_type(const std::string& s);  // Type::parse, src/types.h:468-499
 size_t type_size(int type);
+// bytes of one 32-element block of the converter's gguf block types (convert.py:176-187,
+// quants.py), 0 for any other type: the one table of their names and sizes (xalm_file.cpp)
+size_t block_bytes(int type);
 
 // ---- model ------------------------------------------------------------------------------
 enum class Device { CPU, HIP };

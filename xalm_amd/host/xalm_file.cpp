@@ -12,6 +12,11 @@
 
 namespace xalm {
 
+// the converter's gguf block types: name, id, bytes per 32-element block (quants.py)
+struct BlockType { const char* name; int type; size_t bytes; };
+const BlockType BLOCK_TYPES[] = {{"Q8_0", XH_Q8_0, 34}, {"Q4_0", XH_Q4_0, 18}, {"Q4_1", XH_Q4_1, 20},
+                                 {"Q5_0", XH_Q5_0, 22}, {"Q5_1", XH_Q5_1, 24}};
+
 // Type::parse, src/types.h:468-499 (case-insensitive names)
 int parse_type(const std::string& s) {
     std::string u(s);
@@ -24,9 +29,15 @@ int parse_type(const std::string& s) {
     if (u == "U8") return XH_U8;
     if (u == "Q8") return XH_Q8;
     // the converter's gguf blocks (convert.py:176-187); the reference runtime has no parser
-    if (u == "Q8_0") return XH_Q8_0;
-    if (u == "Q4_0") return XH_Q4_0;
+    for (const BlockType& b : BLOCK_TYPES)
+        if (u == b.name) return b.type;
     throw std::invalid_argument("invalid type: " + u);
+}
+
+size_t block_bytes(int type) {
+    for (const BlockType& b : BLOCK_TYPES)
+        if (type == b.type) return b.bytes;
+    return 0;
 }
 
 size_t type_size(int type) {
