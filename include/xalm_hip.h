@@ -156,6 +156,46 @@ int xh_forward(xh_ctx* ctx, int token, int pos, int mode, float* logits_out);
 int xh_decode_greedy(xh_ctx* ctx, int pos, int n_steps, int stop_token_a, int stop_token_b,
                      int* tokens_out, int* n_done);
 
+/* ---- seeded temperature / top-k / top-p sampling ------------------------------------ */
+typedef struct xh_sampling {
+    float    temperature;  /* >= 0; 0 = greedy                          */
+    int32_t  top_k;        /* >= 0; 0 = off                             */
+    float    top_p;        /* in (0, 1]; 1 = off                        */
+    uint64_t seed;
+} xh_sampling;
+/* The token at position `pos` is drawn from logits l[0..V) as follows.
+ * - Greedy.  temperature == 0 gives exactly Sampler::sample_argmax: the first maximum among
+ *   logits > FLT_MIN, else token 0.  top_k, top_p and seed are ignored.
+ * - Weights.  Otherwise let m = max l and w_i = exp((l_i - m) / temperature), evaluated in f32
+ *   with expf.  A -inf logit has weight 0 and is never drawn.  If no logit is finite, the token
+ *   is 0.  NaN logits are outside the contract.
+ * - Order.  Sort by logit descending, then index ascending.  Equal logits compare by their f32
+ *   bits, so the order is exact.
+ * - top-k.  With top_k > 0, keep the first min(top_k, V) tokens in that order.  Ties at the k-th
+ *   logit go to the lower index.
+ * - top-p.  With top_p < 1, among the kept tokens in that order, keep the shortest prefix whose
+ *   weight reaches top_p x the kept total.  At least one token is always kept.
+ * - Draw.  Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (pos, 0, 0, 0).
+ *   u = (x0 >> 8) * 2^-24, which lies in [0, 1).  The token is the first kept token in
+ *   ascending index order whose cumulative kept weight exceeds u x the final kept total.  The
+ *   counter is the position the sampled token will occupy.  A sequence therefore continues
+ *   identically whether it is generated in one call or in several.
+ * - Invalid parameters.  Negative or NaN temperature, top_k < 0, top_p outside (0, 1] or NaN, or
+ *   a null pointer return XH_E_INVALID.  This is checked before the device is touched.
+ * - Determinism.  The same logits bits, parameters and counter give the same token on every
+ *   run, with graphs on or off.
+ * How the device evaluates it (xalm_amd/csrc/sample.h): the weights as integers, w_i * 2^40
+ * truncated (a sum of them is exact in any order), the top-p cut at the first prefix whose mass
+ * reaches ceil(top_p * kept mass), the draw at the first cumulative mass above floor(u * final
+ * kept mass).  Against the definition in exact arithmetic that moves a cut or a draw by less
+ * than V * 2^-40 of the total, plus expf's error.  The vocabulary is at most 2^17 tokens. */
+
+/* Sampled decode fully on device: xh_decode_greedy's loop with the token drawn as above, step i
+ * at counter pos + i.  `sampling` is copied to a device block before the first step (changing
+ * it needs no new graph capture).  The first token comes from the logits on the device. */
+int xh_decode_sample(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* sampling, int stop_token_a,
+                     int stop_token_b, int* tokens_out, int* n_done);
+
 /* Hydrate: forward tokens[0..n) at positions pos0.. (HYDRATE_KV_CACHE for all but the last,
  * which computes logits if want_logits), the prompt loop of run_completion
  * (src/main.cpp:94-100) in one call.  logits_out may be NULL. */
@@ -257,11 +297,21 @@ int xh_op_mha(float* xout, const uint16_t* kb, const uint16_t* vb, const float* 
 int xh_op_prompt_gemm(float* y, const uint16_t* w, const uint16_t* xh, const uint16_t* xl, int rows, int K, int n,
                       int ks);
 
+/* The sampler of xh_decode_sample (the same device function) on host logits[vocab], no model and
+ * no context: draw d = 0 .. n_draws-1 at counter pos0 + d writes tokens_out[d] and n_kept_out[d],
+ * the size of the kept set (greedy: 1; no finite logit: 0).  n_draws <= 65536. */
+int xh_op_sample(const float* logits, int vocab, const xh_sampling* sampling, uint64_t pos0, int n_draws,
+                 int* tokens_out, int* n_kept_out);
+/* Philox4x32-10 on the host (no device): key (seed & 0xffffffff, seed >> 32), counter
+ * (pos mod 2^32, 0, 0, 0): only the low 32 bits of pos are used. */
+int xh_philox4x32(uint64_t seed, uint64_t pos, uint32_t out[4]);
+
 /* ---- timing hooks used by bench.py (HIP events on the context's own stream) -------- */
 /* Average device time (microseconds) of one launch of kernel `which` (0 = the fused
- * gate/up matvec, 1 = qkv, 2 = wo, 3 = down, 4 = lm_head, 5 = attention) over `iters`
- * back-to-back launches with the current step parameters (layers rotate, so the Infinity Cache
- * never serves a repeat). */
+ * gate/up matvec, 1 = qkv, 2 = wo, 3 = down, 4 = lm_head, 5 = attention, 6 = the sampled step
+ * head of xh_decode_sample under its last parameters) over `iters` back-to-back launches with
+ * the current step parameters (layers rotate, so the Infinity Cache never serves a repeat).
+ * 6 advances the decode loop's position with every launch: reset or re-hydrate afterwards. */
 int xh_time_kernel(xh_ctx* ctx, int which, int iters, float* avg_us);
 /* Bytes one launch of that kernel must move (algorithmic). */
 size_t xh_kernel_bytes(const xh_ctx* ctx, int which, int kv_len);

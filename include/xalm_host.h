@@ -19,6 +19,9 @@ int xalm_read_config(const char* xalm_path, int context, xh_config* out);
 int xalm_encode(const char* xalm_path, const char* text, int encode_bos, int* out, int cap, int* n_out);
 /* Load a .xalm into a new device context (Model::from_xalm, src/model.cpp:48-118). */
 int xalm_load_model(const char* xalm_path, int context, int device_ordinal, xh_ctx** out);
+/* Sampler::sample on a bare logits vector: the host restatement of the xh_sampling definition
+ * (include/xalm_hip.h) at counter `pos`; *n_kept (may be NULL) = size of the kept set.  No device. */
+int xalm_sample(const float* logits, int vocab, const xh_sampling* sampling, uint64_t pos, int* token, int* n_kept);
 const char* xalm_host_last_error(void);
 
 #ifdef __cplusplus

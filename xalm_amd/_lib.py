@@ -50,6 +50,13 @@ class XhConfig(ctypes.Structure):
                 ("qkv_clip", ctypes.c_float), ("tie_word_embeddings", ctypes.c_int32)]
 
 
+class XhSampling(ctypes.Structure):
+    """xh_sampling (include/xalm_hip.h): temperature >= 0 (0 = greedy), top_k >= 0 (0 = off),
+    top_p in (0, 1] (1 = off), seed."""
+    _fields_ = [("temperature", ctypes.c_float), ("top_k", ctypes.c_int32), ("top_p", ctypes.c_float),
+                ("seed", ctypes.c_uint64)]
+
+
 class XhError(RuntimeError):
     pass
 
@@ -72,6 +79,9 @@ _SIGNATURES = {
     "xh_kv_fill_synthetic": (_I, [_P, _I, _I, _I, _I, ctypes.c_uint64, ctypes.c_float]),
     "xh_forward": (_I, [_P, _I, _I, _I, _P]),
     "xh_decode_greedy": (_I, [_P, _I, _I, _I, _I, _P, ctypes.POINTER(_I)]),
+    "xh_decode_sample": (_I, [_P, _I, _I, ctypes.POINTER(XhSampling), _I, _I, _P, ctypes.POINTER(_I)]),
+    "xh_op_sample": (_I, [_P, _I, ctypes.POINTER(XhSampling), ctypes.c_uint64, _I, _P, _P]),
+    "xh_philox4x32": (_I, [ctypes.c_uint64, ctypes.c_uint64, _P]),
     "xh_prefill": (_I, [_P, _P, _I, _I, _I, _P]),
     "xh_perplexity": (_I, [_P, _P, _I, _I, _P]),
     "xh_debug_trace": (_I, [_P, _I, _P, _I, ctypes.POINTER(_I)]),
@@ -138,6 +148,26 @@ def quantize_blocks(dtype: int, values: np.ndarray) -> np.ndarray:
         raise ValueError("quantize_blocks: a block dtype and whole 32-element blocks")
     out = np.empty(v.shape[:-1] + (v.shape[-1] // 32 * GQ_BLOCK_BYTES[dtype],), dtype=np.uint8)
     check(lib().xh_quantize_blocks(dtype, ptr(v), v.size // 32, ptr(out)))
+    return out
+
+
+def op_sample(logits: np.ndarray, temperature: float, top_k: int, top_p: float, seed: int, pos0: int,
+              n_draws: int):
+    """The device sampler on a logits vector (xh_op_sample): draws at counters pos0 .. pos0 +
+    n_draws - 1; returns (tokens, n_kept), int32 [n_draws] each."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    s = XhSampling(temperature, top_k, top_p, seed)
+    toks = np.empty(max(n_draws, 1), dtype=np.int32)
+    kept = np.empty(max(n_draws, 1), dtype=np.int32)
+    check(lib().xh_op_sample(ptr(lg), lg.size, ctypes.byref(s), pos0, n_draws, ptr(toks), ptr(kept)))
+    return toks[:n_draws], kept[:n_draws]
+
+
+def philox4x32(seed: int, pos: int) -> np.ndarray:
+    """Philox4x32-10 of key (seed & 0xffffffff, seed >> 32), counter (pos mod 2^32, 0, 0, 0): the
+    sampler's generator on the host (xh_philox4x32)."""
+    out = np.empty(4, dtype=np.uint32)
+    check(lib().xh_philox4x32(seed, pos, ptr(out)))
     return out
 
 

@@ -74,6 +74,7 @@ struct xh_ctx {
     int* dec_tokens = nullptr;      // device, decode loop output
     unsigned long long* cand = nullptr;  // device [ARGMAX_CANDS]: lm_head workgroups' argmax keys
     bool cand_valid = false;        // cand describes the logits on the device
+    xh_sampling* samp = nullptr;    // device: xh_decode_sample's parameter block (read by its graph)
     int dec_cap = 0;
     int nsplit = 1, t_max = 16;
     // fused attention + Wo launch (attn_wo.h): per-layer hand-off words [n_layers][4]
@@ -120,7 +121,7 @@ struct xh_ctx {
     int ppl_cap = 0;
     int t_max_aw = 16;
     bool use_graphs = true;
-    hipGraphExec_t g_logits = nullptr, g_hydrate = nullptr, g_decode = nullptr;
+    hipGraphExec_t g_logits = nullptr, g_hydrate = nullptr, g_decode = nullptr, g_sample = nullptr;
     int max_gemv_waves = 4096;  // 16 waves per CU
     // the qkv launch: its whole matrix is one round at 16 waves per CU (every wave one group,
     // requested at once); at 8 waves per CU each wave streams two groups back to back
@@ -202,6 +203,7 @@ int check_aw(xh_ctx* ctx);
 void drop_graphs(xh_ctx* ctx);
 int host_step_params(xh_ctx* ctx, int token, int pos);
 int run_step(xh_ctx* ctx, bool with_logits);
+void time_sample_head(xh_ctx* ctx);  // one sample_embed_kernel launch on ctx->stream (xh_time_kernel 6)
 
 // prefill.hip: the pass buffers, and gemm16.h for xh_op_prompt_gemm (device pointers).  mm_op_ks:
 // *ks = 0 picks the K slicing; 0, 1 when K is no multiple of MM_KMULT, 2 when *ks slices do not divide it

@@ -7,6 +7,7 @@
 
 #include "ctx.h"
 #include "dt_launch.h"
+#include "sample.h"
 
 using namespace xalm;
 
@@ -57,6 +58,44 @@ __global__ __launch_bounds__(1024) void argmax_embed_kernel(const unsigned long 
     __syncthreads();
     rope_table(rope_cs, rope_freq, half, pos_s, tid);
     for (int i = tid; i < dim; i += 1024) x[i] = dec_row(dtype, emb, (size_t)tok_s, dim, i);
+}
+
+// Sampled decode step head: the token is drawn from the logits of the previous step
+// (sample_token, sample.h; the definition is in include/xalm_hip.h) at counter sp->pos_next, the
+// position it will occupy; then the bookkeeping and the embedding exactly as argmax_embed_kernel.
+__global__ __launch_bounds__(SMP_THREADS) void sample_embed_kernel(const float* logits, int vocab,
+                                                                   const xh_sampling* samp, StepParams* sp, int* tokens,
+                                                                   int cap, const void* emb, int dtype, int dim, float* x,
+                                                                   const float* rope_freq, float* rope_cs, int half) {
+    __shared__ SampleShared sh;
+    __shared__ int pos_s;
+    const int tid = threadIdx.x;
+    int n_kept;
+    const int tok = sample_token(sh, logits, vocab, *samp, (uint32_t)sp->pos_next, &n_kept);
+    __syncthreads();  // every thread has read pos_next
+    if (tid == 0) {
+        if (sp->step < cap) tokens[sp->step] = tok;
+        sp->step += 1;
+        sp->token = tok;
+        step_positions(sp, sp->pos_next);
+        sp->pos_next += 1;
+        pos_s = sp->pos;
+    }
+    __syncthreads();
+    rope_table(rope_cs, rope_freq, half, pos_s, tid);
+    for (int i = tid; i < dim; i += SMP_THREADS) x[i] = dec_row(dtype, emb, (size_t)tok, dim, i);
+}
+
+// xh_op_sample: workgroup d draws at counter pos0 + d
+__global__ __launch_bounds__(SMP_THREADS) void sample_op_kernel(const float* logits, int vocab, const xh_sampling* samp,
+                                                                uint32_t pos0, int* tokens, int* n_kept_out) {
+    __shared__ SampleShared sh;
+    int n_kept;
+    const int tok = sample_token(sh, logits, vocab, *samp, pos0 + blockIdx.x, &n_kept);
+    if (threadIdx.x == 0) {
+        tokens[blockIdx.x] = tok;
+        n_kept_out[blockIdx.x] = n_kept;
+    }
 }
 
 // Candidates from logits already on the device (the first greedy step after logits that no
@@ -150,11 +189,16 @@ int launch_attn_wo(xh_ctx* ctx, int l, hipStream_t s) {
     }
 }
 
-// greedy: the token is the argmax of the previous step's logits (argmax_embed_kernel)
-int enqueue_step(xh_ctx* ctx, hipStream_t s, bool with_logits, bool greedy = false) {
+// head: HEAD_GREEDY = the token is the argmax of the previous step's logits (argmax_embed_kernel),
+// HEAD_SAMPLE = drawn from them under ctx->samp (sample_embed_kernel)
+enum StepHead { HEAD_GIVEN = 0, HEAD_GREEDY = 1, HEAD_SAMPLE = 2 };
+void launch_sample_head(xh_ctx* ctx, hipStream_t s);
+int enqueue_step(xh_ctx* ctx, hipStream_t s, bool with_logits, int head = HEAD_GIVEN) {
     const xh_config& c = ctx->c;
     const int mb = ctx->max_gemv_waves;
-    if (greedy)
+    if (head == HEAD_SAMPLE)
+        launch_sample_head(ctx, s);
+    else if (head == HEAD_GREEDY)
         hipLaunchKernelGGL(argmax_embed_kernel, dim3(1), dim3(ARGMAX_CANDS), 0, s, (const unsigned long long*)ctx->cand,
                            ctx->sp, ctx->dec_tokens, ctx->dec_cap, (const void*)ctx->embed, ctx->embed_dt, c.dim,
                            ctx->x, (const float*)ctx->rope_freq, ctx->rope_cs, c.head_dim / 2);
@@ -191,10 +235,17 @@ int enqueue_step(xh_ctx* ctx, hipStream_t s, bool with_logits, bool greedy = fal
     return 0;
 }
 
+void launch_sample_head(xh_ctx* ctx, hipStream_t s) {
+    const xh_config& c = ctx->c;
+    hipLaunchKernelGGL(sample_embed_kernel, dim3(1), dim3(SMP_THREADS), 0, s, (const float*)ctx->logits, c.vocab_size,
+                       (const xh_sampling*)ctx->samp, ctx->sp, ctx->dec_tokens, ctx->dec_cap, (const void*)ctx->embed,
+                       ctx->embed_dt, c.dim, ctx->x, (const float*)ctx->rope_freq, ctx->rope_cs, c.head_dim / 2);
+}
+
 int capture(xh_ctx* ctx, int kind, hipGraphExec_t* out) {
     hipGraph_t g = nullptr;
     HIP_TRY(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-    const int rc = enqueue_step(ctx, ctx->stream, kind != 1, kind == 2);
+    const int rc = enqueue_step(ctx, ctx->stream, kind != 1, kind == 2 ? HEAD_GREEDY : kind == 3 ? HEAD_SAMPLE : HEAD_GIVEN);
     hipError_t e = hipStreamEndCapture(ctx->stream, &g);
     if (rc) { if (g) hipGraphDestroy(g); return rc; }
     if (e != hipSuccess) return set_err(ctx, XH_E_HIP, "graph capture failed: %s", hipGetErrorString(e));
@@ -206,8 +257,8 @@ int capture(xh_ctx* ctx, int kind, hipGraphExec_t* out) {
 
 // an eager step that failed part-way: the attention + Wo hand-off words may hold arrivals that
 // the layer's W1/W3 launch never zeroed
-int eager_step(xh_ctx* ctx, bool with_logits, bool greedy) {
-    const int rc = enqueue_step(ctx, ctx->stream, with_logits, greedy);
+int eager_step(xh_ctx* ctx, bool with_logits, int head) {
+    const int rc = enqueue_step(ctx, ctx->stream, with_logits, head);
     if (rc) hipMemsetAsync(ctx->aw_sync, 0, (size_t)ctx->c.n_layers * AW_SYNC_WORDS * 4, ctx->stream);
     return rc;
 }
@@ -303,18 +354,21 @@ int xalm::check_ready(xh_ctx* ctx) {
     return 0;
 }
 
+void xalm::time_sample_head(xh_ctx* ctx) { launch_sample_head(ctx, ctx->stream); }
+
 void xalm::drop_graphs(xh_ctx* ctx) {
     if (ctx->g_logits) hipGraphExecDestroy(ctx->g_logits);
     if (ctx->g_hydrate) hipGraphExecDestroy(ctx->g_hydrate);
     if (ctx->g_decode) hipGraphExecDestroy(ctx->g_decode);
-    ctx->g_logits = ctx->g_hydrate = ctx->g_decode = nullptr;
+    if (ctx->g_sample) hipGraphExecDestroy(ctx->g_sample);
+    ctx->g_logits = ctx->g_hydrate = ctx->g_decode = ctx->g_sample = nullptr;
 }
 
 
 // the step at host_step_params' position
 int xalm::run_step(xh_ctx* ctx, bool with_logits) {
     if (with_logits) ctx->cand_valid = true;  // the lm_head launch writes candidates
-    if (!ctx->use_graphs) return eager_step(ctx, with_logits, false);
+    if (!ctx->use_graphs) return eager_step(ctx, with_logits, HEAD_GIVEN);
     hipGraphExec_t* ge = with_logits ? &ctx->g_logits : &ctx->g_hydrate;
     if (!*ge) {
         int rc = capture(ctx, with_logits ? 0 : 1, ge);
@@ -338,6 +392,13 @@ int xalm::host_step_params(xh_ctx* ctx, int token, int pos) {
     HIP_TRY(ctx, hipMemcpyAsync(ctx->sp, h, sizeof(StepParams), hipMemcpyHostToDevice, ctx->stream));
     return 0;
 }
+
+namespace {
+// xh_sampling as the header defines it: temperature >= 0, top_k >= 0, top_p in (0, 1]; NaN fails each
+bool sampling_ok(const xh_sampling* s) {
+    return s && s->temperature >= 0.f && s->top_k >= 0 && s->top_p > 0.f && s->top_p <= 1.f;
+}
+}  // namespace
 
 extern "C" {
 
@@ -388,7 +449,7 @@ int xh_decode_greedy(xh_ctx* ctx, int pos, int n_steps, int stop_a, int stop_b, 
         if (ctx->use_graphs) {
             HIP_TRY(ctx, hipGraphLaunch(ctx->g_decode, ctx->stream));
         } else {
-            rc = eager_step(ctx, true, true);
+            rc = eager_step(ctx, true, HEAD_GREEDY);
             if (rc) return rc;
         }
         done = i + 1;
@@ -405,6 +466,94 @@ int xh_decode_greedy(xh_ctx* ctx, int pos, int n_steps, int stop_a, int stop_b, 
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (n_done) *n_done = done;
     return check_aw(ctx);
+}
+
+int xh_decode_sample(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* sampling, int stop_a, int stop_b,
+                     int* tokens_out, int* n_done) {
+    if (n_done) *n_done = 0;
+    if (!sampling_ok(sampling)) return set_err(ctx, XH_E_INVALID, "bad sampling parameters");
+    if (!ctx || n_steps < 0) return XH_E_INVALID;
+    if (pos < 0) return set_err(ctx, XH_E_INVALID, "negative pos");
+    if (ctx->c.vocab_size > SMP_MAX_VOCAB) return set_err(ctx, XH_E_INVALID, "vocab_size > %d", SMP_MAX_VOCAB);
+    if (n_steps > ctx->dec_cap) return set_err(ctx, XH_E_INVALID, "n_steps > %d", ctx->dec_cap);
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    int rc = check_ready(ctx);
+    if (rc) return rc;
+    StepParams* h = ctx->sp_host;
+    h->step = 0;
+    h->pos_next = pos;
+    h->max_seq_len = ctx->c.max_seq_len;
+    HIP_TRY(ctx, hipMemcpyAsync(&ctx->sp->step, &h->step, 3 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    // the parameter block: a pageable source, so the copy has left `sampling` when the call returns
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->samp, sampling, sizeof(xh_sampling), hipMemcpyHostToDevice, ctx->stream));
+    if (ctx->use_graphs && n_steps > 0 && !ctx->g_sample) {
+        rc = capture(ctx, 3, &ctx->g_sample);
+        if (rc) return rc;
+    }
+    // the head reads the logits themselves: cand and cand_valid stay as the lm_head left them
+    // (every step's lm_head launch rewrites cand for the logits it leaves)
+    const bool stops = stop_a >= 0 || stop_b >= 0;
+    int done = 0;
+    for (int i = 0; i < n_steps; i++) {
+        if (ctx->use_graphs) {
+            HIP_TRY(ctx, hipGraphLaunch(ctx->g_sample, ctx->stream));
+        } else {
+            rc = eager_step(ctx, true, HEAD_SAMPLE);
+            if (rc) return rc;
+        }
+        ctx->cand_valid = true;
+        done = i + 1;
+        if (stops) {
+            int tok = -1;
+            HIP_TRY(ctx, hipMemcpyAsync(&tok, ctx->dec_tokens + i, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (tok == stop_a || tok == stop_b) break;
+        }
+    }
+    if (tokens_out && done)
+        HIP_TRY(ctx, hipMemcpyAsync(tokens_out, ctx->dec_tokens, (size_t)done * sizeof(int), hipMemcpyDeviceToHost,
+                                    ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_done) *n_done = done;
+    return check_aw(ctx);
+}
+
+int xh_op_sample(const float* logits, int vocab, const xh_sampling* sampling, uint64_t pos0, int n_draws,
+                 int* tokens_out, int* n_kept_out) {
+    if (!sampling_ok(sampling)) return set_err(nullptr, XH_E_INVALID, "bad sampling parameters");
+    if (!logits || !tokens_out || !n_kept_out || vocab <= 0 || vocab > SMP_MAX_VOCAB || n_draws <= 0 || n_draws > 65536)
+        return set_err(nullptr, XH_E_INVALID, "bad sample args");
+    float* d_logits = nullptr;
+    xh_sampling* d_samp = nullptr;
+    int* d_out = nullptr;
+    int rc = 0;
+    if (hipMalloc((void**)&d_logits, (size_t)vocab * 4) != hipSuccess || hipMalloc((void**)&d_samp, sizeof(xh_sampling)) != hipSuccess ||
+        hipMalloc((void**)&d_out, (size_t)2 * n_draws * sizeof(int)) != hipSuccess)
+        rc = set_err(nullptr, XH_E_HIP, "hipMalloc failed");
+    if (!rc && (hipMemcpy(d_logits, logits, (size_t)vocab * 4, hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(d_samp, sampling, sizeof(xh_sampling), hipMemcpyHostToDevice) != hipSuccess))
+        rc = set_err(nullptr, XH_E_HIP, "hipMemcpy failed");
+    if (!rc) {
+        hipLaunchKernelGGL(sample_op_kernel, dim3(n_draws), dim3(SMP_THREADS), 0, nullptr, (const float*)d_logits, vocab,
+                           (const xh_sampling*)d_samp, (uint32_t)pos0, d_out, d_out + n_draws);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipMemcpy(tokens_out, d_out, (size_t)n_draws * sizeof(int), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(n_kept_out, d_out + n_draws, (size_t)n_draws * sizeof(int), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = set_err(nullptr, XH_E_HIP, "sample op failed: %s", hipGetErrorString(e));
+    }
+    hipFree(d_logits);
+    hipFree(d_samp);
+    hipFree(d_out);
+    return rc;
+}
+
+int xh_philox4x32(uint64_t seed, uint64_t pos, uint32_t out[4]) {
+    if (!out) return set_err(nullptr, XH_E_INVALID, "null argument");
+    out[0] = (uint32_t)pos;  // the counter's first word is pos mod 2^32, the other three are 0
+    out[1] = out[2] = out[3] = 0;
+    philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), out);
+    return 0;
 }
 
 int xh_get_logits(xh_ctx* ctx, float* logits_out) {

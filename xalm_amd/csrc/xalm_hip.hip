@@ -117,6 +117,7 @@ int xh_create(const xh_config* cfg, int device_ordinal, xh_ctx** out) {
     CREATE_TRY(dmalloc(ctx, &ctx->aw_sync, (size_t)c.n_layers * AW_SYNC_WORDS));
     CREATE_TRY(dmalloc(ctx, &ctx->cand, (size_t)ARGMAX_CANDS));
     CREATE_TRY(dmalloc(ctx, &ctx->scan_flag, (size_t)1));
+    CREATE_TRY(dmalloc(ctx, &ctx->samp, (size_t)1));
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device_ordinal) != hipSuccess) {
@@ -176,6 +177,7 @@ void xh_destroy(xh_ctx* ctx) {
     hipFree(ctx->embed); hipFree(ctx->final_norm);
     hipFree(ctx->kv); hipFree(ctx->x); hipFree(ctx->q); hipFree(ctx->attn_out); hipFree(ctx->hb);
     hipFree(ctx->logits); hipFree(ctx->part_o); hipFree(ctx->part_ml); hipFree(ctx->attn_cnt); hipFree(ctx->aw_sync); hipFree(ctx->cand); hipFree(ctx->scan_flag);
+    hipFree(ctx->samp);
     pf_free(ctx);
     hipFree(ctx->pf_wdq); hipFree(ctx->ppl_tgt); hipFree(ctx->ppl_prob); hipFree(ctx->rope_freq); hipFree(ctx->rope_cs);
     hipFree(ctx->aw_trace);

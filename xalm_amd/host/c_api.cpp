@@ -40,6 +40,13 @@ int xalm_encode(const char* path, const char* text, int encode_bos, int* out, in
     });
 }
 
+int xalm_sample(const float* logits, int vocab, const xh_sampling* sampling, uint64_t pos, int* token, int* n_kept) {
+    return guard([&] {
+        if (!sampling || !token) throw std::invalid_argument("xalm_sample: null argument");
+        *token = xalm::sample_logits(logits, vocab, *sampling, pos, n_kept);
+    });
+}
+
 int xalm_load_model(const char* path, int context, int device_ordinal, xh_ctx** out) {
     // the Model releases its context on destruction; detach it for the C caller
     return guard([&] {

@@ -2,11 +2,13 @@
 // over the MI355X decode path.
 //
 //   xalm <checkpoint.xalm> [-m completion|perplexity] [-d hip|cpu] [-i prompt | -f file]
-//                          [-T context] [-n steps] [-g 0|1]
+//                          [-T context] [-n steps] [-g 0|1] [-t temperature] [-k top_k] [-p top_p] [-s seed]
 //
 // -d selects the device as in the reference (src/main.cpp:465-477); this build ships the HIP
 // device.  -g 1 runs the greedy loop on the device (no host round trip per token); -g 0
 // (default) samples on the host each step exactly like run_completion (src/main.cpp:105-115).
+// -t > 0 samples (xh_sampling, include/xalm_hip.h): on the device with -g 1, with the host Sampler::sample
+// with -g 0.
 // Stats are wall clock (the reference divides by user+sys CPU time, src/profiler.h:124-129).
 #include <chrono>
 #include <cmath>
@@ -33,7 +35,12 @@ static void error_usage() {
     fprintf(stderr, "  -m [completion,perplexity] which mode to run in (default - completion)\n");
     fprintf(stderr, "  -T <int> sliding window context length (0 - max)\n");
     fprintf(stderr, "  -n <int> number of steps in completion mode, default 128. 0 = max_seq_len, -1 = infinite\n");
-    fprintf(stderr, "  -g <0|1> greedy decode loop on the device (default 0)\n");
+    fprintf(stderr, "  -g <0|1> decode loop on the device (default 0)\n");
+    fprintf(stderr, "  -t <float> sampling temperature (default 0 - greedy)\n");
+    fprintf(stderr, "  -k <int> top-k, 0 = off (default 0)\n");
+    fprintf(stderr, "  -p <float> top-p in (0, 1], 1 = off (default 1)\n");
+    fprintf(stderr, "  -s <int> sampling seed (default 0); -g 0 and -g 1 draw from the same definition and print\n");
+    fprintf(stderr, "     the same ids for a seed, except where a draw falls within rounding of a boundary\n");
     fprintf(stderr, "  Choose one:\n");
     fprintf(stderr, "    -i <string> input prompt\n");
     fprintf(stderr, "    -f <filepath> input file with prompt\n");
@@ -50,7 +57,7 @@ static void print_ids(const std::vector<int>& ids) {
 
 // run_completion, src/main.cpp:44-128
 static void run_completion(const std::string& path, Device dev, const std::string& prompt, int context, int num_steps,
-                           bool device_loop) {
+                           bool device_loop, const xh_sampling& sampling) {
     const XalmFile file = XalmFile::load(path);
     const Model model = Model::from_xalm(file, context, dev);
     InferenceState state(model.config);
@@ -69,8 +76,10 @@ static void run_completion(const std::string& path, Device dev, const std::strin
     for (size_t pos = 0; pos < encoding.size(); pos++) read_bytes += model.active_bytes(pos);
     const auto t1 = clk::now();
     if (device_loop && num_steps > 0) {
-        const std::vector<int> gen = model.decode_greedy((int)encoding.size(), num_steps, tokenizer.eos_id,
-                                                         tokenizer.eot_id);
+        const std::vector<int> gen =
+            sampling.temperature > 0.f
+                ? model.decode_sample((int)encoding.size(), num_steps, sampling, tokenizer.eos_id, tokenizer.eot_id)
+                : model.decode_greedy((int)encoding.size(), num_steps, tokenizer.eos_id, tokenizer.eot_id);
         for (int t : gen) {
             std::cout << tokenizer.decode_one(encoding.back(), t) << std::flush;
             encoding.push_back(t);
@@ -78,7 +87,8 @@ static void run_completion(const std::string& path, Device dev, const std::strin
         }
     } else {
         for (int i = 0; i < num_steps || num_steps == -1; i++) {
-            const int token_id = sampler.sample_argmax(state);
+            const int token_id = sampling.temperature > 0.f ? sampler.sample(state, sampling, (int)encoding.size())
+                                                            : sampler.sample_argmax(state);
             std::cout << tokenizer.decode_one(encoding.back(), token_id) << std::flush;
             encoding.push_back(token_id);
             if (token_id == tokenizer.eos_id || token_id == tokenizer.eot_id) break;
@@ -128,6 +138,7 @@ int main(int argc, char** argv) {
     std::string path, mode = "completion", prompt = "Q: What is the meaning of life? A:", prompt_path;
     std::string device = "hip";
     int context = 0, num_steps = 128, device_loop = 0;
+    xh_sampling sampling{0.f, 0, 1.f, 0};
     if (argc >= 2) path = argv[1];
     else error_usage();
     for (int i = 2; i < argc;) {
@@ -147,6 +158,10 @@ int main(int argc, char** argv) {
         else if (f == 'T') context = std::stoi(v);
         else if (f == 'n') num_steps = std::stoi(v);
         else if (f == 'g') device_loop = std::stoi(v);
+        else if (f == 't') sampling.temperature = std::stof(v);
+        else if (f == 'k') sampling.top_k = std::stoi(v);
+        else if (f == 'p') sampling.top_p = std::stof(v);
+        else if (f == 's') sampling.seed = std::stoull(v);
         else error_usage();
         i += 2;
     }
@@ -162,7 +177,7 @@ int main(int argc, char** argv) {
     }
     const Device dev = device == "cpu" ? Device::CPU : Device::HIP;
     try {
-        if (mode == "completion") run_completion(path, dev, prompt, context, num_steps, device_loop != 0);
+        if (mode == "completion") run_completion(path, dev, prompt, context, num_steps, device_loop != 0, sampling);
         else run_perplexity(path, dev, prompt, context);
     } catch (const std::exception& e) {
         fprintf(stderr, "error: %s\n", e.what());

@@ -1,7 +1,10 @@
 // model.cpp — Model::from_xalm / forward over the C ABI (jubruckne/Xalm src/model.cpp:48-122),
 // Tokenizer (src/tokenizer.cpp) and Sampler (src/sampler.cpp).
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstring>
+#include <numeric>
 #include <cstdio>
 #include <limits>
 #include <stdexcept>
@@ -82,6 +85,16 @@ std::vector<int> Model::decode_greedy(const int pos, const int n_steps, const in
     std::vector<int> toks((size_t)std::max(n_steps, 1));
     int done = 0;
     check(xh_decode_greedy(_ctx, pos, n_steps, stop_a, stop_b, toks.data(), &done), _ctx, "xh_decode_greedy");
+    toks.resize((size_t)done);
+    return toks;
+}
+
+std::vector<int> Model::decode_sample(const int pos, const int n_steps, const xh_sampling& sampling, const int stop_a,
+                                      const int stop_b) const {
+    std::vector<int> toks((size_t)std::max(n_steps, 1));
+    int done = 0;
+    check(xh_decode_sample(_ctx, pos, n_steps, &sampling, stop_a, stop_b, toks.data(), &done), _ctx,
+          "xh_decode_sample");
     toks.resize((size_t)done);
     return toks;
 }
@@ -199,6 +212,86 @@ float Sampler::sample_prob(const int index, const InferenceState& s) const {
     float sum = 0;
     for (int i = 0; i < vocab_size; ++i) sum += expf(logits[i] - max_val);
     return expf(logits[index] - max_val) / sum;
+}
+
+// ---- seeded sampling: the definition of xh_sampling (include/xalm_hip.h), restated -------------
+int sample_logits(const float* logits, const int vocab, const xh_sampling& p, const uint64_t pos, int* n_kept) {
+    if (!logits || vocab <= 0) throw std::invalid_argument("sample: no logits");
+    if (!(p.temperature >= 0.f) || p.top_k < 0 || !(p.top_p > 0.f && p.top_p <= 1.f))
+        throw std::invalid_argument("sample: temperature >= 0, top_k >= 0, top_p in (0, 1]");
+    int kept_n = 1;
+    int token = 0;
+    const auto done = [&] {
+        if (n_kept) *n_kept = kept_n;
+        return token;
+    };
+    if (p.temperature == 0.f) {  // Sampler::sample_argmax
+        float max_val = std::numeric_limits<float>::min();
+        for (int i = 0; i < vocab; ++i)
+            if (logits[i] > max_val) { max_val = logits[i]; token = i; }
+        return done();
+    }
+    float m = logits[0];
+    int first_max = 0;
+    for (int i = 1; i < vocab; ++i)
+        if (logits[i] > m) { m = logits[i]; first_max = i; }
+    if (!std::isfinite(m)) {  // no finite logit: token 0 (+inf, outside the definition: the first of them)
+        kept_n = m > 0 ? 1 : 0;
+        token = m > 0 ? first_max : 0;
+        return done();
+    }
+    std::vector<double> w((size_t)vocab);
+    for (int i = 0; i < vocab; ++i)
+        w[i] = logits[i] == -std::numeric_limits<float>::infinity() ? 0.0 : (double)expf((logits[i] - m) / p.temperature);
+    // logit descending by its f32 bits, then index ascending
+    const auto key = [&](const int i) {
+        uint32_t u;
+        memcpy(&u, &logits[i], 4);
+        return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    };
+    std::vector<int> order((size_t)vocab);
+    std::iota(order.begin(), order.end(), 0);
+    size_t n = p.top_k > 0 && p.top_k < vocab ? (size_t)p.top_k : (size_t)vocab;
+    if (n < (size_t)vocab || p.top_p < 1.f) {
+        const auto before = [&](const int a, const int b) {
+            const uint32_t ka = key(a), kb = key(b);
+            return ka != kb ? ka > kb : a < b;
+        };
+        if (p.top_p < 1.f) std::sort(order.begin(), order.end(), before);
+        else std::partial_sort(order.begin(), order.begin() + (long)n, order.end(), before);
+    }
+    if (p.top_p < 1.f) {
+        double total = 0.0;
+        for (size_t j = 0; j < n; ++j) total += w[order[j]];
+        const double want = (double)p.top_p * total;
+        double cum = 0.0;
+        size_t j = 0;
+        do cum += w[order[j++]];
+        while (j < n && cum < want);
+        n = j;
+    }
+    std::vector<char> kept((size_t)vocab, 0);
+    for (size_t j = 0; j < n; ++j) kept[order[j]] = 1;
+    kept_n = (int)n;
+    uint32_t x[4];
+    xh_philox4x32(p.seed, pos, x);
+    const double u = (double)(x[0] >> 8) * (1.0 / 16777216.0);
+    double total = 0.0;
+    for (int i = 0; i < vocab; ++i)
+        if (kept[i]) total += w[i];
+    const double thr = u * total;
+    double cum = 0.0;
+    token = first_max;  // rounding left no cumulative weight above thr: cannot happen for u < 1
+    for (int i = 0; i < vocab; ++i)
+        if (kept[i]) {
+            cum += w[i];
+            if (cum > thr) { token = i; break; }
+        }
+    return done();
+}
+
+int Sampler::sample(const InferenceState& s, const xh_sampling& sampling, const int pos) const {
+    return sample_logits(s.logits(), vocab_size, sampling, (uint64_t)pos, nullptr);
 }
 
 }  // namespace xalm

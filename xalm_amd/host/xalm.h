@@ -99,6 +99,9 @@ public:
     void prefill(InferenceState& s, const std::vector<int>& tokens, int pos0) const;
     // greedy decode on the device (no host round trip per token); returns the tokens
     std::vector<int> decode_greedy(int pos, int n_steps, int stop_a = -1, int stop_b = -1) const;
+    // sampled decode on the device (xh_decode_sample): step i drawn at counter pos + i
+    std::vector<int> decode_sample(int pos, int n_steps, const xh_sampling& sampling, int stop_a = -1,
+                                   int stop_b = -1) const;
     void fetch_logits(InferenceState& s) const;
     // run_perplexity's loop on the device (xh_perplexity): element i = Sampler::sample_prob of
     // tokens[i + 1] after forwarding tokens[i] at pos0 + i
@@ -133,6 +136,12 @@ struct Sampler {
     int vocab_size;
     int sample_argmax(const InferenceState& s) const;
     float sample_prob(int index, const InferenceState& s) const;
+    // temperature / top-k / top-p under the definition of xh_sampling (include/xalm_hip.h) at
+    // counter `pos`, the position the token will occupy: the host restatement of the device
+    // sampler, sums in double.  Throws std::invalid_argument for parameters outside it.
+    int sample(const InferenceState& s, const xh_sampling& sampling, int pos) const;
 };
+// the same on a bare logits vector; *n_kept (may be null) = size of the kept set
+int sample_logits(const float* logits, int vocab, const xh_sampling& sampling, uint64_t pos, int* n_kept);
 
 }  // namespace xalm

@@ -93,6 +93,17 @@ class Model:
                                          L.ptr(toks), ctypes.byref(done)), self._ctx)
         return toks[: done.value].tolist()
 
+    def decode_sample(self, pos: int, n_steps: int, temperature: float, top_k: int = 0, top_p: float = 1.0,
+                      seed: int = 0, stop=(-1, -1)) -> list[int]:
+        """The device decode loop with seeded temperature / top-k / top-p sampling (xh_sampling,
+        include/xalm_hip.h): step i is drawn at counter pos + i."""
+        toks = np.zeros(max(n_steps, 1), dtype=np.int32)
+        done = ctypes.c_int(0)
+        s = L.XhSampling(temperature, top_k, top_p, seed)
+        L.check(L.lib().xh_decode_sample(self._ctx, int(pos), int(n_steps), ctypes.byref(s), int(stop[0]),
+                                         int(stop[1]), L.ptr(toks), ctypes.byref(done)), self._ctx)
+        return toks[: done.value].tolist()
+
     def prefill(self, tokens, pos0: int, s: InferenceState | None = None) -> None:
         """Hydrate tokens[0..n) at positions pos0.. (the prompt loop of run_completion,
         src/main.cpp:94-100); the last token's logits land in `s` when given."""
