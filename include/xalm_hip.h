@@ -217,6 +217,28 @@ int xh_perplexity(xh_ctx* ctx, const int* tokens, int n, int pos0, float* probs_
  * -1 = unchanged.  Copies min(cap, *len) words of the trace buffer to `out` first. */
 int xh_debug_trace(xh_ctx* ctx, int enable, uint64_t* out, int cap, int* len);
 
+/* Test hook: wait for the context's stream and copy one activation buffer to the host.  which:
+ * XH_READ_X the residual stream [dim], XH_READ_Q the clipped and roped q [n_heads * head_dim],
+ * XH_READ_HB the GLU output [hidden_dim]; each holds what the last layer of the last step left
+ * (with n_layers = 1 after one xh_forward: that layer's q, its GLU output and the final residual
+ * stream).  cap = floats `out` holds; XH_E_INVALID when that is less than the buffer.  It changes
+ * no kernel and no state. */
+enum xh_read { XH_READ_X = 0, XH_READ_Q = 1, XH_READ_HB = 2 };
+int xh_debug_read(xh_ctx* ctx, int which, float* out, size_t cap);
+
+/* Test hook, host only (no context, no device): the launch shape the decode matvec of `role`
+ * takes for weights of `dtype` (enum xh_dtype) at input length n; the launcher itself calls the
+ * same selection.  role: 0 qkv (rmsnorm, clip, rope, K/V write), 1 W1/W3 (rmsnorm, GLU), 2 Wo / W2
+ * (plain input, residual), 3 lm_head (rmsnorm, argmax candidates), 4 plain store (xh_op_matmul).
+ * Returns enum xh_gemv_shape_id, plus XH_SHAPE_BIG_LDS when the staged input exceeds 64 KiB of
+ * LDS (the launch first raises the kernel's dynamic-LDS limit); -1 for a dtype without a matvec,
+ * an n that is no positive multiple of 32, or an input that does not fit the LDS at all. */
+enum xh_gemv_shape_id {
+    XH_SHAPE_Q384 = 0, XH_SHAPE_PF2PB = 1, XH_SHAPE_PF2P = 2, XH_SHAPE_GQ = 3, XH_SHAPE_GQL = 4, XH_SHAPE_PF2 = 5,
+    XH_SHAPE_W2K = 6, XH_SHAPE_PF8 = 7, XH_SHAPE_SHORT = 8, XH_SHAPE_LONG = 9, XH_SHAPE_BIG_LDS = 16
+};
+int xh_gemv_shape(int role, int dtype, int n);
+
 /* Copy the current device logits to the host. */
 int xh_get_logits(xh_ctx* ctx, float* logits_out);
 

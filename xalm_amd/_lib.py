@@ -38,6 +38,12 @@ OPT_PREFILL_ATTN_SPLIT = 6
 # enum xh_tensor_kind
 EMBED, ATTN_NORM, FFN_NORM, WQ, WK, WV, WO, W1, W2, W3, FINAL_NORM, WCLS = range(12)
 HYDRATE_KV_CACHE, OUTPUT_LOGITS = 0, 1
+# enum xh_read (xh_debug_read)
+READ_X, READ_Q, READ_HB = 0, 1, 2
+# xh_gemv_shape: the matvec roles, enum xh_gemv_shape_id by id, and the over-64-KiB-LDS flag
+ROLE_QKV, ROLE_GLU, ROLE_RESID, ROLE_LOGITS, ROLE_STORE = range(5)
+SHAPE_NAMES = ("Q384", "PF2PB", "PF2P", "GQ", "GQL", "PF2", "W2K", "PF8", "Short", "Long")
+SHAPE_BIG_LDS = 16
 ACT_GELU, ACT_SILU = 0, 1
 
 
@@ -85,6 +91,8 @@ _SIGNATURES = {
     "xh_prefill": (_I, [_P, _P, _I, _I, _I, _P]),
     "xh_perplexity": (_I, [_P, _P, _I, _I, _P]),
     "xh_debug_trace": (_I, [_P, _I, _P, _I, ctypes.POINTER(_I)]),
+    "xh_debug_read": (_I, [_P, _I, _P, _SZ]),
+    "xh_gemv_shape": (_I, [_I, _I, _I]),
     "xh_get_logits": (_I, [_P, _P]),
     "xh_reset": (_I, [_P]),
     "xh_kv_write": (_I, [_P, _I, _I, _I, _I, _P]),
@@ -138,6 +146,12 @@ def op_matmul(x: np.ndarray, w: np.ndarray, dtype: int, n: int, d: int) -> np.nd
     out = np.empty(d, dtype=np.float32)
     check(lib().xh_op_matmul(ptr(out), ptr(x), ptr(w), dtype, n, d))
     return out
+
+
+def gemv_shape(role: int, dtype: int, n: int) -> int:
+    """The launch shape the decode matvec of `role` takes at input length n (xh_gemv_shape): an
+    index into SHAPE_NAMES, plus SHAPE_BIG_LDS above 64 KiB of LDS; -1 = none.  No device needed."""
+    return int(lib().xh_gemv_shape(role, dtype, n))
 
 
 def quantize_blocks(dtype: int, values: np.ndarray) -> np.ndarray:

@@ -29,6 +29,12 @@ inline bool matrix_dtype_ok(int dt) {
 inline size_t dev_row_bytes(int dt, size_t n) { return gq_dt(dt) ? gq_pitch(dt, n) : n * dtype_size(dt); }
 inline size_t file_row_bytes(int dt, size_t n) { return gq_dt(dt) ? n / 32 * gq_block_bytes(dt) : n * dtype_size(dt); }
 inline int elems_per_16b(int dt) { return 16 / (int)dtype_size(dt); }
+// LDS bytes of the decode matvec's x image for an n-column matrix of dt (gemv_smem_bytes); the
+// f32 image is the smallest of any dtype
+inline size_t matrix_lds_bytes(int dt, int n) {
+    const bool nib = gq_dt(dt) && dt != XH_Q8_0;
+    return gemv_lds_bytes(nib ? 32 : gq_dt(dt) ? 16 : elems_per_16b(dt), nib, n);
+}
 // the kernel's decode form for a matrix: fp8 with NaN/Inf codes -> the exact bit decoder
 inline int kdt(int dt, bool special) {
     if (!special) return dt;
@@ -184,6 +190,8 @@ constexpr size_t LT_QKV = 0, LT_AW = 8192, LT_W13 = 16384, LT_W2 = 20480, LT_CLS
 // (prologue, epilogue) pair of gemv.h; false = no instantiation for the dtype / head shape.
 enum GemvRole { GEMV_QKV, GEMV_GLU, GEMV_RESID, GEMV_LOGITS, GEMV_STORE };
 bool launch_gemv(GemvRole role, int dt, const GemvArgs& a, hipStream_t s, int max_waves);
+// the shape launch_gemv takes for (role, dt) at input length n (xh_gemv_shape), -1 = none
+int gemv_shape(int role, int dt, int n);
 bool launch_attn(const AttnArgs& a, int hd, int qpk, int n_kv_heads, int t_max, hipStream_t s);
 int attn_nsplit(int n_kv_heads, int max_seq_len);
 // The dynamic-LDS limit of a kernel above 64 KiB (up to the CU's 160 KiB), set once per (kernel,

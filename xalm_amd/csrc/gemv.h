@@ -944,13 +944,17 @@ __global__ __launch_bounds__(S::THREADS, S::MINW) void gemv_kernel(const GemvArg
     gemv_body<DT, PRO, EPI, S>(a, blockIdx.x, gridDim.x, smem);
 }
 
-// LDS bytes and grid of one launch
+// LDS bytes and grid of one launch.  The x image is whole 64-lane chunks of E elements (E: the
+// weight type's elements per 16 B); nib: the nibble blocks' factor times sum(x) per 32-element
+// block after the image (gq4_nxs)
+constexpr size_t GEMV_LDS_MAX = 160 * 1024;  // the CU's LDS: the most ensure_lds can grant
+inline size_t gemv_lds_bytes(const int E, const bool nib, const int n) {
+    const size_t n_it = ((size_t)n + 64 * E - 1) / (64 * E);
+    return LDS_HEAD_BYTES + n_it * 64 * E * sizeof(float) + (nib ? n_it * 64 * sizeof(float) : 0);
+}
 template <int DT, class S>
 inline size_t gemv_smem_bytes(const int n) {
-    constexpr int E = WDec<DT>::E;
-    const int n_it = (n + 64 * E - 1) / (64 * E);
-    // nibble blocks: the factor times sum(x) per 32-element block after the image (gq4_nxs)
-    return LDS_HEAD_BYTES + (size_t)n_it * 64 * E * sizeof(float) + (gq4_image<DT>() ? (size_t)n_it * 64 * sizeof(float) : 0);
+    return gemv_lds_bytes(WDec<DT>::E, gq4_image<DT>() != 0, n);
 }
 // balanced rounds: at most max_blocks * WAVES waves, each with the same group count
 template <class S>

@@ -42,12 +42,14 @@ using ShapePF2 = GemvShape<512, ROWS, UNROLL, true, 4, true, 2>;  // n <= 4096
 using ShapePF8 = GemvShape<512, ROWS, UNROLL, true, 4, true, 8>;  // n <= 16384 (W2 / Wo inputs)
 
 template <int DT, int PRO, int EPI, class S>
-void launch_gemv_s(const GemvArgs& a, hipStream_t s, int max_waves) {
+bool launch_gemv_s(const GemvArgs& a, hipStream_t s, int max_waves) {
     const size_t smem = gemv_smem_bytes<DT, S>(a.n);
     const int blocks = gemv_blocks<S>(a.rows, max_waves / S::WAVES);
     auto k = gemv_kernel<DT, PRO, EPI, S>;
-    if (smem > 64 * 1024) ensure_lds((const void*)k);
+    if (smem > GEMV_LDS_MAX) return false;  // xh_create refuses such a config (gemv_lds_bytes)
+    if (smem > 64 * 1024 && !ensure_lds((const void*)k)) return false;
     hipLaunchKernelGGL(k, dim3(blocks), dim3(S::THREADS), smem, s, a);
+    return true;
 }
 
 // pipelined PF shape (gemv_rows_pipe: the next row step requested before the current one is
@@ -76,89 +78,161 @@ using ShapeW2K = GemvShape<1024, 1, UNROLL, true, 4, true, 4, 1>;  // n <= 16384
 #endif
 
 
+// The launch shape of one (dtype, prologue, epilogue) at input length n: the one selection, read by
+// the launcher below and by xh_gemv_shape.  HAS_*: the shapes this instance can take at all (the
+// launcher instantiates no others).
+enum {
+    SH_Q384 = XH_SHAPE_Q384, SH_PF2PB = XH_SHAPE_PF2PB, SH_PF2P = XH_SHAPE_PF2P, SH_GQ = XH_SHAPE_GQ, SH_GQL = XH_SHAPE_GQL,
+    SH_PF2 = XH_SHAPE_PF2, SH_W2K = XH_SHAPE_W2K, SH_PF8 = XH_SHAPE_PF8, SH_SHORT = XH_SHAPE_SHORT, SH_LONG = XH_SHAPE_LONG
+};
 template <int DT, int PRO, int EPI>
-void launch_gemv_t(const GemvArgs& a, hipStream_t s, int max_waves) {
-    constexpr int E = WDec<DT>::E;
-    // gguf blocks take the staged shapes below (4 rows per wave measured slower: Q8_0 442 ->
-    // 303 tok/s, Q4_0 560 -> 506)
-    // PF needs whole first chunks (n >= 64 E U) and x in XN float4 per thread
-    const bool pf = !gq_dt(DT) && a.n % 4 == 0 && a.n >= 64 * E * UNROLL;
-    if constexpr ((EPI == EPI_QKV || EPI == EPI_GLU) && !gq_dt(DT)) {
-        if constexpr (EPI == EPI_QKV && E <= 8 && QKV_T384) {
-            if (pf && a.n / 4 <= 3 * 384 && a.n % (64 * E * UNROLL) == 0)
-                return launch_gemv_s<DT, PRO, EPI, ShapeQ384>(a, s, 3 * (max_waves / 2));
+struct ShapeSel {
+    static constexpr int E = WDec<DT>::E;
+    static constexpr bool GQ = gq_dt(DT);
+    static constexpr bool HAS_PF2P = (EPI == EPI_QKV || EPI == EPI_GLU) && !GQ;
+    static constexpr bool HAS_Q384 = HAS_PF2P && EPI == EPI_QKV && E <= 8 && QKV_T384;
+    static constexpr bool HAS_PF2PB = HAS_PF2P && EPI == EPI_QKV && E >= 16 && GEMV_BAL_FP8_QKV;
+    static constexpr bool HAS_GQL = GQ && PRO == PRO_PLAIN;
+    static constexpr bool HAS_W2K = PRO == PRO_PLAIN && EPI == EPI_RESID && E >= 16 && W2_T1024;
+    static constexpr bool HAS_PF8 = PRO == PRO_PLAIN && !HAS_W2K;
+    static constexpr bool HAS_SHORT = PRO != PRO_PLAIN;
+    // gguf blocks take the staged shapes (4 rows per wave measured slower: Q8_0 442 -> 303 tok/s,
+    // Q4_0 560 -> 506): the nibble types (Q4_0, Q4_1, Q5_0, Q5_1) hold 32 elements per chunk.
+    // Q4_0 rows of a 4096-wide input are 2 chunks, so 2 chunks per step; W2-long inputs (14336:
+    // 14 / 7 chunks per row) step by 2 (Q8_0) / 1 (Q4_0) chunks
+    static constexpr int UG = E == 32 ? 2 : UNROLL;
+    static constexpr int UL = E == 32 ? 1 : 2;
+
+    static int pick(const int n) {
+        // PF needs whole first chunks (n >= 64 E U) and x in XN float4 per thread
+        const bool pf = !GQ && n % 4 == 0 && n >= 64 * E * UNROLL;
+        if constexpr (HAS_PF2P) {
+            const bool whole = pf && n % (64 * E * UNROLL) == 0;
+            if constexpr (HAS_Q384) {
+                if (whole && n / 4 <= 3 * 384) return SH_Q384;
+            }
+            if constexpr (HAS_PF2PB) {
+                if (whole && n / 4 <= 2 * 512) return SH_PF2PB;
+            }
+            if (whole && n / 4 <= 2 * 512) return SH_PF2P;
         }
-        if constexpr (EPI == EPI_QKV && E >= 16 && GEMV_BAL_FP8_QKV) {
-            // one-byte qkv rows: 3072 one-step groups, 512 workgroups of 6 busy waves (fp8 qkv
-            // 7.3 -> 7.1 us, decode +0.5 %, profiles/r06_decode_ab.txt ab9)
-            using ShapePF2PB = GemvShape<512, ROWS, UNROLL, true, 4, true, 2, 2, true>;
-            if (pf && a.n / 4 <= 2 * 512 && a.n % (64 * E * UNROLL) == 0)
+        if constexpr (GQ) {
+            if (n % 4 == 0 && n / 4 <= 2 * 512 && n % (64 * E * UG) == 0) return SH_GQ;
+            if constexpr (HAS_GQL) {
+                if (n % 4 == 0 && n / 4 <= 8 * 512 && n % (64 * E * UL) == 0) return SH_GQL;
+            }
+        }
+        if (pf && n / 4 <= 2 * 512) return SH_PF2;
+        if constexpr (HAS_W2K) return pf && n / 4 <= 4 * 1024 ? SH_W2K : SH_LONG;
+        else if constexpr (PRO == PRO_PLAIN) return pf && n / 4 <= 8 * 512 ? SH_PF8 : SH_LONG;
+        else return gemv_smem_bytes<DT, ShapeShort>(n) <= 40 * 1024 ? SH_SHORT : SH_LONG;
+    }
+};
+
+template <int DT, int PRO, int EPI>
+bool launch_gemv_t(const GemvArgs& a, hipStream_t s, int max_waves) {
+    using Sel = ShapeSel<DT, PRO, EPI>;
+    switch (Sel::pick(a.n)) {
+        case SH_Q384:
+            if constexpr (Sel::HAS_Q384) return launch_gemv_s<DT, PRO, EPI, ShapeQ384>(a, s, 3 * (max_waves / 2));
+            break;
+        case SH_PF2PB:
+            if constexpr (Sel::HAS_PF2PB) {
+                // one-byte qkv rows: 3072 one-step groups, 512 workgroups of 6 busy waves (fp8 qkv
+                // 7.3 -> 7.1 us, decode +0.5 %, profiles/r06_decode_ab.txt ab9)
+                using ShapePF2PB = GemvShape<512, ROWS, UNROLL, true, 4, true, 2, 2, true>;
                 return launch_gemv_s<DT, PRO, EPI, ShapePF2PB>(a, s, max_waves);
-        }
-        if (pf && a.n / 4 <= 2 * 512 && a.n % (64 * E * UNROLL) == 0)
-            return launch_gemv_s<DT, PRO, EPI, ShapePF2P>(a, s, max_waves);
-    }
-    if constexpr (gq_dt(DT)) {
-        // gguf blocks: the pipelined PF shapes with the block scales loaded beside the codes.
-        // Q4_0 rows of a 4096-wide input are 2 chunks, so 2 chunks per step; W2-long inputs
-        // (14336: 14 / 7 chunks per row) step by 2 (Q8_0) / 1 (Q4_0) chunks
-        constexpr int UG = E == 32 ? 2 : UNROLL;  // the nibble types (Q4_0, Q4_1, Q5_0, Q5_1): 32 elements per chunk
-        // W1/W3 (GEMV_BAL_GQ_GLU): balanced grid, Q4_0 15.0 -> 14.0 us (profiles/r06_decode_ab.txt ab8)
-        using ShapeGQ = GemvShape<512, ROWS, UG, true, 4, true, 2, 2, EPI == EPI_GLU && GEMV_BAL_GQ_GLU>;
-        if (a.n % 4 == 0 && a.n / 4 <= 2 * 512 && a.n % (64 * E * UG) == 0)
-            return launch_gemv_s<DT, PRO, EPI, ShapeGQ>(a, s, max_waves);
-        if constexpr (PRO == PRO_PLAIN) {
-            constexpr int UL = E == 32 ? 1 : 2;
-            using ShapeGQL = GemvShape<512, ROWS, UL, true, 4, true, 8, 2>;
-            if (a.n % 4 == 0 && a.n / 4 <= 8 * 512 && a.n % (64 * E * UL) == 0)
+            }
+            break;
+        case SH_PF2P:
+            if constexpr (Sel::HAS_PF2P) return launch_gemv_s<DT, PRO, EPI, ShapePF2P>(a, s, max_waves);
+            break;
+        case SH_GQ:
+            if constexpr (Sel::GQ) {
+                // gguf blocks: the pipelined PF shapes with the block scales loaded beside the codes.
+                // W1/W3 (GEMV_BAL_GQ_GLU): balanced grid, Q4_0 15.0 -> 14.0 us (profiles/r06_decode_ab.txt ab8)
+                using ShapeGQ = GemvShape<512, ROWS, Sel::UG, true, 4, true, 2, 2, EPI == EPI_GLU && GEMV_BAL_GQ_GLU>;
+                return launch_gemv_s<DT, PRO, EPI, ShapeGQ>(a, s, max_waves);
+            }
+            break;
+        case SH_GQL:
+            if constexpr (Sel::HAS_GQL) {
+                using ShapeGQL = GemvShape<512, ROWS, Sel::UL, true, 4, true, 8, 2>;
                 return launch_gemv_s<DT, PRO, EPI, ShapeGQL>(a, s, max_waves);
-        }
+            }
+            break;
+        case SH_PF2: return launch_gemv_s<DT, PRO, EPI, ShapePF2>(a, s, max_waves);
+        case SH_W2K:
+            if constexpr (Sel::HAS_W2K) return launch_gemv_s<DT, PRO, EPI, ShapeW2K>(a, s, max_waves);
+            break;
+        case SH_PF8:
+            if constexpr (Sel::HAS_PF8) return launch_gemv_s<DT, PRO, EPI, ShapePF8>(a, s, max_waves);
+            break;
+        case SH_SHORT:
+            if constexpr (Sel::HAS_SHORT) return launch_gemv_s<DT, PRO, EPI, ShapeShort>(a, s, max_waves);
+            break;
+        case SH_LONG: return launch_gemv_s<DT, PRO, EPI, ShapeLong>(a, s, max_waves);
     }
-    if (pf && a.n / 4 <= 2 * 512) launch_gemv_s<DT, PRO, EPI, ShapePF2>(a, s, max_waves);
-    else if constexpr (PRO == PRO_PLAIN && EPI == EPI_RESID && E >= 16 && W2_T1024) {
-        if (pf && a.n / 4 <= 4 * 1024) launch_gemv_s<DT, PRO, EPI, ShapeW2K>(a, s, max_waves);
-        else launch_gemv_s<DT, PRO, EPI, ShapeLong>(a, s, max_waves);
-    } else if constexpr (PRO == PRO_PLAIN) {
-        if (pf && a.n / 4 <= 8 * 512) launch_gemv_s<DT, PRO, EPI, ShapePF8>(a, s, max_waves);
-        else launch_gemv_s<DT, PRO, EPI, ShapeLong>(a, s, max_waves);
-    } else if (gemv_smem_bytes<DT, ShapeShort>(a.n) <= 40 * 1024) {
-        launch_gemv_s<DT, PRO, EPI, ShapeShort>(a, s, max_waves);
-    } else {
-        launch_gemv_s<DT, PRO, EPI, ShapeLong>(a, s, max_waves);
-    }
+    return false;
 }
 
+// what launch_gemv_dt does with a (dtype, length): F = Launch (run it) or Pick (name its shape)
 template <int PRO, int EPI>
-bool launch_gemv_dt(int dt, const GemvArgs& a, hipStream_t s, int max_blocks) {
-    switch (dt) {
-        case XH_F32: launch_gemv_t<XH_F32, PRO, EPI>(a, s, max_blocks); return true;
-        case XH_F16: launch_gemv_t<XH_F16, PRO, EPI>(a, s, max_blocks); return true;
-        case XH_BF16: launch_gemv_t<XH_BF16, PRO, EPI>(a, s, max_blocks); return true;
-        case XH_F8_E4M3: launch_gemv_t<XH_F8_E4M3, PRO, EPI>(a, s, max_blocks); return true;
-        case XH_F8_E5M2: launch_gemv_t<XH_F8_E5M2, PRO, EPI>(a, s, max_blocks); return true;
-        case XH_Q8: launch_gemv_t<XH_Q8, PRO, EPI>(a, s, max_blocks); return true;
-        case XH_F8_E4M3_EXACT: launch_gemv_t<XH_F8_E4M3_EXACT, PRO, EPI>(a, s, max_blocks); return true;
-        case XH_F8_E5M2_EXACT: launch_gemv_t<XH_F8_E5M2_EXACT, PRO, EPI>(a, s, max_blocks); return true;
-        case XH_Q8_0: launch_gemv_t<XH_Q8_0, PRO, EPI>(a, s, max_blocks); return true;
-        case XH_Q4_0: launch_gemv_t<XH_Q4_0, PRO, EPI>(a, s, max_blocks); return true;
-        case XH_Q4_1: launch_gemv_t<XH_Q4_1, PRO, EPI>(a, s, max_blocks); return true;
-        case XH_Q5_0: launch_gemv_t<XH_Q5_0, PRO, EPI>(a, s, max_blocks); return true;
-        case XH_Q5_1: launch_gemv_t<XH_Q5_1, PRO, EPI>(a, s, max_blocks); return true;
-        default: return false;
+struct Launch {
+    const GemvArgs& a; hipStream_t s; int max_waves;
+    template <int DT> int run() const { return launch_gemv_t<DT, PRO, EPI>(a, s, max_waves) ? 1 : 0; }
+};
+template <int PRO, int EPI>
+struct Pick {
+    int n;
+    template <int DT> int run() const {
+        const size_t smem = gemv_smem_bytes<DT, ShapeLong>(n);  // the same for every shape
+        if (smem > GEMV_LDS_MAX) return -1;
+        return ShapeSel<DT, PRO, EPI>::pick(n) | (smem > 64 * 1024 ? XH_SHAPE_BIG_LDS : 0);
     }
+};
+// -1: no instantiation for the dtype
+template <class F>
+int for_dt(int dt, const F& f) {
+    switch (dt) {
+        case XH_F32: return f.template run<XH_F32>();
+        case XH_F16: return f.template run<XH_F16>();
+        case XH_BF16: return f.template run<XH_BF16>();
+        case XH_F8_E4M3: return f.template run<XH_F8_E4M3>();
+        case XH_F8_E5M2: return f.template run<XH_F8_E5M2>();
+        case XH_Q8: return f.template run<XH_Q8>();
+        case XH_F8_E4M3_EXACT: return f.template run<XH_F8_E4M3_EXACT>();
+        case XH_F8_E5M2_EXACT: return f.template run<XH_F8_E5M2_EXACT>();
+        case XH_Q8_0: return f.template run<XH_Q8_0>();
+        case XH_Q4_0: return f.template run<XH_Q4_0>();
+        case XH_Q4_1: return f.template run<XH_Q4_1>();
+        case XH_Q5_0: return f.template run<XH_Q5_0>();
+        case XH_Q5_1: return f.template run<XH_Q5_1>();
+        default: return -1;
+    }
+}
+// every role as its (prologue, epilogue) pair
+template <template <int, int> class F, class... A>
+int for_role(int role, int dt, A... args) {
+    switch (role) {
+        case GEMV_QKV: return for_dt(dt, F<PRO_RMSNORM, EPI_QKV>{args...});
+        case GEMV_GLU: return for_dt(dt, F<PRO_RMSNORM, EPI_GLU>{args...});
+        case GEMV_RESID: return for_dt(dt, F<PRO_PLAIN, EPI_RESID>{args...});
+        case GEMV_LOGITS: return for_dt(dt, F<PRO_RMSNORM, EPI_LOGITS>{args...});
+        case GEMV_STORE: return for_dt(dt, F<PRO_PLAIN, EPI_STORE>{args...});
+    }
+    return -1;
 }
 
 }  // namespace
 
 bool xalm::launch_gemv(GemvRole role, int dt, const GemvArgs& a, hipStream_t s, int max_waves) {
-    switch (role) {
-        case GEMV_QKV: return launch_gemv_dt<PRO_RMSNORM, EPI_QKV>(dt, a, s, max_waves);
-        case GEMV_GLU: return launch_gemv_dt<PRO_RMSNORM, EPI_GLU>(dt, a, s, max_waves);
-        case GEMV_RESID: return launch_gemv_dt<PRO_PLAIN, EPI_RESID>(dt, a, s, max_waves);
-        case GEMV_LOGITS: return launch_gemv_dt<PRO_RMSNORM, EPI_LOGITS>(dt, a, s, max_waves);
-        case GEMV_STORE: return launch_gemv_dt<PRO_PLAIN, EPI_STORE>(dt, a, s, max_waves);
-    }
-    return false;
+    return for_role<Launch, const GemvArgs&, hipStream_t, int>(role, dt, a, s, max_waves) == 1;
+}
+
+int xalm::gemv_shape(int role, int dt, int n) {
+    if (n <= 0 || n % 32) return -1;
+    return for_role<Pick, int>(role, dt, n);
 }
 
 namespace {

@@ -47,6 +47,10 @@ int tensor_slot(xh_ctx* ctx, int kind, int layer, int dtype, Slot* out) {
     if (is_norm ? !(dtype == XH_F32 || dtype == XH_BF16) : !matrix_dtype_ok(dtype))
         return set_err(ctx, XH_E_INVALID, "tensor kind %d: unsupported dtype %d", kind, dtype);
     if (gq_dt(dtype) && cols % 32) return set_err(ctx, XH_E_INVALID, "tensor kind %d: %zu columns, not whole 32-element blocks", kind, cols);
+    // a matvec input: its x image must fit the CU's LDS (the embedding is one only when tied)
+    if (!is_norm && (kind != XH_EMBED || c.tie_word_embeddings) && matrix_lds_bytes(dtype, (int)cols) > GEMV_LDS_MAX)
+        return set_err(ctx, XH_E_INVALID, "tensor kind %d: the %zu-element input of dtype %d needs %zu bytes of LDS, over %zu",
+                       kind, cols, dtype, matrix_lds_bytes(dtype, (int)cols), GEMV_LDS_MAX);
     const size_t rb = dev_row_bytes(dtype, cols);
     out->rows = rows;
     out->cols = cols;

@@ -81,6 +81,17 @@ int xh_create(const xh_config* cfg, int device_ordinal, xh_ctx** out) {
                            c.head_dim, qpk);
     }
     if (c.act != XH_ACT_GELU && c.act != XH_ACT_SILU) return set_err(nullptr, XH_E_INVALID, "bad act");
+    {
+        // the matvecs stage their whole input in LDS: dim (qkv, W1/W3, lm_head), hidden_dim (W2) and
+        // n_heads * head_dim (Wo) must fit under the smallest image any weight dtype gives (F32's;
+        // xh_upload checks the dtype's own)
+        const long long widest = std::max({(long long)c.dim, (long long)c.hidden_dim, (long long)c.n_heads * c.head_dim});
+        if (widest > INT32_MAX || matrix_lds_bytes(XH_F32, (int)widest) > GEMV_LDS_MAX)
+            return set_err(nullptr, XH_E_INVALID,
+                           "a matvec input of %lld elements (the widest of dim, hidden_dim, n_heads * head_dim) does not "
+                           "fit the %zu bytes of LDS a workgroup stages it in",
+                           widest, GEMV_LDS_MAX);
+    }
 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -242,6 +253,25 @@ int xh_debug_trace(xh_ctx* ctx, int enable, uint64_t* out, int cap, int* len) {
     }
     return 0;
 }
+
+int xh_debug_read(xh_ctx* ctx, int which, float* out, size_t cap) {
+    if (!ctx || !out) return set_err(ctx, XH_E_INVALID, "null argument");
+    const float* src = nullptr;
+    size_t n = 0;
+    switch (which) {
+        case XH_READ_X: src = ctx->x; n = (size_t)ctx->c.dim; break;
+        case XH_READ_Q: src = ctx->q; n = (size_t)ctx->q_dim; break;
+        case XH_READ_HB: src = ctx->hb; n = (size_t)ctx->c.hidden_dim; break;
+        default: return set_err(ctx, XH_E_INVALID, "xh_debug_read: unknown buffer %d", which);
+    }
+    if (cap < n) return set_err(ctx, XH_E_INVALID, "xh_debug_read: %zu floats do not hold the buffer's %zu", cap, n);
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, copy_sync(ctx, out, src, n * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int xh_gemv_shape(int role, int dtype, int n) { return gemv_shape(role, dtype, n); }
 
 int xh_get_option(const xh_ctx* ctx, int option, int* value) {
     if (!ctx || !value) return XH_E_INVALID;

@@ -129,6 +129,15 @@ class Model:
         L.check(L.lib().xh_debug_trace(self._ctx, int(enable), L.ptr(out), n.value, ctypes.byref(n)), self._ctx)
         return out
 
+    def debug_read(self, which: int) -> np.ndarray:
+        """One activation buffer as the last step left it (xh_debug_read): L.READ_X the residual
+        stream, L.READ_Q the clipped and roped q, L.READ_HB the GLU output."""
+        c = self.config
+        n = {L.READ_X: c.dim, L.READ_Q: c.n_heads * c.head_dim, L.READ_HB: c.hidden_dim}[which]
+        out = np.empty(n, dtype=np.float32)
+        L.check(L.lib().xh_debug_read(self._ctx, int(which), L.ptr(out), n), self._ctx)
+        return out
+
     def get_logits(self, s: InferenceState):
         L.check(L.lib().xh_get_logits(self._ctx, L.ptr(s.logits())), self._ctx)
 
