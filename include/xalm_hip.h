@@ -201,6 +201,13 @@ int xh_decode_sample(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* sampl
  * (src/main.cpp:94-100) in one call.  logits_out may be NULL. */
 int xh_prefill(xh_ctx* ctx, const int* tokens, int n, int pos0, int want_logits, float* logits_out);
 
+/* Host only (no device work): how xh_prefill would run n tokens at pos0 under the context's
+ * current options.  *n_batched = tokens that run in batched passes (the rest take the per-token
+ * loop), *n_passes = the number of those passes; either may be NULL.  xh_prefill plans with the
+ * same function.  Under XH_OPT_PREFILL 4 the pass length is known once a prompt has probed
+ * hipBLASLt's plans. */
+int xh_prefill_route(const xh_ctx* ctx, int n, int pos0, int* n_batched, int* n_passes);
+
 /* Perplexity scoring, the loop of run_perplexity (src/main.cpp:243-254) in one call: forward
  * tokens[0..n-1) at positions pos0.. with logits and write probs_out[i] =
  * Sampler::sample_prob(tokens[i+1]) (src/sampler.cpp:3-17; n-1 floats, caller-owned).  The
@@ -290,12 +297,24 @@ int xh_set_graphs(xh_ctx* ctx, int enable);
  * chip with (KV head, 128-row query tile) workgroups walks a long history in splits (each with its
  * own running max / sum), merged per row in split order afterwards (deterministic); 0 = one
  * workgroup walks the whole history.  Same math up to f32 rounding. */
+/* XH_OPT_PREFILL_RING (default 1): a prompt that reaches past the KV ring (pos0 + n > max_seq_len)
+ * is cut at position max_seq_len; the part below runs the batched passes as ever, the part from
+ * there on — where the reference keeps two sink slots, writes token p to slot 2 + (p - 2) %
+ * (max_seq_len - 2) and re-rotates the sink K rows every step (src/infer.cpp:608-613, :416-431) —
+ * runs ring passes of at most min(pass length, max_seq_len - 2) tokens: each row attends over
+ * the sinks at its own rotation count, the history its predecessors in the pass have not
+ * overwritten, and the pass up to itself; the pass's K/V reach the ring after its attention.
+ * Under XH_OPT_PREFILL_ATTN 1 at head_dim 128 only; other head shapes and modes, and one or two
+ * tokens (alone or left over by the passes) keep the per-token loop there.  0 = any prompt that reaches
+ * past the ring takes the per-token loop as a whole.  Same math up to f32 rounding; the sink
+ * K rows come out bit-identical on both routes. */
 enum xh_option {
     XH_OPT_FUSE_ATTN_WO = 1,
     XH_OPT_PREFILL = 2,
     XH_OPT_PREFILL_GLU_SPLIT = 3,
     XH_OPT_PREFILL_ATTN = 5,
-    XH_OPT_PREFILL_ATTN_SPLIT = 6
+    XH_OPT_PREFILL_ATTN_SPLIT = 6,
+    XH_OPT_PREFILL_RING = 7
 };
 int xh_set_option(xh_ctx* ctx, int option, int value);
 int xh_get_option(const xh_ctx* ctx, int option, int* value);

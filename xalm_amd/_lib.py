@@ -34,6 +34,7 @@ OPT_PREFILL = 2
 OPT_PREFILL_GLU_SPLIT = 3
 OPT_PREFILL_ATTN = 5
 OPT_PREFILL_ATTN_SPLIT = 6
+OPT_PREFILL_RING = 7
 
 # enum xh_tensor_kind
 EMBED, ATTN_NORM, FFN_NORM, WQ, WK, WV, WO, W1, W2, W3, FINAL_NORM, WCLS = range(12)
@@ -89,6 +90,7 @@ _SIGNATURES = {
     "xh_op_sample": (_I, [_P, _I, ctypes.POINTER(XhSampling), ctypes.c_uint64, _I, _P, _P]),
     "xh_philox4x32": (_I, [ctypes.c_uint64, ctypes.c_uint64, _P]),
     "xh_prefill": (_I, [_P, _P, _I, _I, _I, _P]),
+    "xh_prefill_route": (_I, [_P, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "xh_perplexity": (_I, [_P, _P, _I, _I, _P]),
     "xh_debug_trace": (_I, [_P, _I, _P, _I, ctypes.POINTER(_I)]),
     "xh_debug_read": (_I, [_P, _I, _P, _SZ]),

@@ -119,6 +119,11 @@ struct xh_ctx {
     float *pf_po = nullptr, *pf_pml = nullptr;   // [T][nsplit][q_dim], [T][nsplit][n_heads][2]
     int* pf_cnt = nullptr;                       // [T][n_kv_heads] split tickets
     int pf_po_cap = 0;                           // tokens those hold
+    // ring passes (positions >= max_seq_len, XH_OPT_PREFILL_RING; allocated on the first one):
+    bool pf_ring = true;                         // XH_OPT_PREFILL_RING
+    uint16_t *pf_ks = nullptr, *pf_vs = nullptr; // [T][kv_dim] the pass's K / V rows until its attention ran
+    uint16_t* pf_sinkv = nullptr;                // [T][2][kv_dim] sink K rows after 1 .. T re-rotations (one layer's)
+    int pf_ring_cap = 0;                         // tokens those hold
     // xh_perplexity: per-token logits of a pass, targets, probabilities (allocated on first use)
     float* pf_logits = nullptr;                  // [T][vocab]
     int* pf_tgt = nullptr;                       // [T]

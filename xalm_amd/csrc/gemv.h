@@ -257,6 +257,19 @@ __device__ __forceinline__ void rotate_sinks(const GemvArgs& a, const int kv_sin
         }
     }
 }
+// The same step for one (even, odd) pair, as rotate_sinks above is compiled: the compiler contracts
+// its two expressions into fma(fcr, k0, -(fci k1)) and fma(fcr, k1, fci k0), each product and each
+// fma rounded to f32, the fp16 conversion a separate rounding.  A ring pass of a prompt
+// (prefill_sink_versions_kernel, prefill.h) iterates a sink row with this function, spelled out
+// because a contraction left to the compiler may fuse the other product of the sum at another
+// site, and a few hundred fp16 round trips later the rows differ.  The two routes are held
+// together by a test (bit-identical sink rows, tests/test_ring_prefill_gpu.py).  The caller
+// rounds the results to fp16.
+__device__ __forceinline__ void sink_rotate_pair(float& k0, float& k1, const float fcr, const float fci) {
+    const float a = k0, b = k1;
+    k0 = __builtin_fmaf(fcr, a, -(fci * b));
+    k1 = __builtin_fmaf(fcr, b, fci * a);
+}
 
 // SC1: activations another workgroup of the same launch reads are stored write-through, and
 // the residual it may have written is read with sc1 loads; otherwise plain accesses.

@@ -614,6 +614,10 @@ struct PfEpiArgs {
     float qkv_clip;
     int pos0;           // position of token 0 of the pass (ring slot = pos, no wrap in a pass)
     int act;
+    // a ring pass (positions >= max_seq_len): token t's K/V rows go to these staging rows
+    // [n][kv_dim] instead of the ring, which its attention still reads as it stood (null: the ring)
+    uint16_t* kstage;
+    uint16_t* vstage;
 };
 
 __global__ __launch_bounds__(256) void prefill_epi_kernel(const PfEpiArgs a) {
@@ -656,7 +660,8 @@ __global__ __launch_bounds__(256) void prefill_epi_kernel(const PfEpiArgs a) {
             const bool isk = r < a.q_dim + a.kv_dim;
             const int kr = isk ? r - a.q_dim : r - a.q_dim - a.kv_dim;
             if (isk) rope_pair(v0, v1, kr, a.head_dim, pos, a.rope_freq);
-            uint16_t* dst = (isk ? a.kcache : a.vcache) + (size_t)pos * a.kv_dim + kr;
+            uint16_t* dst = a.kstage ? (isk ? a.kstage : a.vstage) + (size_t)t * a.kv_dim + kr
+                                     : (isk ? a.kcache : a.vcache) + (size_t)pos * a.kv_dim + kr;
             *(uint32_t*)dst = (uint32_t)f32_to_f16_bits(v0) | ((uint32_t)f32_to_f16_bits(v1) << 16);
         }
     }
@@ -706,23 +711,33 @@ __global__ __launch_bounds__(ATTN_THREADS) void prefill_attn_kernel(AttnArgs a, 
 // lane pair (l, l ^ 32), p = e^(s - m) split into exact f16 hi + lo (|p - hi - lo| <= 2^-25), O and
 // the running sum rescaled by e^(m_old - m) — skipped when it is 1 in every lane (exact: x * 1 = x).
 // e^x by v_exp_f32 of x log2(e) (__expf: <= 2e-6 relative at the x > -20 that carry weight).
-template <int NDT>
+// LOW (the ring pass, prefill_fa2_ring_kernel): a row also has a first visible key `lo`, masked
+// below it on the tiles where lowdiag (wave-uniform) says some row's `lo` lies inside or past the
+// tile.  A row may then see nothing of a tile, or nothing so far: its running max stays -inf,
+// and the exponentials are taken against 0 instead, so that nothing forms e^(-inf - (-inf)); p
+// and alpha come out 0 and (m, l, O) stay (-inf, 0, 0).
+template <int NDT, bool LOW = false>
 __device__ __forceinline__ void fa_softmax_tile(const f32x16& st, const int b, const int pos, const int h,
                                                 const float sc, const bool diag, float& m, float& lsum,
-                                                f32x16 (&o)[NDT], f16x8 (&ph)[2], f16x8 (&pl)[2]) {
+                                                f32x16 (&o)[NDT], f16x8 (&ph)[2], f16x8 (&pl)[2], const int lo = 0,
+                                                const bool lowdiag = false) {
     float sv[16];
     float tm = -INFINITY;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
         float v = st[r] * sc;
         if (diag) v = b + (r & 3) + 8 * (r >> 2) + 4 * h <= pos ? v : -INFINITY;
+        if constexpr (LOW) {
+            if (lowdiag) v = b + (r & 3) + 8 * (r >> 2) + 4 * h >= lo ? v : -INFINITY;
+        }
         sv[r] = v;
         tm = fmaxf(tm, v);
     }
     tm = fmaxf(tm, __shfl_xor(tm, 32));
-    const float mn = fmaxf(m, tm);  // finite: slot 0 <= pos on the first tile
+    const float mx = fmaxf(m, tm);  // finite: slot 0 <= pos on the first tile (LOW: may be -inf)
+    const float mn = LOW && mx == -INFINITY ? 0.f : mx;
     const float alpha = __expf(m - mn);
-    m = mn;
+    m = mx;
     float ps = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
@@ -920,10 +935,31 @@ typedef short fa_s16x4 __attribute__((ext_vector_type(4)));
 // row's pos and its first tile has a finite max; it writes its unnormalised O and (m, l) to
 // part_o [z][n][q_stride] / part_ml [z][n][n_heads], and prefill_fa_merge_kernel combines the
 // splits in split order (deterministic).
-template <int QPK, int NW>
-__global__ __launch_bounds__(64 * NW, 2) void prefill_fa2_kernel(const float* q, const uint16_t* kc, const uint16_t* vc,
-                                                               float* out, int n, int pos0, int q_stride, int kv_dim,
-                                                               float* part_o, float2* part_ml) {
+//
+// RING (prefill_fa2_ring_kernel: a pass at positions >= max_seq_len = L, where the reference
+// keeps two sink slots and writes token p to slot 2 + (p - 2) % (L - 2), src/infer.cpp:611-613):
+// the same walk over a virtual key sequence of W + n rows, W = L - 2.  Virtual row u < W is
+// ring slot 2 + (hoff + u) % W with hoff = kv_pos(first position of the pass) - 2: the history
+// in the order the pass overwrites it; row W + t is the pass's own token t in the staging rows
+// (ks / vs), for the ring must stay as it stood while the pass attends.  Query row t sees
+// exactly the window u in [t + 1, W + t]: the history its predecessors have not overwritten and
+// pass tokens 0 .. t.  So pos0 = W gives the causal bound as it stands, a second bound masks from
+// below, the walk starts at the stage of the workgroup's first visible row, and the source row
+// of each DMA lane goes through the map above (the interval wraps from slot L - 1 to slot 2
+// inside it).  The sinks (their K differs from row to row) are not walked here: this kernel
+// always writes split partials, and prefill_fa_merge_kernel adds the sinks to them.  Splits divide
+// the workgroup's own stage range evenly, so a split — or the whole walk — can be invisible
+// to a row; it then writes (m, l, O) = (-inf, 0, 0).
+struct FaRing {
+    const uint16_t* ks;  // [n][kv_dim] the pass's K rows (fp16, roped at their positions)
+    const uint16_t* vs;
+    int W;               // max_seq_len - 2
+    int hoff;            // kv_pos(first position of the pass) - 2
+};
+template <int QPK, int NW, bool RING>
+__device__ __forceinline__ void fa2_body(const float* q, const uint16_t* kc, const uint16_t* vc, float* out, const int n,
+                                         const int pos0, const int q_stride, const int kv_dim, float* part_o,
+                                         float2* part_ml, const FaRing rg) {
     constexpr int HD = 128;
     constexpr int TPW = 32 / QPK;        // tokens per wave
     constexpr int KS = HD / 16;          // k steps of q . k
@@ -965,15 +1001,34 @@ __global__ __launch_bounds__(64 * NW, 2) void prefill_fa2_kernel(const float* q,
     const int nst_all = (ntile + FA_TPS - 1) / FA_TPS;
     const int nsplit = gridDim.z, z = blockIdx.z;
     const int hst = pos0 / (32 * FA_TPS);  // stage boundaries at or below pos0
-    const int st0 = nsplit > 1 ? z * hst / nsplit : 0;
-    const int nst = (nsplit > 1 && z < nsplit - 1 ? (z + 1) * hst / nsplit : nst_all) - st0;
+    int st0, nst;
+    if constexpr (RING) {
+        // stages [first, nst_all): first holds row tb + 1, the first one any row of the workgroup sees
+        const int first = (tb + 1) / (32 * FA_TPS), nvis = nst_all - first;
+        st0 = first + z * nvis / nsplit;
+        nst = first + (z + 1) * nvis / nsplit - st0;
+    } else {
+        st0 = nsplit > 1 ? z * hst / nsplit : 0;
+        nst = (nsplit > 1 && z < nsplit - 1 ? (z + 1) * hst / nsplit : nst_all) - st0;
+    }
     auto issue = [&](const int stage, const int st) {
         char* base = fa_smem + stage * FA_STAGE_BYTES;
 #pragma unroll
         for (int k = 0; k < IPW; k++) {
             const int i = wv * IPW + k;
-            const uint16_t* src = (((i >> 3) & 1) ? vc : kc) + (size_t)min(32 * FA_TPS * (st0 + st) + drow[k], last_wg) * kv_dim +
-                                  (size_t)g * HD + 8 * dch[k];
+            const uint16_t* src;
+            if constexpr (RING) {
+                // virtual row -> ring slot (history) or staging row (the pass), clamped as below
+                const int u = min(32 * FA_TPS * (st0 + st) + drow[k], last_wg);
+                const bool isv = (i >> 3) & 1;
+                int s = rg.hoff + u;
+                s = s >= rg.W ? s - rg.W : s;
+                src = u < rg.W ? (isv ? vc : kc) + (size_t)(2 + s) * kv_dim : (isv ? rg.vs : rg.ks) + (size_t)(u - rg.W) * kv_dim;
+                src += (size_t)g * HD + 8 * dch[k];
+            } else {
+                src = (((i >> 3) & 1) ? vc : kc) + (size_t)min(32 * FA_TPS * (st0 + st) + drow[k], last_wg) * kv_dim +
+                      (size_t)g * HD + 8 * dch[k];
+            }
             __builtin_amdgcn_global_load_lds((const void*)src,
                                              (__attribute__((address_space(3))) void*)(base + i * 1024), 16, 0, 0);
         }
@@ -1031,6 +1086,9 @@ __global__ __launch_bounds__(64 * NW, 2) void prefill_fa2_kernel(const float* q,
         for (int sub = 0; sub < FA_TPS; sub++) {
         const int b = 32 * ((st0 + ks) * FA_TPS + sub);
         if (b > last) break;  // wave-uniform: past this wave's rows (it still issues its DMA share)
+        if constexpr (RING) {
+            if (b + 31 <= t0) continue;  // wave-uniform: below the first visible row (t0 + 1) of every row
+        }
         const char* kimg = fa_smem + (ks % FA_NS) * FA_STAGE_BYTES + sub * 2 * FA_TILE_BYTES;
         const char* vimg = kimg + FA_TILE_BYTES;
         // S^T = K Q^T
@@ -1042,7 +1100,11 @@ __global__ __launch_bounds__(64 * NW, 2) void prefill_fa2_kernel(const float* q,
             st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, ql[ks], st, 0, 0, 0);
         }
         f16x8 ph[2], pl[2];
-        fa_softmax_tile<NDT>(st, b, pos, h, inv_s * scale, b + 31 > pos0 + t0, m, lsum, o, ph, pl);
+        if constexpr (RING)  // row t's window starts at virtual row t + 1; rows t0 .. t0 + TPW - 1 in this wave
+            fa_softmax_tile<NDT, true>(st, b, pos, h, inv_s * scale, b + 31 > pos0 + t0, m, lsum, o, ph, pl, tqc + 1,
+                                       b < t0 + TPW);
+        else
+            fa_softmax_tile<NDT>(st, b, pos, h, inv_s * scale, b + 31 > pos0 + t0, m, lsum, o, ph, pl);
         // O^T += V^T P^T: element e of the A fragment = slot 16 s2 + 8 (e >> 2) + 4 h + (e & 3)
 #pragma unroll
         for (int s2 = 0; s2 < 2; s2++) {
@@ -1065,7 +1127,7 @@ __global__ __launch_bounds__(64 * NW, 2) void prefill_fa2_kernel(const float* q,
     }
     const float l = lsum + __shfl_xor(lsum, 32);
     if (tq >= n) return;
-    const bool split = nsplit > 1;
+    const bool split = RING || nsplit > 1;
     const float inv_l = split ? 1.f : 1.f / l;
     float* orow = (split ? part_o + (size_t)z * n * q_stride : out) + (size_t)tq * q_stride + (size_t)head * HD;
     if (split && h == 0) part_ml[((size_t)z * n + tq) * (q_stride / HD) + head] = float2{m, l};
@@ -1078,14 +1140,86 @@ __global__ __launch_bounds__(64 * NW, 2) void prefill_fa2_kernel(const float* q,
                 float4{o[dt][r] * inv_l, o[dt][r + 1] * inv_l, o[dt][r + 2] * inv_l, o[dt][r + 3] * inv_l};
         }
 }
+template <int QPK, int NW>
+__global__ __launch_bounds__(64 * NW, 2) void prefill_fa2_kernel(const float* q, const uint16_t* kc, const uint16_t* vc,
+                                                               float* out, int n, int pos0, int q_stride, int kv_dim,
+                                                               float* part_o, float2* part_ml) {
+    fa2_body<QPK, NW, false>(q, kc, vc, out, n, pos0, q_stride, kv_dim, part_o, part_ml, FaRing{});
+}
+// the ring pass: n <= W query rows over the ring (kc / vc, untouched) and the staging rows
+template <int QPK, int NW>
+__global__ __launch_bounds__(64 * NW, 2) void prefill_fa2_ring_kernel(const float* q, const uint16_t* kc,
+                                                                    const uint16_t* vc, const FaRing rg, int n,
+                                                                    int q_stride, int kv_dim, float* part_o,
+                                                                    float2* part_ml) {
+    fa2_body<QPK, NW, true>(q, kc, vc, nullptr, n, rg.W, q_stride, kv_dim, part_o, part_ml, rg);
+}
+
+// Every version of the two sink K rows a ring pass of m tokens goes through (src/infer.cpp:421-431:
+// each step re-rotates ring K rows 0 and 1 by rope(pos = 1) through an fp16 round trip before it
+// attends): ver[t][r] = row r after t + 1 rotations of the ring's row, the K that token t scores
+// the sinks against; ver[m - 1] is what the pass leaves in the ring.  One thread per (row, pair),
+// sequential in t, on sink_rotate_pair — the decode step's arithmetic (gemv.h).
+__global__ __launch_bounds__(256) void prefill_sink_versions_kernel(const uint16_t* kc, const float* sink_cos,
+                                                                    const float* sink_sin, int kv_dim, int head_dim,
+                                                                    int m, uint16_t* ver) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= kv_dim) return;
+    const int half = kv_dim >> 1;
+    const int r = idx / half, i = (idx - r * half) << 1;
+    const int jh = (i % head_dim) >> 1;
+    const float fcr = sink_cos[jh], fci = sink_sin[jh];
+    uint16_t b0 = kc[(size_t)r * kv_dim + i], b1 = kc[(size_t)r * kv_dim + i + 1];
+    for (int t = 0; t < m; t++) {
+        float k0 = f16_bits_to_f32(b0), k1 = f16_bits_to_f32(b1);
+        sink_rotate_pair(k0, k1, fcr, fci);
+        // the f32 results stand in registers before they are rounded to fp16, as in rotate_sinks:
+        // folded into one mixed-precision fma the two roundings would become the instruction's own
+        asm volatile("" : "+v"(k0), "+v"(k1));
+        b0 = f32_to_f16_bits(k0);
+        b1 = f32_to_f16_bits(k1);
+        *(uint32_t*)(ver + ((size_t)2 * t + r) * kv_dim + i) = (uint32_t)b0 | ((uint32_t)b1 << 16);
+    }
+}
+
+// After a layer's ring-pass attention: staging row t -> ring row 2 + (hoff + t) % W (K and V),
+// and the last sink version -> ring K rows 0 and 1.  grid m + 1 (the last block: the sinks);
+// kv_dim % 8 == 0 (head_dim 128).  m <= W: the rows are distinct.
+__global__ __launch_bounds__(256) void prefill_ring_commit_kernel(const FaRing rg, const uint16_t* ver, uint16_t* kc,
+                                                                  uint16_t* vc, int m, int kv_dim) {
+    const int t = blockIdx.x, nch = kv_dim >> 3;
+    if (t == m) {
+        const u32x4* src = (const u32x4*)(ver + (size_t)2 * (m - 1) * kv_dim);
+        for (int i = threadIdx.x; i < 2 * nch; i += 256) ((u32x4*)kc)[i] = src[i];
+        return;
+    }
+    int s = rg.hoff + t;
+    s = s >= rg.W ? s - rg.W : s;
+    const size_t dst = (size_t)(2 + s) * kv_dim, src = (size_t)t * kv_dim;
+    for (int i = threadIdx.x; i < nch; i += 256) {
+        ((u32x4*)(kc + dst))[i] = ((const u32x4*)(rg.ks + src))[i];
+        ((u32x4*)(vc + dst))[i] = ((const u32x4*)(rg.vs + src))[i];
+    }
+}
 
 // the history splits of prefill_fa2_kernel combined per (token, head), in a fixed order:
 // M = max m_z, out = sum_z e^(m_z - M) o_z / sum_z e^(m_z - M) l_z.  grid (n_heads, n), 256
 // threads = 32 float4 columns of the head (HD = 128) x 8 split groups; group k takes splits
 // k, k + 8, ... (its loads issued together), the 8 group sums are added in group order.
+// SINKS (the ring pass): the two sink slots join here, after the splits and in slot order: score
+// s_r = (q . ver[t][r]) / sqrtf(hd) against this token's version of sink K row r (f32 products of
+// the f16 row, a fixed reduction tree), value row r of the ring's V.  M is then finite (a split
+// that saw nothing carries m = -inf and weighs e^(-inf) = 0).
 constexpr int FA_MERGE_GROUPS = 8;
+struct FaSinks {
+    const float* q;       // [n][q_stride]
+    const uint16_t* ver;  // [n][2][kv_dim] (prefill_sink_versions_kernel)
+    const uint16_t* vc;   // the ring's V rows
+    int kv_dim, qpk;
+};
+template <bool SINKS>
 __global__ __launch_bounds__(256) void prefill_fa_merge_kernel(const float* part_o, const float2* part_ml, float* out,
-                                                               int n, int nsplit, int q_stride) {
+                                                               int n, int nsplit, int q_stride, const FaSinks sk) {
     constexpr int G = FA_MERGE_GROUPS;
     __shared__ float smax[G];
     __shared__ float4 snum[G][32];
@@ -1093,6 +1227,20 @@ __global__ __launch_bounds__(256) void prefill_fa_merge_kernel(const float* part
     const int head = blockIdx.x, t = blockIdx.y;
     const int nh = gridDim.x;
     const int c = threadIdx.x & 31, k = threadIdx.x >> 5;
+    float ss[2] = {-INFINITY, -INFINITY};
+    if constexpr (SINKS) {
+        __shared__ float sdot[4];
+        const int r = threadIdx.x >> 7, d = threadIdx.x & 127;
+        const size_t koff = (size_t)(head / sk.qpk) * 128 + d;
+        float pr = sk.q[(size_t)t * q_stride + (size_t)head * 128 + d] *
+                   f16_bits_to_f32(sk.ver[((size_t)2 * t + r) * sk.kv_dim + koff]);
+        pr = wave_sum(pr);
+        if ((threadIdx.x & 63) == 0) sdot[threadIdx.x >> 6] = pr;
+        __syncthreads();
+        const float scale = 1.0f / sqrtf(128.f);  // src/infer.cpp:338
+        ss[0] = (sdot[0] + sdot[1]) * scale;
+        ss[1] = (sdot[2] + sdot[3]) * scale;
+    }
     auto ml_at = [&](const int z) { return part_ml[((size_t)z * n + t) * nh + head]; };
     float mx = -INFINITY;
     for (int z = k; z < nsplit; z += G) mx = fmaxf(mx, ml_at(z).x);
@@ -1101,6 +1249,7 @@ __global__ __launch_bounds__(256) void prefill_fa_merge_kernel(const float* part
     float M = smax[0];
 #pragma unroll
     for (int i = 1; i < G; i++) M = fmaxf(M, smax[i]);
+    if constexpr (SINKS) M = fmaxf(M, fmaxf(ss[0], ss[1]));
     float4 acc = float4{0.f, 0.f, 0.f, 0.f};
     float l = 0.f;
     for (int z = k; z < nsplit; z += G) {
@@ -1120,6 +1269,18 @@ __global__ __launch_bounds__(256) void prefill_fa_merge_kernel(const float* part
         for (int i = 1; i < G; i++) {
             s4.x += snum[i][c].x; s4.y += snum[i][c].y; s4.z += snum[i][c].z; s4.w += snum[i][c].w;
             den += sden[i];
+        }
+        if constexpr (SINKS) {
+#pragma unroll
+            for (int r = 0; r < 2; r++) {
+                const float w = __expf(ss[r] - M);
+                const uint2 u = *(const uint2*)(sk.vc + (size_t)r * sk.kv_dim + (size_t)(head / sk.qpk) * 128 + 4 * c);
+                den += w;
+                s4.x += w * f16_bits_to_f32((uint16_t)(u.x & 0xffffu));
+                s4.y += w * f16_bits_to_f32((uint16_t)(u.x >> 16));
+                s4.z += w * f16_bits_to_f32((uint16_t)(u.y & 0xffffu));
+                s4.w += w * f16_bits_to_f32((uint16_t)(u.y >> 16));
+            }
         }
         const float inv_l = 1.f / den;
         *(float4*)(out + (size_t)t * q_stride + (size_t)head * 128 + 4 * c) =

@@ -38,12 +38,13 @@ void xalm::pf_free(xh_ctx* ctx) {
     for (void* p : {(void*)ctx->pf_tok, (void*)ctx->pf_x, (void*)ctx->pf_xn, (void*)ctx->pf_q, (void*)ctx->pf_att,
                     (void*)ctx->pf_h, (void*)ctx->pf_part, (void*)ctx->pf_sp, (void*)ctx->pf_xh, (void*)ctx->pf_xl,
                     (void*)ctx->pf_xs, (void*)ctx->pf_logits, (void*)ctx->pf_tgt, (void*)ctx->pf_po,
-                    (void*)ctx->pf_pml, (void*)ctx->pf_cnt})
+                    (void*)ctx->pf_pml, (void*)ctx->pf_cnt, (void*)ctx->pf_ks, (void*)ctx->pf_vs, (void*)ctx->pf_sinkv})
         hipFree(p);
     ctx->pf_tok = nullptr; ctx->pf_x = ctx->pf_xn = ctx->pf_q = ctx->pf_att = ctx->pf_h = ctx->pf_part = nullptr;
     ctx->pf_sp = nullptr; ctx->pf_xh = ctx->pf_xl = nullptr; ctx->pf_xs = nullptr; ctx->pf_logits = nullptr;
     ctx->pf_tgt = nullptr; ctx->pf_po = ctx->pf_pml = nullptr; ctx->pf_cnt = nullptr;
-    ctx->pf_cap = ctx->pf_po_cap = 0;
+    ctx->pf_ks = ctx->pf_vs = ctx->pf_sinkv = nullptr;
+    ctx->pf_cap = ctx->pf_po_cap = ctx->pf_ring_cap = 0;
 }
 
 namespace {
@@ -83,6 +84,20 @@ int pf_alloc_split_attn(xh_ctx* ctx) {
         (rc = dmalloc(ctx, &ctx->pf_cnt, t * ctx->c.n_kv_heads)))
         return rc;
     ctx->pf_po_cap = ctx->pf_cap;
+    return 0;
+}
+
+// a ring pass's staging rows and sink versions, sized for the pass
+int pf_alloc_ring(xh_ctx* ctx) {
+    if (ctx->pf_ring_cap >= ctx->pf_cap) return 0;
+    hipFree(ctx->pf_ks); hipFree(ctx->pf_vs); hipFree(ctx->pf_sinkv);
+    ctx->pf_ks = ctx->pf_vs = ctx->pf_sinkv = nullptr; ctx->pf_ring_cap = 0;
+    const size_t t = (size_t)ctx->pf_cap;
+    int rc;
+    if ((rc = dmalloc(ctx, &ctx->pf_ks, t * ctx->kv_dim)) || (rc = dmalloc(ctx, &ctx->pf_vs, t * ctx->kv_dim)) ||
+        (rc = dmalloc(ctx, &ctx->pf_sinkv, t * 2 * ctx->kv_dim)))
+        return rc;
+    ctx->pf_ring_cap = ctx->pf_cap;
     return 0;
 }
 
@@ -426,8 +441,8 @@ void pf_fa_t(xh_ctx* ctx, const AttnArgs& a, int n, int pos0) {
             hipLaunchKernelGGL(k, dim3(ctx->c.n_kv_heads, nqt, nsplit), dim3(64 * NW), fa_lds_bytes(), ctx->stream, a.q,
                                a.kc, a.vc, a.out, n, pos0, ctx->q_dim, ctx->kv_dim, po, pml);
             if (nsplit > 1)
-                hipLaunchKernelGGL(prefill_fa_merge_kernel, dim3(ctx->c.n_heads, n), dim3(256), 0, ctx->stream, (const float*)po,
-                                   (const float2*)pml, a.out, n, nsplit, ctx->q_dim);
+                hipLaunchKernelGGL(prefill_fa_merge_kernel<false>, dim3(ctx->c.n_heads, n), dim3(256), 0, ctx->stream,
+                                   (const float*)po, (const float2*)pml, a.out, n, nsplit, ctx->q_dim, FaSinks{});
             return;
         }
     }
@@ -476,11 +491,53 @@ int pf_attn(xh_ctx* ctx, const AttnArgs& a, int n, int pos0) {
     return ok ? 0 : set_err(ctx, XH_E_INVALID, "prefill: head shape not instantiated");
 }
 
-// Whether the batched path covers this prompt (else the per-token loop): no ring wrap inside
-// the prompt, an instantiated head shape, K multiples of the chunk pair (always, for K % 32).
-bool pf_supported(const xh_ctx* ctx, int n, int pos0) {
+// Attention of a ring pass (prefill.h, prefill_fa2_ring_kernel): m <= W = max_seq_len - 2 tokens at
+// positions p0.. >= max_seq_len, their K/V in the staging rows.  Four launches per layer: the
+// sink K versions, the window walk into split partials (pf_part: free between the qkv epilogue
+// and the Wo GEMM), the merge that adds the sinks, and the commit of the staged rows and the last
+// sink version to the ring.
+template <int QPK>
+int pf_attn_ring_t(xh_ctx* ctx, int l, int m, int p0) {
+    constexpr int NW = PF_FA_WAVES, TPW = 32 / QPK;
+    const int W = ctx->c.max_seq_len - 2;
+    FaRing rg{ctx->pf_ks, ctx->pf_vs, W, (p0 - 2) % W};
+    const int nqt = (m + NW * TPW - 1) / (NW * TPW);
+    const int nsplit = pf_fa_nsplit(ctx, nqt, m, W);
+    if ((size_t)nsplit * m * (ctx->q_dim + 2 * ctx->c.n_heads) > pf_part_floats(ctx, ctx->pf_cap))
+        return set_err(ctx, XH_E_INVALID, "prefill: the ring pass's attention partials do not fit");
+    float* po = ctx->pf_part;
+    float2* pml = (float2*)(ctx->pf_part + (size_t)nsplit * m * ctx->q_dim);
+    uint16_t *kc = ctx->kcache(l), *vc = ctx->vcache(l);
+    hipStream_t s = ctx->stream;
+    hipLaunchKernelGGL(prefill_sink_versions_kernel, dim3((ctx->kv_dim + 255) / 256), dim3(256), 0, s, (const uint16_t*)kc,
+                       (const float*)ctx->sink_cos, (const float*)ctx->sink_sin, ctx->kv_dim, ctx->c.head_dim, m,
+                       ctx->pf_sinkv);
+    auto k = prefill_fa2_ring_kernel<QPK, NW>;
+    ensure_lds((const void*)k);
+    hipLaunchKernelGGL(k, dim3(ctx->c.n_kv_heads, nqt, nsplit), dim3(64 * NW), fa_lds_bytes(), s, (const float*)ctx->pf_q,
+                       (const uint16_t*)kc, (const uint16_t*)vc, rg, m, ctx->q_dim, ctx->kv_dim, po, pml);
+    const FaSinks sk{ctx->pf_q, ctx->pf_sinkv, vc, ctx->kv_dim, QPK};
+    hipLaunchKernelGGL(prefill_fa_merge_kernel<true>, dim3(ctx->c.n_heads, m), dim3(256), 0, s, (const float*)po,
+                       (const float2*)pml, ctx->pf_att, m, nsplit, ctx->q_dim, sk);
+    hipLaunchKernelGGL(prefill_ring_commit_kernel, dim3(m + 1), dim3(256), 0, s, rg, (const uint16_t*)ctx->pf_sinkv, kc, vc,
+                       m, ctx->kv_dim);
+    return 0;
+}
+int pf_attn_ring(xh_ctx* ctx, int l, int m, int p0) {
+    switch (ctx->qpk) {
+        case 1: return pf_attn_ring_t<1>(ctx, l, m, p0);
+        case 2: return pf_attn_ring_t<2>(ctx, l, m, p0);
+        case 4: return pf_attn_ring_t<4>(ctx, l, m, p0);
+        case 8: return pf_attn_ring_t<8>(ctx, l, m, p0);
+        default: return set_err(ctx, XH_E_INVALID, "prefill: head shape not instantiated");
+    }
+}
+
+// Whether the batched path covers prompts on this model at all (else the per-token loop): an
+// instantiated head shape, K multiples of the chunk pair (always, for K % 32).
+bool pf_supported(const xh_ctx* ctx) {
     const xh_config& c = ctx->c;
-    if (!ctx->prefill_batched || pos0 + n > c.max_seq_len) return false;
+    if (!ctx->prefill_batched) return false;
     const int hd = c.head_dim, qpk = ctx->qpk;
     if (!pf_attn_shape(hd, qpk)) return false;
     // every GEMM's K in whole chunk pairs of its decoder (f32-input kernel; the others need less)
@@ -490,17 +547,56 @@ bool pf_supported(const xh_ctx* ctx, int n, int pos0) {
             return false;
     return ok(ctx->wcls_dt, c.dim) && c.dim % 32 == 0 && c.hidden_dim % 32 == 0 && ctx->q_dim % 32 == 0;
 }
+// Ring passes (positions >= max_seq_len): the shared-tile attention's head shape only
+// (prefill_fa2_ring_kernel is head_dim 128), and a ring with at least two slots behind the sinks
+bool pf_ring_ok(const xh_ctx* ctx) {
+    return ctx->pf_ring && ctx->c.head_dim == 128 && ctx->pf_attn_mode == 1 && ctx->c.max_seq_len - 2 >= 2;
+}
+
+// How a prompt of n tokens at pos0 runs: pieces in order, each batched (PF_RING: ring passes of at
+// most min(pass length, max_seq_len - 2) tokens, all at positions >= max_seq_len) or PF_LOOP, one
+// decode step per token.  The prompt is cut at pos = L = max_seq_len, so no pass straddles it:
+// below L the batched passes as ever (a piece shorter than min_n takes the loop: xh_prefill's
+// one-token rule), from L on ring passes — fewer than PF_RING_MIN tokens, alone or left over by
+// the passes before them, take the loop there too.  Without ring passes (XH_OPT_PREFILL_RING 0, or
+// a head shape they do not cover) a prompt that reaches past L takes the loop as a whole.
+// PF_RING_MIN: at the end of a 32k ring two decode steps take 6.6 ms, a ring pass of two tokens
+// 7.5 ms, of eight 7.5 ms against 26.1 (tools/ring_pass.py, profiles/ring_pass.txt).
+constexpr int PF_RING_MIN = 3;
+enum { PF_LOOP = 0, PF_BATCH = 1, PF_RING = 2 };
+struct PfPiece { int off, n, kind, passes; };
+void pf_plan(const xh_ctx* ctx, int n, int pos0, int min_n, std::vector<PfPiece>& out) {
+    const int L = ctx->c.max_seq_len;
+    out.clear();
+    const bool wraps = pos0 > L - n;  // pos0 + n > L
+    if (!pf_supported(ctx) || (wraps && !pf_ring_ok(ctx))) {
+        out.push_back({0, n, PF_LOOP, 0});
+        return;
+    }
+    const int pass = pf_pass_tokens(ctx);
+    const int na = wraps ? std::max(0, L - pos0) : n, nb = n - na;
+    if (na > 0) out.push_back({0, na, na >= min_n ? PF_BATCH : PF_LOOP, na >= min_n ? (na + pass - 1) / pass : 0});
+    if (nb > 0) {
+        const int rp = std::min(pass, L - 2);
+        const int rem = nb % rp, tail = rem > 0 && rem < PF_RING_MIN ? rem : 0;
+        if (nb > tail) out.push_back({na, nb - tail, PF_RING, (nb - tail + rp - 1) / rp});
+        if (tail) out.push_back({n - tail, tail, PF_LOOP, 0});
+    }
+}
 
 // tokens[0..n) at positions pos0..: HYDRATE for every token, then the last token's logits.
 // probs (device, n floats) != nullptr: also every token's logits (final rmsnorm + lm_head as
 // one GEMM per pass) and probs[i] = sample_prob(targets[i]) (targets: host, n ints).
+// ring: every position is >= max_seq_len (pf_plan): ring passes.
 int prefill_batched(xh_ctx* ctx, const int* tokens, int n, int pos0, int want_logits, const int* targets = nullptr,
-                    float* probs = nullptr) {
+                    float* probs = nullptr, bool ring = false) {
     const xh_config& c = ctx->c;
     int rc = pf_prepare(ctx);
     if (rc) return rc;
-    const int pass = ctx->pf_pass = pf_pass_tokens(ctx);
+    ctx->pf_pass = pf_pass_tokens(ctx);
+    const int pass = ring ? std::min(ctx->pf_pass, c.max_seq_len - 2) : ctx->pf_pass;
     if ((rc = pf_alloc(ctx, std::min(pass, std::max(n, PF_TOK))))) return rc;
+    if (ring && (rc = pf_alloc_ring(ctx))) return rc;
     ctx->pf_split_ready = false;
     if (probs && !ctx->pf_logits &&
         ((rc = dmalloc(ctx, &ctx->pf_logits, (size_t)ctx->pf_cap * c.vocab_size)) ||
@@ -516,9 +612,9 @@ int prefill_batched(xh_ctx* ctx, const int* tokens, int n, int pos0, int want_lo
             h = StepParams{};
             h.token = tokens[off + t];
             h.pos = p0 + t;
-            h.kv_sink = 0;
-            h.kv_pos = p0 + t;
-            h.kv_len = p0 + t + 1;
+            h.kv_sink = ring ? 2 : 0;  // src/infer.cpp:611-613
+            h.kv_pos = ring ? 2 + (p0 + t - 2) % (c.max_seq_len - 2) : p0 + t;
+            h.kv_len = ring ? c.max_seq_len : p0 + t + 1;
             h.max_seq_len = c.max_seq_len;
         }
         HIP_TRY(ctx, hipMemcpyAsync(ctx->pf_sp, sps.data(), (size_t)m * sizeof(StepParams), hipMemcpyHostToDevice,
@@ -537,12 +633,17 @@ int prefill_batched(xh_ctx* ctx, const int* tokens, int n, int pos0, int want_lo
             e.ks = ks; e.n = m; e.rows = qkv_rows; e.epi = EPI_QKV; e.q = ctx->pf_q;
             e.kcache = ctx->kcache(l); e.vcache = ctx->vcache(l); e.q_dim = ctx->q_dim; e.kv_dim = ctx->kv_dim;
             e.head_dim = c.head_dim; e.rope_freq = ctx->rope_freq; e.qkv_clip = c.qkv_clip; e.pos0 = p0; e.act = c.act;
+            if (ring) { e.kstage = ctx->pf_ks; e.vstage = ctx->pf_vs; }
             pf_epi(ctx, e);
-            AttnArgs aa = attn_args(ctx, l);
-            aa.q = ctx->pf_q; aa.out = ctx->pf_att;
-            // splits for this pass's longest row (attn_block: >= ATTN_MIN_T slots per split)
-            aa.nsplit = std::min(ctx->nsplit, std::max(1, (p0 + m + ATTN_MIN_T - 1) / ATTN_MIN_T));
-            if ((rc = pf_attn(ctx, aa, m, p0))) return rc;
+            if (ring) {
+                if ((rc = pf_attn_ring(ctx, l, m, p0))) return rc;
+            } else {
+                AttnArgs aa = attn_args(ctx, l);
+                aa.q = ctx->pf_q; aa.out = ctx->pf_att;
+                // splits for this pass's longest row (attn_block: >= ATTN_MIN_T slots per split)
+                aa.nsplit = std::min(ctx->nsplit, std::max(1, (p0 + m + ATTN_MIN_T - 1) / ATTN_MIN_T));
+                if ((rc = pf_attn(ctx, aa, m, p0))) return rc;
+            }
             if ((rc = pf_gemm(ctx, "wo", kdt(w.wo_dt, w.wo_x), w.wo, ctx->q_dim, c.dim, ctx->pf_att, m, ks))) return rc;
             // residual, then the feed-forward block's rmsnorm (src/infer.cpp:449-452, 455-494)
             if ((rc = pf_resid_norm(ctx, ks, w.ffn_norm, w.fn_dt, m, kdt(w.w13_dt, w.w13_x), 2 * c.hidden_dim))) return rc;
@@ -646,7 +747,59 @@ void xalm::mm_op_launch(const uint16_t* w, const uint16_t* xh, const uint16_t* x
     mm_launch(a, n_cu, nullptr);
 }
 
+namespace {
+// The pieces of pf_plan in order.  probs (device, n floats): xh_perplexity's run, every token with
+// logits and probs[i] = sample_prob(targets[i]); else xh_prefill's, the last token's logits if wanted.
+int run_plan(xh_ctx* ctx, const int* tokens, int n, int pos0, int want_logits, const int* targets, float* probs) {
+    int rc = 0;
+    // hipBLASLt's plans decide the pass length (XH_OPT_PREFILL 4): probe them before planning
+    if (ctx->prefill_gemm == 4 && n >= 2 && pf_supported(ctx) && (rc = pf_prepare(ctx))) return rc;
+    std::vector<PfPiece> plan;
+    pf_plan(ctx, n, pos0, probs ? 1 : 2, plan);
+    const int V = ctx->c.vocab_size;
+    bool tgt_up = false;
+    for (const PfPiece& pc : plan) {
+        const bool last = pc.off + pc.n == n;
+        if (pc.kind != PF_LOOP) {
+            rc = prefill_batched(ctx, tokens + pc.off, pc.n, pos0 + pc.off, last && want_logits,
+                                 probs ? targets + pc.off : nullptr, probs ? probs + pc.off : nullptr, pc.kind == PF_RING);
+            // it leaves the last token's step parameters in flight from the one pinned host slot
+            if (!rc && !last) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        } else {
+            if (probs && !tgt_up) {
+                HIP_TRY(ctx, copy_sync(ctx, ctx->ppl_tgt, targets, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+                tgt_up = true;
+            }
+            for (int i = pc.off; i < pc.off + pc.n && !rc; i++) {
+                rc = host_step_params(ctx, tokens[i], pos0 + i);
+                if (!rc) rc = run_step(ctx, probs || (i == n - 1 && want_logits));
+                if (rc) break;
+                if (probs)
+                    hipLaunchKernelGGL(token_prob_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const float*)ctx->logits, V,
+                                       (size_t)V, (const int*)ctx->ppl_tgt + i, probs + i);
+                // the step parameters are copied from one pinned host slot: drain before reuse
+                if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = set_err(ctx, XH_E_HIP, "hipStreamSynchronize failed");
+            }
+        }
+        if (rc) return rc;
+    }
+    return 0;
+}
+}  // namespace
+
 extern "C" {
+
+int xh_prefill_route(const xh_ctx* ctx, int n, int pos0, int* n_batched, int* n_passes) {
+    if (!ctx || n <= 0 || pos0 < 0) return XH_E_INVALID;
+    std::vector<PfPiece> plan;
+    pf_plan(ctx, n, pos0, 2, plan);
+    int nb = 0, np = 0;
+    for (const PfPiece& pc : plan)
+        if (pc.kind != PF_LOOP) { nb += pc.n; np += pc.passes; }
+    if (n_batched) *n_batched = nb;
+    if (n_passes) *n_passes = np;
+    return 0;
+}
 
 int xh_prefill(xh_ctx* ctx, const int* tokens, int n, int pos0, int want_logits, float* logits_out) {
     if (!ctx || !tokens || n <= 0 || pos0 < 0) return set_err(ctx, XH_E_INVALID, "bad prefill arguments");
@@ -655,20 +808,10 @@ int xh_prefill(xh_ctx* ctx, const int* tokens, int n, int pos0, int want_logits,
     HIP_TRY(ctx, hipSetDevice(ctx->dev));
     int rc = check_ready(ctx);
     if (rc) return rc;
-    // a one-token prompt runs the decode step (one graph replay of the matvecs) rather than a
-    // pass of GEMMs over one token: 3.3 vs 7.3 ms at the end of a 32k ring (tools/short_pass.py)
-    if (n >= 2 && pf_supported(ctx, n, pos0)) {
-        rc = prefill_batched(ctx, tokens, n, pos0, want_logits);
-    } else {
-        for (int i = 0; i < n && !rc; i++) {
-            rc = host_step_params(ctx, tokens[i], pos0 + i);
-            if (!rc) rc = run_step(ctx, i == n - 1 && want_logits);
-            // the step parameters are copied from one pinned host slot: drain before reuse
-            if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess)
-                rc = set_err(ctx, XH_E_HIP, "hipStreamSynchronize failed");
-        }
-    }
-    if (rc) return rc;
+    // pf_plan: batched passes, ring passes from max_seq_len on; a one-token piece runs the decode
+    // step (one graph replay of the matvecs) rather than a pass of GEMMs over one token: 3.3 vs
+    // 7.3 ms at the end of a 32k ring (tools/short_pass.py)
+    if ((rc = run_plan(ctx, tokens, n, pos0, want_logits, nullptr, nullptr))) return rc;
     if (logits_out && want_logits)
         HIP_TRY(ctx, hipMemcpyAsync(logits_out, ctx->logits, (size_t)ctx->c.vocab_size * 4, hipMemcpyDeviceToHost,
                                     ctx->stream));
@@ -679,7 +822,7 @@ int xh_prefill(xh_ctx* ctx, const int* tokens, int n, int pos0, int want_logits,
 // The perplexity loop of run_perplexity (src/main.cpp:243-254): forward tokens[0..n-1) at
 // positions pos0.. with logits, probs_out[i] = Sampler::sample_prob(tokens[i + 1]) after token
 // i (src/sampler.cpp:3-17).  The logits never leave the device; batched passes where the
-// prompt path allows, else token by token.
+// prompt path allows (pf_plan, as xh_prefill), else token by token.
 int xh_perplexity(xh_ctx* ctx, const int* tokens, int n, int pos0, float* probs_out) {
     if (!ctx || !tokens || !probs_out || n < 2 || pos0 < 0) return set_err(ctx, XH_E_INVALID, "bad perplexity arguments");
     for (int i = 0; i < n; i++)
@@ -687,28 +830,14 @@ int xh_perplexity(xh_ctx* ctx, const int* tokens, int n, int pos0, float* probs_
     HIP_TRY(ctx, hipSetDevice(ctx->dev));
     int rc = check_ready(ctx);
     if (rc) return rc;
-    const int m = n - 1, V = ctx->c.vocab_size;
+    const int m = n - 1;
     if (ctx->ppl_cap < m) {
         hipFree(ctx->ppl_tgt); hipFree(ctx->ppl_prob);
         ctx->ppl_tgt = nullptr; ctx->ppl_prob = nullptr; ctx->ppl_cap = 0;
         if ((rc = dmalloc(ctx, &ctx->ppl_tgt, (size_t)m)) || (rc = dmalloc(ctx, &ctx->ppl_prob, (size_t)m))) return rc;
         ctx->ppl_cap = m;
     }
-    if (pf_supported(ctx, m, pos0)) {
-        rc = prefill_batched(ctx, tokens, m, pos0, 0, tokens + 1, ctx->ppl_prob);
-    } else {
-        HIP_TRY(ctx, copy_sync(ctx, ctx->ppl_tgt, tokens + 1, (size_t)m * sizeof(int), hipMemcpyHostToDevice));
-        for (int i = 0; i < m && !rc; i++) {
-            rc = host_step_params(ctx, tokens[i], pos0 + i);
-            if (!rc) rc = run_step(ctx, true);
-            if (rc) break;
-            hipLaunchKernelGGL(token_prob_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const float*)ctx->logits, V,
-                               (size_t)V, (const int*)ctx->ppl_tgt + i, ctx->ppl_prob + i);
-            // the step parameters are copied from one pinned host slot: drain before reuse
-            if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = set_err(ctx, XH_E_HIP, "hipStreamSynchronize failed");
-        }
-    }
-    if (rc) return rc;
+    if ((rc = run_plan(ctx, tokens, m, pos0, 0, tokens + 1, ctx->ppl_prob))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(probs_out, ctx->ppl_prob, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return check_aw(ctx);

@@ -281,6 +281,7 @@ int xh_get_option(const xh_ctx* ctx, int option, int* value) {
         case XH_OPT_PREFILL_GLU_SPLIT: *value = ctx->pf_glu_split ? 1 : 0; return 0;
         case XH_OPT_PREFILL_ATTN: *value = ctx->pf_attn_mode; return 0;
         case XH_OPT_PREFILL_ATTN_SPLIT: *value = ctx->pf_fa_split; return 0;
+        case XH_OPT_PREFILL_RING: *value = ctx->pf_ring ? 1 : 0; return 0;
         default: return XH_E_INVALID;
     }
 }
@@ -310,6 +311,10 @@ int xh_set_option(xh_ctx* ctx, int option, int value) {
         case XH_OPT_PREFILL_ATTN_SPLIT:
             if (value < 0 || value > 1) return set_err(ctx, XH_E_INVALID, "XH_OPT_PREFILL_ATTN_SPLIT: 0 or 1");
             ctx->pf_fa_split = value;
+            return 0;
+        case XH_OPT_PREFILL_RING:
+            if (value < 0 || value > 1) return set_err(ctx, XH_E_INVALID, "XH_OPT_PREFILL_RING: 0 or 1");
+            ctx->pf_ring = value != 0;
             return 0;
         default: return set_err(ctx, XH_E_INVALID, "unknown option %d", option);
     }

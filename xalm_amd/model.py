@@ -112,6 +112,14 @@ class Model:
         L.check(L.lib().xh_prefill(self._ctx, L.ptr(toks), int(toks.size), int(pos0), int(s is not None), out),
                 self._ctx)
 
+    def prefill_route(self, n: int, pos0: int) -> tuple[int, int]:
+        """(tokens that `prefill` of n tokens at pos0 would run in batched passes, the number of
+        passes) under the current options (xh_prefill_route); the rest take the per-token loop."""
+        nb, npass = ctypes.c_int(0), ctypes.c_int(0)
+        L.check(L.lib().xh_prefill_route(self._ctx, int(n), int(pos0), ctypes.byref(nb), ctypes.byref(npass)),
+                self._ctx)
+        return int(nb.value), int(npass.value)
+
     def token_probs(self, tokens, pos0: int = 0) -> np.ndarray:
         """run_perplexity's loop (src/main.cpp:243-254) on the device: forward tokens[:-1] at
         positions pos0.., element i = Sampler::sample_prob(tokens[i + 1]) after token i."""
