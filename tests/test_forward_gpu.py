@@ -302,20 +302,24 @@ def test_long_row_w2_decode(wdt):
         check(st.logits(), om.logits(), what=pos)
 
 
+@pytest.mark.parametrize("mode", [2, 1])
 @pytest.mark.parametrize("wdt", [L.F16, L.F8_E4M3])
-def test_fused_glu_split_is_bit_identical(wdt):
-    # the fused GLU -> split-f16 epilogue and the two-launch route produce the same W2 input
+def test_fused_glu_split_is_bit_identical(wdt, mode):
+    # the fused GLU -> split-f16 and residual + rmsnorm -> split-f16 launches and their two-launch
+    # routes produce the same GEMM inputs, in the fragment layout (mode 2) and the row-major one
+    # (mode 1); 100 tokens: 28 zero rows in the last 32-token tile
     toks = [1] + [3 + (i * 41) % 500 for i in range(99)]
     out = []
     for glu in (1, 0):
         gm, _ = synthetic_pair(wdt)
-        gm.set_option(L.OPT_PREFILL, 2)
+        gm.set_option(L.OPT_PREFILL, mode)
         gm.set_option(L.OPT_PREFILL_GLU_SPLIT, glu)
         assert gm.get_option(L.OPT_PREFILL_GLU_SPLIT) == glu
         st = InferenceState(gm.config)
         gm.prefill(toks, 0, st)
-        out.append(st.logits().copy())
-    assert np.array_equal(out[0], out[1]), float(np.abs(out[0] - out[1]).max())
+        out.append((st.logits().copy(), gm.kv_read(1, 0, 0, len(toks)), gm.kv_read(1, 1, 0, len(toks))))
+    assert np.array_equal(out[0][0], out[1][0]), float(np.abs(out[0][0] - out[1][0]).max())
+    assert np.array_equal(out[0][1], out[1][1]) and np.array_equal(out[0][2], out[1][2])
 
 
 @pytest.mark.parametrize("batched", [1, 2, 3, 4])

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "attention.h"
@@ -56,6 +57,49 @@ struct BlasState;  // hipBLASLt handle, workspace, plans (prefill_blas.hip)
 
 constexpr int ARGMAX_CANDS = 1024;  // the lm_head workgroups' argmax keys (argmax_embed_kernel's block size)
 
+// The batched prefill's device buffers (prefill.hip), in growth groups.  T = cap[PASS] tokens, the
+// pass length in use: a longer pass frees every group and reallocates PASS; the others are
+// allocated on their first use and sized to T.
+struct PfBufs {
+    enum Group { PASS, ATTN0, RING, LOGITS, N_GROUPS };
+    int cap[N_GROUPS] = {};                // tokens each group holds
+    // PASS
+    uint16_t* xh = nullptr;                // [2T][max K] f16 halves of a GEMM input
+    uint16_t* xl = nullptr;                // [PF_TOK][max K] the split kernel's lo fragments
+    float* xs = nullptr;                   // [T] 1 / row scale
+    int* tok = nullptr;                    // [T]
+    float *x = nullptr, *xn = nullptr;     // [T][dim]
+    float *q = nullptr, *att = nullptr;    // [T][q_dim]
+    float* h = nullptr;                    // [T][hidden]
+    float* part = nullptr;                 // split-K partials [ks][n][rows] (pf_part_floats)
+    StepParams* sp = nullptr;              // [T] per-token attention scalars
+    // ATTN0: the per-token split attention (XH_OPT_PREFILL_ATTN 0 only)
+    float *po = nullptr, *pml = nullptr;   // [T][nsplit][q_dim], [T][nsplit][n_heads][2]
+    int* cnt = nullptr;                    // [T][n_kv_heads] split tickets
+    // RING: ring passes (positions >= max_seq_len, XH_OPT_PREFILL_RING)
+    uint16_t *ks = nullptr, *vs = nullptr; // [T][kv_dim] the pass's K / V rows until its attention ran
+    uint16_t* sinkv = nullptr;             // [T][2][kv_dim] sink K rows after 1 .. T re-rotations (one layer's)
+    // LOGITS: xh_perplexity's per-token logits of a pass and their targets
+    float* logits = nullptr;               // [T][vocab]
+    int* tgt = nullptr;                    // [T]
+
+    // every pointer a group owns: what pf_free and the group allocators walk
+    std::vector<void**> owned(int g) {
+        switch (g) {
+            case PASS: return {(void**)&xh, (void**)&xl, (void**)&xs, (void**)&tok, (void**)&x, (void**)&xn,
+                               (void**)&q, (void**)&att, (void**)&h, (void**)&part, (void**)&sp};
+            case ATTN0: return {(void**)&po, (void**)&pml, (void**)&cnt};
+            case RING: return {(void**)&ks, (void**)&vs, (void**)&sinkv};
+            case LOGITS: return {(void**)&logits, (void**)&tgt};
+            default: return {};
+        }
+    }
+    void free_group(int g) {
+        for (void** p : owned(g)) { hipFree(*p); *p = nullptr; }
+        cap[g] = 0;
+    }
+};
+
 }  // namespace xalm
 
 struct xh_ctx {
@@ -92,41 +136,17 @@ struct xh_ctx {
     // as an exact f16 image), f32 MFMA otherwise; 2 = split-f16 register-streaming MFMA wherever the
     // weights convert exactly; 3 = f32 MFMA only; 4 = as 1 with hipBLASLt in place of gemm16.h
     int prefill_gemm = 1;
-    int pf_pass = 0;                             // tokens per pass of the current prefill
-    int pf_cap = 0;                              // tokens the pass buffers hold (pf_alloc)
-    bool pf_scaled = false;                      // the last pf_gemm's partials carry 1 / s_t (pf_xs)
-    int mm_ok = 0;                               // 0 unchecked, 1 every pass GEMM fits gemm16.h, -1 not
     xalm::BlasState* blas = nullptr;             // XH_OPT_PREFILL 4, created on the first prompt that uses it
     uint16_t* pf_wdq = nullptr;                  // f16 image of one fp8 matrix for the f16 GEMMs (pf_prepare)
     size_t pf_wdq_elems = 0;
-    bool pf_split_ready = false;                 // pf_norm left the next GEMM's split input
     bool pf_resid_norm = true;                   // residual + rmsnorm split in one launch (XH_OPT_PREFILL_GLU_SPLIT 0: off)
     bool pf_glu_split = true;                    // XH_OPT_PREFILL_GLU_SPLIT: fused GLU -> split input
     int pf_fa_split = 1;                         // XH_OPT_PREFILL_ATTN_SPLIT: history splits for short passes
     int pf_attn_mode = 1;                        // XH_OPT_PREFILL_ATTN: 1 shared-tile MFMA (v1 for head_dim != 128),
                                                  // 2 per-wave MFMA tiles, 0 per-token split kernel
-    // T = pf_cap tokens (the pass length in use; pf_alloc)
-    uint16_t* pf_xh = nullptr;                   // [2T][max K] f16 halves of a GEMM input (pf_alloc)
-    uint16_t* pf_xl = nullptr;                   // [PF_TOK][max K] the split kernel's lo fragments
-    float* pf_xs = nullptr;                      // [T] 1 / row scale
-    int* pf_tok = nullptr;                       // [T]
-    float *pf_x = nullptr, *pf_xn = nullptr;     // [T][dim]
-    float *pf_q = nullptr, *pf_att = nullptr;    // [T][q_dim]
-    float* pf_h = nullptr;                       // [T][hidden]
-    float* pf_part = nullptr;                    // split-K partials [ks][n][rows] (pf_part_floats)
-    xalm::StepParams* pf_sp = nullptr;           // [T] per-token attention scalars
-    // the per-token split attention (XH_OPT_PREFILL_ATTN 0 only, allocated on its first use):
-    float *pf_po = nullptr, *pf_pml = nullptr;   // [T][nsplit][q_dim], [T][nsplit][n_heads][2]
-    int* pf_cnt = nullptr;                       // [T][n_kv_heads] split tickets
-    int pf_po_cap = 0;                           // tokens those hold
-    // ring passes (positions >= max_seq_len, XH_OPT_PREFILL_RING; allocated on the first one):
-    bool pf_ring = true;                         // XH_OPT_PREFILL_RING
-    uint16_t *pf_ks = nullptr, *pf_vs = nullptr; // [T][kv_dim] the pass's K / V rows until its attention ran
-    uint16_t* pf_sinkv = nullptr;                // [T][2][kv_dim] sink K rows after 1 .. T re-rotations (one layer's)
-    int pf_ring_cap = 0;                         // tokens those hold
-    // xh_perplexity: per-token logits of a pass, targets, probabilities (allocated on first use)
-    float* pf_logits = nullptr;                  // [T][vocab]
-    int* pf_tgt = nullptr;                       // [T]
+    bool pf_ring = true;                         // XH_OPT_PREFILL_RING: ring passes at positions >= max_seq_len
+    xalm::PfBufs pf;                             // the pass buffers
+    // xh_perplexity: targets and probabilities of the whole run (allocated on first use)
     int* ppl_tgt = nullptr;                      // [ppl_cap] targets (per-token path)
     float* ppl_prob = nullptr;                   // [ppl_cap]
     int ppl_cap = 0;
@@ -202,6 +222,39 @@ int attn_nsplit(int n_kv_heads, int max_seq_len);
 // The dynamic-LDS limit of a kernel above 64 KiB (up to the CU's 160 KiB), set once per (kernel,
 // device); false when it could not be set.
 bool ensure_lds(const void* fn, int bytes = 160 * 1024);
+
+// Runtime value -> template argument, for the units that instantiate kernels.  for_dt: f.run<DT>()
+// for a weight dtype; for_qpk: f(std::integral_constant<int, QPK>) for the q heads per KV head.
+// -1: no instantiation for the value (f returns >= 0).
+template <class F>
+int for_dt(int dt, const F& f) {
+    switch (dt) {
+        case XH_F32: return f.template run<XH_F32>();
+        case XH_F16: return f.template run<XH_F16>();
+        case XH_BF16: return f.template run<XH_BF16>();
+        case XH_F8_E4M3: return f.template run<XH_F8_E4M3>();
+        case XH_F8_E5M2: return f.template run<XH_F8_E5M2>();
+        case XH_Q8: return f.template run<XH_Q8>();
+        case XH_F8_E4M3_EXACT: return f.template run<XH_F8_E4M3_EXACT>();
+        case XH_F8_E5M2_EXACT: return f.template run<XH_F8_E5M2_EXACT>();
+        case XH_Q8_0: return f.template run<XH_Q8_0>();
+        case XH_Q4_0: return f.template run<XH_Q4_0>();
+        case XH_Q4_1: return f.template run<XH_Q4_1>();
+        case XH_Q5_0: return f.template run<XH_Q5_0>();
+        case XH_Q5_1: return f.template run<XH_Q5_1>();
+        default: return -1;
+    }
+}
+template <class F>
+int for_qpk(int qpk, const F& f) {
+    switch (qpk) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        default: return -1;
+    }
+}
 
 // decode.hip
 GemvArgs qkv_args(xh_ctx* ctx, int l);

@@ -142,8 +142,23 @@ __device__ __forceinline__ void rope_table(float* cs, const float* freq, const i
     }
 }
 
-// Sum of squares of x[0..n) -> rms scale 1/sqrtf(ss/n + eps), identical in every block of one
-// launch (fixed per-thread stride order, fixed shuffle tree, fixed wave order).
+// Each thread's partial sum of squares of an n-element row -> rms scale 1/sqrtf(ss/n + eps)
+// (fixed shuffle tree, fixed wave order).  ss is the caller's accumulator, reduced in place: by
+// value, block_rms_scale's callers schedule differently.
+template <int THREADS>
+__device__ __forceinline__ float block_rms_of(float& ss, const int n, const float eps, float* red) {
+    const int tid = threadIdx.x;
+    ss = wave_sum(ss);
+    if ((tid & 63) == 0) red[tid >> 6] = ss;
+    __syncthreads();
+    float tot = 0.f;
+#pragma unroll
+    for (int w = 0; w < THREADS / 64; w++) tot += red[w];
+    const float rms = sqrtf(tot / (float)n + eps);
+    return 1.0f / rms;
+}
+// Sum of squares of x[0..n) -> rms scale, identical in every block of one launch (fixed
+// per-thread stride order, then block_rms_of).
 template <int THREADS>
 __device__ __forceinline__ float block_rms_scale(const float* x, const int n, const float eps, float* red) {
     const int tid = threadIdx.x;
@@ -153,14 +168,7 @@ __device__ __forceinline__ float block_rms_scale(const float* x, const int n, co
         const float4 v = x4[i];
         ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
     }
-    ss = wave_sum(ss);
-    if ((tid & 63) == 0) red[tid >> 6] = ss;
-    __syncthreads();
-    float tot = 0.f;
-#pragma unroll
-    for (int w = 0; w < THREADS / 64; w++) tot += red[w];
-    const float rms = sqrtf(tot / (float)n + eps);
-    return 1.0f / rms;
+    return block_rms_of<THREADS>(ss, n, eps, red);
 }
 
 __device__ __forceinline__ float4 load_norm4(const void* w, const int dtype, const int i4) {

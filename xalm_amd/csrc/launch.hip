@@ -191,26 +191,6 @@ struct Pick {
         return ShapeSel<DT, PRO, EPI>::pick(n) | (smem > 64 * 1024 ? XH_SHAPE_BIG_LDS : 0);
     }
 };
-// -1: no instantiation for the dtype
-template <class F>
-int for_dt(int dt, const F& f) {
-    switch (dt) {
-        case XH_F32: return f.template run<XH_F32>();
-        case XH_F16: return f.template run<XH_F16>();
-        case XH_BF16: return f.template run<XH_BF16>();
-        case XH_F8_E4M3: return f.template run<XH_F8_E4M3>();
-        case XH_F8_E5M2: return f.template run<XH_F8_E5M2>();
-        case XH_Q8: return f.template run<XH_Q8>();
-        case XH_F8_E4M3_EXACT: return f.template run<XH_F8_E4M3_EXACT>();
-        case XH_F8_E5M2_EXACT: return f.template run<XH_F8_E5M2_EXACT>();
-        case XH_Q8_0: return f.template run<XH_Q8_0>();
-        case XH_Q4_0: return f.template run<XH_Q4_0>();
-        case XH_Q4_1: return f.template run<XH_Q4_1>();
-        case XH_Q5_0: return f.template run<XH_Q5_0>();
-        case XH_Q5_1: return f.template run<XH_Q5_1>();
-        default: return -1;
-    }
-}
 // every role as its (prologue, epilogue) pair
 template <template <int, int> class F, class... A>
 int for_role(int role, int dt, A... args) {
@@ -250,28 +230,23 @@ void launch_attn_t(const AttnArgs& a, int n_kv_heads, int t_max, hipStream_t s) 
 
 template <int HD>
 bool launch_attn_hd(const AttnArgs& a, int qpk, int n_kv_heads, int t_max, hipStream_t s) {
-    switch (qpk) {
-        case 1: launch_attn_t<HD, 1>(a, n_kv_heads, t_max, s); return true;
-        case 2: launch_attn_t<HD, 2>(a, n_kv_heads, t_max, s); return true;
-        case 4: launch_attn_t<HD, 4>(a, n_kv_heads, t_max, s); return true;
-        case 8: launch_attn_t<HD, 8>(a, n_kv_heads, t_max, s); return true;
-        default: return false;
-    }
+    return for_qpk(qpk, [&](auto Q) {
+        launch_attn_t<HD, decltype(Q)::value>(a, n_kv_heads, t_max, s);
+        return 0;
+    }) == 0;
 }
 
 }  // namespace
 
 bool xalm::launch_attn(const AttnArgs& a, int hd, int qpk, int n_kv_heads, int t_max, hipStream_t s) {
-    bool ok = false;
     switch (hd) {
-        case 16: ok = launch_attn_hd<16>(a, qpk, n_kv_heads, t_max, s); break;
-        case 32: ok = launch_attn_hd<32>(a, qpk, n_kv_heads, t_max, s); break;
-        case 64: ok = launch_attn_hd<64>(a, qpk, n_kv_heads, t_max, s); break;
-        case 128: ok = launch_attn_hd<128>(a, qpk, n_kv_heads, t_max, s); break;
-        case 256: ok = launch_attn_hd<256>(a, qpk, n_kv_heads, t_max, s); break;
+        case 16: return launch_attn_hd<16>(a, qpk, n_kv_heads, t_max, s);
+        case 32: return launch_attn_hd<32>(a, qpk, n_kv_heads, t_max, s);
+        case 64: return launch_attn_hd<64>(a, qpk, n_kv_heads, t_max, s);
+        case 128: return launch_attn_hd<128>(a, qpk, n_kv_heads, t_max, s);
+        case 256: return launch_attn_hd<256>(a, qpk, n_kv_heads, t_max, s);
         default: return false;
     }
-    return ok;
 }
 
 int xalm::attn_nsplit(int n_kv_heads, int max_seq_len) {

@@ -29,7 +29,6 @@ namespace xalm {
 constexpr int PF_TOK = 64;       // tokens per pass of the hand-written MFMA GEMMs (two token tiles)
 constexpr int PF_TOK_MM = 2048;  // tokens per pass of the LDS-tiled f16 GEMM (gemm16.h)
 constexpr int PF_TOK_BLAS = 512; // tokens per pass of the hipBLASLt GEMMs (XH_OPT_PREFILL 4)
-constexpr int PF_TOK_MAX = PF_TOK_MM > PF_TOK_BLAS ? PF_TOK_MM : PF_TOK_BLAS;
 constexpr int PF_THREADS = 256;  // 4 waves
 constexpr int PF_WAVES = PF_THREADS / 64;
 
@@ -198,114 +197,136 @@ __device__ __forceinline__ size_t split_off(const int t, const int k, const int 
     return frag_off(t >> 5, c, m, (t & 31) + 32 * hh, n_c, M);
 }
 
-// one workgroup per token row (grid = 32 x token tiles; rows past n are zero): s_t, hi, lo in
-// the fragment layout, inv_s[t] = 1 / s_t
+// ---- the split-f16 row writer: one workgroup per token row (grid = 32 x token tiles) --------
+// a row past n: zero halves
+template <int THREADS>
+__device__ __forceinline__ void split_zero_row(const int t, const int K, const int E, uint16_t* xh, uint16_t* xl) {
+    for (int i = threadIdx.x; i < K / 8; i += THREADS) {
+        const size_t o = split_off(t, 8 * i, K, E);
+        *(u32x4*)(xh + o) = u32x4{0u, 0u, 0u, 0u};
+        *(u32x4*)(xl + o) = u32x4{0u, 0u, 0u, 0u};
+    }
+}
+// the workgroup's max of m through red[THREADS / 64] (one barrier; red is free again after the next)
+template <int THREADS>
+__device__ __forceinline__ float block_absmax(float m, float* red) {
+    m = wave_max(m);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    m = red[0];
+#pragma unroll
+    for (int w = 1; w < THREADS / 64; w++) m = fmaxf(m, red[w]);
+    return m;
+}
+// row max m = f 2^e with f in [0.5, 1): s = 2^(15 - e) puts s m in [2^14, 2^15); a zero or
+// non-finite row keeps s = 1
+__device__ __forceinline__ float split_scale(const float m) {
+    int e = 0;
+    const bool ok = m > 0.f && m <= FLT_MAX;
+    if (ok) frexpf(m, &e);
+    return ok ? ldexpf(1.f, 15 - e) : 1.f;
+}
+// 8 scaled elements as hi = f16(u), lo = f16(u - hi) at f16 offset o
+__device__ __forceinline__ void split_store8(const float (&u)[8], const size_t o, uint16_t* xh, uint16_t* xl) {
+    f16x8 hi, lo;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        hi[j] = (_Float16)u[j];
+        lo[j] = (_Float16)(u[j] - (float)hi[j]);
+    }
+    *(f16x8*)(xh + o) = hi;
+    *(f16x8*)(xl + o) = lo;
+}
+// elements 8i .. 8i+7 of the normed row (prefill_rmsnorm_kernel's x * scale * w)
+__device__ __forceinline__ void norm8(const float* xr, const float scale, const void* w, const int wdt, const int i,
+                                      float (&v)[8]) {
+    const float4 a = ((const float4*)xr)[2 * i], b = ((const float4*)xr)[2 * i + 1];
+    const float4 wa = load_norm4(w, wdt, 2 * i), wb = load_norm4(w, wdt, 2 * i + 1);
+    v[0] = a.x * scale * wa.x; v[1] = a.y * scale * wa.y; v[2] = a.z * scale * wa.z; v[3] = a.w * scale * wa.w;
+    v[4] = b.x * scale * wb.x; v[5] = b.y * scale * wb.y; v[6] = b.z * scale * wb.z; v[7] = b.w * scale * wb.w;
+}
+// the normed row (norm8 of xr) scaled to its max and split: the tail of both rmsnorm split kernels
+__device__ __forceinline__ void norm_split_row(const float* xr, const float scale, const void* w, const int wdt,
+                                               const int t, const int dim, const int E, uint16_t* xh, uint16_t* xl,
+                                               float* inv_s, float* red) {
+    float m = 0.f;
+    for (int i = threadIdx.x; i < dim / 8; i += 256) {
+        float v[8];
+        norm8(xr, scale, w, wdt, i, v);
+#pragma unroll
+        for (int j = 0; j < 8; j++) m = fmaxf(m, fabsf(v[j]));
+    }
+    const float s = split_scale(block_absmax<256>(m, red));
+    for (int i = threadIdx.x; i < dim / 8; i += 256) {
+        float v[8];
+        norm8(xr, scale, w, wdt, i, v);
+#pragma unroll
+        for (int j = 0; j < 8; j++) v[j] = v[j] * s;
+        split_store8(v, split_off(t, 8 * i, dim, E), xh, xl);
+    }
+    if (threadIdx.x == 0) inv_s[t] = 1.f / s;
+}
+// elements 4i .. 4i+3 of token t's summed K slices (slice order: fixed, as prefill_epi_kernel),
+// times ps where the partials carry a per-token factor (part_s, nullable)
+__device__ __forceinline__ float4 sum_slices4(const float* part, const int ks, const int n, const int t,
+                                              const size_t row_len, const int i, const float* part_s,
+                                              const float ps) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int s = 0; s < ks; s++) {
+        const float4 p = *(const float4*)(part + ((size_t)s * n + t) * row_len + 4 * i);
+        v.x += p.x;
+        v.y += p.y;
+        v.z += p.z;
+        v.w += p.w;
+    }
+    if (part_s) {
+        v.x *= ps;
+        v.y *= ps;
+        v.z *= ps;
+        v.w *= ps;
+    }
+    return v;
+}
+
+// s_t, hi, lo of each row of x in the split layout, inv_s[t] = 1 / s_t
 __global__ __launch_bounds__(256) void prefill_split_kernel(const float* x, int K, int n, int E, uint16_t* xh,
                                                             uint16_t* xl, float* inv_s) {
     __shared__ float red[4];
     const int t = blockIdx.x;
-    if (t >= n) {
-        for (int i = threadIdx.x; i < K / 8; i += 256) {
-            const size_t o = split_off(t, 8 * i, K, E);
-            *(u32x4*)(xh + o) = u32x4{0u, 0u, 0u, 0u};
-            *(u32x4*)(xl + o) = u32x4{0u, 0u, 0u, 0u};
-        }
-        return;
-    }
+    if (t >= n) return split_zero_row<256>(t, K, E, xh, xl);
     const float* xr = x + (size_t)t * K;
     float m = 0.f;
     for (int i = threadIdx.x; i < K; i += 256) m = fmaxf(m, fabsf(xr[i]));
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    // m = f 2^e with f in [0.5, 1): s = 2^(15 - e) puts s m in [2^14, 2^15); a zero or
-    // non-finite row keeps s = 1
-    int e = 0;
-    const bool ok = m > 0.f && m <= FLT_MAX;
-    if (ok) frexpf(m, &e);  // m = f * 2^e, f in [0.5, 1)
-    const float s = ok ? ldexpf(1.f, 15 - e) : 1.f;
+    const float s = split_scale(block_absmax<256>(m, red));
     for (int i = threadIdx.x; i < K / 8; i += 256) {
         const int k = 8 * i;
         const float4 a = *(const float4*)(xr + k), b = *(const float4*)(xr + k + 4);
-        const float v[8] = {a.x * s, a.y * s, a.z * s, a.w * s, b.x * s, b.y * s, b.z * s, b.w * s};
-        f16x8 hi, lo;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            hi[j] = (_Float16)v[j];
-            lo[j] = (_Float16)(v[j] - (float)hi[j]);
-        }
-        const size_t o = split_off(t, k, K, E);
-        *(f16x8*)(xh + o) = hi;
-        *(f16x8*)(xl + o) = lo;
+        const float u[8] = {a.x * s, a.y * s, a.z * s, a.w * s, b.x * s, b.y * s, b.z * s, b.w * s};
+        split_store8(u, split_off(t, k, K, E), xh, xl);
     }
     if (threadIdx.x == 0) inv_s[t] = 1.f / s;
 }
 
 // rmsnorm of each token row (as prefill_rmsnorm_kernel: x * scale * w, same reduction) written
-// straight into the split-f16 fragment layout for the GEMM that consumes it: one launch instead
-// of rmsnorm + split (grid = 32 x token tiles; rows past n are zero)
+// straight into the split-f16 layout for the GEMM that consumes it: one launch instead of
+// rmsnorm + split
 __global__ __launch_bounds__(256) void prefill_rmsnorm_split_kernel(const float* x, int dim, const void* w, int wdt,
                                                                     float eps, int n, int E, uint16_t* xh,
                                                                     uint16_t* xl, float* inv_s) {
     __shared__ float red[4];
     const int t = blockIdx.x;
-    auto frag = [&](const int k) { return split_off(t, k, dim, E); };
-    if (t >= n) {
-        for (int i = threadIdx.x; i < dim / 8; i += 256) {
-            const size_t o = frag(8 * i);
-            *(u32x4*)(xh + o) = u32x4{0u, 0u, 0u, 0u};
-            *(u32x4*)(xl + o) = u32x4{0u, 0u, 0u, 0u};
-        }
-        return;
-    }
+    if (t >= n) return split_zero_row<256>(t, dim, E, xh, xl);
     const float* xr = x + (size_t)t * dim;
     const float scale = block_rms_scale<256>(xr, dim, eps, red);
     __syncthreads();  // red reused below
-    auto norm8 = [&](const int i, float* v) {  // elements 8i .. 8i+7 of the normed row
-        const float4 a = ((const float4*)xr)[2 * i], b = ((const float4*)xr)[2 * i + 1];
-        const float4 wa = load_norm4(w, wdt, 2 * i), wb = load_norm4(w, wdt, 2 * i + 1);
-        v[0] = a.x * scale * wa.x; v[1] = a.y * scale * wa.y; v[2] = a.z * scale * wa.z; v[3] = a.w * scale * wa.w;
-        v[4] = b.x * scale * wb.x; v[5] = b.y * scale * wb.y; v[6] = b.z * scale * wb.z; v[7] = b.w * scale * wb.w;
-    };
-    float m = 0.f;
-    for (int i = threadIdx.x; i < dim / 8; i += 256) {
-        float v[8];
-        norm8(i, v);
-#pragma unroll
-        for (int j = 0; j < 8; j++) m = fmaxf(m, fabsf(v[j]));
-    }
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    int e = 0;
-    const bool ok = m > 0.f && m <= FLT_MAX;
-    if (ok) frexpf(m, &e);
-    const float s = ok ? ldexpf(1.f, 15 - e) : 1.f;
-    for (int i = threadIdx.x; i < dim / 8; i += 256) {
-        float v[8];
-        norm8(i, v);
-        f16x8 hi, lo;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const float u = v[j] * s;
-            hi[j] = (_Float16)u;
-            lo[j] = (_Float16)(u - (float)hi[j]);
-        }
-        const size_t o = frag(8 * i);
-        *(f16x8*)(xh + o) = hi;
-        *(f16x8*)(xl + o) = lo;
-    }
-    if (threadIdx.x == 0) inv_s[t] = 1.f / s;
+    norm_split_row(xr, scale, w, wdt, t, dim, E, xh, xl, inv_s, red);
 }
 
-// EPI_RESID of a GEMM's partials (x += the summed K-slices, slice order, times part_s, as
-// prefill_epi_kernel) and the rmsnorm split of the updated row for the next GEMM (as
-// prefill_rmsnorm_split_kernel: the same per-thread float4 order, reduction and split), in one
-// launch: the residual row is read once.  part_s and inv_s may both be pf_xs: a workgroup reads
-// its token's factor before the first barrier and writes the new one after the last.  Dynamic
-// LDS: the updated row (dim floats).  grid = 32 x token tiles; rows past n are zero.
+// EPI_RESID of a GEMM's partials (x += sum_slices4, as prefill_epi_kernel) and the rmsnorm split
+// of the updated row for the next GEMM (as prefill_rmsnorm_split_kernel: the same per-thread
+// float4 order, reduction and split), in one launch: the residual row is read once.  part_s and
+// inv_s may both be pf.xs: a workgroup reads its token's factor before the first barrier and
+// writes the new one after the last.  Dynamic LDS: the updated row (dim floats).
 __global__ __launch_bounds__(256) void prefill_resid_norm_split_kernel(const float* part, int ks, const float* part_s,
                                                                        float* x, int dim, const void* w, int wdt,
                                                                        float eps, int n, int E, uint16_t* xh,
@@ -313,33 +334,12 @@ __global__ __launch_bounds__(256) void prefill_resid_norm_split_kernel(const flo
     extern __shared__ __attribute__((aligned(16))) float xrow[];  // float4 reads and writes
     __shared__ float red[4];
     const int t = blockIdx.x;
-    auto frag = [&](const int k) { return split_off(t, k, dim, E); };
-    if (t >= n) {
-        for (int i = threadIdx.x; i < dim / 8; i += 256) {
-            const size_t o = frag(8 * i);
-            *(u32x4*)(xh + o) = u32x4{0u, 0u, 0u, 0u};
-            *(u32x4*)(xl + o) = u32x4{0u, 0u, 0u, 0u};
-        }
-        return;
-    }
+    if (t >= n) return split_zero_row<256>(t, dim, E, xh, xl);
     float4* xr4 = (float4*)(x + (size_t)t * dim);
     const float ps = part_s ? part_s[t] : 1.f;
     float ss = 0.f;
     for (int i = threadIdx.x; i < (dim >> 2); i += 256) {
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int s = 0; s < ks; s++) {  // slice order: fixed
-            const float4 p = *(const float4*)(part + ((size_t)s * n + t) * dim + 4 * i);
-            v.x += p.x;
-            v.y += p.y;
-            v.z += p.z;
-            v.w += p.w;
-        }
-        if (part_s) {
-            v.x *= ps;
-            v.y *= ps;
-            v.z *= ps;
-            v.w *= ps;
-        }
+        const float4 v = sum_slices4(part, ks, n, t, (size_t)dim, i, part_s, ps);
         float4 r = xr4[i];
         r.x += v.x;
         r.y += v.y;
@@ -349,58 +349,14 @@ __global__ __launch_bounds__(256) void prefill_resid_norm_split_kernel(const flo
         ((float4*)xrow)[i] = r;
         ss += r.x * r.x + r.y * r.y + r.z * r.z + r.w * r.w;
     }
-    // block_rms_scale<256>'s reduction
-    ss = wave_sum(ss);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
-    __syncthreads();
-    float tot = 0.f;
-#pragma unroll
-    for (int wv = 0; wv < 4; wv++) tot += red[wv];
-    const float rms = sqrtf(tot / (float)dim + eps);
-    const float scale = 1.0f / rms;
+    const float scale = block_rms_of<256>(ss, dim, eps, red);
     __syncthreads();  // red reused below
-    auto norm8 = [&](const int i, float* v) {  // elements 8i .. 8i+7 of the normed row
-        const float4 a = ((const float4*)xrow)[2 * i], b = ((const float4*)xrow)[2 * i + 1];
-        const float4 wa = load_norm4(w, wdt, 2 * i), wb = load_norm4(w, wdt, 2 * i + 1);
-        v[0] = a.x * scale * wa.x; v[1] = a.y * scale * wa.y; v[2] = a.z * scale * wa.z; v[3] = a.w * scale * wa.w;
-        v[4] = b.x * scale * wb.x; v[5] = b.y * scale * wb.y; v[6] = b.z * scale * wb.z; v[7] = b.w * scale * wb.w;
-    };
-    float m = 0.f;
-    for (int i = threadIdx.x; i < dim / 8; i += 256) {
-        float v[8];
-        norm8(i, v);
-#pragma unroll
-        for (int j = 0; j < 8; j++) m = fmaxf(m, fabsf(v[j]));
-    }
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    int e = 0;
-    const bool ok = m > 0.f && m <= FLT_MAX;
-    if (ok) frexpf(m, &e);
-    const float s = ok ? ldexpf(1.f, 15 - e) : 1.f;
-    for (int i = threadIdx.x; i < dim / 8; i += 256) {
-        float v[8];
-        norm8(i, v);
-        f16x8 hi, lo;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const float u = v[j] * s;
-            hi[j] = (_Float16)u;
-            lo[j] = (_Float16)(u - (float)hi[j]);
-        }
-        const size_t o = frag(8 * i);
-        *(f16x8*)(xh + o) = hi;
-        *(f16x8*)(xl + o) = lo;
-    }
-    if (threadIdx.x == 0) inv_s[t] = 1.f / s;
+    norm_split_row(xrow, scale, w, wdt, t, dim, E, xh, xl, inv_s, red);
 }
 
-// EPI_GLU (act(g) * u of the summed K-slices, slice order as prefill_epi_kernel) written
-// straight into the split-f16 fragments of the W2 GEMM's input: one launch instead of GLU
-// epilogue + split.  The row (hidden f32) is held in dynamic LDS between the max and the split
-// (grid = 32 x token tiles; rows past n are zero)
+// EPI_GLU (act(g) * u of sum_slices4) written straight into the split-f16 layout of the W2
+// GEMM's input: one launch instead of GLU epilogue + split.  The row (hidden f32) is held in
+// dynamic LDS between the max and the split.
 // part_s (nullable): per-token factor of the partials (the hipBLASLt GEMM's 1 / s of its input)
 __global__ __launch_bounds__(1024) void prefill_glu_split_kernel(const float* part, int ks, int n, int hidden, int act,
                                                                 int E, uint16_t* xh, uint16_t* xl, float* inv_s,
@@ -408,15 +364,7 @@ __global__ __launch_bounds__(1024) void prefill_glu_split_kernel(const float* pa
     extern __shared__ float hrow[];
     __shared__ float red[16];
     const int t = blockIdx.x;
-    auto frag = [&](const int k) { return split_off(t, k, hidden, E); };
-    if (t >= n) {
-        for (int i = threadIdx.x; i < hidden / 8; i += 1024) {
-            const size_t o = frag(8 * i);
-            *(u32x4*)(xh + o) = u32x4{0u, 0u, 0u, 0u};
-            *(u32x4*)(xl + o) = u32x4{0u, 0u, 0u, 0u};
-        }
-        return;
-    }
+    if (t >= n) return split_zero_row<1024>(t, hidden, E, xh, xl);
     const size_t rows = 2 * (size_t)hidden;
     float m = 0.f;
     // two (g, u) pairs per 16-byte load (hidden % 32 == 0 on the batched path): 73.6 -> 53.9 us per
@@ -424,45 +372,18 @@ __global__ __launch_bounds__(1024) void prefill_glu_split_kernel(const float* pa
     const float ps = part_s ? part_s[t] : 1.f;
 #pragma unroll 4
     for (int i = threadIdx.x; i < (hidden >> 1); i += 1024) {
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int s = 0; s < ks; s++) {  // slice order: fixed
-            const float4 p = *(const float4*)(part + ((size_t)s * n + t) * rows + 4 * i);
-            v.x += p.x;
-            v.y += p.y;
-            v.z += p.z;
-            v.w += p.w;
-        }
-        if (part_s) {
-            v.x *= ps;
-            v.y *= ps;
-            v.z *= ps;
-            v.w *= ps;
-        }
+        const float4 v = sum_slices4(part, ks, n, t, rows, i, part_s, ps);
         const float h0 = act_fn(act, v.x) * v.y, h1 = act_fn(act, v.z) * v.w;
         hrow[2 * i] = h0;
         hrow[2 * i + 1] = h1;
         m = fmaxf(m, fmaxf(fabsf(h0), fabsf(h1)));
     }
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    m = red[0];
-    for (int w = 1; w < 16; w++) m = fmaxf(m, red[w]);
-    int e = 0;
-    const bool ok = m > 0.f && m <= FLT_MAX;
-    if (ok) frexpf(m, &e);
-    const float s = ok ? ldexpf(1.f, 15 - e) : 1.f;
+    const float s = split_scale(block_absmax<1024>(m, red));
     for (int i = threadIdx.x; i < hidden / 8; i += 1024) {
-        f16x8 hi, lo;
+        float u[8];
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const float u = hrow[8 * i + j] * s;
-            hi[j] = (_Float16)u;
-            lo[j] = (_Float16)(u - (float)hi[j]);
-        }
-        const size_t o = frag(8 * i);
-        *(f16x8*)(xh + o) = hi;
-        *(f16x8*)(xl + o) = lo;
+        for (int j = 0; j < 8; j++) u[j] = hrow[8 * i + j] * s;
+        split_store8(u, split_off(t, 8 * i, hidden, E), xh, xl);
     }
     if (threadIdx.x == 0) inv_s[t] = 1.f / s;
 }

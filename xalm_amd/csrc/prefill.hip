@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <vector>
 
 #include "ctx.h"
@@ -35,70 +36,86 @@ size_t pf_part_floats(const xh_ctx* ctx, const int T) {
 }  // namespace
 
 void xalm::pf_free(xh_ctx* ctx) {
-    for (void* p : {(void*)ctx->pf_tok, (void*)ctx->pf_x, (void*)ctx->pf_xn, (void*)ctx->pf_q, (void*)ctx->pf_att,
-                    (void*)ctx->pf_h, (void*)ctx->pf_part, (void*)ctx->pf_sp, (void*)ctx->pf_xh, (void*)ctx->pf_xl,
-                    (void*)ctx->pf_xs, (void*)ctx->pf_logits, (void*)ctx->pf_tgt, (void*)ctx->pf_po,
-                    (void*)ctx->pf_pml, (void*)ctx->pf_cnt, (void*)ctx->pf_ks, (void*)ctx->pf_vs, (void*)ctx->pf_sinkv})
-        hipFree(p);
-    ctx->pf_tok = nullptr; ctx->pf_x = ctx->pf_xn = ctx->pf_q = ctx->pf_att = ctx->pf_h = ctx->pf_part = nullptr;
-    ctx->pf_sp = nullptr; ctx->pf_xh = ctx->pf_xl = nullptr; ctx->pf_xs = nullptr; ctx->pf_logits = nullptr;
-    ctx->pf_tgt = nullptr; ctx->pf_po = ctx->pf_pml = nullptr; ctx->pf_cnt = nullptr;
-    ctx->pf_ks = ctx->pf_vs = ctx->pf_sinkv = nullptr;
-    ctx->pf_cap = ctx->pf_po_cap = ctx->pf_ring_cap = 0;
+    for (int g = 0; g < PfBufs::N_GROUPS; g++) ctx->pf.free_group(g);
 }
 
 namespace {
 
 // pass buffers for T tokens (kept while later passes fit; a longer pass length reallocates)
 int pf_alloc(xh_ctx* ctx, const int T) {
-    if (ctx->pf_cap >= T) return 0;
+    PfBufs& b = ctx->pf;
+    if (b.cap[PfBufs::PASS] >= T) return 0;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     pf_free(ctx);
     const xh_config& c = ctx->c;
     const size_t t = (size_t)T;
     int rc;
-    if ((rc = dmalloc(ctx, &ctx->pf_tok, t)) || (rc = dmalloc(ctx, &ctx->pf_x, t * c.dim)) ||
-        (rc = dmalloc(ctx, &ctx->pf_xn, t * c.dim)) || (rc = dmalloc(ctx, &ctx->pf_q, t * ctx->q_dim)) ||
-        (rc = dmalloc(ctx, &ctx->pf_att, t * ctx->q_dim)) || (rc = dmalloc(ctx, &ctx->pf_h, t * c.hidden_dim)) ||
-        (rc = dmalloc(ctx, &ctx->pf_part, pf_part_floats(ctx, T))) || (rc = dmalloc(ctx, &ctx->pf_sp, t)))
+    if ((rc = dmalloc(ctx, &b.tok, t)) || (rc = dmalloc(ctx, &b.x, t * c.dim)) ||
+        (rc = dmalloc(ctx, &b.xn, t * c.dim)) || (rc = dmalloc(ctx, &b.q, t * ctx->q_dim)) ||
+        (rc = dmalloc(ctx, &b.att, t * ctx->q_dim)) || (rc = dmalloc(ctx, &b.h, t * c.hidden_dim)) ||
+        (rc = dmalloc(ctx, &b.part, pf_part_floats(ctx, T))) || (rc = dmalloc(ctx, &b.sp, t)))
         return rc;
-    // pf_xh: the split-kernel fragments of <= 64 tokens, or hi rows then lo rows of a row-major
-    // pass input (gemm16.h / hipBLASLt); pf_xl: the split kernel's lo fragments
+    // xh: the split-kernel fragments of <= 64 tokens, or hi rows then lo rows of a row-major
+    // pass input (gemm16.h / hipBLASLt); xl: the split kernel's lo fragments
     const size_t kmax = std::max({(size_t)c.dim, (size_t)c.hidden_dim, (size_t)ctx->q_dim});
-    if ((rc = dmalloc(ctx, &ctx->pf_xh, 2 * std::max(t, (size_t)PF_TOK) * kmax)) ||
-        (rc = dmalloc(ctx, &ctx->pf_xl, PF_TOK * kmax)) || (rc = dmalloc(ctx, &ctx->pf_xs, std::max(t, (size_t)PF_TOK))))
+    if ((rc = dmalloc(ctx, &b.xh, 2 * std::max(t, (size_t)PF_TOK) * kmax)) ||
+        (rc = dmalloc(ctx, &b.xl, PF_TOK * kmax)) || (rc = dmalloc(ctx, &b.xs, std::max(t, (size_t)PF_TOK))))
         return rc;
-    ctx->pf_cap = T;
+    b.cap[PfBufs::PASS] = T;
     return 0;
 }
 
-// the per-token split attention's partials (XH_OPT_PREFILL_ATTN 0), sized for the pass
-int pf_alloc_split_attn(xh_ctx* ctx) {
-    if (ctx->pf_po_cap >= ctx->pf_cap) return 0;
-    hipFree(ctx->pf_po); hipFree(ctx->pf_pml); hipFree(ctx->pf_cnt);
-    ctx->pf_po = ctx->pf_pml = nullptr; ctx->pf_cnt = nullptr; ctx->pf_po_cap = 0;
-    const size_t t = (size_t)ctx->pf_cap;
-    int rc;
-    if ((rc = dmalloc(ctx, &ctx->pf_po, t * ctx->nsplit * ctx->q_dim)) ||
-        (rc = dmalloc(ctx, &ctx->pf_pml, t * ctx->nsplit * ctx->c.n_heads * 2)) ||
-        (rc = dmalloc(ctx, &ctx->pf_cnt, t * ctx->c.n_kv_heads)))
-        return rc;
-    ctx->pf_po_cap = ctx->pf_cap;
-    return 0;
+// A group beside the pass buffers, allocated on its first use and sized for the pass: the
+// per-token split attention's partials (XH_OPT_PREFILL_ATTN 0), a ring pass's staging rows and
+// sink versions, a perplexity pass's logits and targets.  Keeps dmalloc's code and message.
+int pf_alloc_group(xh_ctx* ctx, const int g) {
+    PfBufs& b = ctx->pf;
+    if (b.cap[g] >= b.cap[PfBufs::PASS]) return 0;
+    b.free_group(g);
+    const size_t t = (size_t)b.cap[PfBufs::PASS];
+    int rc = 0;
+    auto get = [&](auto** p, const size_t n) {
+        if (!rc) rc = dmalloc(ctx, p, n);
+    };
+    if (g == PfBufs::ATTN0) {
+        get(&b.po, t * ctx->nsplit * ctx->q_dim);
+        get(&b.pml, t * ctx->nsplit * ctx->c.n_heads * 2);
+        get(&b.cnt, t * ctx->c.n_kv_heads);
+    } else if (g == PfBufs::RING) {
+        get(&b.ks, t * ctx->kv_dim);
+        get(&b.vs, t * ctx->kv_dim);
+        get(&b.sinkv, t * 2 * ctx->kv_dim);
+    } else {
+        get(&b.logits, t * ctx->c.vocab_size);
+        get(&b.tgt, t);
+    }
+    if (!rc) b.cap[g] = b.cap[PfBufs::PASS];
+    return rc;
 }
 
-// a ring pass's staging rows and sink versions, sized for the pass
-int pf_alloc_ring(xh_ctx* ctx) {
-    if (ctx->pf_ring_cap >= ctx->pf_cap) return 0;
-    hipFree(ctx->pf_ks); hipFree(ctx->pf_vs); hipFree(ctx->pf_sinkv);
-    ctx->pf_ks = ctx->pf_vs = ctx->pf_sinkv = nullptr; ctx->pf_ring_cap = 0;
-    const size_t t = (size_t)ctx->pf_cap;
-    int rc;
-    if ((rc = dmalloc(ctx, &ctx->pf_ks, t * ctx->kv_dim)) || (rc = dmalloc(ctx, &ctx->pf_vs, t * ctx->kv_dim)) ||
-        (rc = dmalloc(ctx, &ctx->pf_sinkv, t * 2 * ctx->kv_dim)))
-        return rc;
-    ctx->pf_ring_cap = ctx->pf_cap;
-    return 0;
+// The model's GEMMs: W [rows][K] of decode form dt.  A layer's four in launch order, and the
+// lm_head (all vocab_size rows; it runs in chunks of PF_CLS_CHUNK).
+struct PfMat { const char* what; int dt; const void* w; int K, rows; };
+enum { PF_QKV, PF_WO, PF_W13, PF_W2 };
+std::array<PfMat, 4> pf_layer_mats(const xh_ctx* ctx, const int l) {
+    const xh_config& c = ctx->c;
+    const LayerW& w = ctx->L[l];
+    return {{{"qkv", kdt(w.qkv_dt, w.qkv_x), w.wqkv, c.dim, ctx->q_dim + 2 * ctx->kv_dim},
+             {"wo", kdt(w.wo_dt, w.wo_x), w.wo, ctx->q_dim, c.dim},
+             {"w1/w3", kdt(w.w13_dt, w.w13_x), w.w13, c.dim, 2 * c.hidden_dim},
+             {"w2", kdt(w.w2_dt, w.w2_x), w.w2, c.hidden_dim, c.dim}}};
+}
+PfMat pf_cls_mat(const xh_ctx* ctx) {
+    return {"lm_head", kdt(ctx->wcls_dt, ctx->wcls_x), ctx->wcls, ctx->c.dim, ctx->c.vocab_size};
+}
+// every layer's GEMMs, then one lm_head chunk
+std::vector<PfMat> pf_all_mats(const xh_ctx* ctx) {
+    std::vector<PfMat> gs;
+    for (int l = 0; l < (int)ctx->L.size(); l++)
+        for (const PfMat& g : pf_layer_mats(ctx, l)) gs.push_back(g);
+    gs.push_back(pf_cls_mat(ctx));
+    gs.back().rows = std::min(PF_CLS_CHUNK, gs.back().rows);
+    return gs;
 }
 
 // K slices for a GEMM of `rows` outputs: about PF_WAVE_TARGET waves, K divisible into whole
@@ -162,19 +179,10 @@ bool pf_lay0(const xh_ctx* ctx, int dt, int K) {
 // full-pass GEMM of the model (if not, every dtype keeps the MFMA kernels); and the f16 image
 // buffer of the largest fp8 matrix that goes to the f16 GEMMs.
 int pf_prepare(xh_ctx* ctx) {
-    const xh_config& c = ctx->c;
-    struct G { int dt, rows, K; };
-    std::vector<G> gs;
-    for (const LayerW& w : ctx->L) {
-        gs.push_back({kdt(w.qkv_dt, w.qkv_x), ctx->q_dim + 2 * ctx->kv_dim, c.dim});
-        gs.push_back({kdt(w.wo_dt, w.wo_x), c.dim, ctx->q_dim});
-        gs.push_back({kdt(w.w13_dt, w.w13_x), 2 * c.hidden_dim, c.dim});
-        gs.push_back({kdt(w.w2_dt, w.w2_x), c.dim, c.hidden_dim});
-    }
-    gs.push_back({kdt(ctx->wcls_dt, ctx->wcls_x), std::min(PF_CLS_CHUNK, c.vocab_size), c.dim});
+    const std::vector<PfMat> gs = pf_all_mats(ctx);
     if (ctx->prefill_gemm == 4 && !blas_ok(ctx)) {
         int ok = 1;
-        for (const G& g : gs) {
+        for (const PfMat& g : gs) {
             if (!pf_f16w(g.dt)) continue;
             bool have = false;
             int rc = blas_has_plan(ctx, g.rows, g.K, 2 * PF_TOK_BLAS, &have);
@@ -184,7 +192,7 @@ int pf_prepare(xh_ctx* ctx) {
         blas_set_ok(ctx, ok);
     }
     size_t wdq = 0;  // fp8: one f16 image; gguf blocks: hi and lo images
-    for (const G& g : gs)
+    for (const PfMat& g : gs)
         if ((pf_f8(g.dt) || gq_dt(g.dt)) && pf_lay0(ctx, g.dt, g.K))
             wdq = std::max(wdq, (size_t)g.rows * g.K * (gq_dt(g.dt) ? 2 : 1));
     if (wdq > ctx->pf_wdq_elems) {
@@ -212,37 +220,41 @@ int pf_layout(const xh_ctx* ctx, int dt, int K, int rows) {
     const int E = elems_per_16b(dt);
     return pf_ks16(rows, K, E) ? E : -1;
 }
-// split-f16 halves of a pass's rows: hi into pf_xh; lo into pf_xl (fragments) or right after
+// split-f16 halves of a pass's rows: hi into pf.xh; lo into pf.xl (fragments) or right after
 // the hi rows (row-major)
 uint16_t* pf_lo(xh_ctx* ctx, int layout, int n, int K) {
-    return layout ? ctx->pf_xl : ctx->pf_xh + (size_t)n * K;
+    return layout ? ctx->pf.xl : ctx->pf.xh + (size_t)n * K;
 }
 // grid of the split kernels: one workgroup per token row, fragments padded to 32-token tiles
 int pf_split_grid(int layout, int n) { return layout ? 32 * ((n + 31) / 32) : n; }
+int pf_layout(const xh_ctx* ctx, const PfMat& g) { return pf_layout(ctx, g.dt, g.K, g.rows); }
 // Tokens per pass: PF_TOK_MM (gemm16.h) / PF_TOK_BLAS (hipBLASLt) when every layer GEMM takes the
 // row-major input (the lm_head of a perplexity pass aside: it runs on 64-token slices when it
 // cannot), else 64 (the register-streaming MFMA kernels' two token tiles)
 int pf_pass_tokens(const xh_ctx* ctx) {
-    const xh_config& c = ctx->c;
-    for (const LayerW& w : ctx->L)
-        if (!pf_lay0(ctx, kdt(w.qkv_dt, w.qkv_x), c.dim) || !pf_lay0(ctx, kdt(w.wo_dt, w.wo_x), ctx->q_dim) ||
-            !pf_lay0(ctx, kdt(w.w13_dt, w.w13_x), c.dim) || !pf_lay0(ctx, kdt(w.w2_dt, w.w2_x), c.hidden_dim))
-            return PF_TOK;
+    for (int l = 0; l < (int)ctx->L.size(); l++)
+        for (const PfMat& g : pf_layer_mats(ctx, l))
+            if (!pf_lay0(ctx, g.dt, g.K)) return PF_TOK;
     return ctx->prefill_gemm == 4 ? PF_TOK_BLAS : PF_TOK_MM;
 }
-// rmsnorm of the pass's rows (pf_x) as the input of the GEMM over W (dt, [rows][dim]): written
-// straight into the split-f16 halves when that GEMM takes a split input (one launch)
-void pf_norm(xh_ctx* ctx, const void* nw, int ndt, int m, int dt, int rows) {
+// One pass of prefill_batched: m tokens at positions p0.. (ring: all >= max_seq_len), and what one
+// launch leaves for the next.  scaled: the last pf_gemm's partials carry 1 / s_t (pf.xs);
+// split_ready: the next GEMM's split input is already in pf.xh (pf_norm, pf_resid_norm, pf_glu).
+struct PfPass { int m, p0; bool ring; bool scaled; bool split_ready; };
+// rmsnorm of the pass's rows (pf.x) as the input of the GEMM g (K = dim): written straight into
+// the split-f16 halves when that GEMM takes a split input (one launch)
+void pf_norm(xh_ctx* ctx, PfPass& ps, const void* nw, int ndt, const PfMat& g) {
     const xh_config& c = ctx->c;
-    const int lay = pf_layout(ctx, dt, c.dim, rows);
+    PfBufs& b = ctx->pf;
+    const int lay = pf_layout(ctx, g);
     if (lay >= 0) {
-        hipLaunchKernelGGL(prefill_rmsnorm_split_kernel, dim3(pf_split_grid(lay, m)), dim3(256), 0, ctx->stream,
-                           (const float*)ctx->pf_x, c.dim, nw, ndt, c.norm_eps, m, lay, ctx->pf_xh,
-                           pf_lo(ctx, lay, m, c.dim), ctx->pf_xs);
-        ctx->pf_split_ready = true;
+        hipLaunchKernelGGL(prefill_rmsnorm_split_kernel, dim3(pf_split_grid(lay, ps.m)), dim3(256), 0, ctx->stream,
+                           (const float*)b.x, c.dim, nw, ndt, c.norm_eps, ps.m, lay, b.xh, pf_lo(ctx, lay, ps.m, c.dim),
+                           b.xs);
+        ps.split_ready = true;
     } else {
-        hipLaunchKernelGGL(prefill_rmsnorm_kernel, dim3(m), dim3(256), 0, ctx->stream, (const float*)ctx->pf_x, c.dim,
-                           nw, ndt, c.norm_eps, ctx->pf_xn);
+        hipLaunchKernelGGL(prefill_rmsnorm_kernel, dim3(ps.m), dim3(256), 0, ctx->stream, (const float*)b.x, c.dim, nw,
+                           ndt, c.norm_eps, b.xn);
     }
 }
 // one prompt GEMM launch (gemm16.h): the 4-wave instantiation when the launch has at least
@@ -257,17 +269,23 @@ void mm_launch(const MmArgs& a, int n_cu, hipStream_t s) {
         hipLaunchKernelGGL(mm_f16_kernel, dim3(grid), dim3(MM_THREADS), MM_LDS, s, a);
     }
 }
-// Y partials of W[rows][K] . X[n][K] into pf_part ([ks][n][rows]).  Split-f16 paths convert x
-// first unless pf_norm / the fused GLU already left its halves.  0 or an error code.
-int pf_gemm(xh_ctx* ctx, const char* what, int dt, const void* w, int K, int rows, const float* x, int n, int& ks) {
-    const int lay = pf_layout(ctx, dt, K, rows);
-    ctx->pf_scaled = false;
+struct PfGemmF32 {  // for_dt: the f32-input MFMA kernel of a dtype
+    const PfGemmArgs& a; hipStream_t s;
+    template <int DT> int run() const { pf_gemm_t<DT>(a, s); return 0; }
+};
+// Y partials of g's W[rows][K] . X[n][K] into pf.part ([ks][n][rows]).  Split-f16 paths convert x
+// first unless ps.split_ready says its halves are there already.  0 or an error code.
+int pf_gemm(xh_ctx* ctx, PfPass& ps, const PfMat& g, const float* x, int n, int& ks) {
+    PfBufs& b = ctx->pf;
+    const int dt = g.dt, K = g.K, rows = g.rows;
+    const void* w = g.w;
+    const int lay = pf_layout(ctx, g);
+    ps.scaled = false;
     if (lay >= 0) {
-        if (ctx->pf_split_ready)
-            ctx->pf_split_ready = false;
-        else
+        if (!ps.split_ready)
             hipLaunchKernelGGL(prefill_split_kernel, dim3(pf_split_grid(lay, n)), dim3(256), 0, ctx->stream, x, K, n,
-                               lay, ctx->pf_xh, pf_lo(ctx, lay, n, K), ctx->pf_xs);
+                               lay, b.xh, pf_lo(ctx, lay, n, K), b.xs);
+        ps.split_ready = false;
     }
     if (lay == 0) {
         // row-major hi rows then lo rows; partials unscaled, the epilogue multiplies by 1 / s_t
@@ -275,7 +293,7 @@ int pf_gemm(xh_ctx* ctx, const char* what, int dt, const void* w, int K, int row
             // the matrix's exact f16 image first (one streaming pass: 1 B read, 2 B written per weight)
             const size_t n16 = (size_t)rows * K / 16;
             if ((size_t)rows * K > ctx->pf_wdq_elems || K % 16)
-                return set_err(ctx, XH_E_INVALID, "prefill: %s fp8 image does not fit", what);
+                return set_err(ctx, XH_E_INVALID, "prefill: %s fp8 image does not fit", g.what);
             const int grid = (int)std::min<size_t>((n16 + 255) / 256, 8192);
             if (dt == XH_F8_E4M3)
                 hipLaunchKernelGGL(pf_dequant_f16_kernel<XH_F8_E4M3>, dim3(grid), dim3(256), 0, ctx->stream,
@@ -288,7 +306,7 @@ int pf_gemm(xh_ctx* ctx, const char* what, int dt, const void* w, int K, int row
         const uint16_t* w_lo = nullptr;  // gguf blocks: the lo image, a second GEMM into more partials
         if (gq_dt(dt)) {
             if ((size_t)2 * rows * K > ctx->pf_wdq_elems || K % 32)
-                return set_err(ctx, XH_E_INVALID, "prefill: %s block image does not fit", what);
+                return set_err(ctx, XH_E_INVALID, "prefill: %s block image does not fit", g.what);
             const size_t chunks = (size_t)rows * K / 8;
             const int grid = (int)std::min<size_t>((chunks + 255) / 256, 8192);
             uint16_t* hi = ctx->pf_wdq;
@@ -305,7 +323,7 @@ int pf_gemm(xh_ctx* ctx, const char* what, int dt, const void* w, int K, int row
             w = hi;
             w_lo = lo;
         }
-        ctx->pf_scaled = true;
+        ps.scaled = true;
         if (ctx->prefill_gemm == 4) {
             // hi and lo rows as one B operand of 2n columns: partials [2][n][rows]; a pass length
             // hipBLASLt has no algorithm for runs on gemm16.h instead (same layout, same bound)
@@ -313,24 +331,24 @@ int pf_gemm(xh_ctx* ctx, const char* what, int dt, const void* w, int K, int row
             int rc = blas_has_plan(ctx, rows, K, 2 * n, &have);
             if (rc) return rc;
             if (have || K % MM_KMULT) {
-                rc = blas_gemm(ctx, w, K, rows, ctx->pf_xh, 2 * n, ctx->pf_part);
+                rc = blas_gemm(ctx, w, K, rows, b.xh, 2 * n, b.part);
                 if (rc) return rc;
                 ks = 2;
                 return 0;
             }
         }
         const int images = w_lo ? 2 : 1;
-        const size_t cap = pf_part_floats(ctx, ctx->pf_cap);
+        const size_t cap = pf_part_floats(ctx, b.cap[PfBufs::PASS]);
         MmArgs a{};
-        a.w = (const uint16_t*)w; a.xh = ctx->pf_xh; a.xl = ctx->pf_xh + (size_t)n * K; a.out = ctx->pf_part;
+        a.w = (const uint16_t*)w; a.xh = b.xh; a.xl = b.xh + (size_t)n * K; a.out = b.part;
         a.rows = rows; a.K = K; a.n = n; a.ks = mm_pick_ks(rows, K, n, cap / images, ctx->n_cu);
         a.n_rt = mm_row_tiles(rows); a.n_tt = mm_tok_tiles(n);
         if (a.ks <= 0 || (size_t)images * a.ks * n * rows > cap)
-            return set_err(ctx, XH_E_INVALID, "prefill: %s GEMM %d x %d over %d tokens does not fit", what, rows, K, n);
+            return set_err(ctx, XH_E_INVALID, "prefill: %s GEMM %d x %d over %d tokens does not fit", g.what, rows, K, n);
         mm_launch(a, ctx->n_cu, ctx->stream);
         if (w_lo) {  // partials [ks, 2 ks): W_lo . X, summed after W_hi's by the epilogue
             a.w = w_lo;
-            a.out = ctx->pf_part + (size_t)a.ks * n * rows;
+            a.out = b.part + (size_t)a.ks * n * rows;
             mm_launch(a, ctx->n_cu, ctx->stream);
         }
         ks = images * a.ks;
@@ -339,8 +357,8 @@ int pf_gemm(xh_ctx* ctx, const char* what, int dt, const void* w, int K, int row
     if (lay > 0) {
         PfGemm16Args a{};
         a.w = w; a.row_bytes = (size_t)K * (16 / lay); a.K = K; a.rows = rows;
-        a.xh = ctx->pf_xh; a.xl = ctx->pf_xl; a.inv_s = ctx->pf_xs; a.n = n; a.ks = pf_ks16(rows, K, lay);
-        a.part = ctx->pf_part;
+        a.xh = b.xh; a.xl = b.xl; a.inv_s = b.xs; a.n = n; a.ks = pf_ks16(rows, K, lay);
+        a.part = b.part;
         switch (dt) {
             case XH_F16: pf_gemm16_t<XH_F16>(a, ctx->stream); break;
             case XH_F8_E4M3: pf_gemm16_t<XH_F8_E4M3>(a, ctx->stream); break;
@@ -350,59 +368,69 @@ int pf_gemm(xh_ctx* ctx, const char* what, int dt, const void* w, int K, int row
         return 0;
     }
     const int E = pf_elems(dt);
-    if (K % (2 * E) || n > PF_TOK) return set_err(ctx, XH_E_INVALID, "prefill: %s shape not supported", what);
+    if (K % (2 * E) || n > PF_TOK) return set_err(ctx, XH_E_INVALID, "prefill: %s shape not supported", g.what);
     PfGemmArgs a{};
-    a.w = w; a.K = K; a.rows = rows; a.x = x; a.n = n; a.part = ctx->pf_part;
+    a.w = w; a.K = K; a.rows = rows; a.x = x; a.n = n; a.part = b.part;
     a.row_bytes = gq_dt(dt) ? gq_pitch(dt, K) : (size_t)K * (16 / E);
     a.ks = pf_ks(rows, K, E);
-    if ((size_t)a.ks * rows > PF_PART_ROWS) return set_err(ctx, XH_E_INVALID, "prefill: %s shape not supported", what);
-    hipStream_t s = ctx->stream;
-    switch (dt) {
-        case XH_F32: pf_gemm_t<XH_F32>(a, s); break;
-        case XH_F16: pf_gemm_t<XH_F16>(a, s); break;
-        case XH_BF16: pf_gemm_t<XH_BF16>(a, s); break;
-        case XH_F8_E4M3: pf_gemm_t<XH_F8_E4M3>(a, s); break;
-        case XH_F8_E5M2: pf_gemm_t<XH_F8_E5M2>(a, s); break;
-        case XH_Q8: pf_gemm_t<XH_Q8>(a, s); break;
-        case XH_Q8_0: pf_gemm_t<XH_Q8_0>(a, s); break;
-        case XH_Q4_0: pf_gemm_t<XH_Q4_0>(a, s); break;
-        case XH_Q4_1: pf_gemm_t<XH_Q4_1>(a, s); break;
-        case XH_Q5_0: pf_gemm_t<XH_Q5_0>(a, s); break;
-        case XH_Q5_1: pf_gemm_t<XH_Q5_1>(a, s); break;
-        case XH_F8_E4M3_EXACT: pf_gemm_t<XH_F8_E4M3_EXACT>(a, s); break;
-        case XH_F8_E5M2_EXACT: pf_gemm_t<XH_F8_E5M2_EXACT>(a, s); break;
-        default: return set_err(ctx, XH_E_INVALID, "prefill: %s dtype %d not supported", what, dt);
-    }
+    if ((size_t)a.ks * rows > PF_PART_ROWS) return set_err(ctx, XH_E_INVALID, "prefill: %s shape not supported", g.what);
+    if (for_dt(dt, PfGemmF32{a, ctx->stream}) < 0)
+        return set_err(ctx, XH_E_INVALID, "prefill: %s dtype %d not supported", g.what, dt);
     ks = a.ks;
     return 0;
 }
-void pf_epi(xh_ctx* ctx, PfEpiArgs e) {
-    e.part = ctx->pf_part;
-    e.part_s = ctx->pf_scaled ? ctx->pf_xs : nullptr;
+void pf_epi(xh_ctx* ctx, const PfPass& ps, PfEpiArgs e) {
+    e.part = ctx->pf.part;
+    e.part_s = ps.scaled ? ctx->pf.xs : nullptr;
     const int threads = e.n * ((e.rows + 1) / 2);
     hipLaunchKernelGGL(prefill_epi_kernel, dim3((threads + 255) / 256), dim3(256), 0, ctx->stream, e);
 }
 // x += the last GEMM's partials (EPI_RESID), then the rmsnorm of the updated rows as the input of
-// the GEMM over W (dt, [rows][dim]): one launch when that GEMM takes the split input and the
-// rows fit the LDS, else pf_epi + pf_norm (the same bits either way)
-int pf_resid_norm(xh_ctx* ctx, int ks, const void* nw, int ndt, int m, int dt, int rows) {
+// the GEMM g (K = dim): one launch when that GEMM takes the split input and the rows fit the
+// LDS, else pf_epi + pf_norm (the same bits either way)
+int pf_resid_norm(xh_ctx* ctx, PfPass& ps, int ks, const void* nw, int ndt, const PfMat& g) {
     const xh_config& c = ctx->c;
-    const int lay = pf_layout(ctx, dt, c.dim, rows);
+    PfBufs& b = ctx->pf;
+    const int lay = pf_layout(ctx, g);
     const size_t lds = (size_t)c.dim * sizeof(float);  // + the kernel's static red[4]
     if (lay >= 0 && ctx->pf_resid_norm && c.dim % 8 == 0 && lds + 4 * sizeof(float) <= 64 * 1024) {
         HIP_TRY(ctx, hipGetLastError());  // an earlier launch's error is reported as such
-        hipLaunchKernelGGL(prefill_resid_norm_split_kernel, dim3(pf_split_grid(lay, m)), dim3(256), lds, ctx->stream,
-                           (const float*)ctx->pf_part, ks, (const float*)(ctx->pf_scaled ? ctx->pf_xs : nullptr),
-                           ctx->pf_x, c.dim, nw, ndt, c.norm_eps, m, lay, ctx->pf_xh, pf_lo(ctx, lay, m, c.dim),
-                           ctx->pf_xs);
+        hipLaunchKernelGGL(prefill_resid_norm_split_kernel, dim3(pf_split_grid(lay, ps.m)), dim3(256), lds, ctx->stream,
+                           (const float*)b.part, ks, (const float*)(ps.scaled ? b.xs : nullptr), b.x, c.dim, nw, ndt,
+                           c.norm_eps, ps.m, lay, b.xh, pf_lo(ctx, lay, ps.m, c.dim), b.xs);
         HIP_TRY(ctx, hipGetLastError());
-        ctx->pf_split_ready = true;
+        ps.split_ready = true;
         return 0;
     }
     PfEpiArgs e{};
-    e.ks = ks; e.n = m; e.rows = c.dim; e.epi = EPI_RESID; e.out = ctx->pf_x;
-    pf_epi(ctx, e);
-    pf_norm(ctx, nw, ndt, m, dt, rows);
+    e.ks = ks; e.n = ps.m; e.rows = c.dim; e.epi = EPI_RESID; e.out = b.x;
+    pf_epi(ctx, ps, e);
+    pf_norm(ctx, ps, nw, ndt, g);
+    return 0;
+}
+// h = act(g) * u of the W1/W3 partials (EPI_GLU) as the input of the W2 GEMM: straight into its
+// split-f16 halves in one launch when it takes a split input and a row of h fits the LDS (the
+// launch's only precondition, so any error here is real), else into pf.h
+int pf_glu(xh_ctx* ctx, PfPass& ps, int ks, const PfMat& w2) {
+    const xh_config& c = ctx->c;
+    PfBufs& b = ctx->pf;
+    const int lay = pf_layout(ctx, w2);
+    // dynamic LDS = one f32 row of h; the kernel adds a static 16-float reduction array
+    const size_t lds = (size_t)c.hidden_dim * sizeof(float);
+    if (lay >= 0 && ctx->pf_glu_split && lds + 16 * sizeof(float) <= 64 * 1024) {
+        // part_s and inv_s are both pf.xs: a workgroup reads its token's factor before the
+        // barrier and writes the new one after it
+        HIP_TRY(ctx, hipGetLastError());  // an earlier launch's error is reported as such
+        hipLaunchKernelGGL(prefill_glu_split_kernel, dim3(pf_split_grid(lay, ps.m)), dim3(1024), lds, ctx->stream,
+                           (const float*)b.part, ks, ps.m, c.hidden_dim, c.act, lay, b.xh,
+                           pf_lo(ctx, lay, ps.m, c.hidden_dim), b.xs, (const float*)(ps.scaled ? b.xs : nullptr));
+        HIP_TRY(ctx, hipGetLastError());
+        ps.split_ready = true;
+        return 0;
+    }
+    PfEpiArgs e{};
+    e.ks = ks; e.n = ps.m; e.rows = 2 * c.hidden_dim; e.epi = EPI_GLU; e.out = b.h; e.act = c.act;
+    pf_epi(ctx, ps, e);
     return 0;
 }
 template <int HD, int QPK>
@@ -411,19 +439,19 @@ void pf_attn_t(xh_ctx* ctx, const AttnArgs& a, int n) {
     auto k = prefill_attn_kernel<HD, QPK>;
     if (smem > 64 * 1024) ensure_lds((const void*)k);
     hipLaunchKernelGGL(k, dim3(ctx->c.n_kv_heads, a.nsplit, n), dim3(ATTN_THREADS), smem, ctx->stream, a,
-                       (const StepParams*)ctx->pf_sp, ctx->q_dim, ctx->c.n_kv_heads);
+                       (const StepParams*)ctx->pf.sp, ctx->q_dim, ctx->c.n_kv_heads);
 }
 // History splits of the shared-tile prompt attention: a pass whose (KV head, query tile)
 // workgroups cannot fill two per CU (a short pass: 8 workgroups for <= 32 tokens at 8 KV heads)
 // walks its history in up to that many splits of >= FA_MIN_SPLIT_STAGES ring stages each (the
-// split partials live in pf_part, free between the qkv epilogue and the Wo GEMM).
+// split partials live in pf.part, free between the qkv epilogue and the Wo GEMM).
 constexpr int FA_MIN_SPLIT_STAGES = 4;
 int pf_fa_nsplit(const xh_ctx* ctx, int nqt, int n, int pos0) {
     if (!ctx->pf_fa_split) return 1;
     const int wg = ctx->c.n_kv_heads * nqt;
     int ns = std::min((2 * ctx->n_cu + wg - 1) / wg, pos0 / (32 * FA_TPS) / FA_MIN_SPLIT_STAGES);
     const size_t per = (size_t)n * (ctx->q_dim + 2 * ctx->c.n_heads);
-    ns = (int)std::min<size_t>((size_t)ns, pf_part_floats(ctx, ctx->pf_cap) / per);
+    ns = (int)std::min<size_t>((size_t)ns, pf_part_floats(ctx, ctx->pf.cap[PfBufs::PASS]) / per);
     return std::max(ns, 1);
 }
 template <int HD, int QPK>
@@ -436,8 +464,8 @@ void pf_fa_t(xh_ctx* ctx, const AttnArgs& a, int n, int pos0) {
             ensure_lds((const void*)k);
             const int nqt = (n + NW * TPW - 1) / (NW * TPW);
             const int nsplit = pf_fa_nsplit(ctx, nqt, n, pos0);
-            float* po = nsplit > 1 ? ctx->pf_part : nullptr;
-            float2* pml = nsplit > 1 ? (float2*)(ctx->pf_part + (size_t)nsplit * n * ctx->q_dim) : nullptr;
+            float* po = nsplit > 1 ? ctx->pf.part : nullptr;
+            float2* pml = nsplit > 1 ? (float2*)(ctx->pf.part + (size_t)nsplit * n * ctx->q_dim) : nullptr;
             hipLaunchKernelGGL(k, dim3(ctx->c.n_kv_heads, nqt, nsplit), dim3(64 * NW), fa_lds_bytes(), ctx->stream, a.q,
                                a.kc, a.vc, a.out, n, pos0, ctx->q_dim, ctx->kv_dim, po, pml);
             if (nsplit > 1)
@@ -451,101 +479,82 @@ void pf_fa_t(xh_ctx* ctx, const AttnArgs& a, int n, int pos0) {
 }
 // head shapes of the batched path's attention: head_dim 128 / 64 with 1, 2, 4 or 8 q heads per KV
 // head (MHA through GQA), and the test fixtures' head_dim 16 x 2
-bool pf_attn_shape(int hd, int qpk) {
+constexpr bool pf_attn_shape(int hd, int qpk) {
     return ((hd == 128 || hd == 64) && (qpk == 1 || qpk == 2 || qpk == 4 || qpk == 8)) || (hd == 16 && qpk == 2);
 }
+// the shapes of pf_attn_shape are the only instantiations; -1 for another one
 template <int HD>
-bool pf_attn_hd(xh_ctx* ctx, const AttnArgs& a, int n, int pos0, int qpk) {
-    if (ctx->pf_attn_mode != 0) {
-        switch (qpk) {
-            case 1: pf_fa_t<HD, 1>(ctx, a, n, pos0); return true;
-            case 2: pf_fa_t<HD, 2>(ctx, a, n, pos0); return true;
-            case 4: pf_fa_t<HD, 4>(ctx, a, n, pos0); return true;
-            case 8: pf_fa_t<HD, 8>(ctx, a, n, pos0); return true;
-            default: return false;
+int pf_attn_hd(xh_ctx* ctx, const AttnArgs& a, int n, int pos0) {
+    return for_qpk(ctx->qpk, [&](auto Q) {
+        constexpr int QPK = decltype(Q)::value;
+        if constexpr (pf_attn_shape(HD, QPK)) {
+            if (ctx->pf_attn_mode != 0) pf_fa_t<HD, QPK>(ctx, a, n, pos0);
+            else pf_attn_t<HD, QPK>(ctx, a, n);
+            return 0;
         }
-    }
-    switch (qpk) {
-        case 1: pf_attn_t<HD, 1>(ctx, a, n); return true;
-        case 2: pf_attn_t<HD, 2>(ctx, a, n); return true;
-        case 4: pf_attn_t<HD, 4>(ctx, a, n); return true;
-        case 8: pf_attn_t<HD, 8>(ctx, a, n); return true;
-        default: return false;
-    }
+        return -1;
+    });
 }
 // 0, XH_E_INVALID for a head shape with no prompt attention, or the split buffers' allocation error
 int pf_attn(xh_ctx* ctx, const AttnArgs& a, int n, int pos0) {
-    const int hd = ctx->c.head_dim, qpk = ctx->qpk;
-    if (!pf_attn_shape(hd, qpk)) return set_err(ctx, XH_E_INVALID, "prefill: head shape not instantiated");
+    const int hd = ctx->c.head_dim;
     AttnArgs b = a;
-    if (ctx->pf_attn_mode == 0) {
-        const int rc = pf_alloc_split_attn(ctx);  // keeps dmalloc's code and message
+    if (pf_attn_shape(hd, ctx->qpk) && ctx->pf_attn_mode == 0) {
+        const int rc = pf_alloc_group(ctx, PfBufs::ATTN0);
         if (rc) return rc;
-        b.part_o = ctx->pf_po; b.part_ml = ctx->pf_pml; b.counters = ctx->pf_cnt;
+        b.part_o = ctx->pf.po; b.part_ml = ctx->pf.pml; b.counters = ctx->pf.cnt;
     }
-    bool ok = true;
-    if (hd == 128) ok = pf_attn_hd<128>(ctx, b, n, pos0, qpk);
-    else if (hd == 64) ok = pf_attn_hd<64>(ctx, b, n, pos0, qpk);
-    else if (ctx->pf_attn_mode != 0) pf_fa_t<16, 2>(ctx, b, n, pos0);
-    else pf_attn_t<16, 2>(ctx, b, n);
-    return ok ? 0 : set_err(ctx, XH_E_INVALID, "prefill: head shape not instantiated");
+    const int rc = hd == 128 ? pf_attn_hd<128>(ctx, b, n, pos0) : hd == 64 ? pf_attn_hd<64>(ctx, b, n, pos0)
+                   : hd == 16 ? pf_attn_hd<16>(ctx, b, n, pos0) : -1;
+    return rc < 0 ? set_err(ctx, XH_E_INVALID, "prefill: head shape not instantiated") : 0;
 }
 
 // Attention of a ring pass (prefill.h, prefill_fa2_ring_kernel): m <= W = max_seq_len - 2 tokens at
 // positions p0.. >= max_seq_len, their K/V in the staging rows.  Four launches per layer: the
-// sink K versions, the window walk into split partials (pf_part: free between the qkv epilogue
+// sink K versions, the window walk into split partials (pf.part: free between the qkv epilogue
 // and the Wo GEMM), the merge that adds the sinks, and the commit of the staged rows and the last
 // sink version to the ring.
 template <int QPK>
 int pf_attn_ring_t(xh_ctx* ctx, int l, int m, int p0) {
     constexpr int NW = PF_FA_WAVES, TPW = 32 / QPK;
     const int W = ctx->c.max_seq_len - 2;
-    FaRing rg{ctx->pf_ks, ctx->pf_vs, W, (p0 - 2) % W};
+    FaRing rg{ctx->pf.ks, ctx->pf.vs, W, (p0 - 2) % W};
     const int nqt = (m + NW * TPW - 1) / (NW * TPW);
     const int nsplit = pf_fa_nsplit(ctx, nqt, m, W);
-    if ((size_t)nsplit * m * (ctx->q_dim + 2 * ctx->c.n_heads) > pf_part_floats(ctx, ctx->pf_cap))
+    if ((size_t)nsplit * m * (ctx->q_dim + 2 * ctx->c.n_heads) > pf_part_floats(ctx, ctx->pf.cap[PfBufs::PASS]))
         return set_err(ctx, XH_E_INVALID, "prefill: the ring pass's attention partials do not fit");
-    float* po = ctx->pf_part;
-    float2* pml = (float2*)(ctx->pf_part + (size_t)nsplit * m * ctx->q_dim);
+    float* po = ctx->pf.part;
+    float2* pml = (float2*)(ctx->pf.part + (size_t)nsplit * m * ctx->q_dim);
     uint16_t *kc = ctx->kcache(l), *vc = ctx->vcache(l);
     hipStream_t s = ctx->stream;
     hipLaunchKernelGGL(prefill_sink_versions_kernel, dim3((ctx->kv_dim + 255) / 256), dim3(256), 0, s, (const uint16_t*)kc,
                        (const float*)ctx->sink_cos, (const float*)ctx->sink_sin, ctx->kv_dim, ctx->c.head_dim, m,
-                       ctx->pf_sinkv);
+                       ctx->pf.sinkv);
     auto k = prefill_fa2_ring_kernel<QPK, NW>;
     ensure_lds((const void*)k);
-    hipLaunchKernelGGL(k, dim3(ctx->c.n_kv_heads, nqt, nsplit), dim3(64 * NW), fa_lds_bytes(), s, (const float*)ctx->pf_q,
+    hipLaunchKernelGGL(k, dim3(ctx->c.n_kv_heads, nqt, nsplit), dim3(64 * NW), fa_lds_bytes(), s, (const float*)ctx->pf.q,
                        (const uint16_t*)kc, (const uint16_t*)vc, rg, m, ctx->q_dim, ctx->kv_dim, po, pml);
-    const FaSinks sk{ctx->pf_q, ctx->pf_sinkv, vc, ctx->kv_dim, QPK};
+    const FaSinks sk{ctx->pf.q, ctx->pf.sinkv, vc, ctx->kv_dim, QPK};
     hipLaunchKernelGGL(prefill_fa_merge_kernel<true>, dim3(ctx->c.n_heads, m), dim3(256), 0, s, (const float*)po,
-                       (const float2*)pml, ctx->pf_att, m, nsplit, ctx->q_dim, sk);
-    hipLaunchKernelGGL(prefill_ring_commit_kernel, dim3(m + 1), dim3(256), 0, s, rg, (const uint16_t*)ctx->pf_sinkv, kc, vc,
+                       (const float2*)pml, ctx->pf.att, m, nsplit, ctx->q_dim, sk);
+    hipLaunchKernelGGL(prefill_ring_commit_kernel, dim3(m + 1), dim3(256), 0, s, rg, (const uint16_t*)ctx->pf.sinkv, kc, vc,
                        m, ctx->kv_dim);
     return 0;
 }
 int pf_attn_ring(xh_ctx* ctx, int l, int m, int p0) {
-    switch (ctx->qpk) {
-        case 1: return pf_attn_ring_t<1>(ctx, l, m, p0);
-        case 2: return pf_attn_ring_t<2>(ctx, l, m, p0);
-        case 4: return pf_attn_ring_t<4>(ctx, l, m, p0);
-        case 8: return pf_attn_ring_t<8>(ctx, l, m, p0);
-        default: return set_err(ctx, XH_E_INVALID, "prefill: head shape not instantiated");
-    }
+    const int rc = for_qpk(ctx->qpk, [&](auto Q) { return pf_attn_ring_t<decltype(Q)::value>(ctx, l, m, p0); });
+    return rc < 0 ? set_err(ctx, XH_E_INVALID, "prefill: head shape not instantiated") : rc;
 }
 
 // Whether the batched path covers prompts on this model at all (else the per-token loop): an
 // instantiated head shape, K multiples of the chunk pair (always, for K % 32).
 bool pf_supported(const xh_ctx* ctx) {
     const xh_config& c = ctx->c;
-    if (!ctx->prefill_batched) return false;
-    const int hd = c.head_dim, qpk = ctx->qpk;
-    if (!pf_attn_shape(hd, qpk)) return false;
+    if (!ctx->prefill_batched || !pf_attn_shape(c.head_dim, ctx->qpk)) return false;
     // every GEMM's K in whole chunk pairs of its decoder (f32-input kernel; the others need less)
-    auto ok = [](int dt, int K) { return K % (2 * pf_elems(dt)) == 0; };
-    for (const LayerW& w : ctx->L)
-        if (!ok(w.qkv_dt, c.dim) || !ok(w.wo_dt, ctx->q_dim) || !ok(w.w13_dt, c.dim) || !ok(w.w2_dt, c.hidden_dim))
-            return false;
-    return ok(ctx->wcls_dt, c.dim) && c.dim % 32 == 0 && c.hidden_dim % 32 == 0 && ctx->q_dim % 32 == 0;
+    for (const PfMat& g : pf_all_mats(ctx))
+        if (g.K % (2 * pf_elems(g.dt))) return false;
+    return c.dim % 32 == 0 && c.hidden_dim % 32 == 0 && ctx->q_dim % 32 == 0;
 }
 // Ring passes (positions >= max_seq_len): the shared-tile attention's head shape only
 // (prefill_fa2_ring_kernel is head_dim 128), and a ring with at least two slots behind the sinks
@@ -584,6 +593,104 @@ void pf_plan(const xh_ctx* ctx, int n, int pos0, int min_n, std::vector<PfPiece>
     }
 }
 
+// A pass's tokens and per-token step parameters to the device (sps: host staging, reused by the
+// next pass after the driver's synchronize), then its embedding rows into pf.x
+int pf_stage(xh_ctx* ctx, const PfPass& ps, const int* tokens, std::vector<StepParams>& sps) {
+    const xh_config& c = ctx->c;
+    PfBufs& b = ctx->pf;
+    HIP_TRY(ctx, hipMemcpyAsync(b.tok, tokens, (size_t)ps.m * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    for (int t = 0; t < ps.m; t++) {
+        StepParams& h = sps[t];
+        h = StepParams{};
+        h.token = tokens[t];
+        h.pos = ps.p0 + t;
+        h.kv_sink = ps.ring ? 2 : 0;  // src/infer.cpp:611-613
+        h.kv_pos = ps.ring ? 2 + (ps.p0 + t - 2) % (c.max_seq_len - 2) : ps.p0 + t;
+        h.kv_len = ps.ring ? c.max_seq_len : ps.p0 + t + 1;
+        h.max_seq_len = c.max_seq_len;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(b.sp, sps.data(), (size_t)ps.m * sizeof(StepParams), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(prefill_embed_kernel, dim3(ps.m), dim3(256), 0, ctx->stream, (const int*)b.tok,
+                       (const void*)ctx->embed, ctx->embed_dt, c.dim, b.x);
+    return 0;
+}
+// Layer l over the pass's rows: pf.x in, pf.x out, K/V rows written
+int pf_layer(xh_ctx* ctx, PfPass& ps, int l) {
+    const xh_config& c = ctx->c;
+    PfBufs& b = ctx->pf;
+    const LayerW& w = ctx->L[l];
+    const auto mats = pf_layer_mats(ctx, l);
+    const int m = ps.m;
+    int rc, ks = 0;
+    // attention block (src/infer.cpp:380-452)
+    // layers after the first: the previous W2 residual and this rmsnorm ran as one launch
+    if (l == 0) pf_norm(ctx, ps, w.attn_norm, w.an_dt, mats[PF_QKV]);
+    if ((rc = pf_gemm(ctx, ps, mats[PF_QKV], b.xn, m, ks))) return rc;
+    PfEpiArgs e{};
+    e.ks = ks; e.n = m; e.rows = mats[PF_QKV].rows; e.epi = EPI_QKV; e.q = b.q;
+    e.kcache = ctx->kcache(l); e.vcache = ctx->vcache(l); e.q_dim = ctx->q_dim; e.kv_dim = ctx->kv_dim;
+    e.head_dim = c.head_dim; e.rope_freq = ctx->rope_freq; e.qkv_clip = c.qkv_clip; e.pos0 = ps.p0; e.act = c.act;
+    if (ps.ring) { e.kstage = b.ks; e.vstage = b.vs; }
+    pf_epi(ctx, ps, e);
+    if (ps.ring) {
+        if ((rc = pf_attn_ring(ctx, l, m, ps.p0))) return rc;
+    } else {
+        AttnArgs aa = attn_args(ctx, l);
+        aa.q = b.q; aa.out = b.att;
+        // splits for this pass's longest row (attn_block: >= ATTN_MIN_T slots per split)
+        aa.nsplit = std::min(ctx->nsplit, std::max(1, (ps.p0 + m + ATTN_MIN_T - 1) / ATTN_MIN_T));
+        if ((rc = pf_attn(ctx, aa, m, ps.p0))) return rc;
+    }
+    if ((rc = pf_gemm(ctx, ps, mats[PF_WO], b.att, m, ks))) return rc;
+    // residual, then the feed-forward block's rmsnorm (src/infer.cpp:449-452, 455-494)
+    if ((rc = pf_resid_norm(ctx, ps, ks, w.ffn_norm, w.fn_dt, mats[PF_W13]))) return rc;
+    if ((rc = pf_gemm(ctx, ps, mats[PF_W13], b.xn, m, ks))) return rc;
+    if ((rc = pf_glu(ctx, ps, ks, mats[PF_W2]))) return rc;
+    if ((rc = pf_gemm(ctx, ps, mats[PF_W2], b.h, m, ks))) return rc;
+    if (l + 1 < c.n_layers) {
+        // residual, then the next layer's attention rmsnorm (src/infer.cpp:491-494, 380)
+        const LayerW& wn = ctx->L[l + 1];
+        return pf_resid_norm(ctx, ps, ks, wn.attn_norm, wn.an_dt, pf_layer_mats(ctx, l + 1)[PF_QKV]);
+    }
+    e = PfEpiArgs{};
+    e.ks = ks; e.n = m; e.rows = c.dim; e.epi = EPI_RESID; e.out = b.x;
+    pf_epi(ctx, ps, e);
+    return 0;
+}
+// Model::forward's OUTPUT_LOGITS tail (src/infer.cpp:620-637) for every token of the pass, then
+// probs[t] = Sampler::sample_prob of token t's target (targets: host, probs: device, m each)
+int pf_logits_probs(xh_ctx* ctx, PfPass& ps, const int* targets, float* probs) {
+    const xh_config& c = ctx->c;
+    PfBufs& b = ctx->pf;
+    const int m = ps.m;
+    int rc;
+    HIP_TRY(ctx, hipMemcpyAsync(b.tgt, targets, (size_t)m * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(prefill_rmsnorm_kernel, dim3(m), dim3(256), 0, ctx->stream, (const float*)b.x, c.dim,
+                       (const void*)ctx->final_norm, ctx->final_norm_dt, c.norm_eps, b.xn);
+    const PfMat cls = pf_cls_mat(ctx);
+    const size_t cls_rb = dev_row_bytes(ctx->wcls_dt, c.dim);
+    // lm_head weights off the hipBLASLt path (bf16 on the fp8 checkpoints): 64-token slices
+    const int tstep = pf_lay0(ctx, cls.dt, c.dim) ? m : PF_TOK;
+    for (int r0 = 0; r0 < c.vocab_size; r0 += PF_CLS_CHUNK) {
+        PfMat g = cls;
+        g.w = (const char*)cls.w + (size_t)r0 * cls_rb;
+        g.rows = std::min(PF_CLS_CHUNK, c.vocab_size - r0);
+        for (int t0 = 0; t0 < m; t0 += tstep) {
+            const int mt = std::min(tstep, m - t0);
+            int ks = 0;
+            if ((rc = pf_gemm(ctx, ps, g, b.xn + (size_t)t0 * c.dim, mt, ks))) return rc;
+            PfEpiArgs e{};
+            e.ks = ks; e.n = mt; e.rows = g.rows; e.epi = EPI_STORE;
+            e.out = b.logits + (size_t)t0 * c.vocab_size + r0;
+            e.out_stride = (size_t)c.vocab_size;
+            pf_epi(ctx, ps, e);
+        }
+    }
+    hipLaunchKernelGGL(token_prob_kernel, dim3(m), dim3(1024), 0, ctx->stream, (const float*)b.logits, c.vocab_size,
+                       (size_t)c.vocab_size, (const int*)b.tgt, probs);
+    return 0;
+}
+
 // tokens[0..n) at positions pos0..: HYDRATE for every token, then the last token's logits.
 // probs (device, n floats) != nullptr: also every token's logits (final rmsnorm + lm_head as
 // one GEMM per pass) and probs[i] = sample_prob(targets[i]) (targets: host, n ints).
@@ -593,129 +700,21 @@ int prefill_batched(xh_ctx* ctx, const int* tokens, int n, int pos0, int want_lo
     const xh_config& c = ctx->c;
     int rc = pf_prepare(ctx);
     if (rc) return rc;
-    ctx->pf_pass = pf_pass_tokens(ctx);
-    const int pass = ring ? std::min(ctx->pf_pass, c.max_seq_len - 2) : ctx->pf_pass;
+    const int pass = ring ? std::min(pf_pass_tokens(ctx), c.max_seq_len - 2) : pf_pass_tokens(ctx);
     if ((rc = pf_alloc(ctx, std::min(pass, std::max(n, PF_TOK))))) return rc;
-    if (ring && (rc = pf_alloc_ring(ctx))) return rc;
-    ctx->pf_split_ready = false;
-    if (probs && !ctx->pf_logits &&
-        ((rc = dmalloc(ctx, &ctx->pf_logits, (size_t)ctx->pf_cap * c.vocab_size)) ||
-         (rc = dmalloc(ctx, &ctx->pf_tgt, (size_t)ctx->pf_cap))))
-        return rc;
+    if (ring && (rc = pf_alloc_group(ctx, PfBufs::RING))) return rc;
+    if (probs && (rc = pf_alloc_group(ctx, PfBufs::LOGITS))) return rc;
     std::vector<StepParams> sps(pass);
     for (int off = 0; off < n; off += pass) {
-        const int m = std::min(n - off, pass);
-        const int p0 = pos0 + off;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->pf_tok, tokens + off, (size_t)m * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        for (int t = 0; t < m; t++) {
-            StepParams& h = sps[t];
-            h = StepParams{};
-            h.token = tokens[off + t];
-            h.pos = p0 + t;
-            h.kv_sink = ring ? 2 : 0;  // src/infer.cpp:611-613
-            h.kv_pos = ring ? 2 + (p0 + t - 2) % (c.max_seq_len - 2) : p0 + t;
-            h.kv_len = ring ? c.max_seq_len : p0 + t + 1;
-            h.max_seq_len = c.max_seq_len;
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->pf_sp, sps.data(), (size_t)m * sizeof(StepParams), hipMemcpyHostToDevice,
-                                    ctx->stream));
-        hipLaunchKernelGGL(prefill_embed_kernel, dim3(m), dim3(256), 0, ctx->stream, (const int*)ctx->pf_tok,
-                           (const void*)ctx->embed, ctx->embed_dt, c.dim, ctx->pf_x);
-        for (int l = 0; l < c.n_layers; l++) {
-            const LayerW& w = ctx->L[l];
-            // attention block (src/infer.cpp:380-452)
-            const int qkv_rows = ctx->q_dim + 2 * ctx->kv_dim;
-            int ks = 0;
-            // layers after the first: the previous W2 residual and this rmsnorm ran as one launch
-            if (l == 0) pf_norm(ctx, w.attn_norm, w.an_dt, m, kdt(w.qkv_dt, w.qkv_x), qkv_rows);
-            if ((rc = pf_gemm(ctx, "qkv", kdt(w.qkv_dt, w.qkv_x), w.wqkv, c.dim, qkv_rows, ctx->pf_xn, m, ks))) return rc;
-            PfEpiArgs e{};
-            e.ks = ks; e.n = m; e.rows = qkv_rows; e.epi = EPI_QKV; e.q = ctx->pf_q;
-            e.kcache = ctx->kcache(l); e.vcache = ctx->vcache(l); e.q_dim = ctx->q_dim; e.kv_dim = ctx->kv_dim;
-            e.head_dim = c.head_dim; e.rope_freq = ctx->rope_freq; e.qkv_clip = c.qkv_clip; e.pos0 = p0; e.act = c.act;
-            if (ring) { e.kstage = ctx->pf_ks; e.vstage = ctx->pf_vs; }
-            pf_epi(ctx, e);
-            if (ring) {
-                if ((rc = pf_attn_ring(ctx, l, m, p0))) return rc;
-            } else {
-                AttnArgs aa = attn_args(ctx, l);
-                aa.q = ctx->pf_q; aa.out = ctx->pf_att;
-                // splits for this pass's longest row (attn_block: >= ATTN_MIN_T slots per split)
-                aa.nsplit = std::min(ctx->nsplit, std::max(1, (p0 + m + ATTN_MIN_T - 1) / ATTN_MIN_T));
-                if ((rc = pf_attn(ctx, aa, m, p0))) return rc;
-            }
-            if ((rc = pf_gemm(ctx, "wo", kdt(w.wo_dt, w.wo_x), w.wo, ctx->q_dim, c.dim, ctx->pf_att, m, ks))) return rc;
-            // residual, then the feed-forward block's rmsnorm (src/infer.cpp:449-452, 455-494)
-            if ((rc = pf_resid_norm(ctx, ks, w.ffn_norm, w.fn_dt, m, kdt(w.w13_dt, w.w13_x), 2 * c.hidden_dim))) return rc;
-            if ((rc = pf_gemm(ctx, "w1/w3", kdt(w.w13_dt, w.w13_x), w.w13, c.dim, 2 * c.hidden_dim, ctx->pf_xn, m, ks)))
-                return rc;
-            const int lay2 = pf_layout(ctx, kdt(w.w2_dt, w.w2_x), c.hidden_dim, c.dim);
-            // dynamic LDS = one f32 row of h; the kernel adds a static 16-float reduction array
-            const size_t glu_lds = (size_t)c.hidden_dim * sizeof(float);
-            bool glu_fused = false;
-            if (lay2 >= 0 && ctx->pf_glu_split && glu_lds + 16 * sizeof(float) <= 64 * 1024) {
-                // GLU epilogue straight into the W2 GEMM's split-f16 input (one launch); the size
-                // check above is the launch's only precondition, so any error here is real.
-                // part_s and inv_s are both pf_xs: a workgroup reads its token's factor before
-                // the barrier and writes the new one after it.
-                HIP_TRY(ctx, hipGetLastError());  // an earlier launch's error is reported as such
-                hipLaunchKernelGGL(prefill_glu_split_kernel, dim3(pf_split_grid(lay2, m)), dim3(1024), glu_lds,
-                                   ctx->stream, (const float*)ctx->pf_part, ks, m, c.hidden_dim, c.act, lay2,
-                                   ctx->pf_xh, pf_lo(ctx, lay2, m, c.hidden_dim), ctx->pf_xs,
-                                   (const float*)(ctx->pf_scaled ? ctx->pf_xs : nullptr));
-                HIP_TRY(ctx, hipGetLastError());
-                glu_fused = true;
-                ctx->pf_split_ready = true;
-            }
-            if (!glu_fused) {
-                e = PfEpiArgs{};
-                e.ks = ks; e.n = m; e.rows = 2 * c.hidden_dim; e.epi = EPI_GLU; e.out = ctx->pf_h; e.act = c.act;
-                pf_epi(ctx, e);
-            }
-            if ((rc = pf_gemm(ctx, "w2", kdt(w.w2_dt, w.w2_x), w.w2, c.hidden_dim, c.dim, ctx->pf_h, m, ks))) return rc;
-            if (l + 1 < c.n_layers) {
-                // residual, then the next layer's attention rmsnorm (src/infer.cpp:491-494, 380)
-                const LayerW& wn = ctx->L[l + 1];
-                if ((rc = pf_resid_norm(ctx, ks, wn.attn_norm, wn.an_dt, m, kdt(wn.qkv_dt, wn.qkv_x), qkv_rows))) return rc;
-            } else {
-                e = PfEpiArgs{};
-                e.ks = ks; e.n = m; e.rows = c.dim; e.epi = EPI_RESID; e.out = ctx->pf_x;
-                pf_epi(ctx, e);
-            }
-        }
-        if (probs) {
-            // Model::forward's OUTPUT_LOGITS tail (src/infer.cpp:620-637) for every token of the
-            // pass, then Sampler::sample_prob of each token's target
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->pf_tgt, targets + off, (size_t)m * sizeof(int), hipMemcpyHostToDevice,
-                                        ctx->stream));
-            hipLaunchKernelGGL(prefill_rmsnorm_kernel, dim3(m), dim3(256), 0, ctx->stream, (const float*)ctx->pf_x, c.dim,
-                               (const void*)ctx->final_norm, ctx->final_norm_dt, c.norm_eps, ctx->pf_xn);
-            const size_t cls_rb = dev_row_bytes(ctx->wcls_dt, c.dim);
-            const int cls_dt = kdt(ctx->wcls_dt, ctx->wcls_x);
-            // lm_head weights off the hipBLASLt path (bf16 on the fp8 checkpoints): 64-token slices
-            const int tstep = pf_lay0(ctx, cls_dt, c.dim) ? m : PF_TOK;
-            for (int r0 = 0; r0 < c.vocab_size; r0 += PF_CLS_CHUNK) {
-                const int rows = std::min(PF_CLS_CHUNK, c.vocab_size - r0);
-                for (int t0 = 0; t0 < m; t0 += tstep) {
-                    const int mt = std::min(tstep, m - t0);
-                    int ks = 0;
-                    if ((rc = pf_gemm(ctx, "lm_head", cls_dt, (const char*)ctx->wcls + (size_t)r0 * cls_rb, c.dim, rows,
-                                      ctx->pf_xn + (size_t)t0 * c.dim, mt, ks)))
-                        return rc;
-                    PfEpiArgs e{};
-                    e.ks = ks; e.n = mt; e.rows = rows; e.epi = EPI_STORE;
-                    e.out = ctx->pf_logits + (size_t)t0 * c.vocab_size + r0;
-                    e.out_stride = (size_t)c.vocab_size;
-                    pf_epi(ctx, e);
-                }
-            }
-            hipLaunchKernelGGL(token_prob_kernel, dim3(m), dim3(1024), 0, ctx->stream, (const float*)ctx->pf_logits,
-                               c.vocab_size, (size_t)c.vocab_size, (const int*)ctx->pf_tgt, probs + off);
-        }
+        PfPass ps{std::min(n - off, pass), pos0 + off, ring, false, false};
+        if ((rc = pf_stage(ctx, ps, tokens + off, sps))) return rc;
+        for (int l = 0; l < c.n_layers; l++)
+            if ((rc = pf_layer(ctx, ps, l))) return rc;
+        if (probs && (rc = pf_logits_probs(ctx, ps, targets + off, probs + off))) return rc;
         HIP_TRY(ctx, hipGetLastError());
-        if (off + m == n) {
+        if (off + ps.m == n) {
             // the last token's residual stream is the decode path's x
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->x, ctx->pf_x + (size_t)(m - 1) * c.dim, (size_t)c.dim * 4,
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->x, ctx->pf.x + (size_t)(ps.m - 1) * c.dim, (size_t)c.dim * 4,
                                         hipMemcpyDeviceToDevice, ctx->stream));
         }
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // sps / token staging reused by the next pass
@@ -724,13 +723,14 @@ int prefill_batched(xh_ctx* ctx, const int* tokens, int n, int pos0, int want_lo
     rc = host_step_params(ctx, tokens[n - 1], pos0 + n - 1);
     if (rc) return rc;
     if (want_logits) {
-        if (!launch_gemv(GEMV_LOGITS, kdt(ctx->wcls_dt, ctx->wcls_x), cls_args(ctx), ctx->stream, ctx->max_gemv_waves))
+        if (!launch_gemv(GEMV_LOGITS, pf_cls_mat(ctx).dt, cls_args(ctx), ctx->stream, ctx->max_gemv_waves))
             return set_err(ctx, XH_E_INVALID, "unsupported wcls dtype");
         ctx->cand_valid = true;
     }
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
+
 
 }  // namespace
 
