@@ -196,6 +196,61 @@ typedef struct xh_sampling {
 int xh_decode_sample(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* sampling, int stop_token_a,
                      int stop_token_b, int* tokens_out, int* n_done);
 
+/* ---- repetition penalties, logit bias, min-p and log-probabilities ---------------------- */
+#define XH_CTL_MAX_WINDOW 1024
+#define XH_CTL_MAX_BIAS   256
+typedef struct xh_logit_ctl {
+    float   repeat_penalty;     /* > 0, finite; 1 = off                                   */
+    float   presence_penalty;   /* finite; 0 = off                                        */
+    float   frequency_penalty;  /* finite; 0 = off                                        */
+    int32_t last_n;             /* 0 .. XH_CTL_MAX_WINDOW; 0 = the three penalties off    */
+    float   min_p;              /* in [0, 1]; 0 = off                                     */
+    int32_t n_bias;             /* 0 .. XH_CTL_MAX_BIAS                                   */
+    const int32_t* bias_token;  /* n_bias distinct ids in [0, vocab)                      */
+    const float*   bias_value;  /* finite, or -inf (ban)                                  */
+} xh_logit_ctl;
+/* The extended draw: xh_sampling's definition applied to adjusted logits l', plus min-p.
+ * - Window.  At step i of a call the token for position pos + i is drawn.  The window is the
+ *   last min(last_n, n_history + i) entries of history ++ generated[0..i).  `history` holds the
+ *   n_history tokens at positions pos - n_history .. pos - 1; the caller supplies it (the context
+ *   does not record prompts; only its last XH_CTL_MAX_WINDOW entries can matter), it is copied to
+ *   the device once per call, and generated tokens join the window on the device.  c_t is the
+ *   number of occurrences of token t in the window.
+ * - Adjusted logits.  Every operation below is one IEEE f32 operation rounded once (no fused
+ *   multiply-add).  A token with a bias entry gets a = l_t + b_t, any other a = l_t.  With
+ *   c_t > 0:  r = (a > 0) ? a / repeat_penalty : a * repeat_penalty;
+ *             r = r - (float)c_t * frequency_penalty   (the product rounded, then the difference);
+ *             l' = r - presence_penalty.
+ *   With c_t == 0, l' = a.  So a token with no bias entry and c_t == 0 keeps l_t bit for bit (-0
+ *   included: the sampler orders by f32 bits).  -inf stays -inf; NaN or +inf produced by the
+ *   adjustment is outside the contract.
+ * - min-p.  With min_p > 0 and temperature > 0 let w_i = expf((l'_i - m) / temperature) in f32, m
+ *   the maximum of l', and n_minp the number of tokens with w_i >= min_p (at least 1: the maximum
+ *   has w = 1).  The top-k stage keeps the first min(top_k or V, n_minp) tokens of the order;
+ *   top-p then works over that set as before.
+ * - Greedy.  temperature == 0 is the first maximum among l' > FLT_MIN, else token 0: min_p,
+ *   top_k, top_p and seed are ignored, penalties and biases apply.
+ * - Counter, Philox, determinism and "one call equals two" as xh_sampling; for the last, the
+ *   second call is given history ++ the first call's tokens.
+ * - Log-probability (Sampler::sample_prob, src/sampler.cpp:3-17, in log; what xh_perplexity
+ *   reports): lp = (l_tok - M) - logf(sum_j expf(l_j - M)) over the RAW logits, M their maximum.
+ *   No temperature, bias, penalty or cut enters it.
+ * - Invalid parameters.  A field outside its stated range or NaN, a bias id duplicated or out of
+ *   range, n_bias > 0 with a null array, n_history < 0, n_history > 0 with a null history, or a
+ *   history token outside [0, vocab) return XH_E_INVALID before the device is touched.  A null
+ *   ctl means all controls off.
+ * How the device evaluates it (xalm_amd/csrc/sample_ext.h): the step head copies the raw logits to
+ * a context-owned buffer, fixes the at most 1024 + 256 entries the window and the biases touch
+ * (one owner thread per distinct token), and runs the sampler of xh_sampling on that buffer; the
+ * logits xh_get_logits returns stay raw. */
+
+/* xh_decode_sample's loop with the extended draw (its own step head and graph; the greedy and the
+ * sampled loop are untouched).  logprobs_out (may be NULL) receives one log-probability per
+ * token. */
+int xh_decode_sample_ext(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* sampling, const xh_logit_ctl* ctl,
+                         const int* history, int n_history, int stop_token_a, int stop_token_b,
+                         int* tokens_out, float* logprobs_out, int* n_done);
+
 /* Hydrate: forward tokens[0..n) at positions pos0.. (HYDRATE_KV_CACHE for all but the last,
  * which computes logits if want_logits), the prompt loop of run_completion
  * (src/main.cpp:94-100) in one call.  logits_out may be NULL. */
@@ -343,6 +398,17 @@ int xh_op_prompt_gemm(float* y, const uint16_t* w, const uint16_t* xh, const uin
  * the size of the kept set (greedy: 1; no finite logit: 0).  n_draws <= 65536. */
 int xh_op_sample(const float* logits, int vocab, const xh_sampling* sampling, uint64_t pos0, int n_draws,
                  int* tokens_out, int* n_kept_out);
+/* The extended draw (xh_logit_ctl above; the same device functions as xh_decode_sample_ext) on host
+ * logits[vocab], no model and no context: draw d at counter pos0 + d, all draws over the same fixed
+ * window (its last min(last_n, n_window) tokens); adjusted_out (may be NULL) receives l'[vocab] as
+ * the device computed it, logprob_out (may be NULL) the n_draws log-probabilities. */
+int xh_op_sample_ext(const float* logits, int vocab, const xh_sampling* sampling, const xh_logit_ctl* ctl,
+                     const int* window, int n_window, uint64_t pos0, int n_draws,
+                     int* tokens_out, int* n_kept_out, float* adjusted_out, float* logprob_out);
+/* Host only, no device: the adjustment of xh_logit_ctl in plain C++ (also what the host Sampler
+ * uses): out[vocab] = l' for logits[vocab] under the window's last min(last_n, n_window) tokens. */
+int xh_adjust_logits(const float* logits, int vocab, const xh_logit_ctl* ctl, const int* window,
+                     int n_window, float* out);
 /* Philox4x32-10 on the host (no device): key (seed & 0xffffffff, seed >> 32), counter
  * (pos mod 2^32, 0, 0, 0): only the low 32 bits of pos are used. */
 int xh_philox4x32(uint64_t seed, uint64_t pos, uint32_t out[4]);
@@ -350,9 +416,11 @@ int xh_philox4x32(uint64_t seed, uint64_t pos, uint32_t out[4]);
 /* ---- timing hooks used by bench.py (HIP events on the context's own stream) -------- */
 /* Average device time (microseconds) of one launch of kernel `which` (0 = the fused
  * gate/up matvec, 1 = qkv, 2 = wo, 3 = down, 4 = lm_head, 5 = attention, 6 = the sampled step
- * head of xh_decode_sample under its last parameters) over `iters` back-to-back launches with
+ * head of xh_decode_sample under its last parameters, 7 = the extended step head of
+ * xh_decode_sample_ext under its last parameters) over `iters` back-to-back launches with
  * the current step parameters (layers rotate, so the Infinity Cache never serves a repeat).
- * 6 advances the decode loop's position with every launch: reset or re-hydrate afterwards. */
+ * 6 and 7 advance the decode loop's position with every launch (7 also appends to its window):
+ * reset or re-hydrate afterwards. */
 int xh_time_kernel(xh_ctx* ctx, int which, int iters, float* avg_us);
 /* Bytes one launch of that kernel must move (algorithmic). */
 size_t xh_kernel_bytes(const xh_ctx* ctx, int which, int kv_len);

@@ -64,6 +64,28 @@ class XhSampling(ctypes.Structure):
                 ("seed", ctypes.c_uint64)]
 
 
+CTL_MAX_WINDOW, CTL_MAX_BIAS = 1024, 256
+
+
+class XhLogitCtl(ctypes.Structure):
+    """xh_logit_ctl (include/xalm_hip.h): repeat / presence / frequency penalties over the last
+    last_n tokens, min_p, and n_bias (token, value) logit biases."""
+    _fields_ = [("repeat_penalty", ctypes.c_float), ("presence_penalty", ctypes.c_float),
+                ("frequency_penalty", ctypes.c_float), ("last_n", ctypes.c_int32), ("min_p", ctypes.c_float),
+                ("n_bias", ctypes.c_int32), ("bias_token", ctypes.c_void_p), ("bias_value", ctypes.c_void_p)]
+
+
+def logit_ctl(repeat_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, last_n=0, min_p=0.0, logit_bias=None):
+    """(XhLogitCtl, the arrays it points to: keep them alive for the call).  logit_bias: a dict or
+    a sequence of (token, value) pairs."""
+    pairs = list(logit_bias.items()) if isinstance(logit_bias, dict) else list(logit_bias or ())
+    btok = np.ascontiguousarray([int(t) for t, _ in pairs], dtype=np.int32)
+    bval = np.ascontiguousarray([float(v) for _, v in pairs], dtype=np.float32)
+    c = XhLogitCtl(repeat_penalty, presence_penalty, frequency_penalty, last_n, min_p, len(pairs),
+                   btok.ctypes.data if pairs else None, bval.ctypes.data if pairs else None)
+    return c, (btok, bval)
+
+
 class XhError(RuntimeError):
     pass
 
@@ -87,6 +109,11 @@ _SIGNATURES = {
     "xh_forward": (_I, [_P, _I, _I, _I, _P]),
     "xh_decode_greedy": (_I, [_P, _I, _I, _I, _I, _P, ctypes.POINTER(_I)]),
     "xh_decode_sample": (_I, [_P, _I, _I, ctypes.POINTER(XhSampling), _I, _I, _P, ctypes.POINTER(_I)]),
+    "xh_decode_sample_ext": (_I, [_P, _I, _I, ctypes.POINTER(XhSampling), ctypes.POINTER(XhLogitCtl), _P, _I, _I, _I, _P,
+                                  _P, ctypes.POINTER(_I)]),
+    "xh_op_sample_ext": (_I, [_P, _I, ctypes.POINTER(XhSampling), ctypes.POINTER(XhLogitCtl), _P, _I, ctypes.c_uint64,
+                              _I, _P, _P, _P, _P]),
+    "xh_adjust_logits": (_I, [_P, _I, ctypes.POINTER(XhLogitCtl), _P, _I, _P]),
     "xh_op_sample": (_I, [_P, _I, ctypes.POINTER(XhSampling), ctypes.c_uint64, _I, _P, _P]),
     "xh_philox4x32": (_I, [ctypes.c_uint64, ctypes.c_uint64, _P]),
     "xh_prefill": (_I, [_P, _P, _I, _I, _I, _P]),
@@ -177,6 +204,36 @@ def op_sample(logits: np.ndarray, temperature: float, top_k: int, top_p: float, 
     kept = np.empty(max(n_draws, 1), dtype=np.int32)
     check(lib().xh_op_sample(ptr(lg), lg.size, ctypes.byref(s), pos0, n_draws, ptr(toks), ptr(kept)))
     return toks[:n_draws], kept[:n_draws]
+
+
+def op_sample_ext(logits: np.ndarray, temperature: float, top_k: int, top_p: float, seed: int, pos0: int,
+                  n_draws: int, window=(), **controls):
+    """The extended draw on a logits vector (xh_op_sample_ext; controls as `logit_ctl`): draws at
+    counters pos0 .. pos0 + n_draws - 1 over the fixed `window`; returns (tokens, n_kept, adjusted
+    logits l' [V], log-probabilities [n_draws])."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    s = XhSampling(temperature, top_k, top_p, seed)
+    c, keep = logit_ctl(**controls)
+    win = np.ascontiguousarray(np.asarray(window, dtype=np.int32))
+    toks = np.empty(max(n_draws, 1), dtype=np.int32)
+    kept = np.empty(max(n_draws, 1), dtype=np.int32)
+    adj = np.empty(lg.size, dtype=np.float32)
+    lp = np.empty(max(n_draws, 1), dtype=np.float32)
+    check(lib().xh_op_sample_ext(ptr(lg), lg.size, ctypes.byref(s), ctypes.byref(c), ptr(win) if win.size else None,
+                                 win.size, pos0, n_draws, ptr(toks), ptr(kept), ptr(adj), ptr(lp)))
+    del keep
+    return toks[:n_draws], kept[:n_draws], adj, lp[:n_draws]
+
+
+def adjust_logits(logits: np.ndarray, window=(), **controls) -> np.ndarray:
+    """l' of xh_logit_ctl on the host (xh_adjust_logits; controls as `logit_ctl`).  No device needed."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    c, keep = logit_ctl(**controls)
+    win = np.ascontiguousarray(np.asarray(window, dtype=np.int32))
+    out = np.empty(lg.size, dtype=np.float32)
+    check(lib().xh_adjust_logits(ptr(lg), lg.size, ctypes.byref(c), ptr(win) if win.size else None, win.size, ptr(out)))
+    del keep
+    return out
 
 
 def philox4x32(seed: int, pos: int) -> np.ndarray:

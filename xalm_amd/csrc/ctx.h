@@ -55,6 +55,18 @@ struct LayerW {
 
 struct BlasState;  // hipBLASLt handle, workspace, plans (prefill_blas.hip)
 
+// xh_decode_sample_ext's device parameter block (sample_ext.h): xh_sampling, the scalars of
+// xh_logit_ctl, and the number of tokens the window ring has received (history, then one per step:
+// the step head itself appends)
+struct ExtCtl {
+    xh_sampling samp;
+    float repeat_penalty, presence_penalty, frequency_penalty;
+    int last_n;
+    float min_p;
+    int n_bias;
+    int count;
+};
+
 constexpr int ARGMAX_CANDS = 1024;  // the lm_head workgroups' argmax keys (argmax_embed_kernel's block size)
 
 // The batched prefill's device buffers (prefill.hip), in growth groups.  T = cap[PASS] tokens, the
@@ -125,6 +137,14 @@ struct xh_ctx {
     unsigned long long* cand = nullptr;  // device [ARGMAX_CANDS]: lm_head workgroups' argmax keys
     bool cand_valid = false;        // cand describes the logits on the device
     xh_sampling* samp = nullptr;    // device: xh_decode_sample's parameter block (read by its graph)
+    // xh_decode_sample_ext (sample_ext.h): parameter block, window ring [XH_CTL_MAX_WINDOW], bias
+    // table [XH_CTL_MAX_BIAS] each, adjusted logits [vocab], per-step log-probabilities [dec_cap]
+    xalm::ExtCtl* ext = nullptr;
+    int* ext_ring = nullptr;
+    int* ext_btok = nullptr;
+    float* ext_bval = nullptr;
+    float* ext_adj = nullptr;
+    float* dec_logprobs = nullptr;
     int dec_cap = 0;
     int nsplit = 1, t_max = 16;
     // fused attention + Wo launch (attn_wo.h): per-layer hand-off words [n_layers][4]
@@ -152,7 +172,8 @@ struct xh_ctx {
     int ppl_cap = 0;
     int t_max_aw = 16;
     bool use_graphs = true;
-    hipGraphExec_t g_logits = nullptr, g_hydrate = nullptr, g_decode = nullptr, g_sample = nullptr;
+    hipGraphExec_t g_logits = nullptr, g_hydrate = nullptr, g_decode = nullptr, g_sample = nullptr,
+                   g_sample_ext = nullptr;
     int max_gemv_waves = 4096;  // 16 waves per CU
     // the qkv launch: its whole matrix is one round at 16 waves per CU (every wave one group,
     // requested at once); at 8 waves per CU each wave streams two groups back to back
@@ -270,6 +291,7 @@ void drop_graphs(xh_ctx* ctx);
 int host_step_params(xh_ctx* ctx, int token, int pos);
 int run_step(xh_ctx* ctx, bool with_logits);
 void time_sample_head(xh_ctx* ctx);  // one sample_embed_kernel launch on ctx->stream (xh_time_kernel 6)
+void time_sample_ext_head(xh_ctx* ctx);  // one sample_ext_embed_kernel launch (xh_time_kernel 7)
 
 // prefill.hip: the pass buffers, and gemm16.h for xh_op_prompt_gemm (device pointers).  mm_op_ks:
 // *ks = 0 picks the K slicing; 0, 1 when K is no multiple of MM_KMULT, 2 when *ks slices do not divide it

@@ -2,12 +2,15 @@
 // capture and replay, and the ABI entries that run it (xh_forward, xh_decode_greedy, xh_get_logits).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cfloat>
+#include <cmath>
 #include <vector>
 
 #include "ctx.h"
 #include "dt_launch.h"
 #include "sample.h"
+#include "sample_ext.h"
 
 using namespace xalm;
 
@@ -95,6 +98,69 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_op_kernel(const float* log
     if (threadIdx.x == 0) {
         tokens[blockIdx.x] = tok;
         n_kept_out[blockIdx.x] = n_kept;
+    }
+}
+
+// Extended sampled decode step head (xh_decode_sample_ext): the adjusted logits l' go to `adj`
+// (ext_prepare, sample_ext.h; `logits` stay raw), the token is drawn from them by sample_token
+// under the effective top-k, its log-probability comes from the raw logits, the token joins the
+// window ring, and then the bookkeeping and the embedding exactly as sample_embed_kernel.
+__global__ __launch_bounds__(SMP_THREADS) void sample_ext_embed_kernel(
+    const float* logits, int vocab, ExtCtl* ctl, int* ring, const int* btok, const float* bval, float* adj,
+    StepParams* sp, int* tokens, float* logprobs, int cap, const void* emb, int dtype, int dim, float* x,
+    const float* rope_freq, float* rope_cs, int half) {
+    __shared__ SampleShared sh;
+    __shared__ ExtShared es;
+    __shared__ int pos_s;
+    const int tid = threadIdx.x;
+    const ExtCtl c = *ctl;
+    const ExtPrep pr = ext_prepare(es, logits, adj, vocab, c, ring, btok, bval);
+    xh_sampling p = c.samp;
+    p.top_k = pr.top_k;
+    int n_kept;
+    const int tok = sample_token(sh, adj, vocab, p, (uint32_t)sp->pos_next, &n_kept);
+    __syncthreads();  // every thread has read pos_next, the block and the ring
+    if (tid == 0) {
+        if (sp->step < cap) {
+            tokens[sp->step] = tok;
+            logprobs[sp->step] = (logits[tok] - pr.M) - pr.lse;
+        }
+        ring[c.count & (EXT_RING - 1)] = tok;
+        ctl->count = c.count + 1;
+        sp->step += 1;
+        sp->token = tok;
+        step_positions(sp, sp->pos_next);
+        sp->pos_next += 1;
+        pos_s = sp->pos;
+    }
+    __syncthreads();
+    rope_table(rope_cs, rope_freq, half, pos_s, tid);
+    for (int i = tid; i < dim; i += SMP_THREADS) x[i] = dec_row(dtype, emb, (size_t)tok, dim, i);
+}
+
+// xh_op_sample_ext: one workgroup prepares l' and the scalars of the draw ...
+__global__ __launch_bounds__(SMP_THREADS) void sample_ext_prep_kernel(const float* logits, int vocab, const ExtCtl* ctl,
+                                                                      const int* ring, const int* btok,
+                                                                      const float* bval, float* adj, ExtPrep* prep) {
+    __shared__ ExtShared es;
+    const ExtPrep pr = ext_prepare(es, logits, adj, vocab, *ctl, ring, btok, bval);
+    if (threadIdx.x == 0) *prep = pr;
+}
+// ... and workgroup d draws at counter pos0 + d from l'
+__global__ __launch_bounds__(SMP_THREADS) void sample_ext_op_kernel(const float* logits, const float* adj, int vocab,
+                                                                    const ExtCtl* ctl, const ExtPrep* prep,
+                                                                    uint32_t pos0, int* tokens, int* n_kept_out,
+                                                                    float* logprobs) {
+    __shared__ SampleShared sh;
+    const ExtPrep pr = *prep;
+    xh_sampling p = ctl->samp;
+    p.top_k = pr.top_k;
+    int n_kept;
+    const int tok = sample_token(sh, adj, vocab, p, pos0 + blockIdx.x, &n_kept);
+    if (threadIdx.x == 0) {
+        tokens[blockIdx.x] = tok;
+        n_kept_out[blockIdx.x] = n_kept;
+        logprobs[blockIdx.x] = (logits[tok] - pr.M) - pr.lse;
     }
 }
 
@@ -190,13 +256,17 @@ int launch_attn_wo(xh_ctx* ctx, int l, hipStream_t s) {
 }
 
 // head: HEAD_GREEDY = the token is the argmax of the previous step's logits (argmax_embed_kernel),
-// HEAD_SAMPLE = drawn from them under ctx->samp (sample_embed_kernel)
-enum StepHead { HEAD_GIVEN = 0, HEAD_GREEDY = 1, HEAD_SAMPLE = 2 };
+// HEAD_SAMPLE = drawn from them under ctx->samp (sample_embed_kernel), HEAD_SAMPLE_EXT = drawn from
+// their adjusted copy under ctx->ext (sample_ext_embed_kernel)
+enum StepHead { HEAD_GIVEN = 0, HEAD_GREEDY = 1, HEAD_SAMPLE = 2, HEAD_SAMPLE_EXT = 3 };
 void launch_sample_head(xh_ctx* ctx, hipStream_t s);
+void launch_sample_ext_head(xh_ctx* ctx, hipStream_t s);
 int enqueue_step(xh_ctx* ctx, hipStream_t s, bool with_logits, int head = HEAD_GIVEN) {
     const xh_config& c = ctx->c;
     const int mb = ctx->max_gemv_waves;
-    if (head == HEAD_SAMPLE)
+    if (head == HEAD_SAMPLE_EXT)
+        launch_sample_ext_head(ctx, s);
+    else if (head == HEAD_SAMPLE)
         launch_sample_head(ctx, s);
     else if (head == HEAD_GREEDY)
         hipLaunchKernelGGL(argmax_embed_kernel, dim3(1), dim3(ARGMAX_CANDS), 0, s, (const unsigned long long*)ctx->cand,
@@ -242,10 +312,18 @@ void launch_sample_head(xh_ctx* ctx, hipStream_t s) {
                        ctx->embed_dt, c.dim, ctx->x, (const float*)ctx->rope_freq, ctx->rope_cs, c.head_dim / 2);
 }
 
+void launch_sample_ext_head(xh_ctx* ctx, hipStream_t s) {
+    const xh_config& c = ctx->c;
+    hipLaunchKernelGGL(sample_ext_embed_kernel, dim3(1), dim3(SMP_THREADS), 0, s, (const float*)ctx->logits, c.vocab_size,
+                       ctx->ext, ctx->ext_ring, (const int*)ctx->ext_btok, (const float*)ctx->ext_bval, ctx->ext_adj,
+                       ctx->sp, ctx->dec_tokens, ctx->dec_logprobs, ctx->dec_cap, (const void*)ctx->embed, ctx->embed_dt,
+                       c.dim, ctx->x, (const float*)ctx->rope_freq, ctx->rope_cs, c.head_dim / 2);
+}
+
 int capture(xh_ctx* ctx, int kind, hipGraphExec_t* out) {
     hipGraph_t g = nullptr;
     HIP_TRY(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-    const int rc = enqueue_step(ctx, ctx->stream, kind != 1, kind == 2 ? HEAD_GREEDY : kind == 3 ? HEAD_SAMPLE : HEAD_GIVEN);
+    const int rc = enqueue_step(ctx, ctx->stream, kind != 1, kind == 2 ? HEAD_GREEDY : kind == 3 ? HEAD_SAMPLE : kind == 4 ? HEAD_SAMPLE_EXT : HEAD_GIVEN);
     hipError_t e = hipStreamEndCapture(ctx->stream, &g);
     if (rc) { if (g) hipGraphDestroy(g); return rc; }
     if (e != hipSuccess) return set_err(ctx, XH_E_HIP, "graph capture failed: %s", hipGetErrorString(e));
@@ -355,13 +433,15 @@ int xalm::check_ready(xh_ctx* ctx) {
 }
 
 void xalm::time_sample_head(xh_ctx* ctx) { launch_sample_head(ctx, ctx->stream); }
+void xalm::time_sample_ext_head(xh_ctx* ctx) { launch_sample_ext_head(ctx, ctx->stream); }
 
 void xalm::drop_graphs(xh_ctx* ctx) {
     if (ctx->g_logits) hipGraphExecDestroy(ctx->g_logits);
     if (ctx->g_hydrate) hipGraphExecDestroy(ctx->g_hydrate);
     if (ctx->g_decode) hipGraphExecDestroy(ctx->g_decode);
     if (ctx->g_sample) hipGraphExecDestroy(ctx->g_sample);
-    ctx->g_logits = ctx->g_hydrate = ctx->g_decode = ctx->g_sample = nullptr;
+    if (ctx->g_sample_ext) hipGraphExecDestroy(ctx->g_sample_ext);
+    ctx->g_logits = ctx->g_hydrate = ctx->g_decode = ctx->g_sample = ctx->g_sample_ext = nullptr;
 }
 
 
@@ -397,6 +477,47 @@ namespace {
 // xh_sampling as the header defines it: temperature >= 0, top_k >= 0, top_p in (0, 1]; NaN fails each
 bool sampling_ok(const xh_sampling* s) {
     return s && s->temperature >= 0.f && s->top_k >= 0 && s->top_p > 0.f && s->top_p <= 1.f;
+}
+
+// xh_logit_ctl as the header defines it (null = all off), with the token list that feeds the
+// window; vocab <= 0: unknown (no context), the ids are only checked for sign.  nullptr = valid.
+const char* ctl_error(const xh_logit_ctl* c, const int* toks, int n_toks, int vocab) {
+    if (n_toks < 0) return "negative token count";
+    if (n_toks > 0 && !toks) return "null token list";
+    for (int i = std::max(0, n_toks - XH_CTL_MAX_WINDOW); i < n_toks; i++)
+        if (toks[i] < 0 || (vocab > 0 && toks[i] >= vocab)) return "window token out of range";
+    if (!c) return nullptr;
+    if (!(c->repeat_penalty > 0.f) || !std::isfinite(c->repeat_penalty)) return "repeat_penalty must be > 0 and finite";
+    if (!std::isfinite(c->presence_penalty) || !std::isfinite(c->frequency_penalty)) return "penalties must be finite";
+    if (c->last_n < 0 || c->last_n > XH_CTL_MAX_WINDOW) return "last_n outside 0 .. XH_CTL_MAX_WINDOW";
+    if (!(c->min_p >= 0.f && c->min_p <= 1.f)) return "min_p outside [0, 1]";
+    if (c->n_bias < 0 || c->n_bias > XH_CTL_MAX_BIAS) return "n_bias outside 0 .. XH_CTL_MAX_BIAS";
+    if (c->n_bias > 0 && (!c->bias_token || !c->bias_value)) return "null bias array";
+    std::vector<int> ids(c->bias_token, c->bias_token + c->n_bias);
+    std::sort(ids.begin(), ids.end());
+    for (int i = 0; i < c->n_bias; i++) {
+        if (ids[i] < 0 || (vocab > 0 && ids[i] >= vocab)) return "bias id out of range";
+        if (i && ids[i] == ids[i - 1]) return "duplicate bias id";
+        const float b = c->bias_value[i];
+        if (std::isnan(b) || b == INFINITY) return "bias value must be finite or -inf";
+    }
+    return nullptr;
+}
+
+const xh_logit_ctl CTL_OFF = {1.f, 0.f, 0.f, 0, 0.f, 0, nullptr, nullptr};
+
+// the device block of (sampling, ctl) with `count` tokens in the ring
+ExtCtl ext_block(const xh_sampling& s, const xh_logit_ctl& c, int count) {
+    ExtCtl e{};
+    e.samp = s;
+    e.repeat_penalty = c.repeat_penalty;
+    e.presence_penalty = c.presence_penalty;
+    e.frequency_penalty = c.frequency_penalty;
+    e.last_n = c.last_n;
+    e.min_p = c.min_p;
+    e.n_bias = c.n_bias;
+    e.count = count;
+    return e;
 }
 }  // namespace
 
@@ -546,6 +667,147 @@ int xh_op_sample(const float* logits, int vocab, const xh_sampling* sampling, ui
     hipFree(d_samp);
     hipFree(d_out);
     return rc;
+}
+
+int xh_adjust_logits(const float* logits, int vocab, const xh_logit_ctl* ctl, const int* window, int n_window,
+                     float* out) {
+    if (!logits || !out || vocab <= 0) return set_err(nullptr, XH_E_INVALID, "bad adjust args");
+    if (const char* why = ctl_error(ctl, window, n_window, vocab)) return set_err(nullptr, XH_E_INVALID, "%s", why);
+    const xh_logit_ctl& c = ctl ? *ctl : CTL_OFF;
+    std::copy(logits, logits + vocab, out);
+    // (token, count) of the window's distinct tokens
+    const int n_win = std::min(c.last_n, n_window);
+    std::vector<int> win(window + (n_window - n_win), window + n_window);
+    std::sort(win.begin(), win.end());
+    std::vector<char> seen;  // bias entries whose token the window holds
+    seen.assign((size_t)c.n_bias, 0);
+    for (size_t i = 0; i < win.size();) {
+        size_t j = i;
+        while (j < win.size() && win[j] == win[i]) j++;
+        const int t = win[i];
+        bool biased = false;
+        float b = 0.f;
+        for (int k = 0; k < c.n_bias; k++)
+            if (c.bias_token[k] == t) { biased = true; b = c.bias_value[k]; seen[k] = 1; }
+        out[t] = ctl_adjust(logits[t], (int)(j - i), biased, b, c.repeat_penalty, c.presence_penalty, c.frequency_penalty);
+        i = j;
+    }
+    for (int k = 0; k < c.n_bias; k++)
+        if (!seen[k]) {
+            const int t = c.bias_token[k];
+            out[t] = ctl_adjust(logits[t], 0, true, c.bias_value[k], c.repeat_penalty, c.presence_penalty, c.frequency_penalty);
+        }
+    return 0;
+}
+
+int xh_decode_sample_ext(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* sampling, const xh_logit_ctl* ctl,
+                         const int* history, int n_history, int stop_a, int stop_b, int* tokens_out,
+                         float* logprobs_out, int* n_done) {
+    if (n_done) *n_done = 0;
+    if (!sampling_ok(sampling)) return set_err(ctx, XH_E_INVALID, "bad sampling parameters");
+    if (const char* why = ctl_error(ctl, history, n_history, ctx ? ctx->c.vocab_size : 0))
+        return set_err(ctx, XH_E_INVALID, "%s", why);
+    if (!ctx || n_steps < 0) return XH_E_INVALID;
+    if (pos < 0) return set_err(ctx, XH_E_INVALID, "negative pos");
+    if (ctx->c.vocab_size > SMP_MAX_VOCAB) return set_err(ctx, XH_E_INVALID, "vocab_size > %d", SMP_MAX_VOCAB);
+    if (n_steps > ctx->dec_cap) return set_err(ctx, XH_E_INVALID, "n_steps > %d", ctx->dec_cap);
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    int rc = check_ready(ctx);
+    if (rc) return rc;
+    const xh_logit_ctl& c = ctl ? *ctl : CTL_OFF;
+    StepParams* h = ctx->sp_host;
+    h->step = 0;
+    h->pos_next = pos;
+    h->max_seq_len = ctx->c.max_seq_len;
+    HIP_TRY(ctx, hipMemcpyAsync(&ctx->sp->step, &h->step, 3 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    // the parameter block, the bias table and the history's tail (ring slots 0 .. n_hist - 1):
+    // pageable sources, so the copies have left them when the call returns
+    const int n_hist = std::min(n_history, XH_CTL_MAX_WINDOW);
+    const ExtCtl blk = ext_block(*sampling, c, n_hist);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->ext, &blk, sizeof blk, hipMemcpyHostToDevice, ctx->stream));
+    if (c.n_bias > 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_btok, c.bias_token, (size_t)c.n_bias * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_bval, c.bias_value, (size_t)c.n_bias * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (n_hist > 0)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_ring, history + (n_history - n_hist), (size_t)n_hist * sizeof(int),
+                                    hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->use_graphs && n_steps > 0 && !ctx->g_sample_ext) {
+        rc = capture(ctx, 4, &ctx->g_sample_ext);
+        if (rc) return rc;
+    }
+    // the head reads the logits themselves; every step's lm_head launch rewrites cand for the raw
+    // logits it leaves, so a greedy call may follow
+    const bool stops = stop_a >= 0 || stop_b >= 0;
+    int done = 0;
+    for (int i = 0; i < n_steps; i++) {
+        if (ctx->use_graphs) {
+            HIP_TRY(ctx, hipGraphLaunch(ctx->g_sample_ext, ctx->stream));
+        } else {
+            rc = eager_step(ctx, true, HEAD_SAMPLE_EXT);
+            if (rc) return rc;
+        }
+        ctx->cand_valid = true;
+        done = i + 1;
+        if (stops) {
+            int tok = -1;
+            HIP_TRY(ctx, hipMemcpyAsync(&tok, ctx->dec_tokens + i, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (tok == stop_a || tok == stop_b) break;
+        }
+    }
+    if (tokens_out && done)
+        HIP_TRY(ctx, hipMemcpyAsync(tokens_out, ctx->dec_tokens, (size_t)done * sizeof(int), hipMemcpyDeviceToHost,
+                                    ctx->stream));
+    if (logprobs_out && done)
+        HIP_TRY(ctx, hipMemcpyAsync(logprobs_out, ctx->dec_logprobs, (size_t)done * sizeof(float), hipMemcpyDeviceToHost,
+                                    ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_done) *n_done = done;
+    return check_aw(ctx);
+}
+
+int xh_op_sample_ext(const float* logits, int vocab, const xh_sampling* sampling, const xh_logit_ctl* ctl,
+                     const int* window, int n_window, uint64_t pos0, int n_draws, int* tokens_out, int* n_kept_out,
+                     float* adjusted_out, float* logprob_out) {
+    if (!sampling_ok(sampling)) return set_err(nullptr, XH_E_INVALID, "bad sampling parameters");
+    if (!logits || !tokens_out || !n_kept_out || vocab <= 0 || vocab > SMP_MAX_VOCAB || n_draws <= 0 || n_draws > 65536)
+        return set_err(nullptr, XH_E_INVALID, "bad sample args");
+    if (const char* why = ctl_error(ctl, window, n_window, vocab)) return set_err(nullptr, XH_E_INVALID, "%s", why);
+    const xh_logit_ctl& c = ctl ? *ctl : CTL_OFF;
+    const int n_win = std::min(n_window, XH_CTL_MAX_WINDOW);
+    const ExtCtl blk = ext_block(*sampling, c, n_win);
+    struct Buf {
+        void* p = nullptr;
+        ~Buf() { if (p) hipFree(p); }
+        bool alloc(size_t bytes, const void* src, size_t src_bytes) {
+            if (hipMalloc(&p, bytes) != hipSuccess) return false;
+            return !src_bytes || hipMemcpy(p, src, src_bytes, hipMemcpyHostToDevice) == hipSuccess;
+        }
+    } d_logits, d_adj, d_blk, d_ring, d_btok, d_bval, d_prep, d_out, d_lp;
+    if (!d_logits.alloc((size_t)vocab * 4, logits, (size_t)vocab * 4) || !d_adj.alloc((size_t)vocab * 4, nullptr, 0) ||
+        !d_blk.alloc(sizeof blk, &blk, sizeof blk) ||
+        !d_ring.alloc(XH_CTL_MAX_WINDOW * sizeof(int), n_win ? window + (n_window - n_win) : nullptr, (size_t)n_win * sizeof(int)) ||
+        !d_btok.alloc(XH_CTL_MAX_BIAS * sizeof(int), c.bias_token, (size_t)c.n_bias * sizeof(int)) ||
+        !d_bval.alloc(XH_CTL_MAX_BIAS * sizeof(float), c.bias_value, (size_t)c.n_bias * sizeof(float)) ||
+        !d_prep.alloc(sizeof(ExtPrep), nullptr, 0) || !d_out.alloc((size_t)2 * n_draws * sizeof(int), nullptr, 0) ||
+        !d_lp.alloc((size_t)n_draws * sizeof(float), nullptr, 0))
+        return set_err(nullptr, XH_E_HIP, "hipMalloc / hipMemcpy failed");
+    hipLaunchKernelGGL(sample_ext_prep_kernel, dim3(1), dim3(SMP_THREADS), 0, nullptr, (const float*)d_logits.p, vocab,
+                       (const ExtCtl*)d_blk.p, (const int*)d_ring.p, (const int*)d_btok.p, (const float*)d_bval.p,
+                       (float*)d_adj.p, (ExtPrep*)d_prep.p);
+    hipLaunchKernelGGL(sample_ext_op_kernel, dim3(n_draws), dim3(SMP_THREADS), 0, nullptr, (const float*)d_logits.p,
+                       (const float*)d_adj.p, vocab, (const ExtCtl*)d_blk.p, (const ExtPrep*)d_prep.p, (uint32_t)pos0,
+                       (int*)d_out.p, (int*)d_out.p + n_draws, (float*)d_lp.p);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(tokens_out, d_out.p, (size_t)n_draws * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(n_kept_out, (int*)d_out.p + n_draws, (size_t)n_draws * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && adjusted_out) e = hipMemcpy(adjusted_out, d_adj.p, (size_t)vocab * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && logprob_out) e = hipMemcpy(logprob_out, d_lp.p, (size_t)n_draws * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return set_err(nullptr, XH_E_HIP, "sample_ext op failed: %s", hipGetErrorString(e));
+    return 0;
 }
 
 int xh_philox4x32(uint64_t seed, uint64_t pos, uint32_t out[4]) {

@@ -150,7 +150,7 @@ int xh_op_prompt_gemm(float* y, const uint16_t* w, const uint16_t* xh, const uin
 // timing hooks for bench.py
 // ---------------------------------------------------------------------------------------
 int xh_time_kernel(xh_ctx* ctx, int which, int iters, float* avg_us) {
-    if (!ctx || !avg_us || iters <= 0 || which < 0 || which > 6) return XH_E_INVALID;
+    if (!ctx || !avg_us || iters <= 0 || which < 0 || which > 7) return XH_E_INVALID;
     HIP_TRY(ctx, hipSetDevice(ctx->dev));
     int rc = check_ready(ctx);
     if (rc) return rc;
@@ -168,6 +168,7 @@ int xh_time_kernel(xh_ctx* ctx, int which, int iters, float* avg_us) {
             case 3: return launch_gemv(GEMV_RESID, kdt(ctx->L[l].w2_dt, ctx->L[l].w2_x), w2_args(ctx, l), ctx->stream, mb);
             case 4: return launch_gemv(GEMV_LOGITS, kdt(ctx->wcls_dt, ctx->wcls_x), cls_args(ctx), ctx->stream, mb);
             case 6: time_sample_head(ctx); return true;
+            case 7: time_sample_ext_head(ctx); return true;
             default:
                 return launch_attn(attn_args(ctx, l), ctx->c.head_dim, ctx->qpk, ctx->c.n_kv_heads, ctx->t_max,
                                    ctx->stream);
@@ -205,6 +206,7 @@ size_t xh_kernel_bytes(const xh_ctx* ctx, int which, int kv_len) {
         case 4: return (size_t)c.vocab_size * file_row_bytes(ctx->wcls ? ctx->wcls_dt : ctx->embed_dt, c.dim) +
                        c.dim * (vec + dtype_size(ctx->final_norm_dt)) + (size_t)c.vocab_size * vec;
         case 6: return (size_t)c.vocab_size * vec + file_row_bytes(ctx->embed_dt, c.dim) + c.dim * vec;
+        case 7: return (size_t)2 * c.vocab_size * vec + file_row_bytes(ctx->embed_dt, c.dim) + c.dim * vec;
         default: return (size_t)2 * kv_len * ctx->kv_dim * 2 + 2 * (size_t)ctx->q_dim * vec;
     }
 }

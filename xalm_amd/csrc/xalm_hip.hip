@@ -129,6 +129,11 @@ int xh_create(const xh_config* cfg, int device_ordinal, xh_ctx** out) {
     CREATE_TRY(dmalloc(ctx, &ctx->cand, (size_t)ARGMAX_CANDS));
     CREATE_TRY(dmalloc(ctx, &ctx->scan_flag, (size_t)1));
     CREATE_TRY(dmalloc(ctx, &ctx->samp, (size_t)1));
+    CREATE_TRY(dmalloc(ctx, &ctx->ext, (size_t)1));
+    CREATE_TRY(dmalloc(ctx, &ctx->ext_ring, (size_t)XH_CTL_MAX_WINDOW));
+    CREATE_TRY(dmalloc(ctx, &ctx->ext_btok, (size_t)XH_CTL_MAX_BIAS));
+    CREATE_TRY(dmalloc(ctx, &ctx->ext_bval, (size_t)XH_CTL_MAX_BIAS));
+    CREATE_TRY(dmalloc(ctx, &ctx->ext_adj, (size_t)c.vocab_size));
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device_ordinal) != hipSuccess) {
@@ -147,6 +152,7 @@ int xh_create(const xh_config* cfg, int device_ordinal, xh_ctx** out) {
     CREATE_TRY(dmalloc(ctx, &ctx->sp, 1));
     ctx->dec_cap = 1 << 16;
     CREATE_TRY(dmalloc(ctx, &ctx->dec_tokens, (size_t)ctx->dec_cap));
+    CREATE_TRY(dmalloc(ctx, &ctx->dec_logprobs, (size_t)ctx->dec_cap));
     if (hipHostMalloc((void**)&ctx->sp_host, sizeof(StepParams), hipHostMallocDefault) != hipSuccess) {
         g_create_error = "hipHostMalloc failed";
         xh_destroy(ctx);
@@ -189,6 +195,8 @@ void xh_destroy(xh_ctx* ctx) {
     hipFree(ctx->kv); hipFree(ctx->x); hipFree(ctx->q); hipFree(ctx->attn_out); hipFree(ctx->hb);
     hipFree(ctx->logits); hipFree(ctx->part_o); hipFree(ctx->part_ml); hipFree(ctx->attn_cnt); hipFree(ctx->aw_sync); hipFree(ctx->cand); hipFree(ctx->scan_flag);
     hipFree(ctx->samp);
+    hipFree(ctx->ext); hipFree(ctx->ext_ring); hipFree(ctx->ext_btok); hipFree(ctx->ext_bval); hipFree(ctx->ext_adj);
+    hipFree(ctx->dec_logprobs);
     pf_free(ctx);
     hipFree(ctx->pf_wdq); hipFree(ctx->ppl_tgt); hipFree(ctx->ppl_prob); hipFree(ctx->rope_freq); hipFree(ctx->rope_cs);
     hipFree(ctx->aw_trace);

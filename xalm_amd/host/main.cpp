@@ -3,12 +3,15 @@
 //
 //   xalm <checkpoint.xalm> [-m completion|perplexity] [-d hip|cpu] [-i prompt | -f file]
 //                          [-T context] [-n steps] [-g 0|1] [-t temperature] [-k top_k] [-p top_p] [-s seed]
+//                          [-r repeat_penalty] [-w window] [-P presence] [-F frequency] [-M min_p]
 //
 // -d selects the device as in the reference (src/main.cpp:465-477); this build ships the HIP
 // device.  -g 1 runs the greedy loop on the device (no host round trip per token); -g 0
 // (default) samples on the host each step exactly like run_completion (src/main.cpp:105-115).
 // -t > 0 samples (xh_sampling, include/xalm_hip.h): on the device with -g 1, with the host Sampler::sample
-// with -g 0.
+// with -g 0.  -r / -w / -P / -F / -M (xh_logit_ctl) penalise the tokens of the last -w ids of prompt +
+// output and cut by min-p, at any temperature: xh_decode_sample_ext with -g 1, the host Sampler over
+// xh_adjust_logits with -g 0.
 // Stats are wall clock (the reference divides by user+sys CPU time, src/profiler.h:124-129).
 #include <chrono>
 #include <cmath>
@@ -41,6 +44,11 @@ static void error_usage() {
     fprintf(stderr, "  -p <float> top-p in (0, 1], 1 = off (default 1)\n");
     fprintf(stderr, "  -s <int> sampling seed (default 0); -g 0 and -g 1 draw from the same definition and print\n");
     fprintf(stderr, "     the same ids for a seed, except where a draw falls within rounding of a boundary\n");
+    fprintf(stderr, "  -r <float> repeat penalty > 0, 1 = off (default 1)\n");
+    fprintf(stderr, "  -w <int> penalty window: the last 0 .. 1024 ids of prompt + output (default 64; 0 = penalties off)\n");
+    fprintf(stderr, "  -P <float> presence penalty, 0 = off (default 0)\n");
+    fprintf(stderr, "  -F <float> frequency penalty, 0 = off (default 0)\n");
+    fprintf(stderr, "  -M <float> min-p in [0, 1], 0 = off (default 0)\n");
     fprintf(stderr, "  Choose one:\n");
     fprintf(stderr, "    -i <string> input prompt\n");
     fprintf(stderr, "    -f <filepath> input file with prompt\n");
@@ -57,7 +65,7 @@ static void print_ids(const std::vector<int>& ids) {
 
 // run_completion, src/main.cpp:44-128
 static void run_completion(const std::string& path, Device dev, const std::string& prompt, int context, int num_steps,
-                           bool device_loop, const xh_sampling& sampling) {
+                           bool device_loop, const xh_sampling& sampling, const xh_logit_ctl& ctl) {
     const XalmFile file = XalmFile::load(path);
     const Model model = Model::from_xalm(file, context, dev);
     InferenceState state(model.config);
@@ -75,9 +83,14 @@ static void run_completion(const std::string& path, Device dev, const std::strin
     model.prefill(state, encoding, 0);
     for (size_t pos = 0; pos < encoding.size(); pos++) read_bytes += model.active_bytes(pos);
     const auto t1 = clk::now();
+    // any control on: the extended draw on both routes, prompt + output as the history
+    const bool ext = ctl.repeat_penalty != 1.f || ctl.presence_penalty != 0.f || ctl.frequency_penalty != 0.f ||
+                     ctl.min_p != 0.f;
     if (device_loop && num_steps > 0) {
         const std::vector<int> gen =
-            sampling.temperature > 0.f
+            ext ? model.decode_sample_ext((int)encoding.size(), num_steps, sampling, ctl, encoding, tokenizer.eos_id,
+                                          tokenizer.eot_id)
+            : sampling.temperature > 0.f
                 ? model.decode_sample((int)encoding.size(), num_steps, sampling, tokenizer.eos_id, tokenizer.eot_id)
                 : model.decode_greedy((int)encoding.size(), num_steps, tokenizer.eos_id, tokenizer.eot_id);
         for (int t : gen) {
@@ -87,8 +100,9 @@ static void run_completion(const std::string& path, Device dev, const std::strin
         }
     } else {
         for (int i = 0; i < num_steps || num_steps == -1; i++) {
-            const int token_id = sampling.temperature > 0.f ? sampler.sample(state, sampling, (int)encoding.size())
-                                                            : sampler.sample_argmax(state);
+            const int token_id = ext ? sampler.sample(state, sampling, ctl, encoding, (int)encoding.size())
+                                 : sampling.temperature > 0.f ? sampler.sample(state, sampling, (int)encoding.size())
+                                                              : sampler.sample_argmax(state);
             std::cout << tokenizer.decode_one(encoding.back(), token_id) << std::flush;
             encoding.push_back(token_id);
             if (token_id == tokenizer.eos_id || token_id == tokenizer.eot_id) break;
@@ -139,6 +153,7 @@ int main(int argc, char** argv) {
     std::string device = "hip";
     int context = 0, num_steps = 128, device_loop = 0;
     xh_sampling sampling{0.f, 0, 1.f, 0};
+    xh_logit_ctl ctl{1.f, 0.f, 0.f, 64, 0.f, 0, nullptr, nullptr};
     if (argc >= 2) path = argv[1];
     else error_usage();
     for (int i = 2; i < argc;) {
@@ -162,6 +177,11 @@ int main(int argc, char** argv) {
         else if (f == 'k') sampling.top_k = std::stoi(v);
         else if (f == 'p') sampling.top_p = std::stof(v);
         else if (f == 's') sampling.seed = std::stoull(v);
+        else if (f == 'r') ctl.repeat_penalty = std::stof(v);
+        else if (f == 'w') ctl.last_n = std::stoi(v);
+        else if (f == 'P') ctl.presence_penalty = std::stof(v);
+        else if (f == 'F') ctl.frequency_penalty = std::stof(v);
+        else if (f == 'M') ctl.min_p = std::stof(v);
         else error_usage();
         i += 2;
     }
@@ -177,7 +197,7 @@ int main(int argc, char** argv) {
     }
     const Device dev = device == "cpu" ? Device::CPU : Device::HIP;
     try {
-        if (mode == "completion") run_completion(path, dev, prompt, context, num_steps, device_loop != 0, sampling);
+        if (mode == "completion") run_completion(path, dev, prompt, context, num_steps, device_loop != 0, sampling, ctl);
         else run_perplexity(path, dev, prompt, context);
     } catch (const std::exception& e) {
         fprintf(stderr, "error: %s\n", e.what());

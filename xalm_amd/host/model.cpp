@@ -99,6 +99,21 @@ std::vector<int> Model::decode_sample(const int pos, const int n_steps, const xh
     return toks;
 }
 
+std::vector<int> Model::decode_sample_ext(const int pos, const int n_steps, const xh_sampling& sampling,
+                                          const xh_logit_ctl& ctl, const std::vector<int>& history, const int stop_a,
+                                          const int stop_b, std::vector<float>* logprobs) const {
+    std::vector<int> toks((size_t)std::max(n_steps, 1));
+    std::vector<float> lp((size_t)std::max(n_steps, 1));
+    int done = 0;
+    check(xh_decode_sample_ext(_ctx, pos, n_steps, &sampling, &ctl, history.data(), (int)history.size(), stop_a, stop_b,
+                               toks.data(), lp.data(), &done),
+          _ctx, "xh_decode_sample_ext");
+    toks.resize((size_t)done);
+    lp.resize((size_t)done);
+    if (logprobs) *logprobs = lp;
+    return toks;
+}
+
 std::vector<float> Model::token_probs(const std::vector<int>& tokens, const int pos0) const {
     if (tokens.size() < 2) return {};
     std::vector<float> p(tokens.size() - 1);
@@ -215,10 +230,12 @@ float Sampler::sample_prob(const int index, const InferenceState& s) const {
 }
 
 // ---- seeded sampling: the definition of xh_sampling (include/xalm_hip.h), restated -------------
-int sample_logits(const float* logits, const int vocab, const xh_sampling& p, const uint64_t pos, int* n_kept) {
+int sample_logits(const float* logits, const int vocab, const xh_sampling& p, const uint64_t pos, int* n_kept,
+                  const float min_p) {
     if (!logits || vocab <= 0) throw std::invalid_argument("sample: no logits");
     if (!(p.temperature >= 0.f) || p.top_k < 0 || !(p.top_p > 0.f && p.top_p <= 1.f))
         throw std::invalid_argument("sample: temperature >= 0, top_k >= 0, top_p in (0, 1]");
+    if (!(min_p >= 0.f && min_p <= 1.f)) throw std::invalid_argument("sample: min_p in [0, 1]");
     int kept_n = 1;
     int token = 0;
     const auto done = [&] {
@@ -252,6 +269,12 @@ int sample_logits(const float* logits, const int vocab, const xh_sampling& p, co
     std::vector<int> order((size_t)vocab);
     std::iota(order.begin(), order.end(), 0);
     size_t n = p.top_k > 0 && p.top_k < vocab ? (size_t)p.top_k : (size_t)vocab;
+    if (min_p > 0.f) {  // a prefix of the order: the weight is monotone in the logit
+        size_t n_minp = 0;
+        for (int i = 0; i < vocab; ++i)
+            n_minp += logits[i] != -std::numeric_limits<float>::infinity() && expf((logits[i] - m) / p.temperature) >= min_p;
+        if (n_minp >= 1 && n_minp < n) n = n_minp;
+    }
     if (n < (size_t)vocab || p.top_p < 1.f) {
         const auto before = [&](const int a, const int b) {
             const uint32_t ka = key(a), kb = key(b);
@@ -292,6 +315,15 @@ int sample_logits(const float* logits, const int vocab, const xh_sampling& p, co
 
 int Sampler::sample(const InferenceState& s, const xh_sampling& sampling, const int pos) const {
     return sample_logits(s.logits(), vocab_size, sampling, (uint64_t)pos, nullptr);
+}
+
+int Sampler::sample(const InferenceState& s, const xh_sampling& sampling, const xh_logit_ctl& ctl,
+                    const std::vector<int>& history, const int pos) const {
+    std::vector<float> adj((size_t)vocab_size);
+    const size_t n_win = std::min(history.size(), (size_t)XH_CTL_MAX_WINDOW);
+    if (xh_adjust_logits(s.logits(), vocab_size, &ctl, history.data() + (history.size() - n_win), (int)n_win, adj.data()))
+        throw std::invalid_argument(std::string("sample: ") + xh_last_error(nullptr));
+    return sample_logits(adj.data(), vocab_size, sampling, (uint64_t)pos, nullptr, ctl.min_p);
 }
 
 }  // namespace xalm

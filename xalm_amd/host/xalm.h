@@ -102,6 +102,12 @@ public:
     // sampled decode on the device (xh_decode_sample): step i drawn at counter pos + i
     std::vector<int> decode_sample(int pos, int n_steps, const xh_sampling& sampling, int stop_a = -1,
                                    int stop_b = -1) const;
+    // the same loop with repetition penalties, logit bias and min-p (xh_decode_sample_ext, xh_logit_ctl):
+    // `history` = the tokens before pos (prompt and earlier output); logprobs (may be null) receives
+    // one log-probability per token
+    std::vector<int> decode_sample_ext(int pos, int n_steps, const xh_sampling& sampling, const xh_logit_ctl& ctl,
+                                       const std::vector<int>& history, int stop_a = -1, int stop_b = -1,
+                                       std::vector<float>* logprobs = nullptr) const;
     void fetch_logits(InferenceState& s) const;
     // run_perplexity's loop on the device (xh_perplexity): element i = Sampler::sample_prob of
     // tokens[i + 1] after forwarding tokens[i] at pos0 + i
@@ -140,8 +146,14 @@ struct Sampler {
     // counter `pos`, the position the token will occupy: the host restatement of the device
     // sampler, sums in double.  Throws std::invalid_argument for parameters outside it.
     int sample(const InferenceState& s, const xh_sampling& sampling, int pos) const;
+    // the same on the logits adjusted under `ctl` (xh_logit_ctl, through xh_adjust_logits) over the
+    // window `history` gives, with min-p; temperature 0 = sample_argmax of the adjusted logits
+    int sample(const InferenceState& s, const xh_sampling& sampling, const xh_logit_ctl& ctl,
+               const std::vector<int>& history, int pos) const;
 };
 // the same on a bare logits vector; *n_kept (may be null) = size of the kept set
-int sample_logits(const float* logits, int vocab, const xh_sampling& sampling, uint64_t pos, int* n_kept);
+// min_p > 0 (xh_logit_ctl): the top-k stage keeps at most the tokens of weight >= min_p
+int sample_logits(const float* logits, int vocab, const xh_sampling& sampling, uint64_t pos, int* n_kept,
+                  float min_p = 0.f);
 
 }  // namespace xalm

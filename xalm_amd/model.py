@@ -104,6 +104,28 @@ class Model:
                                          int(stop[1]), L.ptr(toks), ctypes.byref(done)), self._ctx)
         return toks[: done.value].tolist()
 
+    def decode_sample_ext(self, pos: int, n_steps: int, temperature: float, top_k: int = 0, top_p: float = 1.0,
+                          seed: int = 0, repeat_penalty: float = 1.0, presence_penalty: float = 0.0,
+                          frequency_penalty: float = 0.0, last_n: int = 0, min_p: float = 0.0, logit_bias=None,
+                          history=(), logprobs: bool = False, stop=(-1, -1)):
+        """decode_sample with repetition penalties over the last `last_n` tokens of history +
+        output, logit biases (a dict or (token, value) pairs; -inf bans), min-p, and the
+        log-probability of each token (xh_logit_ctl, include/xalm_hip.h).  `history` = the tokens
+        at the positions before `pos`.  Returns the tokens, or (tokens, log-probabilities) with
+        `logprobs`."""
+        toks = np.zeros(max(n_steps, 1), dtype=np.int32)
+        lps = np.zeros(max(n_steps, 1), dtype=np.float32)
+        done = ctypes.c_int(0)
+        s = L.XhSampling(temperature, top_k, top_p, seed)
+        c, keep = L.logit_ctl(repeat_penalty, presence_penalty, frequency_penalty, last_n, min_p, logit_bias)
+        hist = np.ascontiguousarray(np.asarray(history, dtype=np.int32))
+        L.check(L.lib().xh_decode_sample_ext(self._ctx, int(pos), int(n_steps), ctypes.byref(s), ctypes.byref(c),
+                                             L.ptr(hist) if hist.size else None, int(hist.size), int(stop[0]),
+                                             int(stop[1]), L.ptr(toks), L.ptr(lps), ctypes.byref(done)), self._ctx)
+        del keep
+        out = toks[: done.value].tolist()
+        return (out, lps[: done.value].copy()) if logprobs else out
+
     def prefill(self, tokens, pos0: int, s: InferenceState | None = None) -> None:
         """Hydrate tokens[0..n) at positions pos0.. (the prompt loop of run_completion,
         src/main.cpp:94-100); the last token's logits land in `s` when given."""
