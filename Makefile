@@ -36,6 +36,11 @@ $(OBJ)/%.o: xalm_amd/csrc/%.hip
 $(OBJ)/dt_launch_dt%.o: xalm_amd/csrc/dt_launch.hip
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -MMD -MP -DPK_DT=$* -c -o $@ $<
+# the regex compiler and the host mask: plain C++, no HIP
+$(OBJ)/constraint.o: xalm_amd/csrc/constraint.cpp
+	@mkdir -p $(OBJ)
+	$(CXX) $(HOSTFLAGS) -MMD -MP -c -o $@ $<
+HIP_OBJS += $(OBJ)/constraint.o
 $(LIB)/libxalm_hip.so: $(HIP_OBJS)
 	@mkdir -p $(LIB)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $^

@@ -251,6 +251,62 @@ int xh_decode_sample_ext(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* s
                          const int* history, int n_history, int stop_token_a, int stop_token_b,
                          int* tokens_out, float* logprobs_out, int* n_done);
 
+/* ---- regex-constrained decoding: a byte-level DFA masks the tokens ------------------------- */
+#define XH_DFA_DEAD 0xFFFFu            /* no transition; also the "stuck" state */
+#define XH_DFA_MAX_STATES 65535
+typedef struct xh_byte_dfa {
+    int32_t n_states;                  /* 1 .. XH_DFA_MAX_STATES */
+    int32_t start;                     /* in [0, n_states) */
+    const uint16_t* next;              /* [n_states][256]: next state or XH_DFA_DEAD */
+    const uint8_t*  accept;            /* [n_states]: nonzero = the text so far may end here */
+} xh_byte_dfa;
+/* The constrained draw: xh_logit_ctl's definition applied to masked logits l''.
+ * - Pieces.  Token t has a byte string piece[t], given once per context as a blob plus
+ *   offsets[vocab + 1] (piece[t] = bytes[offsets[t] .. offsets[t + 1])), ascending from 0, at most
+ *   16 MiB in all.  The host mirror fills it from the tokenizer: the vocab string, the single byte
+ *   for a byte-fallback token; decode_one's strip of the space after BOS is not applied.
+ * - Allowed set in state s.  A token with a non-empty piece is allowed when walking `next` from s
+ *   over its bytes never meets XH_DFA_DEAD; its successor state is where the walk ends.  A token
+ *   with an empty piece is never allowed.  The call's end tokens (stop_token_a / b, where >= 0) are
+ *   allowed exactly when accept[s] is set, whatever their piece, and leave the state unchanged.
+ * - Masked logits.  l''_t = l'_t if t is allowed, else -inf; l' are the adjusted logits of
+ *   xh_logit_ctl (a null ctl: the raw logits).  Unmasked entries keep their bits.  min-p, top-k,
+ *   top-p, Philox at counter pos + i and the integer-mass evaluation work on l'' exactly as
+ *   xh_decode_sample_ext's on l'.  Log-probabilities stay over the raw logits.  If every allowed
+ *   token carries -inf (all banned by bias), "no finite logit: the token is 0" holds as there, and
+ *   the state is token 0's successor, XH_DFA_DEAD when 0 is forbidden.
+ * - Greedy.  temperature == 0 takes the first token of the sampler's order (logit descending by f32
+ *   bits, then index ascending) among the allowed tokens, that is top_k = 1.  The "> FLT_MIN, else
+ *   token 0" rule of sample_argmax does not apply: token 0 may be forbidden.
+ * - Stuck.  If no token is allowed, the step emits stop_token_a if it is >= 0, else stop_token_b,
+ *   else 0, and the state becomes XH_DFA_DEAD.  In XH_DFA_DEAD every later step of the call emits
+ *   that same token, without masking.  xh_regex_compile never produces such a DFA (every state
+ *   reaches an accepting one, so some byte continues it, or it accepts); hand-made tables and
+ *   vocabularies that lack the needed piece can.
+ * - One call equals two.  The call takes state_in, the DFA's start or a previous call's state_out,
+ *   and returns state_out; tokens and states are identical whether a run is one call or split
+ *   anywhere (the second call given history ++ the first call's tokens, as xh_decode_sample_ext).
+ * - Invalid arguments.  n_states out of range; start or state_in out of range (state_in ==
+ *   XH_DFA_DEAD is accepted); a next entry that is neither < n_states nor XH_DFA_DEAD; a null
+ *   table; offsets not ascending from 0; the blob over 16 MiB; a vocabulary over 2^17; a stop token
+ *   >= vocab (the stuck state emits it); a constrained decode before both uploads: XH_E_INVALID
+ *   before the device is touched.
+ * How the device evaluates it (xalm_amd/csrc/sample_dfa.h): between the adjustment and the
+ * sampler, threads stride over the vocabulary, each walking its pieces from the current state (a
+ * device word the head advances) and writing -inf over forbidden tokens. */
+
+/* Copy the pieces of the context's vocab_size tokens to the device (replacing earlier ones). */
+int xh_constraint_set_vocab(xh_ctx* ctx, const uint8_t* bytes, const uint32_t* offsets);
+/* Validate the DFA and copy it to the device (replacing an earlier one; no new graph capture).
+ * NULL clears it. */
+int xh_constraint_set(xh_ctx* ctx, const xh_byte_dfa* dfa);
+/* xh_decode_sample_ext's loop with the constrained draw (its own step head and graph; the other
+ * loops never read the constraint).  state_out (may be NULL) receives the state after the last
+ * emitted token, state_in when n_steps is 0. */
+int xh_decode_sample_dfa(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* sampling, const xh_logit_ctl* ctl,
+                         const int* history, int n_history, uint32_t state_in, int stop_token_a, int stop_token_b,
+                         int* tokens_out, float* logprobs_out, uint32_t* state_out, int* n_done);
+
 /* Hydrate: forward tokens[0..n) at positions pos0.. (HYDRATE_KV_CACHE for all but the last,
  * which computes logits if want_logits), the prompt loop of run_completion
  * (src/main.cpp:94-100) in one call.  logits_out may be NULL. */
@@ -409,6 +465,32 @@ int xh_op_sample_ext(const float* logits, int vocab, const xh_sampling* sampling
  * uses): out[vocab] = l' for logits[vocab] under the window's last min(last_n, n_window) tokens. */
 int xh_adjust_logits(const float* logits, int vocab, const xh_logit_ctl* ctl, const int* window,
                      int n_window, float* out);
+/* The constrained draw (the same device functions as xh_decode_sample_dfa) on host logits[vocab],
+ * no model and no context: draw d at counter pos0 + d, every draw from `state` over the same window;
+ * masked_out (may be NULL) receives l''[vocab] as the device computed it (l' when state is
+ * XH_DFA_DEAD), next_state_out[n_draws] each draw's successor state, n_kept_out 0 for a stuck draw,
+ * logprob_out (may be NULL) the log-probabilities. */
+int xh_op_sample_dfa(const float* logits, int vocab, const xh_sampling* sampling, const xh_logit_ctl* ctl,
+                     const int* window, int n_window, const xh_byte_dfa* dfa, const uint8_t* bytes,
+                     const uint32_t* offsets, uint32_t state, int stop_token_a, int stop_token_b, uint64_t pos0,
+                     int n_draws, int* tokens_out, int* n_kept_out, float* masked_out, uint32_t* next_state_out,
+                     float* logprob_out);
+/* Host only, no device, plain C++ (also what the host Sampler uses): allowed_out[t] = 1 if token t
+ * is allowed in `state`, else 0, and next_state_out[t] its successor state (XH_DFA_DEAD when
+ * forbidden); nothing is allowed in XH_DFA_DEAD. */
+int xh_constraint_mask(const xh_byte_dfa* dfa, const uint8_t* bytes, const uint32_t* offsets, int vocab, uint32_t state,
+                       int stop_token_a, int stop_token_b, uint8_t* allowed_out, uint16_t* next_state_out);
+/* Host only, no context, no device: compile a regular expression, matched against the whole text
+ * byte by byte, into a trimmed DFA: every state reaches an accepting state, and a transition into a
+ * removed state is XH_DFA_DEAD.  Syntax: literal bytes (UTF-8 as its bytes); \\ \. \n \t \r \xHH
+ * \d \w \s and any escaped punctuation; . (any byte but \n); [a-z], [^...] (escapes allowed, a
+ * leading ] is literal); ( ), |, * + ?, {m}, {m,n}, {m,} with counts <= 256.  One quantifier per
+ * atom (no lazy or stacked ones); a literal { is escaped; groups nest at most 256 deep.  Thompson NFA, subset construction, no
+ * minimisation.  next [cap_states][256] and accept [cap_states] are caller-owned (may be NULL with
+ * cap_states 0 to ask for the size).  XH_E_INVALID: a syntax error, the empty language, or more than
+ * XH_DFA_MAX_STATES states before trimming; XH_E_NOMEM, with *n_states set: cap_states is too
+ * small. */
+int xh_regex_compile(const char* pattern, uint16_t* next, uint8_t* accept, int cap_states, int* n_states, int* start);
 /* Philox4x32-10 on the host (no device): key (seed & 0xffffffff, seed >> 32), counter
  * (pos mod 2^32, 0, 0, 0): only the low 32 bits of pos are used. */
 int xh_philox4x32(uint64_t seed, uint64_t pos, uint32_t out[4]);
@@ -417,10 +499,12 @@ int xh_philox4x32(uint64_t seed, uint64_t pos, uint32_t out[4]);
 /* Average device time (microseconds) of one launch of kernel `which` (0 = the fused
  * gate/up matvec, 1 = qkv, 2 = wo, 3 = down, 4 = lm_head, 5 = attention, 6 = the sampled step
  * head of xh_decode_sample under its last parameters, 7 = the extended step head of
- * xh_decode_sample_ext under its last parameters) over `iters` back-to-back launches with
+ * xh_decode_sample_ext under its last parameters, 8 = the constrained step head of
+ * xh_decode_sample_dfa under its last parameters) over `iters` back-to-back launches with
  * the current step parameters (layers rotate, so the Infinity Cache never serves a repeat).
- * 6 and 7 advance the decode loop's position with every launch (7 also appends to its window):
- * reset or re-hydrate afterwards. */
+ * 6, 7 and 8 advance the decode loop's position with every launch (7 and 8 also append to their
+ * window, 8 also advances the DFA state): reset or re-hydrate afterwards.  8 needs an xh_decode_sample_dfa
+ * call since the last xh_constraint_set / xh_constraint_set_vocab, else XH_E_STATE. */
 int xh_time_kernel(xh_ctx* ctx, int which, int iters, float* avg_us);
 /* Bytes one launch of that kernel must move (algorithmic). */
 size_t xh_kernel_bytes(const xh_ctx* ctx, int which, int kv_len);

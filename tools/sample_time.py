@@ -9,6 +9,13 @@ three parameter sets, and the extended step head's (xh_time_kernel 7, xh_decode_
 first of them with its controls off, with a 64-token window, and with a 1024-token window and 256
 biases.  The comparison is the greedy loop of the same process on the same box.
 
+Then the constrained step head (xh_time_kernel 8, xh_decode_sample_dfa) next to the extended head
+of the same run under the same parameters, with synthetic pieces of realistic lengths (1 .. 12
+bytes, mean about 5) and two permissive DFAs under which every piece is walked to its end: `.*`
+(one state: the table sits in LDS) and a 700-state cycle over every byte (walked from global
+memory); and the ms/step and tok/s of 128-step xh_decode_sample_dfa and xh_decode_sample_ext
+calls in turn.
+
 Run under a time limit:  timeout -k 10 600 python tools/sample_time.py
 """
 import argparse
@@ -18,7 +25,10 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+
 import bench  # noqa: E402
+from xalm_amd import _lib as L  # noqa: E402
 from xalm_amd.model import InferenceState, Model  # noqa: E402
 
 PARAMS = (0.8, 40, 0.95)
@@ -37,11 +47,57 @@ def ext_sets(vocab):
             ("window 1024 bias 256", hist1024, dict(PENALTIES, last_n=1024, logit_bias=bias))]
 
 
+def synthetic_pieces(vocab):
+    """Lower-case pieces of 1 .. 12 bytes, short ones most frequent (mean about 5), no newline."""
+    rng = np.random.default_rng(vocab)
+    lens = np.minimum(1 + rng.geometric(0.22, vocab), 12)
+    letters = rng.integers(ord("a"), ord("z") + 1, int(lens.sum())).astype(np.uint8)
+    offs = np.concatenate(([0], np.cumsum(lens)))
+    return [letters[offs[t]:offs[t + 1]].tobytes() for t in range(vocab)]
+
+
+def cycle_dfa(n):
+    """n states, every byte leads from state i to i + 1 (mod n), every state accepts."""
+    nxt = np.repeat(((np.arange(n) + 1) % n).astype(np.uint16)[:, None], 256, axis=1)
+    return L.ByteDfa(nxt, np.ones(n, np.uint8))
+
+
+def constrained_rows(m, c, n, args):
+    t, k, p = PARAMS
+    pieces = synthetic_pieces(c.vocab_size)
+    m.set_constraint_vocab(pieces)
+    print(f"  pieces: {sum(map(len, pieces)) / len(pieces):.2f} bytes mean, {max(map(len, pieces))} longest")
+    for label, dfa in ((".* (1 state, LDS)", L.regex_compile(".*")), ("700-state cycle (global)", cycle_dfa(700))):
+        m.set_constraint(dfa)
+        m.decode_sample_ext(n, 1, t, k, p, seed=3)
+        ext_us = m.time_kernel(7, args.head_iters)
+        m.decode_sample_dfa(n, 1, t, dfa.start, k, p, seed=3)
+        dfa_us = m.time_kernel(8, args.head_iters)
+        print(f"  heads alone, t {t} k {k} p {p}, {label:<24}: extended {ext_us:8.2f} us   constrained {dfa_us:8.2f} us"
+              f"   ({dfa_us - ext_us:+.2f} us)", flush=True)
+        m.decode_sample_ext(n, 8, t, k, p, seed=1)  # both graphs exist and are warm
+        m.decode_sample_dfa(n, 8, t, dfa.start, k, p, seed=1)
+        ext, con = [], []
+        for r in range(args.rounds):
+            t0 = time.perf_counter()
+            m.decode_sample_ext(n, args.steps, t, k, p, seed=r)
+            t1 = time.perf_counter()
+            toks, _, _ = m.decode_sample_dfa(n, args.steps, t, dfa.start, k, p, seed=r)
+            t2 = time.perf_counter()
+            assert len(toks) == args.steps
+            ext.append((t1 - t0) * 1e3 / args.steps)
+            con.append((t2 - t1) * 1e3 / args.steps)
+        me, mc = statistics.median(ext), statistics.median(con)
+        print(f"  loops, {label:<24}: extended {me:.4f} ms/step ({1e3 / me:.1f} tok/s)   constrained {mc:.4f} ms/step "
+              f"({1e3 / mc:.1f} tok/s)   {(mc - me) * 1e3:+.1f} us/step ({100 * (mc - me) / me:+.2f} %)", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--rounds", type=int, default=6)
     ap.add_argument("--head-iters", type=int, default=200)
+    ap.add_argument("--constrained", type=int, default=1, help="also time the constrained head and loop")
     args = ap.parse_args()
     for name in ("mistral-7b-f16", "llama3-8b-f16"):
         w = bench.WORKLOADS[name]
@@ -78,6 +134,9 @@ def main():
             m.decode_sample_ext(n, 1, t, k, p, seed=3, history=hist, **ctl)  # sets the blocks and the ring
             us = m.time_kernel(7, args.head_iters)
             print(f"  extended head alone, t {t} k {k} p {p}, {label:<22}: {us:8.2f} us", flush=True)
+        if args.constrained:
+            m.prefill(prompt, 0, st)  # the timed heads moved the position: hydrate again
+            constrained_rows(m, c, n, args)
         m.close()
 
 

@@ -86,6 +86,54 @@ def logit_ctl(repeat_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, l
     return c, (btok, bval)
 
 
+DFA_DEAD, DFA_MAX_STATES = 0xFFFF, 65535
+
+
+class XhByteDfa(ctypes.Structure):
+    """xh_byte_dfa (include/xalm_hip.h): next [n_states][256] uint16 (DFA_DEAD = no transition),
+    accept [n_states] uint8."""
+    _fields_ = [("n_states", ctypes.c_int32), ("start", ctypes.c_int32), ("next", ctypes.c_void_p),
+                ("accept", ctypes.c_void_p)]
+
+
+class ByteDfa:
+    """A byte DFA held as numpy arrays: next uint16 [n_states, 256], accept uint8 [n_states], start."""
+
+    def __init__(self, next, accept, start=0):
+        self.next = np.ascontiguousarray(next, dtype=np.uint16).reshape(-1, 256)
+        self.accept = np.ascontiguousarray(accept, dtype=np.uint8)
+        self.start = int(start)
+
+    @property
+    def n_states(self):
+        return int(self.accept.size)
+
+    def abi(self, n_states=None):
+        return XhByteDfa(self.n_states if n_states is None else n_states, self.start, self.next.ctypes.data,
+                         self.accept.ctypes.data)
+
+
+def pieces_blob(pieces):
+    """(bytes uint8 [total], offsets uint32 [V + 1]) of a list of byte strings: the piece table of
+    xh_constraint_set_vocab."""
+    offsets = np.zeros(len(pieces) + 1, dtype=np.uint32)
+    np.cumsum([len(p) for p in pieces], out=offsets[1:])
+    blob = np.frombuffer(b"".join(pieces) or b"\0", dtype=np.uint8).copy()
+    return blob, offsets
+
+
+def token_pieces(tokens):
+    """The pieces of a .xalm vocabulary (XalmFile.tokens()), as the host Tokenizer::pieces: the
+    vocab string, and the single byte for the byte-fallback tokens, the 256 ids from <0x00> on (a
+    vocabulary whose run <0x00> .. <0xFF> is not whole keeps the names)."""
+    out = list(tokens)
+    if b"<0x00>" in out:
+        b0 = out.index(b"<0x00>")
+        if out[b0:b0 + 256] == [b"<0x%02X>" % i for i in range(256)]:
+            out[b0:b0 + 256] = [bytes([i]) for i in range(256)]
+    return out
+
+
 class XhError(RuntimeError):
     pass
 
@@ -113,6 +161,15 @@ _SIGNATURES = {
                                   _P, ctypes.POINTER(_I)]),
     "xh_op_sample_ext": (_I, [_P, _I, ctypes.POINTER(XhSampling), ctypes.POINTER(XhLogitCtl), _P, _I, ctypes.c_uint64,
                               _I, _P, _P, _P, _P]),
+    "xh_constraint_set_vocab": (_I, [_P, _P, _P]),
+    "xh_constraint_set": (_I, [_P, ctypes.POINTER(XhByteDfa)]),
+    "xh_decode_sample_dfa": (_I, [_P, _I, _I, ctypes.POINTER(XhSampling), ctypes.POINTER(XhLogitCtl), _P, _I,
+                                  ctypes.c_uint32, _I, _I, _P, _P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_I)]),
+    "xh_op_sample_dfa": (_I, [_P, _I, ctypes.POINTER(XhSampling), ctypes.POINTER(XhLogitCtl), _P, _I,
+                              ctypes.POINTER(XhByteDfa), _P, _P, ctypes.c_uint32, _I, _I, ctypes.c_uint64, _I, _P, _P, _P,
+                              _P, _P]),
+    "xh_constraint_mask": (_I, [ctypes.POINTER(XhByteDfa), _P, _P, _I, ctypes.c_uint32, _I, _I, _P, _P]),
+    "xh_regex_compile": (_I, [ctypes.c_char_p, _P, _P, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "xh_adjust_logits": (_I, [_P, _I, ctypes.POINTER(XhLogitCtl), _P, _I, _P]),
     "xh_op_sample": (_I, [_P, _I, ctypes.POINTER(XhSampling), ctypes.c_uint64, _I, _P, _P]),
     "xh_philox4x32": (_I, [ctypes.c_uint64, ctypes.c_uint64, _P]),
@@ -234,6 +291,54 @@ def adjust_logits(logits: np.ndarray, window=(), **controls) -> np.ndarray:
     check(lib().xh_adjust_logits(ptr(lg), lg.size, ctypes.byref(c), ptr(win) if win.size else None, win.size, ptr(out)))
     del keep
     return out
+
+
+def regex_compile(pattern) -> ByteDfa:
+    """xh_regex_compile: the trimmed byte DFA of a full-match regular expression (str: its UTF-8
+    bytes).  No device needed."""
+    pat = pattern.encode() if isinstance(pattern, str) else bytes(pattern)
+    n, start = ctypes.c_int(0), ctypes.c_int(0)
+    rc = lib().xh_regex_compile(pat, None, None, 0, ctypes.byref(n), ctypes.byref(start))
+    if rc != 4:  # XH_E_NOMEM carries the size
+        raise XhError(f"xh error {rc}: cannot compile {pat!r}")
+    nxt = np.empty((n.value, 256), dtype=np.uint16)
+    acc = np.empty(n.value, dtype=np.uint8)
+    check(lib().xh_regex_compile(pat, ptr(nxt), ptr(acc), n.value, ctypes.byref(n), ctypes.byref(start)))
+    return ByteDfa(nxt, acc, start.value)
+
+
+def constraint_mask(dfa: ByteDfa, blob: np.ndarray, offsets: np.ndarray, state: int, stop=(-1, -1)):
+    """xh_constraint_mask: (allowed uint8 [V], successor states uint16 [V]) in `state`.  No device
+    needed."""
+    V = offsets.size - 1
+    allowed = np.empty(V, dtype=np.uint8)
+    nxt = np.empty(V, dtype=np.uint16)
+    d = dfa.abi()
+    check(lib().xh_constraint_mask(ctypes.byref(d), ptr(blob), ptr(offsets), V, int(state), int(stop[0]), int(stop[1]),
+                                   ptr(allowed), ptr(nxt)))
+    return allowed, nxt
+
+
+def op_sample_dfa(logits: np.ndarray, temperature: float, top_k: int, top_p: float, seed: int, pos0: int, n_draws: int,
+                  dfa: ByteDfa, blob: np.ndarray, offsets: np.ndarray, state: int, stop=(-1, -1), window=(), **controls):
+    """The constrained draw on a logits vector (xh_op_sample_dfa; controls as `logit_ctl`): every
+    draw from `state`; returns (tokens, n_kept, masked logits l'' [V], successor states [n_draws],
+    log-probabilities [n_draws])."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    s = XhSampling(temperature, top_k, top_p, seed)
+    c, keep = logit_ctl(**controls)
+    win = np.ascontiguousarray(np.asarray(window, dtype=np.int32))
+    toks = np.empty(max(n_draws, 1), dtype=np.int32)
+    kept = np.empty(max(n_draws, 1), dtype=np.int32)
+    masked = np.empty(lg.size, dtype=np.float32)
+    states = np.empty(max(n_draws, 1), dtype=np.uint32)
+    lp = np.empty(max(n_draws, 1), dtype=np.float32)
+    d = dfa.abi()
+    check(lib().xh_op_sample_dfa(ptr(lg), lg.size, ctypes.byref(s), ctypes.byref(c), ptr(win) if win.size else None,
+                                 win.size, ctypes.byref(d), ptr(blob), ptr(offsets), int(state), int(stop[0]),
+                                 int(stop[1]), pos0, n_draws, ptr(toks), ptr(kept), ptr(masked), ptr(states), ptr(lp)))
+    del keep
+    return toks[:n_draws], kept[:n_draws], masked, states[:n_draws], lp[:n_draws]
 
 
 def philox4x32(seed: int, pos: int) -> np.ndarray:

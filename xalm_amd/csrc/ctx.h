@@ -67,6 +67,19 @@ struct ExtCtl {
     int count;
 };
 
+// xh_decode_sample_dfa's device block (sample_dfa.h): the tables of xh_byte_dfa and the pieces
+// (device pointers: a new DFA changes the block, not the graph), the current state, which the step
+// head advances, and the call's end tokens
+struct DfaCtl {
+    const uint16_t* next;
+    const uint8_t* accept;
+    const uint8_t* bytes;
+    const uint32_t* offsets;
+    int n_states;
+    uint32_t state;
+    int stop_a, stop_b;
+};
+
 constexpr int ARGMAX_CANDS = 1024;  // the lm_head workgroups' argmax keys (argmax_embed_kernel's block size)
 
 // The batched prefill's device buffers (prefill.hip), in growth groups.  T = cap[PASS] tokens, the
@@ -145,6 +158,17 @@ struct xh_ctx {
     float* ext_bval = nullptr;
     float* ext_adj = nullptr;
     float* dec_logprobs = nullptr;
+    // xh_decode_sample_dfa (sample_dfa.h): parameter block, the pieces (xh_constraint_set_vocab), the
+    // DFA (xh_constraint_set; dfa_n_states 0 = none), per-step successor states [dec_cap]
+    xalm::DfaCtl* dfa = nullptr;
+    uint8_t* dfa_bytes = nullptr;
+    uint32_t* dfa_offsets = nullptr;
+    bool dfa_vocab_set = false;
+    uint16_t* dfa_next = nullptr;
+    uint8_t* dfa_accept = nullptr;
+    int dfa_n_states = 0;
+    bool dfa_block_valid = false;  // the block's pointers are the current tables' (a decode call wrote it since)
+    uint32_t* dec_states = nullptr;
     int dec_cap = 0;
     int nsplit = 1, t_max = 16;
     // fused attention + Wo launch (attn_wo.h): per-layer hand-off words [n_layers][4]
@@ -173,7 +197,7 @@ struct xh_ctx {
     int t_max_aw = 16;
     bool use_graphs = true;
     hipGraphExec_t g_logits = nullptr, g_hydrate = nullptr, g_decode = nullptr, g_sample = nullptr,
-                   g_sample_ext = nullptr;
+                   g_sample_ext = nullptr, g_sample_dfa = nullptr;
     int max_gemv_waves = 4096;  // 16 waves per CU
     // the qkv launch: its whole matrix is one round at 16 waves per CU (every wave one group,
     // requested at once); at 8 waves per CU each wave streams two groups back to back
@@ -292,6 +316,7 @@ int host_step_params(xh_ctx* ctx, int token, int pos);
 int run_step(xh_ctx* ctx, bool with_logits);
 void time_sample_head(xh_ctx* ctx);  // one sample_embed_kernel launch on ctx->stream (xh_time_kernel 6)
 void time_sample_ext_head(xh_ctx* ctx);  // one sample_ext_embed_kernel launch (xh_time_kernel 7)
+void time_sample_dfa_head(xh_ctx* ctx);  // one sample_dfa_embed_kernel launch (xh_time_kernel 8)
 
 // prefill.hip: the pass buffers, and gemm16.h for xh_op_prompt_gemm (device pointers).  mm_op_ks:
 // *ks = 0 picks the K slicing; 0, 1 when K is no multiple of MM_KMULT, 2 when *ks slices do not divide it

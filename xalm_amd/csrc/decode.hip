@@ -7,9 +7,11 @@
 #include <cmath>
 #include <vector>
 
+#include "constraint.h"
 #include "ctx.h"
 #include "dt_launch.h"
 #include "sample.h"
+#include "sample_dfa.h"
 #include "sample_ext.h"
 
 using namespace xalm;
@@ -164,6 +166,86 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_ext_op_kernel(const float*
     }
 }
 
+// Constrained sampled decode step head (xh_decode_sample_dfa): sample_ext_embed_kernel's work with
+// the byte-DFA mask written over l' before anything is computed from it (DfaMask, sample_dfa.h), the
+// draw of dfa_draw, and the successor state stored in the block and in the per-step log.
+__global__ __launch_bounds__(SMP_THREADS) void sample_dfa_embed_kernel(
+    const float* logits, int vocab, ExtCtl* ctl, DfaCtl* dfa, int* ring, const int* btok, const float* bval, float* adj,
+    StepParams* sp, int* tokens, float* logprobs, uint32_t* states, int cap, const void* emb, int dtype, int dim,
+    float* x, const float* rope_freq, float* rope_cs, int half) {
+    __shared__ SampleShared sh;
+    __shared__ ExtShared es;
+    __shared__ DfaShared ds;
+    __shared__ int pos_s;
+    const int tid = threadIdx.x;
+    const ExtCtl c = *ctl;
+    const DfaCtl d = *dfa;
+    const ExtPrep pr = ext_prepare(es, logits, adj, vocab, c, ring, btok, bval, DfaMask{&ds, d});
+    const DfaDraw dr = dfa_draw(sh, ds, adj, vocab, c, pr, d, (uint32_t)sp->pos_next);
+    const int tok = dr.token;
+    __syncthreads();  // every thread has read pos_next, the blocks and the ring
+    if (tid == 0) {
+        if (sp->step < cap) {
+            tokens[sp->step] = tok;
+            logprobs[sp->step] = (logits[tok] - pr.M) - pr.lse;
+            states[sp->step] = dr.state;
+        }
+        dfa->state = dr.state;
+        ring[c.count & (EXT_RING - 1)] = tok;
+        ctl->count = c.count + 1;
+        sp->step += 1;
+        sp->token = tok;
+        step_positions(sp, sp->pos_next);
+        sp->pos_next += 1;
+        pos_s = sp->pos;
+    }
+    __syncthreads();
+    rope_table(rope_cs, rope_freq, half, pos_s, tid);
+    for (int i = tid; i < dim; i += SMP_THREADS) x[i] = dec_row(dtype, emb, (size_t)tok, dim, i);
+}
+
+// xh_op_sample_dfa: one workgroup prepares the masked l', the scalars of the draw, the allowed count
+// and the constrained greedy key ...
+struct DfaPrep {
+    ExtPrep ext;
+    unsigned long long best;
+    unsigned n_allowed;
+};
+__global__ __launch_bounds__(SMP_THREADS) void sample_dfa_prep_kernel(const float* logits, int vocab, const ExtCtl* ctl,
+                                                                      const DfaCtl* dfa, const int* ring, const int* btok,
+                                                                      const float* bval, float* adj, DfaPrep* prep) {
+    __shared__ ExtShared es;
+    __shared__ DfaShared ds;
+    const DfaCtl d = *dfa;
+    const ExtPrep pr = ext_prepare(es, logits, adj, vocab, *ctl, ring, btok, bval, DfaMask{&ds, d});
+    if (threadIdx.x == 0) {
+        prep->ext = pr;
+        prep->best = d.state == XH_DFA_DEAD ? 0ull : ds.best;
+        prep->n_allowed = d.state == XH_DFA_DEAD ? 0u : ds.n_allowed;
+    }
+}
+// ... and workgroup i draws at counter pos0 + i from it, every draw from the same state
+__global__ __launch_bounds__(SMP_THREADS) void sample_dfa_op_kernel(const float* logits, const float* adj, int vocab,
+                                                                    const ExtCtl* ctl, const DfaCtl* dfa,
+                                                                    const DfaPrep* prep, uint32_t pos0, int* tokens,
+                                                                    int* n_kept_out, uint32_t* states, float* logprobs) {
+    __shared__ SampleShared sh;
+    __shared__ DfaShared ds;
+    const DfaPrep pp = *prep;
+    if (threadIdx.x == 0) {
+        ds.best = pp.best;
+        ds.n_allowed = pp.n_allowed;
+    }
+    __syncthreads();
+    const DfaDraw dr = dfa_draw(sh, ds, adj, vocab, *ctl, pp.ext, *dfa, pos0 + blockIdx.x);
+    if (threadIdx.x == 0) {
+        tokens[blockIdx.x] = dr.token;
+        n_kept_out[blockIdx.x] = dr.n_kept;
+        states[blockIdx.x] = dr.state;
+        logprobs[blockIdx.x] = (logits[dr.token] - pp.ext.M) - pp.ext.lse;
+    }
+}
+
 // Candidates from logits already on the device (the first greedy step after logits that no
 // EPI_LOGITS launch produced): cand[0] = best key, the rest 0.
 __global__ __launch_bounds__(1024) void logits_cand_kernel(const float* logits, int vocab, unsigned long long* cand) {
@@ -258,13 +340,18 @@ int launch_attn_wo(xh_ctx* ctx, int l, hipStream_t s) {
 // head: HEAD_GREEDY = the token is the argmax of the previous step's logits (argmax_embed_kernel),
 // HEAD_SAMPLE = drawn from them under ctx->samp (sample_embed_kernel), HEAD_SAMPLE_EXT = drawn from
 // their adjusted copy under ctx->ext (sample_ext_embed_kernel)
-enum StepHead { HEAD_GIVEN = 0, HEAD_GREEDY = 1, HEAD_SAMPLE = 2, HEAD_SAMPLE_EXT = 3 };
+// HEAD_SAMPLE_DFA = drawn from their adjusted and masked copy under ctx->ext and ctx->dfa
+// (sample_dfa_embed_kernel)
+enum StepHead { HEAD_GIVEN = 0, HEAD_GREEDY = 1, HEAD_SAMPLE = 2, HEAD_SAMPLE_EXT = 3, HEAD_SAMPLE_DFA = 4 };
 void launch_sample_head(xh_ctx* ctx, hipStream_t s);
 void launch_sample_ext_head(xh_ctx* ctx, hipStream_t s);
+void launch_sample_dfa_head(xh_ctx* ctx, hipStream_t s);
 int enqueue_step(xh_ctx* ctx, hipStream_t s, bool with_logits, int head = HEAD_GIVEN) {
     const xh_config& c = ctx->c;
     const int mb = ctx->max_gemv_waves;
-    if (head == HEAD_SAMPLE_EXT)
+    if (head == HEAD_SAMPLE_DFA)
+        launch_sample_dfa_head(ctx, s);
+    else if (head == HEAD_SAMPLE_EXT)
         launch_sample_ext_head(ctx, s);
     else if (head == HEAD_SAMPLE)
         launch_sample_head(ctx, s);
@@ -320,10 +407,21 @@ void launch_sample_ext_head(xh_ctx* ctx, hipStream_t s) {
                        c.dim, ctx->x, (const float*)ctx->rope_freq, ctx->rope_cs, c.head_dim / 2);
 }
 
+void launch_sample_dfa_head(xh_ctx* ctx, hipStream_t s) {
+    const xh_config& c = ctx->c;
+    hipLaunchKernelGGL(sample_dfa_embed_kernel, dim3(1), dim3(SMP_THREADS), 0, s, (const float*)ctx->logits, c.vocab_size,
+                       ctx->ext, ctx->dfa, ctx->ext_ring, (const int*)ctx->ext_btok, (const float*)ctx->ext_bval,
+                       ctx->ext_adj, ctx->sp, ctx->dec_tokens, ctx->dec_logprobs, ctx->dec_states, ctx->dec_cap,
+                       (const void*)ctx->embed, ctx->embed_dt, c.dim, ctx->x, (const float*)ctx->rope_freq, ctx->rope_cs,
+                       c.head_dim / 2);
+}
+
+// kind: 0 a step with logits, 1 without (hydrate), 2 .. 5 a decode step under the greedy, sampled,
+// extended and constrained head
 int capture(xh_ctx* ctx, int kind, hipGraphExec_t* out) {
     hipGraph_t g = nullptr;
     HIP_TRY(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-    const int rc = enqueue_step(ctx, ctx->stream, kind != 1, kind == 2 ? HEAD_GREEDY : kind == 3 ? HEAD_SAMPLE : kind == 4 ? HEAD_SAMPLE_EXT : HEAD_GIVEN);
+    const int rc = enqueue_step(ctx, ctx->stream, kind != 1, kind == 2 ? HEAD_GREEDY : kind == 3 ? HEAD_SAMPLE : kind == 4 ? HEAD_SAMPLE_EXT : kind == 5 ? HEAD_SAMPLE_DFA : HEAD_GIVEN);
     hipError_t e = hipStreamEndCapture(ctx->stream, &g);
     if (rc) { if (g) hipGraphDestroy(g); return rc; }
     if (e != hipSuccess) return set_err(ctx, XH_E_HIP, "graph capture failed: %s", hipGetErrorString(e));
@@ -434,6 +532,7 @@ int xalm::check_ready(xh_ctx* ctx) {
 
 void xalm::time_sample_head(xh_ctx* ctx) { launch_sample_head(ctx, ctx->stream); }
 void xalm::time_sample_ext_head(xh_ctx* ctx) { launch_sample_ext_head(ctx, ctx->stream); }
+void xalm::time_sample_dfa_head(xh_ctx* ctx) { launch_sample_dfa_head(ctx, ctx->stream); }
 
 void xalm::drop_graphs(xh_ctx* ctx) {
     if (ctx->g_logits) hipGraphExecDestroy(ctx->g_logits);
@@ -441,7 +540,8 @@ void xalm::drop_graphs(xh_ctx* ctx) {
     if (ctx->g_decode) hipGraphExecDestroy(ctx->g_decode);
     if (ctx->g_sample) hipGraphExecDestroy(ctx->g_sample);
     if (ctx->g_sample_ext) hipGraphExecDestroy(ctx->g_sample_ext);
-    ctx->g_logits = ctx->g_hydrate = ctx->g_decode = ctx->g_sample = ctx->g_sample_ext = nullptr;
+    if (ctx->g_sample_dfa) hipGraphExecDestroy(ctx->g_sample_dfa);
+    ctx->g_logits = ctx->g_hydrate = ctx->g_decode = ctx->g_sample = ctx->g_sample_ext = ctx->g_sample_dfa = nullptr;
 }
 
 
@@ -807,6 +907,203 @@ int xh_op_sample_ext(const float* logits, int vocab, const xh_sampling* sampling
     if (e == hipSuccess && adjusted_out) e = hipMemcpy(adjusted_out, d_adj.p, (size_t)vocab * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && logprob_out) e = hipMemcpy(logprob_out, d_lp.p, (size_t)n_draws * sizeof(float), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return set_err(nullptr, XH_E_HIP, "sample_ext op failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+int xh_constraint_set_vocab(xh_ctx* ctx, const uint8_t* bytes, const uint32_t* offsets) {
+    if (!ctx) return XH_E_INVALID;
+    const int V = ctx->c.vocab_size;
+    if (const char* why = pieces_error(bytes, offsets, V)) return set_err(ctx, XH_E_INVALID, "%s", why);
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    // the new tables are whole on the device before the old ones go: a failure keeps the old constraint
+    uint8_t* d_bytes = nullptr;
+    uint32_t* d_offsets = nullptr;
+    int rc = dmalloc(ctx, &d_bytes, (size_t)offsets[V]);
+    if (!rc) rc = dmalloc(ctx, &d_offsets, (size_t)V + 1);
+    hipError_t e = hipSuccess;
+    if (!rc && offsets[V]) e = copy_sync(ctx, d_bytes, bytes, offsets[V], hipMemcpyHostToDevice);
+    if (!rc && e == hipSuccess) e = copy_sync(ctx, d_offsets, offsets, ((size_t)V + 1) * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (!rc && e != hipSuccess) rc = set_err(ctx, XH_E_HIP, "piece upload failed: %s", hipGetErrorString(e));
+    if (rc) {
+        hipFree(d_bytes);
+        hipFree(d_offsets);
+        return rc;
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // no step reads the old table any more
+    hipFree(ctx->dfa_bytes);
+    hipFree(ctx->dfa_offsets);
+    ctx->dfa_bytes = d_bytes;
+    ctx->dfa_offsets = d_offsets;
+    ctx->dfa_vocab_set = true;
+    ctx->dfa_block_valid = false;  // the device block still points at the freed tables
+    return 0;
+}
+
+int xh_constraint_set(xh_ctx* ctx, const xh_byte_dfa* dfa) {
+    if (!ctx) return XH_E_INVALID;
+    if (dfa)
+        if (const char* why = dfa_error(dfa)) return set_err(ctx, XH_E_INVALID, "%s", why);
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    uint16_t* d_next = nullptr;
+    uint8_t* d_accept = nullptr;
+    if (dfa) {
+        const size_t n = (size_t)dfa->n_states;
+        int rc = dmalloc(ctx, &d_next, n * 256);
+        if (!rc) rc = dmalloc(ctx, &d_accept, n);
+        hipError_t e = hipSuccess;
+        if (!rc) e = copy_sync(ctx, d_next, dfa->next, n * 256 * sizeof(uint16_t), hipMemcpyHostToDevice);
+        if (!rc && e == hipSuccess) e = copy_sync(ctx, d_accept, dfa->accept, n, hipMemcpyHostToDevice);
+        if (!rc && e != hipSuccess) rc = set_err(ctx, XH_E_HIP, "dfa upload failed: %s", hipGetErrorString(e));
+        if (rc) {
+            hipFree(d_next);
+            hipFree(d_accept);
+            return rc;
+        }
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    hipFree(ctx->dfa_next);
+    hipFree(ctx->dfa_accept);
+    ctx->dfa_next = d_next;
+    ctx->dfa_accept = d_accept;
+    ctx->dfa_n_states = dfa ? dfa->n_states : 0;
+    ctx->dfa_block_valid = false;
+    return 0;
+}
+
+int xh_decode_sample_dfa(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* sampling, const xh_logit_ctl* ctl,
+                         const int* history, int n_history, uint32_t state_in, int stop_a, int stop_b, int* tokens_out,
+                         float* logprobs_out, uint32_t* state_out, int* n_done) {
+    if (n_done) *n_done = 0;
+    if (!sampling_ok(sampling)) return set_err(ctx, XH_E_INVALID, "bad sampling parameters");
+    if (const char* why = ctl_error(ctl, history, n_history, ctx ? ctx->c.vocab_size : 0))
+        return set_err(ctx, XH_E_INVALID, "%s", why);
+    if (!ctx || n_steps < 0) return XH_E_INVALID;
+    if (pos < 0) return set_err(ctx, XH_E_INVALID, "negative pos");
+    if (ctx->c.vocab_size > SMP_MAX_VOCAB) return set_err(ctx, XH_E_INVALID, "vocab_size > %d", SMP_MAX_VOCAB);
+    if (n_steps > ctx->dec_cap) return set_err(ctx, XH_E_INVALID, "n_steps > %d", ctx->dec_cap);
+    if (!ctx->dfa_vocab_set || !ctx->dfa_n_states)
+        return set_err(ctx, XH_E_INVALID, "constrained decode before xh_constraint_set_vocab and xh_constraint_set");
+    if (state_in != XH_DFA_DEAD && state_in >= (uint32_t)ctx->dfa_n_states)
+        return set_err(ctx, XH_E_INVALID, "state_in %u out of range", state_in);
+    // an end token is emitted in the stuck state, so it has to be a token
+    if (stop_a >= ctx->c.vocab_size || stop_b >= ctx->c.vocab_size)
+        return set_err(ctx, XH_E_INVALID, "stop token out of range");
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    int rc = check_ready(ctx);
+    if (rc) return rc;
+    const xh_logit_ctl& c = ctl ? *ctl : CTL_OFF;
+    StepParams* h = ctx->sp_host;
+    h->step = 0;
+    h->pos_next = pos;
+    h->max_seq_len = ctx->c.max_seq_len;
+    HIP_TRY(ctx, hipMemcpyAsync(&ctx->sp->step, &h->step, 3 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    const int n_hist = std::min(n_history, XH_CTL_MAX_WINDOW);
+    const ExtCtl blk = ext_block(*sampling, c, n_hist);
+    const DfaCtl dblk = {ctx->dfa_next, ctx->dfa_accept, ctx->dfa_bytes, ctx->dfa_offsets, ctx->dfa_n_states, state_in,
+                         stop_a < 0 ? -1 : stop_a, stop_b < 0 ? -1 : stop_b};
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->ext, &blk, sizeof blk, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->dfa, &dblk, sizeof dblk, hipMemcpyHostToDevice, ctx->stream));
+    ctx->dfa_block_valid = true;
+    if (c.n_bias > 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_btok, c.bias_token, (size_t)c.n_bias * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_bval, c.bias_value, (size_t)c.n_bias * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (n_hist > 0)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_ring, history + (n_history - n_hist), (size_t)n_hist * sizeof(int),
+                                    hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->use_graphs && n_steps > 0 && !ctx->g_sample_dfa) {
+        rc = capture(ctx, 5, &ctx->g_sample_dfa);
+        if (rc) return rc;
+    }
+    const bool stops = stop_a >= 0 || stop_b >= 0;
+    int done = 0;
+    for (int i = 0; i < n_steps; i++) {
+        if (ctx->use_graphs) {
+            HIP_TRY(ctx, hipGraphLaunch(ctx->g_sample_dfa, ctx->stream));
+        } else {
+            rc = eager_step(ctx, true, HEAD_SAMPLE_DFA);
+            if (rc) return rc;
+        }
+        ctx->cand_valid = true;
+        done = i + 1;
+        if (stops) {
+            int tok = -1;
+            HIP_TRY(ctx, hipMemcpyAsync(&tok, ctx->dec_tokens + i, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (tok == stop_a || tok == stop_b) break;
+        }
+    }
+    if (tokens_out && done)
+        HIP_TRY(ctx, hipMemcpyAsync(tokens_out, ctx->dec_tokens, (size_t)done * sizeof(int), hipMemcpyDeviceToHost,
+                                    ctx->stream));
+    if (logprobs_out && done)
+        HIP_TRY(ctx, hipMemcpyAsync(logprobs_out, ctx->dec_logprobs, (size_t)done * sizeof(float), hipMemcpyDeviceToHost,
+                                    ctx->stream));
+    uint32_t st = state_in;
+    if (done)
+        HIP_TRY(ctx, hipMemcpyAsync(&st, ctx->dec_states + (done - 1), sizeof st, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (state_out) *state_out = st;
+    if (n_done) *n_done = done;
+    return check_aw(ctx);
+}
+
+int xh_op_sample_dfa(const float* logits, int vocab, const xh_sampling* sampling, const xh_logit_ctl* ctl,
+                     const int* window, int n_window, const xh_byte_dfa* dfa, const uint8_t* bytes,
+                     const uint32_t* offsets, uint32_t state, int stop_a, int stop_b, uint64_t pos0, int n_draws,
+                     int* tokens_out, int* n_kept_out, float* masked_out, uint32_t* next_state_out, float* logprob_out) {
+    if (!sampling_ok(sampling)) return set_err(nullptr, XH_E_INVALID, "bad sampling parameters");
+    if (!logits || !tokens_out || !n_kept_out || !next_state_out || vocab <= 0 || vocab > SMP_MAX_VOCAB || n_draws <= 0 ||
+        n_draws > 65536)
+        return set_err(nullptr, XH_E_INVALID, "bad sample args");
+    if (const char* why = ctl_error(ctl, window, n_window, vocab)) return set_err(nullptr, XH_E_INVALID, "%s", why);
+    if (const char* why = dfa_error(dfa)) return set_err(nullptr, XH_E_INVALID, "%s", why);
+    if (const char* why = pieces_error(bytes, offsets, vocab)) return set_err(nullptr, XH_E_INVALID, "%s", why);
+    if (const char* why = dfa_state_error(dfa, state)) return set_err(nullptr, XH_E_INVALID, "%s", why);
+    if (stop_a >= vocab || stop_b >= vocab) return set_err(nullptr, XH_E_INVALID, "stop token out of range");
+    const xh_logit_ctl& c = ctl ? *ctl : CTL_OFF;
+    const int n_win = std::min(n_window, XH_CTL_MAX_WINDOW);
+    const ExtCtl blk = ext_block(*sampling, c, n_win);
+    struct Buf {
+        void* p = nullptr;
+        ~Buf() { if (p) hipFree(p); }
+        bool alloc(size_t bytes, const void* src, size_t src_bytes) {
+            if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return false;
+            return !src_bytes || hipMemcpy(p, src, src_bytes, hipMemcpyHostToDevice) == hipSuccess;
+        }
+    } d_logits, d_adj, d_blk, d_dfa, d_ring, d_btok, d_bval, d_prep, d_out, d_lp, d_next, d_acc, d_bytes, d_offs;
+    const size_t ns = (size_t)dfa->n_states;
+    if (!d_logits.alloc((size_t)vocab * 4, logits, (size_t)vocab * 4) || !d_adj.alloc((size_t)vocab * 4, nullptr, 0) ||
+        !d_blk.alloc(sizeof blk, &blk, sizeof blk) ||
+        !d_ring.alloc(XH_CTL_MAX_WINDOW * sizeof(int), n_win ? window + (n_window - n_win) : nullptr, (size_t)n_win * sizeof(int)) ||
+        !d_btok.alloc(XH_CTL_MAX_BIAS * sizeof(int), c.bias_token, (size_t)c.n_bias * sizeof(int)) ||
+        !d_bval.alloc(XH_CTL_MAX_BIAS * sizeof(float), c.bias_value, (size_t)c.n_bias * sizeof(float)) ||
+        !d_prep.alloc(sizeof(DfaPrep), nullptr, 0) || !d_out.alloc((size_t)3 * n_draws * sizeof(int), nullptr, 0) ||
+        !d_lp.alloc((size_t)n_draws * sizeof(float), nullptr, 0) ||
+        !d_next.alloc(ns * 512, dfa->next, ns * 512) || !d_acc.alloc(ns, dfa->accept, ns) ||
+        !d_bytes.alloc(offsets[vocab], bytes, offsets[vocab]) ||
+        !d_offs.alloc(((size_t)vocab + 1) * 4, offsets, ((size_t)vocab + 1) * 4))
+        return set_err(nullptr, XH_E_HIP, "hipMalloc / hipMemcpy failed");
+    const DfaCtl dblk = {(const uint16_t*)d_next.p, (const uint8_t*)d_acc.p, (const uint8_t*)d_bytes.p,
+                         (const uint32_t*)d_offs.p, dfa->n_states, state, stop_a < 0 ? -1 : stop_a, stop_b < 0 ? -1 : stop_b};
+    if (!d_dfa.alloc(sizeof dblk, &dblk, sizeof dblk)) return set_err(nullptr, XH_E_HIP, "hipMalloc / hipMemcpy failed");
+    hipLaunchKernelGGL(sample_dfa_prep_kernel, dim3(1), dim3(SMP_THREADS), 0, nullptr, (const float*)d_logits.p, vocab,
+                       (const ExtCtl*)d_blk.p, (const DfaCtl*)d_dfa.p, (const int*)d_ring.p, (const int*)d_btok.p,
+                       (const float*)d_bval.p, (float*)d_adj.p, (DfaPrep*)d_prep.p);
+    hipLaunchKernelGGL(sample_dfa_op_kernel, dim3(n_draws), dim3(SMP_THREADS), 0, nullptr, (const float*)d_logits.p,
+                       (const float*)d_adj.p, vocab, (const ExtCtl*)d_blk.p, (const DfaCtl*)d_dfa.p,
+                       (const DfaPrep*)d_prep.p, (uint32_t)pos0, (int*)d_out.p, (int*)d_out.p + n_draws,
+                       (uint32_t*)d_out.p + 2 * (size_t)n_draws, (float*)d_lp.p);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(tokens_out, d_out.p, (size_t)n_draws * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(n_kept_out, (int*)d_out.p + n_draws, (size_t)n_draws * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess)
+        e = hipMemcpy(next_state_out, (int*)d_out.p + 2 * (size_t)n_draws, (size_t)n_draws * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && masked_out) e = hipMemcpy(masked_out, d_adj.p, (size_t)vocab * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && logprob_out) e = hipMemcpy(logprob_out, d_lp.p, (size_t)n_draws * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return set_err(nullptr, XH_E_HIP, "sample_dfa op failed: %s", hipGetErrorString(e));
     return 0;
 }
 

@@ -150,10 +150,13 @@ int xh_op_prompt_gemm(float* y, const uint16_t* w, const uint16_t* xh, const uin
 // timing hooks for bench.py
 // ---------------------------------------------------------------------------------------
 int xh_time_kernel(xh_ctx* ctx, int which, int iters, float* avg_us) {
-    if (!ctx || !avg_us || iters <= 0 || which < 0 || which > 7) return XH_E_INVALID;
+    if (!ctx || !avg_us || iters <= 0 || which < 0 || which > 8) return XH_E_INVALID;
     HIP_TRY(ctx, hipSetDevice(ctx->dev));
     int rc = check_ready(ctx);
     if (rc) return rc;
+    // the constrained head reads its tables through the block xh_decode_sample_dfa writes
+    if (which == 8 && !(ctx->dfa_vocab_set && ctx->dfa_n_states && ctx->dfa_block_valid))
+        return set_err(ctx, XH_E_STATE, "xh_time_kernel 8: no xh_decode_sample_dfa call under the current constraint");
     const int mb = ctx->max_gemv_waves;
     // launches rotate over the layers, so a repeat never finds its weights in the 256 MB
     // Infinity Cache (a decode step streams every layer once)
@@ -169,6 +172,7 @@ int xh_time_kernel(xh_ctx* ctx, int which, int iters, float* avg_us) {
             case 4: return launch_gemv(GEMV_LOGITS, kdt(ctx->wcls_dt, ctx->wcls_x), cls_args(ctx), ctx->stream, mb);
             case 6: time_sample_head(ctx); return true;
             case 7: time_sample_ext_head(ctx); return true;
+            case 8: time_sample_dfa_head(ctx); return true;
             default:
                 return launch_attn(attn_args(ctx, l), ctx->c.head_dim, ctx->qpk, ctx->c.n_kv_heads, ctx->t_max,
                                    ctx->stream);

@@ -50,10 +50,18 @@ struct ExtPrep {
     int top_k;  // the effective top-k: min(top_k or V, n_minp), 0 = off
 };
 
+// ext_prepare's hook between steps 3 and 4: every thread calls mask(adj, V) once l' is whole, and
+// steps 4 and 5 see what it leaves (sample_dfa.h writes -inf over forbidden tokens there).  A thread
+// may write only the entries tid, tid + SMP_THREADS, ...: step 4 reads them back with no barrier.
+struct ExtNoMask {
+    __device__ __forceinline__ void operator()(float*, int) const {}
+};
+
 // Every thread of the 1024-thread workgroup calls it and gets the same result.  `count` tokens have
 // been appended to the ring so far (slot = index mod EXT_RING).
+template <class Mask = ExtNoMask>
 __device__ ExtPrep ext_prepare(ExtShared& es, const float* raw, float* adj, const int V, const ExtCtl c,
-                               const int* ring, const int* btok, const float* bval) {
+                               const int* ring, const int* btok, const float* bval, const Mask mask = Mask()) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int n_win = min(min(c.last_n, c.count), EXT_RING);
     const int n_bias = min(c.n_bias, XH_CTL_MAX_BIAS);
@@ -106,6 +114,7 @@ __device__ ExtPrep ext_prepare(ExtShared& es, const float* raw, float* adj, cons
             adj[t] = ctl_adjust(raw[t], 0, true, es.bval[tid], c.repeat_penalty, c.presence_penalty, c.frequency_penalty);
     }
     __syncthreads();  // adj holds l'; wkey is reused below
+    mask(adj, V);
 
     const bool minp = c.min_p > 0.f && c.samp.temperature > 0.f;
     float s = 0.f;

@@ -153,6 +153,8 @@ int xh_create(const xh_config* cfg, int device_ordinal, xh_ctx** out) {
     ctx->dec_cap = 1 << 16;
     CREATE_TRY(dmalloc(ctx, &ctx->dec_tokens, (size_t)ctx->dec_cap));
     CREATE_TRY(dmalloc(ctx, &ctx->dec_logprobs, (size_t)ctx->dec_cap));
+    CREATE_TRY(dmalloc(ctx, &ctx->dfa, (size_t)1));
+    CREATE_TRY(dmalloc(ctx, &ctx->dec_states, (size_t)ctx->dec_cap));
     if (hipHostMalloc((void**)&ctx->sp_host, sizeof(StepParams), hipHostMallocDefault) != hipSuccess) {
         g_create_error = "hipHostMalloc failed";
         xh_destroy(ctx);
@@ -197,6 +199,8 @@ void xh_destroy(xh_ctx* ctx) {
     hipFree(ctx->samp);
     hipFree(ctx->ext); hipFree(ctx->ext_ring); hipFree(ctx->ext_btok); hipFree(ctx->ext_bval); hipFree(ctx->ext_adj);
     hipFree(ctx->dec_logprobs);
+    hipFree(ctx->dfa); hipFree(ctx->dfa_bytes); hipFree(ctx->dfa_offsets); hipFree(ctx->dfa_next); hipFree(ctx->dfa_accept);
+    hipFree(ctx->dec_states);
     pf_free(ctx);
     hipFree(ctx->pf_wdq); hipFree(ctx->ppl_tgt); hipFree(ctx->ppl_prob); hipFree(ctx->rope_freq); hipFree(ctx->rope_cs);
     hipFree(ctx->aw_trace);

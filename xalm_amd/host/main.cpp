@@ -3,7 +3,7 @@
 //
 //   xalm <checkpoint.xalm> [-m completion|perplexity] [-d hip|cpu] [-i prompt | -f file]
 //                          [-T context] [-n steps] [-g 0|1] [-t temperature] [-k top_k] [-p top_p] [-s seed]
-//                          [-r repeat_penalty] [-w window] [-P presence] [-F frequency] [-M min_p]
+//                          [-r repeat_penalty] [-w window] [-P presence] [-F frequency] [-M min_p] [-R regex]
 //
 // -d selects the device as in the reference (src/main.cpp:465-477); this build ships the HIP
 // device.  -g 1 runs the greedy loop on the device (no host round trip per token); -g 0
@@ -12,6 +12,9 @@
 // with -g 0.  -r / -w / -P / -F / -M (xh_logit_ctl) penalise the tokens of the last -w ids of prompt +
 // output and cut by min-p, at any temperature: xh_decode_sample_ext with -g 1, the host Sampler over
 // xh_adjust_logits with -g 0.
+// -R constrains the output to a regular expression matched against the whole generated text
+// (xh_regex_compile, xh_byte_dfa): xh_decode_sample_dfa with -g 1, the host Sampler over
+// xh_constraint_mask with -g 0; eos / eot may end the text where the expression is matched.
 // Stats are wall clock (the reference divides by user+sys CPU time, src/profiler.h:124-129).
 #include <chrono>
 #include <cmath>
@@ -49,6 +52,7 @@ static void error_usage() {
     fprintf(stderr, "  -P <float> presence penalty, 0 = off (default 0)\n");
     fprintf(stderr, "  -F <float> frequency penalty, 0 = off (default 0)\n");
     fprintf(stderr, "  -M <float> min-p in [0, 1], 0 = off (default 0)\n");
+    fprintf(stderr, "  -R <regex> constrain the generated text to this regular expression (whole match, bytes)\n");
     fprintf(stderr, "  Choose one:\n");
     fprintf(stderr, "    -i <string> input prompt\n");
     fprintf(stderr, "    -f <filepath> input file with prompt\n");
@@ -65,7 +69,8 @@ static void print_ids(const std::vector<int>& ids) {
 
 // run_completion, src/main.cpp:44-128
 static void run_completion(const std::string& path, Device dev, const std::string& prompt, int context, int num_steps,
-                           bool device_loop, const xh_sampling& sampling, const xh_logit_ctl& ctl) {
+                           bool device_loop, const xh_sampling& sampling, const xh_logit_ctl& ctl,
+                           const std::string& regex) {
     const XalmFile file = XalmFile::load(path);
     const Model model = Model::from_xalm(file, context, dev);
     InferenceState state(model.config);
@@ -86,9 +91,18 @@ static void run_completion(const std::string& path, Device dev, const std::strin
     // any control on: the extended draw on both routes, prompt + output as the history
     const bool ext = ctl.repeat_penalty != 1.f || ctl.presence_penalty != 0.f || ctl.frequency_penalty != 0.f ||
                      ctl.min_p != 0.f;
+    Constraint constraint;
+    uint32_t dfa_state = 0;
+    if (!regex.empty()) {
+        constraint = Constraint::compile(regex, tokenizer);
+        dfa_state = (uint32_t)constraint.start;
+        if (device_loop) model.set_constraint(constraint);
+    }
     if (device_loop && num_steps > 0) {
         const std::vector<int> gen =
-            ext ? model.decode_sample_ext((int)encoding.size(), num_steps, sampling, ctl, encoding, tokenizer.eos_id,
+            !regex.empty() ? model.decode_sample_dfa((int)encoding.size(), num_steps, sampling, ctl, encoding, dfa_state,
+                                                     tokenizer.eos_id, tokenizer.eot_id)
+            : ext ? model.decode_sample_ext((int)encoding.size(), num_steps, sampling, ctl, encoding, tokenizer.eos_id,
                                           tokenizer.eot_id)
             : sampling.temperature > 0.f
                 ? model.decode_sample((int)encoding.size(), num_steps, sampling, tokenizer.eos_id, tokenizer.eot_id)
@@ -100,7 +114,9 @@ static void run_completion(const std::string& path, Device dev, const std::strin
         }
     } else {
         for (int i = 0; i < num_steps || num_steps == -1; i++) {
-            const int token_id = ext ? sampler.sample(state, sampling, ctl, encoding, (int)encoding.size())
+            const int token_id = !regex.empty() ? sampler.sample(state, sampling, ctl, encoding, (int)encoding.size(),
+                                                                 constraint, dfa_state, tokenizer.eos_id, tokenizer.eot_id)
+                                 : ext ? sampler.sample(state, sampling, ctl, encoding, (int)encoding.size())
                                  : sampling.temperature > 0.f ? sampler.sample(state, sampling, (int)encoding.size())
                                                               : sampler.sample_argmax(state);
             std::cout << tokenizer.decode_one(encoding.back(), token_id) << std::flush;
@@ -150,7 +166,7 @@ static void run_perplexity(const std::string& path, Device dev, const std::strin
 
 int main(int argc, char** argv) {
     std::string path, mode = "completion", prompt = "Q: What is the meaning of life? A:", prompt_path;
-    std::string device = "hip";
+    std::string device = "hip", regex;
     int context = 0, num_steps = 128, device_loop = 0;
     xh_sampling sampling{0.f, 0, 1.f, 0};
     xh_logit_ctl ctl{1.f, 0.f, 0.f, 64, 0.f, 0, nullptr, nullptr};
@@ -182,6 +198,7 @@ int main(int argc, char** argv) {
         else if (f == 'P') ctl.presence_penalty = std::stof(v);
         else if (f == 'F') ctl.frequency_penalty = std::stof(v);
         else if (f == 'M') ctl.min_p = std::stof(v);
+        else if (f == 'R') regex = v;
         else error_usage();
         i += 2;
     }
@@ -197,7 +214,7 @@ int main(int argc, char** argv) {
     }
     const Device dev = device == "cpu" ? Device::CPU : Device::HIP;
     try {
-        if (mode == "completion") run_completion(path, dev, prompt, context, num_steps, device_loop != 0, sampling, ctl);
+        if (mode == "completion") run_completion(path, dev, prompt, context, num_steps, device_loop != 0, sampling, ctl, regex);
         else run_perplexity(path, dev, prompt, context);
     } catch (const std::exception& e) {
         fprintf(stderr, "error: %s\n", e.what());

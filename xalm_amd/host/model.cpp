@@ -114,6 +114,42 @@ std::vector<int> Model::decode_sample_ext(const int pos, const int n_steps, cons
     return toks;
 }
 
+void Model::set_constraint(const Constraint& c) const {
+    check(xh_constraint_set_vocab(_ctx, c.bytes.data(), c.offsets.data()), _ctx, "xh_constraint_set_vocab");
+    const xh_byte_dfa d = c.dfa();
+    check(xh_constraint_set(_ctx, &d), _ctx, "xh_constraint_set");
+}
+
+std::vector<int> Model::decode_sample_dfa(const int pos, const int n_steps, const xh_sampling& sampling,
+                                          const xh_logit_ctl& ctl, const std::vector<int>& history,
+                                          const uint32_t state_in, const int stop_a, const int stop_b,
+                                          uint32_t* state_out, std::vector<float>* logprobs) const {
+    std::vector<int> toks((size_t)std::max(n_steps, 1));
+    std::vector<float> lp((size_t)std::max(n_steps, 1));
+    int done = 0;
+    check(xh_decode_sample_dfa(_ctx, pos, n_steps, &sampling, &ctl, history.data(), (int)history.size(), state_in, stop_a,
+                               stop_b, toks.data(), lp.data(), state_out, &done),
+          _ctx, "xh_decode_sample_dfa");
+    toks.resize((size_t)done);
+    lp.resize((size_t)done);
+    if (logprobs) *logprobs = lp;
+    return toks;
+}
+
+Constraint Constraint::compile(const std::string& regex, const Tokenizer& tokenizer) {
+    Constraint c;
+    int rc = xh_regex_compile(regex.c_str(), nullptr, nullptr, 0, &c.n_states, &c.start);
+    if (rc == XH_E_NOMEM) {  // the size query
+        c.next.resize((size_t)c.n_states * 256);
+        c.accept.resize((size_t)c.n_states);
+        rc = xh_regex_compile(regex.c_str(), c.next.data(), c.accept.data(), c.n_states, &c.n_states, &c.start);
+    }
+    if (rc != XH_OK)
+        throw std::invalid_argument("-R: not a supported regular expression, or one no text matches: " + regex);
+    tokenizer.pieces(c.bytes, c.offsets);
+    return c;
+}
+
 std::vector<float> Model::token_probs(const std::vector<int>& tokens, const int pos0) const {
     if (tokens.size() < 2) return {};
     std::vector<float> p(tokens.size() - 1);
@@ -181,6 +217,18 @@ std::string Tokenizer::decode_one(const int prev_token, const int token) const {
     if (byte_fallback_start >= 0 && token >= byte_fallback_start && token - byte_fallback_start < 256)
         return byte_pieces[token - byte_fallback_start];
     return piece;
+}
+
+void Tokenizer::pieces(std::vector<uint8_t>& bytes, std::vector<uint32_t>& offsets) const {
+    bytes.clear();
+    offsets.assign(1, 0u);
+    for (size_t t = 0; t < vocab.size(); t++) {
+        const bool fallback = byte_fallback_start >= 0 && (int)t >= byte_fallback_start && (int)t - byte_fallback_start < 256;
+        const std::string& piece = fallback ? byte_pieces[t - (size_t)byte_fallback_start] : vocab[t];
+        bytes.insert(bytes.end(), piece.begin(), piece.end());
+        offsets.push_back((uint32_t)bytes.size());
+    }
+    if (bytes.empty()) bytes.push_back(0);  // data() stays non-null
 }
 
 // greedy longest match over the vocab trie with byte fallback (src/tokenizer.cpp:82-119)
@@ -324,6 +372,43 @@ int Sampler::sample(const InferenceState& s, const xh_sampling& sampling, const 
     if (xh_adjust_logits(s.logits(), vocab_size, &ctl, history.data() + (history.size() - n_win), (int)n_win, adj.data()))
         throw std::invalid_argument(std::string("sample: ") + xh_last_error(nullptr));
     return sample_logits(adj.data(), vocab_size, sampling, (uint64_t)pos, nullptr, ctl.min_p);
+}
+
+int Sampler::sample(const InferenceState& s, const xh_sampling& sampling, const xh_logit_ctl& ctl,
+                    const std::vector<int>& history, const int pos, const Constraint& constraint, uint32_t& state,
+                    const int stop_a, const int stop_b) const {
+    const int stuck = stop_a >= 0 ? stop_a : stop_b >= 0 ? stop_b : 0;
+    if (state == XH_DFA_DEAD) return stuck;
+    std::vector<float> adj((size_t)vocab_size);
+    const size_t n_win = std::min(history.size(), (size_t)XH_CTL_MAX_WINDOW);
+    if (xh_adjust_logits(s.logits(), vocab_size, &ctl, history.data() + (history.size() - n_win), (int)n_win, adj.data()))
+        throw std::invalid_argument(std::string("sample: ") + xh_last_error(nullptr));
+    std::vector<uint8_t> allowed((size_t)vocab_size);
+    std::vector<uint16_t> succ((size_t)vocab_size);
+    const xh_byte_dfa d = constraint.dfa();
+    if (xh_constraint_mask(&d, constraint.bytes.data(), constraint.offsets.data(), vocab_size, state, stop_a, stop_b,
+                           allowed.data(), succ.data()))
+        throw std::invalid_argument("sample: bad constraint or state");
+    // logit descending by its f32 bits, then index ascending, among the allowed tokens
+    const auto key = [&](const int i) {
+        uint32_t u;
+        memcpy(&u, &adj[(size_t)i], 4);
+        return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    };
+    int first = -1;
+    for (int i = 0; i < vocab_size; ++i) {
+        if (!allowed[(size_t)i]) adj[(size_t)i] = -std::numeric_limits<float>::infinity();
+        else if (first < 0 || key(i) > key(first)) first = i;
+    }
+    if (first < 0) {  // stuck
+        state = XH_DFA_DEAD;
+        return stuck;
+    }
+    const int token = sampling.temperature == 0.f
+                          ? first
+                          : sample_logits(adj.data(), vocab_size, sampling, (uint64_t)pos, nullptr, ctl.min_p);
+    state = succ[(size_t)token];
+    return token;
 }
 
 }  // namespace xalm

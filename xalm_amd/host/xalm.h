@@ -82,6 +82,21 @@ private:
     std::vector<float> _logits;
 };
 
+struct Tokenizer;
+
+// A regex constraint for decoding (xh_byte_dfa, include/xalm_hip.h): the trimmed byte DFA of
+// xh_regex_compile and the tokenizer's piece table, on the host
+struct Constraint {
+    std::vector<uint16_t> next;     // [n_states][256]
+    std::vector<uint8_t> accept;    // [n_states]
+    int n_states = 0, start = 0;
+    std::vector<uint8_t> bytes;     // the pieces, back to back
+    std::vector<uint32_t> offsets;  // [vocab + 1]
+    // throws std::invalid_argument for a pattern xh_regex_compile refuses
+    static Constraint compile(const std::string& regex, const Tokenizer& tokenizer);
+    xh_byte_dfa dfa() const { return {n_states, start, next.data(), accept.data()}; }
+};
+
 class Model {
 public:
     static Model from_xalm(const XalmFile& xalm, int context = 0, Device device = Device::HIP, int ordinal = 0);
@@ -107,6 +122,14 @@ public:
     // one log-probability per token
     std::vector<int> decode_sample_ext(int pos, int n_steps, const xh_sampling& sampling, const xh_logit_ctl& ctl,
                                        const std::vector<int>& history, int stop_a = -1, int stop_b = -1,
+                                       std::vector<float>* logprobs = nullptr) const;
+    // upload a constraint's pieces and DFA (xh_constraint_set_vocab, xh_constraint_set)
+    void set_constraint(const Constraint& c) const;
+    // decode_sample_ext under the uploaded constraint (xh_decode_sample_dfa): state_in = the DFA's
+    // start or an earlier call's *state_out
+    std::vector<int> decode_sample_dfa(int pos, int n_steps, const xh_sampling& sampling, const xh_logit_ctl& ctl,
+                                       const std::vector<int>& history, uint32_t state_in, int stop_a = -1,
+                                       int stop_b = -1, uint32_t* state_out = nullptr,
                                        std::vector<float>* logprobs = nullptr) const;
     void fetch_logits(InferenceState& s) const;
     // run_perplexity's loop on the device (xh_perplexity): element i = Sampler::sample_prob of
@@ -135,6 +158,9 @@ struct Tokenizer {
     explicit Tokenizer(const XalmFile& data);
     std::vector<int> encode(const std::string& text, bool encode_bos) const;
     std::string decode_one(int prev_token, int token) const;
+    // the piece table of xh_constraint_set_vocab: the vocab string of every token, the single byte
+    // for a byte-fallback token; decode_one's strip of the space after BOS is not applied
+    void pieces(std::vector<uint8_t>& bytes, std::vector<uint32_t>& offsets) const;
 };
 
 struct Sampler {
@@ -150,6 +176,12 @@ struct Sampler {
     // window `history` gives, with min-p; temperature 0 = sample_argmax of the adjusted logits
     int sample(const InferenceState& s, const xh_sampling& sampling, const xh_logit_ctl& ctl,
                const std::vector<int>& history, int pos) const;
+    // the same under a constraint (the definition of xh_byte_dfa, through xh_constraint_mask): the
+    // draw from the masked logits, temperature 0 = the first allowed token of the sampler's order;
+    // `state` is the DFA state before the token and is advanced by it (XH_DFA_DEAD once stuck)
+    int sample(const InferenceState& s, const xh_sampling& sampling, const xh_logit_ctl& ctl,
+               const std::vector<int>& history, int pos, const Constraint& constraint, uint32_t& state, int stop_a,
+               int stop_b) const;
 };
 // the same on a bare logits vector; *n_kept (may be null) = size of the kept set
 // min_p > 0 (xh_logit_ctl): the top-k stage keeps at most the tokens of weight >= min_p

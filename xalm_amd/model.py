@@ -126,6 +126,44 @@ class Model:
         out = toks[: done.value].tolist()
         return (out, lps[: done.value].copy()) if logprobs else out
 
+    def set_constraint_vocab(self, pieces) -> None:
+        """The byte string of every token (xh_constraint_set_vocab): a list of vocab_size bytes
+        objects, e.g. L.token_pieces(xf.tokens())."""
+        blob, offsets = L.pieces_blob(list(pieces))
+        if offsets.size - 1 != self.config.vocab_size:
+            raise ValueError(f"{offsets.size - 1} pieces for a vocabulary of {self.config.vocab_size}")
+        L.check(L.lib().xh_constraint_set_vocab(self._ctx, L.ptr(blob), L.ptr(offsets)), self._ctx)
+
+    def set_constraint(self, dfa: "L.ByteDfa | None") -> None:
+        """The byte DFA decode_sample_dfa masks with (xh_constraint_set); None clears it."""
+        if dfa is None:
+            L.check(L.lib().xh_constraint_set(self._ctx, None), self._ctx)
+        else:
+            d = dfa.abi()
+            L.check(L.lib().xh_constraint_set(self._ctx, ctypes.byref(d)), self._ctx)
+
+    def decode_sample_dfa(self, pos: int, n_steps: int, temperature: float, state: int, top_k: int = 0, top_p: float = 1.0,
+                          seed: int = 0, repeat_penalty: float = 1.0, presence_penalty: float = 0.0,
+                          frequency_penalty: float = 0.0, last_n: int = 0, min_p: float = 0.0, logit_bias=None,
+                          history=(), stop=(-1, -1)):
+        """decode_sample_ext under the byte-DFA constraint (xh_byte_dfa, include/xalm_hip.h): only
+        tokens whose bytes the DFA can read from `state` are drawn; `stop` tokens are allowed where
+        the DFA accepts.  `state` = the DFA's start, or the state a previous call returned.  Returns
+        (tokens, log-probabilities, state after the last token)."""
+        toks = np.zeros(max(n_steps, 1), dtype=np.int32)
+        lps = np.zeros(max(n_steps, 1), dtype=np.float32)
+        done = ctypes.c_int(0)
+        state_out = ctypes.c_uint32(0)
+        s = L.XhSampling(temperature, top_k, top_p, seed)
+        c, keep = L.logit_ctl(repeat_penalty, presence_penalty, frequency_penalty, last_n, min_p, logit_bias)
+        hist = np.ascontiguousarray(np.asarray(history, dtype=np.int32))
+        L.check(L.lib().xh_decode_sample_dfa(self._ctx, int(pos), int(n_steps), ctypes.byref(s), ctypes.byref(c),
+                                             L.ptr(hist) if hist.size else None, int(hist.size), int(state),
+                                             int(stop[0]), int(stop[1]), L.ptr(toks), L.ptr(lps),
+                                             ctypes.byref(state_out), ctypes.byref(done)), self._ctx)
+        del keep
+        return toks[: done.value].tolist(), lps[: done.value].copy(), int(state_out.value)
+
     def prefill(self, tokens, pos0: int, s: InferenceState | None = None) -> None:
         """Hydrate tokens[0..n) at positions pos0.. (the prompt loop of run_completion,
         src/main.cpp:94-100); the last token's logits land in `s` when given."""
