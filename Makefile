@@ -40,7 +40,11 @@ $(OBJ)/dt_launch_dt%.o: xalm_amd/csrc/dt_launch.hip
 $(OBJ)/constraint.o: xalm_amd/csrc/constraint.cpp
 	@mkdir -p $(OBJ)
 	$(CXX) $(HOSTFLAGS) -MMD -MP -c -o $@ $<
-HIP_OBJS += $(OBJ)/constraint.o
+# the host top-N log-probabilities and their argument checks: plain C++ likewise
+$(OBJ)/top_logprobs.o: xalm_amd/csrc/top_logprobs.cpp
+	@mkdir -p $(OBJ)
+	$(CXX) $(HOSTFLAGS) -MMD -MP -c -o $@ $<
+HIP_OBJS += $(OBJ)/constraint.o $(OBJ)/top_logprobs.o
 $(LIB)/libxalm_hip.so: $(HIP_OBJS)
 	@mkdir -p $(LIB)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $^

@@ -307,6 +307,57 @@ int xh_decode_sample_dfa(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* s
                          const int* history, int n_history, uint32_t state_in, int stop_token_a, int stop_token_b,
                          int* tokens_out, float* logprobs_out, uint32_t* state_out, int* n_done);
 
+/* ---- top-N alternative log-probabilities and ranks ------------------------------------------ */
+#define XH_TOP_MAX 32
+/* The top list of a logits row l[0..V), and the log-probability and rank of one of its tokens.
+ * - Order.  The sampler's: logit descending by f32 bits (the key of xh_sampling's order, so +0 sorts
+ *   above -0), then index ascending.
+ * - Top list.  top[j], j < n_top, is the j-th token of that order.
+ * - Log-probability.  lp_t = (l_t - M) - logf(sum_j expf(l_j - M)), M the row maximum: the
+ *   log-probability of xh_logit_ctl, over the RAW logits only.  No temperature, bias, penalty or DFA
+ *   mask enters it.  A -inf logit has lp = -inf; it still takes its place in the order when fewer
+ *   than n_top logits are finite.  NaN is outside the contract.
+ * - Rank.  The number of tokens that precede a token in the order, 0-based: 0 = the greedy choice.
+ * - Range.  1 <= n_top <= min(XH_TOP_MAX, vocab); the vocabulary is at most 2^17, as for the sampler.
+ * - Determinism.  Ids and ranks are decided in integers only (keys and indices), so they are exact.
+ *   The same logits bits give the same ids, ranks and lp bits on every run, with graphs on or off.
+ * - Invalid arguments.  n_top out of range, a null required pointer, a target outside [0, vocab), a
+ *   vocabulary over 2^17, n < 2 for xh_score: XH_E_INVALID before the device is touched.
+ * How the device evaluates it (xalm_amd/csrc/top_logprobs.h): one 1024-thread workgroup per row; the
+ * maximum, the sum, a radix selection of the n_top-th key over LDS count histograms, a gather of
+ * the keys above it plus the lowest indices of that key, and a sort of those at most 32 entries. */
+
+/* Host only, plain C++, no device (also what the host Sampler uses): for each of the n_rows rows of
+ * logits[n_rows][vocab], ids_out / lps_out [n_rows][n_top], and with targets[n_rows] that token's
+ * target_lp_out / target_rank_out [n_rows].  targets, target_lp_out and target_rank_out are NULL
+ * together or given together.  The sum is accumulated in double. */
+int xh_top_logprobs_host(const float* logits, int vocab, int n_rows, int n_top, const int* targets, int* ids_out,
+                         float* lps_out, float* target_lp_out, int* target_rank_out);
+/* The same through the device kernel (the one the decode loops and xh_score launch) on host
+ * pointers, no model and no context. */
+int xh_op_top_logprobs(const float* logits, int vocab, int n_rows, int n_top, const int* targets, int* ids_out,
+                       float* lps_out, float* target_lp_out, int* target_rank_out);
+/* n_top > 0: every device decode loop (xh_decode_greedy, _sample, _sample_ext, _sample_dfa) also
+ * records, per step, the top list of the raw logits its token was chosen from and that token's
+ * rank, in context-owned buffers (one launch of the row kernel beside the step head, which itself
+ * is unchanged: the tokens are those of n_top = 0).  0 (the default) = off: the steps are exactly
+ * those of a context that never called this.  n_top lives in a device word: changing it between
+ * positive values needs no new graph capture; switching between 0 and positive recaptures. */
+int xh_set_top_logprobs(xh_ctx* ctx, int n_top);
+/* The first n_steps rows of the last decode call: ids_out / lps_out [n_steps][n_top], rank_out
+ * [n_steps] (any may be NULL).  XH_E_STATE when no decode call has run since n_top was set (or it is
+ * 0), XH_E_INVALID when n_steps exceeds the steps that call completed. */
+int xh_get_top_logprobs(xh_ctx* ctx, int n_steps, int* ids_out, float* lps_out, int* rank_out);
+/* Prompt scoring: xh_perplexity's passes (the same planning, every XH_OPT_PREFILL value, across the
+ * ring wrap) with the row kernel as the per-row tail.  For i < n - 1, after tokens[i] at position
+ * pos0 + i: logprobs_out[i] / ranks_out[i] = the log-probability and rank of tokens[i + 1],
+ * top_ids_out / top_lps_out [n - 1][n_top] the top list, logits_out [n - 1][vocab] the raw logits
+ * the rows were computed from ("echo logits").  n_top may be 0 (no top list); any output may be
+ * NULL.  n >= 2.  Unlike xh_perplexity's probabilities these do not underflow, and the maximum is
+ * the row's own. */
+int xh_score(xh_ctx* ctx, const int* tokens, int n, int pos0, int n_top, float* logprobs_out, int* ranks_out,
+             int* top_ids_out, float* top_lps_out, float* logits_out);
+
 /* Hydrate: forward tokens[0..n) at positions pos0.. (HYDRATE_KV_CACHE for all but the last,
  * which computes logits if want_logits), the prompt loop of run_completion
  * (src/main.cpp:94-100) in one call.  logits_out may be NULL. */
@@ -500,7 +551,8 @@ int xh_philox4x32(uint64_t seed, uint64_t pos, uint32_t out[4]);
  * gate/up matvec, 1 = qkv, 2 = wo, 3 = down, 4 = lm_head, 5 = attention, 6 = the sampled step
  * head of xh_decode_sample under its last parameters, 7 = the extended step head of
  * xh_decode_sample_ext under its last parameters, 8 = the constrained step head of
- * xh_decode_sample_dfa under its last parameters) over `iters` back-to-back launches with
+ * xh_decode_sample_dfa under its last parameters, 9 = the top-N row kernel on the context's logits
+ * under the current xh_set_top_logprobs width, XH_E_STATE when that is 0) over `iters` back-to-back launches with
  * the current step parameters (layers rotate, so the Infinity Cache never serves a repeat).
  * 6, 7 and 8 advance the decode loop's position with every launch (7 and 8 also append to their
  * window, 8 also advances the DFA state): reset or re-hydrate afterwards.  8 needs an xh_decode_sample_dfa

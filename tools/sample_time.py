@@ -16,6 +16,11 @@ bytes, mean about 5) and two permissive DFAs under which every piece is walked t
 memory); and the ms/step and tok/s of 128-step xh_decode_sample_dfa and xh_decode_sample_ext
 calls in turn.
 
+With --top-logprobs 1 (profiles/top_logprobs_time.txt; --only-top 1 leaves the sections above
+out): the top-N row kernel alone (xh_time_kernel 9) at n_top 1, 5 and 32; the extended loop's
+ms/step under xh_set_top_logprobs 0, 5 and 32, the three in turn within every round; and xh_score
+(n_top 0 and 5) against xh_perplexity over 2048 tokens, from a reset context each.
+
 Run under a time limit:  timeout -k 10 600 python tools/sample_time.py
 """
 import argparse
@@ -92,12 +97,70 @@ def constrained_rows(m, c, n, args):
               f"({1e3 / mc:.1f} tok/s)   {(mc - me) * 1e3:+.1f} us/step ({100 * (mc - me) / me:+.2f} %)", flush=True)
 
 
+def ext_loop_rounds(m, n, args, widths):
+    """ms/step of `rounds` xh_decode_sample_ext calls per top-N width, the widths in turn within a
+    round (width None: xh_set_top_logprobs is never called, for a library without it)."""
+    t, k, p = PARAMS
+    out = {w: [] for w in widths}
+    for w in widths:  # every graph exists and is warm
+        if w is not None:
+            m.set_top_logprobs(w)
+        m.decode_sample_ext(n, 8, t, k, p, seed=1)
+    for r in range(args.rounds):
+        for w in widths:
+            if w is not None:
+                m.set_top_logprobs(w)
+                m.decode_sample_ext(n, 1, t, k, p, seed=1)  # 0 <-> positive captures anew: outside the timing
+            t0 = time.perf_counter()
+            toks = m.decode_sample_ext(n, args.steps, t, k, p, seed=r)
+            out[w].append((time.perf_counter() - t0) * 1e3 / args.steps)
+            assert len(toks) == args.steps
+    return out
+
+
+def top_logprobs_rows(m, c, n, args, prompt, st):
+    for w in (1, 5, 32):
+        m.set_top_logprobs(w)
+        us = m.time_kernel(9, args.head_iters)
+        print(f"  top-N row kernel alone, n_top {w:<2}: {us:8.2f} us", flush=True)
+    loops = ext_loop_rounds(m, n, args, (0, 5, 32))
+    base = statistics.median(loops[0])
+    for w, v in loops.items():
+        med = statistics.median(v)
+        print(f"  extended loop, n_top {w:<2}: " + " ".join(f"{x:.4f}" for x in v) + f"   median {med:.4f} ms/step"
+              + (f"   {(med - base) * 1e3:+.1f} us/step ({100 * (med - base) / base:+.2f} %)" if w else ""), flush=True)
+    m.set_top_logprobs(0)
+    toks = [1] + [(i * 7919 + 13) % c.vocab_size for i in range(args.score_tokens - 1)]
+    rows = {"xh_perplexity": lambda: m.token_probs(toks, 0), "xh_score n_top 0": lambda: m.score(toks, 0, 0),
+            "xh_score n_top 5": lambda: m.score(toks, 0, 5)}
+    for fn in rows.values():  # buffers allocated, kernels loaded
+        m.reset()
+        fn()
+    times = {k: [] for k in rows}
+    for r in range(args.rounds):
+        for label, fn in rows.items():
+            m.reset()
+            t0 = time.perf_counter()
+            fn()
+            times[label].append((time.perf_counter() - t0) * 1e3)
+    ppl = statistics.median(times["xh_perplexity"])
+    for label, v in times.items():
+        med = statistics.median(v)
+        print(f"  {label:<17} {args.score_tokens} tokens: " + " ".join(f"{x:.2f}" for x in v) + f"   median {med:.2f} ms"
+              + (f"   {med - ppl:+.2f} ms ({100 * (med - ppl) / ppl:+.2f} %)" if label != "xh_perplexity" else ""), flush=True)
+    m.reset()
+    m.prefill(prompt, 0, st)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--rounds", type=int, default=6)
     ap.add_argument("--head-iters", type=int, default=200)
     ap.add_argument("--constrained", type=int, default=1, help="also time the constrained head and loop")
+    ap.add_argument("--top-logprobs", type=int, default=0, help="also time the top-N row kernel, loop and xh_score")
+    ap.add_argument("--only-top", type=int, default=0, help="with --top-logprobs: nothing else")
+    ap.add_argument("--score-tokens", type=int, default=2048)
     args = ap.parse_args()
     for name in ("mistral-7b-f16", "llama3-8b-f16"):
         w = bench.WORKLOADS[name]
@@ -109,6 +172,11 @@ def main():
         prompt = bench.prompt_tokens(c.vocab_size)
         m.prefill(prompt, 0, st)
         n = len(prompt)
+        if args.top_logprobs and args.only_top:
+            print(f"{name} (V = {c.vocab_size}), {args.steps} steps per call")
+            top_logprobs_rows(m, c, n, args, prompt, st)
+            m.close()
+            continue
         m.decode_greedy(n, 8)  # capture both graphs and warm up before timing
         m.decode_sample(n, 8, *PARAMS, seed=1)
         greedy, sampled = [], []
@@ -137,6 +205,9 @@ def main():
         if args.constrained:
             m.prefill(prompt, 0, st)  # the timed heads moved the position: hydrate again
             constrained_rows(m, c, n, args)
+        if args.top_logprobs:
+            m.prefill(prompt, 0, st)
+            top_logprobs_rows(m, c, n, args, prompt, st)
         m.close()
 
 

@@ -173,6 +173,11 @@ _SIGNATURES = {
     "xh_adjust_logits": (_I, [_P, _I, ctypes.POINTER(XhLogitCtl), _P, _I, _P]),
     "xh_op_sample": (_I, [_P, _I, ctypes.POINTER(XhSampling), ctypes.c_uint64, _I, _P, _P]),
     "xh_philox4x32": (_I, [ctypes.c_uint64, ctypes.c_uint64, _P]),
+    "xh_top_logprobs_host": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "xh_op_top_logprobs": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "xh_set_top_logprobs": (_I, [_P, _I]),
+    "xh_get_top_logprobs": (_I, [_P, _I, _P, _P, _P]),
+    "xh_score": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "xh_prefill": (_I, [_P, _P, _I, _I, _I, _P]),
     "xh_prefill_route": (_I, [_P, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "xh_perplexity": (_I, [_P, _P, _I, _I, _P]),
@@ -339,6 +344,40 @@ def op_sample_dfa(logits: np.ndarray, temperature: float, top_k: int, top_p: flo
                                  int(stop[1]), pos0, n_draws, ptr(toks), ptr(kept), ptr(masked), ptr(states), ptr(lp)))
     del keep
     return toks[:n_draws], kept[:n_draws], masked, states[:n_draws], lp[:n_draws]
+
+
+TOP_MAX = 32
+
+
+def _top_logprobs(fn, logits, n_top, targets):
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    lg = lg.reshape(1, -1) if lg.ndim == 1 else lg
+    rows, V = lg.shape
+    ids = np.empty((rows, max(n_top, 1)), dtype=np.int32)
+    lps = np.empty((rows, max(n_top, 1)), dtype=np.float32)
+    if targets is None:
+        check(fn(ptr(lg), V, rows, n_top, None, ptr(ids), ptr(lps), None, None))
+        return ids[:, :n_top], lps[:, :n_top]
+    tg = np.ascontiguousarray(np.asarray(targets, dtype=np.int32).reshape(-1))
+    if tg.size != rows:
+        raise ValueError(f"{tg.size} targets for {rows} rows")
+    tlp = np.empty(rows, dtype=np.float32)
+    rank = np.empty(rows, dtype=np.int32)
+    check(fn(ptr(lg), V, rows, n_top, ptr(tg), ptr(ids), ptr(lps), ptr(tlp), ptr(rank)))
+    return ids[:, :n_top], lps[:, :n_top], tlp, rank
+
+
+def top_logprobs_host(logits: np.ndarray, n_top: int, targets=None):
+    """The top list of each row of logits [rows, V] (or [V]) on the host (xh_top_logprobs_host; the
+    definition: XH_TOP_MAX in include/xalm_hip.h): (ids int32 [rows, n_top], log-probabilities
+    float32 [rows, n_top]), and with `targets` [rows] also (their log-probabilities [rows], their
+    0-based ranks [rows]).  No device needed."""
+    return _top_logprobs(lib().xh_top_logprobs_host, logits, n_top, targets)
+
+
+def op_top_logprobs(logits: np.ndarray, n_top: int, targets=None):
+    """top_logprobs_host through the device row kernel (xh_op_top_logprobs), one workgroup per row."""
+    return _top_logprobs(lib().xh_op_top_logprobs, logits, n_top, targets)
 
 
 def philox4x32(seed: int, pos: int) -> np.ndarray:

@@ -170,6 +170,17 @@ struct xh_ctx {
     bool dfa_block_valid = false;  // the block's pointers are the current tables' (a decode call wrote it since)
     uint32_t* dec_states = nullptr;
     int dec_cap = 0;
+    // xh_set_top_logprobs (top_logprobs.h): the width on the host and in a device word the row
+    // kernel reads, per-step top lists [dec_cap][XH_TOP_MAX] and ranks / log-probabilities of the
+    // emitted tokens [dec_cap] (allocated by the first positive width), and the steps the last
+    // decode call completed under the current width (-1: none yet)
+    int top_n = 0;
+    int* top_n_dev = nullptr;
+    int* top_ids = nullptr;
+    float* top_lps = nullptr;
+    int* top_rank = nullptr;
+    float* top_tlp = nullptr;
+    int top_steps = -1;
     int nsplit = 1, t_max = 16;
     // fused attention + Wo launch (attn_wo.h): per-layer hand-off words [n_layers][4]
     bool fuse_attn_wo = true;
@@ -317,6 +328,12 @@ int run_step(xh_ctx* ctx, bool with_logits);
 void time_sample_head(xh_ctx* ctx);  // one sample_embed_kernel launch on ctx->stream (xh_time_kernel 6)
 void time_sample_ext_head(xh_ctx* ctx);  // one sample_ext_embed_kernel launch (xh_time_kernel 7)
 void time_sample_dfa_head(xh_ctx* ctx);  // one sample_dfa_embed_kernel launch (xh_time_kernel 8)
+// top_logprobs_kernel (top_logprobs.h; defined in decode.hip) over n_rows rows on stream s: the
+// kernel's arguments in its order
+void launch_top_logprobs(const float* logits, int vocab, size_t stride, int n_rows, const int* n_top_dev, int n_top,
+                         const StepParams* sp, int cap, const int* targets, int out_stride, int* ids, float* lps,
+                         float* target_lp, int* target_rank, hipStream_t s);
+void time_top_logprobs(xh_ctx* ctx);  // one row-kernel launch on ctx->logits (xh_time_kernel 9)
 
 // prefill.hip: the pass buffers, and gemm16.h for xh_op_prompt_gemm (device pointers).  mm_op_ks:
 // *ks = 0 picks the K slicing; 0, 1 when K is no multiple of MM_KMULT, 2 when *ks slices do not divide it

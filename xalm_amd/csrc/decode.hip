@@ -13,6 +13,8 @@
 #include "sample.h"
 #include "sample_dfa.h"
 #include "sample_ext.h"
+#include "top_logprobs.h"
+#include "top_logprobs_host.h"
 
 using namespace xalm;
 
@@ -363,6 +365,11 @@ int enqueue_step(xh_ctx* ctx, hipStream_t s, bool with_logits, int head = HEAD_G
         hipLaunchKernelGGL(embed_kernel, dim3((c.dim + 255) / 256), dim3(256), 0, s, (const void*)ctx->embed,
                            ctx->embed_dt, c.dim, ctx->x, (const StepParams*)ctx->sp, (const float*)ctx->rope_freq,
                            ctx->rope_cs, c.head_dim / 2);
+    // xh_set_top_logprobs: the row kernel on the raw logits the head chose from (the lm_head at the
+    // end of this step is their next writer), as row sp->step - 1 with the head's token as target
+    if (head != HEAD_GIVEN && ctx->top_n > 0)
+        launch_top_logprobs(ctx->logits, c.vocab_size, 0, 1, ctx->top_n_dev, 0, ctx->sp, ctx->dec_cap, ctx->dec_tokens,
+                            XH_TOP_MAX, ctx->top_ids, ctx->top_lps, ctx->top_tlp, ctx->top_rank, s);
     for (int l = 0; l < c.n_layers; l++) {
         const LayerW& w = ctx->L[l];
         if (!launch_gemv(GEMV_QKV, kdt(w.qkv_dt, w.qkv_x), qkv_args(ctx, l), s, qkv_launch_waves(ctx, l)))
@@ -534,6 +541,18 @@ void xalm::time_sample_head(xh_ctx* ctx) { launch_sample_head(ctx, ctx->stream);
 void xalm::time_sample_ext_head(xh_ctx* ctx) { launch_sample_ext_head(ctx, ctx->stream); }
 void xalm::time_sample_dfa_head(xh_ctx* ctx) { launch_sample_dfa_head(ctx, ctx->stream); }
 
+void xalm::launch_top_logprobs(const float* logits, int vocab, size_t stride, int n_rows, const int* n_top_dev, int n_top,
+                               const StepParams* sp, int cap, const int* targets, int out_stride, int* ids, float* lps,
+                               float* target_lp, int* target_rank, hipStream_t s) {
+    hipLaunchKernelGGL(top_logprobs_kernel, dim3(n_rows), dim3(SMP_THREADS), 0, s, logits, vocab, stride, n_top_dev, n_top,
+                       sp, cap, targets, out_stride, ids, lps, target_lp, target_rank);
+}
+// row 0 of the context's buffers, no target
+void xalm::time_top_logprobs(xh_ctx* ctx) {
+    launch_top_logprobs(ctx->logits, ctx->c.vocab_size, 0, 1, ctx->top_n_dev, 0, nullptr, 0, nullptr, XH_TOP_MAX,
+                        ctx->top_ids, ctx->top_lps, nullptr, nullptr, ctx->stream);
+}
+
 void xalm::drop_graphs(xh_ctx* ctx) {
     if (ctx->g_logits) hipGraphExecDestroy(ctx->g_logits);
     if (ctx->g_hydrate) hipGraphExecDestroy(ctx->g_hydrate);
@@ -686,6 +705,7 @@ int xh_decode_greedy(xh_ctx* ctx, int pos, int n_steps, int stop_a, int stop_b, 
                                     ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (n_done) *n_done = done;
+    ctx->top_steps = ctx->top_n > 0 ? done : -1;
     return check_aw(ctx);
 }
 
@@ -736,6 +756,7 @@ int xh_decode_sample(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* sampl
                                     ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (n_done) *n_done = done;
+    ctx->top_steps = ctx->top_n > 0 ? done : -1;
     return check_aw(ctx);
 }
 
@@ -865,6 +886,7 @@ int xh_decode_sample_ext(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* s
                                     ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (n_done) *n_done = done;
+    ctx->top_steps = ctx->top_n > 0 ? done : -1;
     return check_aw(ctx);
 }
 
@@ -1046,6 +1068,7 @@ int xh_decode_sample_dfa(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* s
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (state_out) *state_out = st;
     if (n_done) *n_done = done;
+    ctx->top_steps = ctx->top_n > 0 ? done : -1;
     return check_aw(ctx);
 }
 
@@ -1104,6 +1127,82 @@ int xh_op_sample_dfa(const float* logits, int vocab, const xh_sampling* sampling
     if (e == hipSuccess && masked_out) e = hipMemcpy(masked_out, d_adj.p, (size_t)vocab * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && logprob_out) e = hipMemcpy(logprob_out, d_lp.p, (size_t)n_draws * sizeof(float), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return set_err(nullptr, XH_E_HIP, "sample_dfa op failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+int xh_op_top_logprobs(const float* logits, int vocab, int n_rows, int n_top, const int* targets, int* ids_out,
+                       float* lps_out, float* target_lp_out, int* target_rank_out) {
+    if (const char* why = top_args_error(logits, vocab, n_rows, n_top, 1, targets, ids_out, lps_out, target_lp_out,
+                                         target_rank_out))
+        return set_err(nullptr, XH_E_INVALID, "%s", why);
+    struct Buf {
+        void* p = nullptr;
+        ~Buf() { if (p) hipFree(p); }
+        bool alloc(size_t bytes, const void* src) {
+            if (hipMalloc(&p, bytes) != hipSuccess) return false;
+            return !src || hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+        }
+    } d_logits, d_tgt, d_ids, d_lps, d_tlp, d_rank;
+    const size_t rows = (size_t)n_rows, top = rows * (size_t)n_top;
+    if (!d_logits.alloc(rows * vocab * 4, logits) || !d_ids.alloc(top * sizeof(int), nullptr) ||
+        !d_lps.alloc(top * sizeof(float), nullptr) ||
+        (targets && (!d_tgt.alloc(rows * sizeof(int), targets) || !d_tlp.alloc(rows * sizeof(float), nullptr) ||
+                     !d_rank.alloc(rows * sizeof(int), nullptr))))
+        return set_err(nullptr, XH_E_HIP, "hipMalloc / hipMemcpy failed");
+    launch_top_logprobs((const float*)d_logits.p, vocab, (size_t)vocab, n_rows, nullptr, n_top, nullptr, 0,
+                        (const int*)d_tgt.p, n_top, (int*)d_ids.p, (float*)d_lps.p, (float*)d_tlp.p, (int*)d_rank.p, nullptr);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(ids_out, d_ids.p, top * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(lps_out, d_lps.p, top * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && targets) e = hipMemcpy(target_lp_out, d_tlp.p, rows * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && targets) e = hipMemcpy(target_rank_out, d_rank.p, rows * sizeof(int), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return set_err(nullptr, XH_E_HIP, "top_logprobs op failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+int xh_set_top_logprobs(xh_ctx* ctx, int n_top) {
+    if (!ctx) return XH_E_INVALID;
+    if (n_top < 0 || n_top > XH_TOP_MAX || n_top > ctx->c.vocab_size)
+        return set_err(ctx, XH_E_INVALID, "n_top %d outside 0 .. min(%d, vocab)", n_top, XH_TOP_MAX);
+    if (n_top > 0 && ctx->c.vocab_size > SMP_MAX_VOCAB) return set_err(ctx, XH_E_INVALID, "vocab_size > %d", SMP_MAX_VOCAB);
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_top > 0 && !ctx->top_ids) {
+        const size_t cap = (size_t)ctx->dec_cap;
+        int rc;
+        if ((rc = dmalloc(ctx, &ctx->top_n_dev, (size_t)1)) || (rc = dmalloc(ctx, &ctx->top_lps, cap * XH_TOP_MAX)) ||
+            (rc = dmalloc(ctx, &ctx->top_rank, cap)) || (rc = dmalloc(ctx, &ctx->top_tlp, cap)) ||
+            (rc = dmalloc(ctx, &ctx->top_ids, cap * XH_TOP_MAX)))  // top_ids last: it marks the set as whole
+            return rc;
+    }
+    if (n_top > 0) HIP_TRY(ctx, copy_sync(ctx, ctx->top_n_dev, &n_top, sizeof(int), hipMemcpyHostToDevice));
+    // the decode graphs hold the row kernel's launch or do not: 0 <-> positive captures anew
+    if ((ctx->top_n > 0) != (n_top > 0)) drop_graphs(ctx);
+    ctx->top_n = n_top;
+    ctx->top_steps = -1;
+    return 0;
+}
+
+int xh_get_top_logprobs(xh_ctx* ctx, int n_steps, int* ids_out, float* lps_out, int* rank_out) {
+    if (!ctx || n_steps < 0) return XH_E_INVALID;
+    if (ctx->top_n <= 0 || ctx->top_steps < 0)
+        return set_err(ctx, XH_E_STATE, "no decode call since xh_set_top_logprobs set a positive n_top");
+    if (n_steps > ctx->top_steps)
+        return set_err(ctx, XH_E_INVALID, "n_steps %d exceeds the %d steps of the last decode call", n_steps, ctx->top_steps);
+    if (n_steps == 0) return 0;
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    const size_t rows = (size_t)n_steps, n = (size_t)ctx->top_n;
+    std::vector<int> ids(ids_out ? rows * XH_TOP_MAX : 0);
+    std::vector<float> lps(lps_out ? rows * XH_TOP_MAX : 0);
+    if (ids_out) HIP_TRY(ctx, hipMemcpyAsync(ids.data(), ctx->top_ids, ids.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (lps_out) HIP_TRY(ctx, hipMemcpyAsync(lps.data(), ctx->top_lps, lps.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (rank_out) HIP_TRY(ctx, hipMemcpyAsync(rank_out, ctx->top_rank, rows * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t r = 0; r < rows; r++) {
+        if (ids_out) std::copy_n(ids.begin() + r * XH_TOP_MAX, n, ids_out + r * n);
+        if (lps_out) std::copy_n(lps.begin() + r * XH_TOP_MAX, n, lps_out + r * n);
+    }
     return 0;
 }
 

@@ -150,13 +150,14 @@ int xh_op_prompt_gemm(float* y, const uint16_t* w, const uint16_t* xh, const uin
 // timing hooks for bench.py
 // ---------------------------------------------------------------------------------------
 int xh_time_kernel(xh_ctx* ctx, int which, int iters, float* avg_us) {
-    if (!ctx || !avg_us || iters <= 0 || which < 0 || which > 8) return XH_E_INVALID;
+    if (!ctx || !avg_us || iters <= 0 || which < 0 || which > 9) return XH_E_INVALID;
     HIP_TRY(ctx, hipSetDevice(ctx->dev));
     int rc = check_ready(ctx);
     if (rc) return rc;
     // the constrained head reads its tables through the block xh_decode_sample_dfa writes
     if (which == 8 && !(ctx->dfa_vocab_set && ctx->dfa_n_states && ctx->dfa_block_valid))
         return set_err(ctx, XH_E_STATE, "xh_time_kernel 8: no xh_decode_sample_dfa call under the current constraint");
+    if (which == 9 && ctx->top_n <= 0) return set_err(ctx, XH_E_STATE, "xh_time_kernel 9: xh_set_top_logprobs is 0");
     const int mb = ctx->max_gemv_waves;
     // launches rotate over the layers, so a repeat never finds its weights in the 256 MB
     // Infinity Cache (a decode step streams every layer once)
@@ -173,6 +174,7 @@ int xh_time_kernel(xh_ctx* ctx, int which, int iters, float* avg_us) {
             case 6: time_sample_head(ctx); return true;
             case 7: time_sample_ext_head(ctx); return true;
             case 8: time_sample_dfa_head(ctx); return true;
+            case 9: time_top_logprobs(ctx); return true;
             default:
                 return launch_attn(attn_args(ctx, l), ctx->c.head_dim, ctx->qpk, ctx->c.n_kv_heads, ctx->t_max,
                                    ctx->stream);
@@ -211,6 +213,7 @@ size_t xh_kernel_bytes(const xh_ctx* ctx, int which, int kv_len) {
                        c.dim * (vec + dtype_size(ctx->final_norm_dt)) + (size_t)c.vocab_size * vec;
         case 6: return (size_t)c.vocab_size * vec + file_row_bytes(ctx->embed_dt, c.dim) + c.dim * vec;
         case 7: return (size_t)2 * c.vocab_size * vec + file_row_bytes(ctx->embed_dt, c.dim) + c.dim * vec;
+        case 9: return (size_t)c.vocab_size * vec + (size_t)2 * ctx->top_n * vec;
         default: return (size_t)2 * kv_len * ctx->kv_dim * 2 + 2 * (size_t)ctx->q_dim * vec;
     }
 }

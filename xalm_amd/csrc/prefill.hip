@@ -9,6 +9,7 @@
 
 #include "ctx.h"
 #include "prefill.h"
+#include "top_logprobs_host.h"
 
 using namespace xalm;
 
@@ -657,9 +658,32 @@ int pf_layer(xh_ctx* ctx, PfPass& ps, int l) {
     pf_epi(ctx, ps, e);
     return 0;
 }
+// xh_score's per-row tail in place of token_prob_kernel: the row kernel of top_logprobs.h.  The
+// run's `probs` buffer is `lp` (the targets' log-probabilities), so a row's offset into every
+// whole-run device buffer here is probs - lp.
+struct ScoreTail {
+    int n_top;            // 0: no top list
+    float* lp;            // [rows]
+    int* rank;            // [rows]
+    int* ids;             // [rows][n_top]
+    float* lps;           // [rows][n_top]
+    float* logits_host;   // [rows][vocab] on the host, or nullptr: the echo of the rows' raw logits
+};
+// m rows at `logits` (row stride = vocab) with device targets `tgt`, the first of them row
+// probs - sc.lp of the run
+int score_rows(xh_ctx* ctx, const ScoreTail& sc, const float* logits, int m, const int* tgt, float* probs) {
+    const size_t V = (size_t)ctx->c.vocab_size, off = (size_t)(probs - sc.lp), nt = (size_t)sc.n_top;
+    launch_top_logprobs(logits, (int)V, V, m, nullptr, sc.n_top, nullptr, 0, tgt, sc.n_top, sc.n_top ? sc.ids + off * nt : nullptr,
+                        sc.n_top ? sc.lps + off * nt : nullptr, probs, sc.rank + off, ctx->stream);
+    if (sc.logits_host)
+        HIP_TRY(ctx, hipMemcpyAsync(sc.logits_host + off * V, logits, (size_t)m * V * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return 0;
+}
+
 // Model::forward's OUTPUT_LOGITS tail (src/infer.cpp:620-637) for every token of the pass, then
-// probs[t] = Sampler::sample_prob of token t's target (targets: host, probs: device, m each)
-int pf_logits_probs(xh_ctx* ctx, PfPass& ps, const int* targets, float* probs) {
+// probs[t] = Sampler::sample_prob of token t's target (targets: host, probs: device, m each);
+// under sc, xh_score's tail instead
+int pf_logits_probs(xh_ctx* ctx, PfPass& ps, const int* targets, float* probs, const ScoreTail* sc) {
     const xh_config& c = ctx->c;
     PfBufs& b = ctx->pf;
     const int m = ps.m;
@@ -686,6 +710,7 @@ int pf_logits_probs(xh_ctx* ctx, PfPass& ps, const int* targets, float* probs) {
             pf_epi(ctx, ps, e);
         }
     }
+    if (sc) return score_rows(ctx, *sc, b.logits, m, b.tgt, probs);
     hipLaunchKernelGGL(token_prob_kernel, dim3(m), dim3(1024), 0, ctx->stream, (const float*)b.logits, c.vocab_size,
                        (size_t)c.vocab_size, (const int*)b.tgt, probs);
     return 0;
@@ -696,7 +721,7 @@ int pf_logits_probs(xh_ctx* ctx, PfPass& ps, const int* targets, float* probs) {
 // one GEMM per pass) and probs[i] = sample_prob(targets[i]) (targets: host, n ints).
 // ring: every position is >= max_seq_len (pf_plan): ring passes.
 int prefill_batched(xh_ctx* ctx, const int* tokens, int n, int pos0, int want_logits, const int* targets = nullptr,
-                    float* probs = nullptr, bool ring = false) {
+                    float* probs = nullptr, bool ring = false, const ScoreTail* sc = nullptr) {
     const xh_config& c = ctx->c;
     int rc = pf_prepare(ctx);
     if (rc) return rc;
@@ -710,7 +735,7 @@ int prefill_batched(xh_ctx* ctx, const int* tokens, int n, int pos0, int want_lo
         if ((rc = pf_stage(ctx, ps, tokens + off, sps))) return rc;
         for (int l = 0; l < c.n_layers; l++)
             if ((rc = pf_layer(ctx, ps, l))) return rc;
-        if (probs && (rc = pf_logits_probs(ctx, ps, targets + off, probs + off))) return rc;
+        if (probs && (rc = pf_logits_probs(ctx, ps, targets + off, probs + off, sc))) return rc;
         HIP_TRY(ctx, hipGetLastError());
         if (off + ps.m == n) {
             // the last token's residual stream is the decode path's x
@@ -750,7 +775,9 @@ void xalm::mm_op_launch(const uint16_t* w, const uint16_t* xh, const uint16_t* x
 namespace {
 // The pieces of pf_plan in order.  probs (device, n floats): xh_perplexity's run, every token with
 // logits and probs[i] = sample_prob(targets[i]); else xh_prefill's, the last token's logits if wanted.
-int run_plan(xh_ctx* ctx, const int* tokens, int n, int pos0, int want_logits, const int* targets, float* probs) {
+// sc: xh_score's run, probs = sc->lp and the row kernel as the per-row tail.
+int run_plan(xh_ctx* ctx, const int* tokens, int n, int pos0, int want_logits, const int* targets, float* probs,
+             const ScoreTail* sc = nullptr) {
     int rc = 0;
     // hipBLASLt's plans decide the pass length (XH_OPT_PREFILL 4): probe them before planning
     if (ctx->prefill_gemm == 4 && n >= 2 && pf_supported(ctx) && (rc = pf_prepare(ctx))) return rc;
@@ -762,7 +789,7 @@ int run_plan(xh_ctx* ctx, const int* tokens, int n, int pos0, int want_logits, c
         const bool last = pc.off + pc.n == n;
         if (pc.kind != PF_LOOP) {
             rc = prefill_batched(ctx, tokens + pc.off, pc.n, pos0 + pc.off, last && want_logits,
-                                 probs ? targets + pc.off : nullptr, probs ? probs + pc.off : nullptr, pc.kind == PF_RING);
+                                 probs ? targets + pc.off : nullptr, probs ? probs + pc.off : nullptr, pc.kind == PF_RING, sc);
             // it leaves the last token's step parameters in flight from the one pinned host slot
             if (!rc && !last) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         } else {
@@ -774,9 +801,12 @@ int run_plan(xh_ctx* ctx, const int* tokens, int n, int pos0, int want_logits, c
                 rc = host_step_params(ctx, tokens[i], pos0 + i);
                 if (!rc) rc = run_step(ctx, probs || (i == n - 1 && want_logits));
                 if (rc) break;
-                if (probs)
+                if (sc)
+                    rc = score_rows(ctx, *sc, ctx->logits, 1, ctx->ppl_tgt + i, probs + i);
+                else if (probs)
                     hipLaunchKernelGGL(token_prob_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const float*)ctx->logits, V,
                                        (size_t)V, (const int*)ctx->ppl_tgt + i, probs + i);
+                if (rc) break;
                 // the step parameters are copied from one pinned host slot: drain before reuse
                 if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = set_err(ctx, XH_E_HIP, "hipStreamSynchronize failed");
             }
@@ -839,6 +869,49 @@ int xh_perplexity(xh_ctx* ctx, const int* tokens, int n, int pos0, float* probs_
     }
     if ((rc = run_plan(ctx, tokens, m, pos0, 0, tokens + 1, ctx->ppl_prob))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(probs_out, ctx->ppl_prob, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return check_aw(ctx);
+}
+
+// xh_perplexity's run (the same plan, passes and buffers for the targets and the per-token
+// figure) with the row kernel of top_logprobs.h as the per-row tail: log-probability and rank of
+// tokens[i + 1], the top list, and on request the rows' raw logits.
+int xh_score(xh_ctx* ctx, const int* tokens, int n, int pos0, int n_top, float* logprobs_out, int* ranks_out,
+             int* top_ids_out, float* top_lps_out, float* logits_out) {
+    if (!ctx || !tokens || n < 2 || pos0 < 0) return set_err(ctx, XH_E_INVALID, "bad score arguments");
+    if (n_top < 0 || n_top > XH_TOP_MAX || n_top > ctx->c.vocab_size)
+        return set_err(ctx, XH_E_INVALID, "n_top %d outside 0 .. min(%d, vocab)", n_top, XH_TOP_MAX);
+    if (ctx->c.vocab_size > TOP_MAX_VOCAB) return set_err(ctx, XH_E_INVALID, "vocab_size > %d", TOP_MAX_VOCAB);
+    for (int i = 0; i < n; i++)
+        if (tokens[i] < 0 || tokens[i] >= ctx->c.vocab_size) return set_err(ctx, XH_E_INVALID, "token out of range");
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    int rc = check_ready(ctx);
+    if (rc) return rc;
+    const int m = n - 1;
+    if (ctx->ppl_cap < m) {
+        hipFree(ctx->ppl_tgt); hipFree(ctx->ppl_prob);
+        ctx->ppl_tgt = nullptr; ctx->ppl_prob = nullptr; ctx->ppl_cap = 0;
+        if ((rc = dmalloc(ctx, &ctx->ppl_tgt, (size_t)m)) || (rc = dmalloc(ctx, &ctx->ppl_prob, (size_t)m))) return rc;
+        ctx->ppl_cap = m;
+    }
+    // the run's ranks and top lists: this call's own
+    struct Buf {
+        void* p = nullptr;
+        ~Buf() { if (p) hipFree(p); }
+    } d_rank, d_ids, d_lps;
+    const size_t top = (size_t)m * (size_t)n_top;
+    if (hipMalloc(&d_rank.p, (size_t)m * sizeof(int)) != hipSuccess ||
+        (n_top && (hipMalloc(&d_ids.p, top * sizeof(int)) != hipSuccess || hipMalloc(&d_lps.p, top * sizeof(float)) != hipSuccess)))
+        return set_err(ctx, XH_E_HIP, "hipMalloc failed");
+    const ScoreTail sc = {n_top, ctx->ppl_prob, (int*)d_rank.p, (int*)d_ids.p, (float*)d_lps.p, logits_out};
+    if ((rc = run_plan(ctx, tokens, m, pos0, 0, tokens + 1, ctx->ppl_prob, &sc))) return rc;
+    if (logprobs_out)
+        HIP_TRY(ctx, hipMemcpyAsync(logprobs_out, ctx->ppl_prob, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (ranks_out) HIP_TRY(ctx, hipMemcpyAsync(ranks_out, d_rank.p, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (top_ids_out && n_top)
+        HIP_TRY(ctx, hipMemcpyAsync(top_ids_out, d_ids.p, top * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (top_lps_out && n_top)
+        HIP_TRY(ctx, hipMemcpyAsync(top_lps_out, d_lps.p, top * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return check_aw(ctx);
 }

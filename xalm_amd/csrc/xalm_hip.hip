@@ -201,6 +201,7 @@ void xh_destroy(xh_ctx* ctx) {
     hipFree(ctx->dec_logprobs);
     hipFree(ctx->dfa); hipFree(ctx->dfa_bytes); hipFree(ctx->dfa_offsets); hipFree(ctx->dfa_next); hipFree(ctx->dfa_accept);
     hipFree(ctx->dec_states);
+    hipFree(ctx->top_n_dev); hipFree(ctx->top_ids); hipFree(ctx->top_lps); hipFree(ctx->top_rank); hipFree(ctx->top_tlp);
     pf_free(ctx);
     hipFree(ctx->pf_wdq); hipFree(ctx->ppl_tgt); hipFree(ctx->ppl_prob); hipFree(ctx->rope_freq); hipFree(ctx->rope_cs);
     hipFree(ctx->aw_trace);

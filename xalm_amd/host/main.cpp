@@ -4,6 +4,7 @@
 //   xalm <checkpoint.xalm> [-m completion|perplexity] [-d hip|cpu] [-i prompt | -f file]
 //                          [-T context] [-n steps] [-g 0|1] [-t temperature] [-k top_k] [-p top_p] [-s seed]
 //                          [-r repeat_penalty] [-w window] [-P presence] [-F frequency] [-M min_p] [-R regex]
+//                          [-L top_logprobs]
 //
 // -d selects the device as in the reference (src/main.cpp:465-477); this build ships the HIP
 // device.  -g 1 runs the greedy loop on the device (no host round trip per token); -g 0
@@ -15,6 +16,10 @@
 // -R constrains the output to a regular expression matched against the whole generated text
 // (xh_regex_compile, xh_byte_dfa): xh_decode_sample_dfa with -g 1, the host Sampler over
 // xh_constraint_mask with -g 0; eos / eot may end the text where the expression is matched.
+// -L n (1 .. 32) prints, per generated token, its rank and the n most likely tokens of the raw logits
+// with their log-probabilities (XH_TOP_MAX, include/xalm_hip.h): xh_set_top_logprobs with -g 1, the
+// host Sampler over xh_top_logprobs_host with -g 0; in perplexity mode, how often the scored token
+// had rank 0 (xh_score).
 // Stats are wall clock (the reference divides by user+sys CPU time, src/profiler.h:124-129).
 #include <chrono>
 #include <cmath>
@@ -53,6 +58,8 @@ static void error_usage() {
     fprintf(stderr, "  -F <float> frequency penalty, 0 = off (default 0)\n");
     fprintf(stderr, "  -M <float> min-p in [0, 1], 0 = off (default 0)\n");
     fprintf(stderr, "  -R <regex> constrain the generated text to this regular expression (whole match, bytes)\n");
+    fprintf(stderr, "  -L <int> per generated token, print its rank and the 1 .. 32 most likely tokens with their\n");
+    fprintf(stderr, "     log-probabilities; in perplexity mode, how often the scored token had rank 0 (default 0 - off)\n");
     fprintf(stderr, "  Choose one:\n");
     fprintf(stderr, "    -i <string> input prompt\n");
     fprintf(stderr, "    -f <filepath> input file with prompt\n");
@@ -68,9 +75,15 @@ static void print_ids(const std::vector<int>& ids) {
 }
 
 // run_completion, src/main.cpp:44-128
+static void print_top(int token, int rank, const int* ids, const float* lps, int n) {
+    printf("top: token %d rank %d |", token, rank);
+    for (int j = 0; j < n; j++) printf(" %d:%.6g", ids[j], lps[j]);
+    printf("\n");
+}
+
 static void run_completion(const std::string& path, Device dev, const std::string& prompt, int context, int num_steps,
                            bool device_loop, const xh_sampling& sampling, const xh_logit_ctl& ctl,
-                           const std::string& regex) {
+                           const std::string& regex, int top_n) {
     const XalmFile file = XalmFile::load(path);
     const Model model = Model::from_xalm(file, context, dev);
     InferenceState state(model.config);
@@ -98,7 +111,11 @@ static void run_completion(const std::string& path, Device dev, const std::strin
         dfa_state = (uint32_t)constraint.start;
         if (device_loop) model.set_constraint(constraint);
     }
+    // -L: the generated tokens' top lists, printed after the text
+    Model::TopLogprobs tops;
+    tops.n_top = top_n;
     if (device_loop && num_steps > 0) {
+        if (top_n > 0) model.set_top_logprobs(top_n);
         const std::vector<int> gen =
             !regex.empty() ? model.decode_sample_dfa((int)encoding.size(), num_steps, sampling, ctl, encoding, dfa_state,
                                                      tokenizer.eos_id, tokenizer.eot_id)
@@ -107,6 +124,7 @@ static void run_completion(const std::string& path, Device dev, const std::strin
             : sampling.temperature > 0.f
                 ? model.decode_sample((int)encoding.size(), num_steps, sampling, tokenizer.eos_id, tokenizer.eot_id)
                 : model.decode_greedy((int)encoding.size(), num_steps, tokenizer.eos_id, tokenizer.eot_id);
+        if (top_n > 0) tops = model.top_logprobs((int)gen.size());
         for (int t : gen) {
             std::cout << tokenizer.decode_one(encoding.back(), t) << std::flush;
             encoding.push_back(t);
@@ -119,6 +137,16 @@ static void run_completion(const std::string& path, Device dev, const std::strin
                                  : ext ? sampler.sample(state, sampling, ctl, encoding, (int)encoding.size())
                                  : sampling.temperature > 0.f ? sampler.sample(state, sampling, (int)encoding.size())
                                                               : sampler.sample_argmax(state);
+            if (top_n > 0) {
+                std::vector<int> ids;
+                std::vector<float> lps;
+                float lp = 0.f;
+                int rank = 0;
+                sampler.top_logprobs(state, top_n, token_id, ids, lps, lp, rank);
+                tops.ids.insert(tops.ids.end(), ids.begin(), ids.end());
+                tops.lps.insert(tops.lps.end(), lps.begin(), lps.end());
+                tops.ranks.push_back(rank);
+            }
             std::cout << tokenizer.decode_one(encoding.back(), token_id) << std::flush;
             encoding.push_back(token_id);
             if (token_id == tokenizer.eos_id || token_id == tokenizer.eot_id) break;
@@ -128,6 +156,9 @@ static void run_completion(const std::string& path, Device dev, const std::strin
     }
     const auto t2 = clk::now();
     std::cout << "\n" << std::endl;
+    for (size_t i = 0; i < tops.ranks.size(); i++)
+        print_top(encoding[n_prompt + i], tops.ranks[i], tops.ids.data() + i * (size_t)top_n, tops.lps.data() + i * (size_t)top_n,
+                  top_n);
     const double elapsed = secs(t0, t2), decode = secs(t1, t2);
     const size_t gen = encoding.size() - n_prompt;
     printf("Generation stats (wall clock):\n  %zu tokens (%zu prompt + %zu generated)\n  throughput: %.5g tok/s\n"
@@ -138,7 +169,7 @@ static void run_completion(const std::string& path, Device dev, const std::strin
 }
 
 // run_perplexity, src/main.cpp:198-268
-static void run_perplexity(const std::string& path, Device dev, const std::string& prompt, int context) {
+static void run_perplexity(const std::string& path, Device dev, const std::string& prompt, int context, int top_n) {
     const XalmFile file = XalmFile::load(path);
     const Model model = Model::from_xalm(file, context, dev);
     InferenceState state(model.config);
@@ -162,12 +193,18 @@ static void run_perplexity(const std::string& path, Device dev, const std::strin
     printf("Stats:\n  %zu tokens\n  perplexity: %.5g +- %.5g\n  throughput: %.5g tok/s\n  total: %.5gs\n", N, ppl, err,
            N / elapsed, elapsed);
     printf("perplexity: %.9g\n", ppl);
+    if (top_n > 0) {
+        const Model::Score sc = model.score(encoding, 0, 0);
+        size_t first = 0;
+        for (int r : sc.ranks) first += r == 0 ? 1 : 0;
+        printf("rank 0: %zu of %zu scored tokens (%.4g%%)\n", first, N, 100.0 * (double)first / (double)N);
+    }
 }
 
 int main(int argc, char** argv) {
     std::string path, mode = "completion", prompt = "Q: What is the meaning of life? A:", prompt_path;
     std::string device = "hip", regex;
-    int context = 0, num_steps = 128, device_loop = 0;
+    int context = 0, num_steps = 128, device_loop = 0, top_n = 0;
     xh_sampling sampling{0.f, 0, 1.f, 0};
     xh_logit_ctl ctl{1.f, 0.f, 0.f, 64, 0.f, 0, nullptr, nullptr};
     if (argc >= 2) path = argv[1];
@@ -199,6 +236,7 @@ int main(int argc, char** argv) {
         else if (f == 'F') ctl.frequency_penalty = std::stof(v);
         else if (f == 'M') ctl.min_p = std::stof(v);
         else if (f == 'R') regex = v;
+        else if (f == 'L') top_n = std::stoi(v);
         else error_usage();
         i += 2;
     }
@@ -212,10 +250,14 @@ int main(int argc, char** argv) {
         buffer << file.rdbuf();
         prompt = buffer.str();
     }
+    if (top_n < 0 || top_n > XH_TOP_MAX) {
+        fprintf(stderr, "error: -L takes 0 .. %d\n", XH_TOP_MAX);
+        return 1;
+    }
     const Device dev = device == "cpu" ? Device::CPU : Device::HIP;
     try {
-        if (mode == "completion") run_completion(path, dev, prompt, context, num_steps, device_loop != 0, sampling, ctl, regex);
-        else run_perplexity(path, dev, prompt, context);
+        if (mode == "completion") run_completion(path, dev, prompt, context, num_steps, device_loop != 0, sampling, ctl, regex, top_n);
+        else run_perplexity(path, dev, prompt, context, top_n);
     } catch (const std::exception& e) {
         fprintf(stderr, "error: %s\n", e.what());
         return 1;

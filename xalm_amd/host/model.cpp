@@ -65,7 +65,7 @@ Model Model::from_xalm(const XalmFile& xalm, const int context, const Device dev
     return m;
 }
 
-Model::Model(Model&& o) noexcept : config(o.config), _ctx(o._ctx) { o._ctx = nullptr; }
+Model::Model(Model&& o) noexcept : config(o.config), _ctx(o._ctx), _n_top(o._n_top) { o._ctx = nullptr; }
 
 Model::~Model() {
     if (_ctx) xh_destroy(_ctx);
@@ -155,6 +155,39 @@ std::vector<float> Model::token_probs(const std::vector<int>& tokens, const int 
     std::vector<float> p(tokens.size() - 1);
     check(xh_perplexity(_ctx, tokens.data(), (int)tokens.size(), pos0, p.data()), _ctx, "xh_perplexity");
     return p;
+}
+
+void Model::set_top_logprobs(const int n_top) const {
+    check(xh_set_top_logprobs(_ctx, n_top), _ctx, "xh_set_top_logprobs");
+    _n_top = n_top;
+}
+
+Model::TopLogprobs Model::top_logprobs(const int n_steps) const {
+    TopLogprobs t;
+    t.n_top = _n_top;
+    t.ids.resize((size_t)std::max(n_steps, 1) * (size_t)std::max(_n_top, 1));
+    t.lps.resize(t.ids.size());
+    t.ranks.resize((size_t)std::max(n_steps, 1));
+    check(xh_get_top_logprobs(_ctx, n_steps, t.ids.data(), t.lps.data(), t.ranks.data()), _ctx, "xh_get_top_logprobs");
+    t.ids.resize((size_t)n_steps * (size_t)_n_top);
+    t.lps.resize(t.ids.size());
+    t.ranks.resize((size_t)n_steps);
+    return t;
+}
+
+Model::Score Model::score(const std::vector<int>& tokens, const int pos0, const int n_top) const {
+    Score r;
+    r.n_top = n_top;
+    if (tokens.size() < 2) return r;
+    const size_t m = tokens.size() - 1;
+    r.logprobs.resize(m);
+    r.ranks.resize(m);
+    r.top_ids.resize(m * (size_t)std::max(n_top, 0));
+    r.top_lps.resize(r.top_ids.size());
+    check(xh_score(_ctx, tokens.data(), (int)tokens.size(), pos0, n_top, r.logprobs.data(), r.ranks.data(),
+                   n_top > 0 ? r.top_ids.data() : nullptr, n_top > 0 ? r.top_lps.data() : nullptr, nullptr),
+          _ctx, "xh_score");
+    return r;
 }
 
 void Model::fetch_logits(InferenceState& s) const { check(xh_get_logits(_ctx, s.logits()), _ctx, "xh_get_logits"); }
@@ -265,6 +298,16 @@ int Sampler::sample_argmax(const InferenceState& s) const {
     for (int i = 0; i < vocab_size; ++i)
         if (logits[i] > max_val) { max_val = logits[i]; argmax = i; }
     return argmax;
+}
+
+void Sampler::top_logprobs(const InferenceState& s, const int n_top, const int token, std::vector<int>& ids,
+                           std::vector<float>& lps, float& token_lp, int& token_rank) const {
+    ids.assign((size_t)std::max(n_top, 1), 0);
+    lps.assign(ids.size(), 0.f);
+    if (xh_top_logprobs_host(s.logits(), vocab_size, 1, n_top, &token, ids.data(), lps.data(), &token_lp, &token_rank))
+        throw std::invalid_argument("top_logprobs: 1 <= n_top <= min(XH_TOP_MAX, vocab) and a token of the vocabulary");
+    ids.resize((size_t)n_top);
+    lps.resize((size_t)n_top);
 }
 
 float Sampler::sample_prob(const int index, const InferenceState& s) const {

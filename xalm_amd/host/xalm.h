@@ -131,6 +131,27 @@ public:
                                        const std::vector<int>& history, uint32_t state_in, int stop_a = -1,
                                        int stop_b = -1, uint32_t* state_out = nullptr,
                                        std::vector<float>* logprobs = nullptr) const;
+    // n_top > 0: the device decode loops also record each step's top list and the emitted token's
+    // rank (xh_set_top_logprobs); 0 = off
+    void set_top_logprobs(int n_top) const;
+    // the first n_steps steps of the last decode call (xh_get_top_logprobs): ids and lps
+    // [n_steps][n_top], ranks [n_steps]
+    struct TopLogprobs {
+        int n_top = 0;
+        std::vector<int> ids;
+        std::vector<float> lps;
+        std::vector<int> ranks;
+    };
+    TopLogprobs top_logprobs(int n_steps) const;
+    // prompt scoring (xh_score): for i < tokens.size() - 1 the log-probability and rank of
+    // tokens[i + 1] after tokens[i] at pos0 + i, and the top lists [n - 1][n_top]
+    struct Score {
+        int n_top = 0;
+        std::vector<float> logprobs;
+        std::vector<int> ranks, top_ids;
+        std::vector<float> top_lps;
+    };
+    Score score(const std::vector<int>& tokens, int pos0, int n_top = 0) const;
     void fetch_logits(InferenceState& s) const;
     // run_perplexity's loop on the device (xh_perplexity): element i = Sampler::sample_prob of
     // tokens[i + 1] after forwarding tokens[i] at pos0 + i
@@ -141,6 +162,7 @@ public:
 private:
     Model(const Config& c, xh_ctx* ctx) : config(c), _ctx(ctx) {}
     xh_ctx* _ctx = nullptr;
+    mutable int _n_top = 0;  // the width set last: the row length of top_logprobs
 };
 
 // ---- tokenizer / sampler ------------------------------------------------------------------
@@ -168,6 +190,11 @@ struct Sampler {
     int vocab_size;
     int sample_argmax(const InferenceState& s) const;
     float sample_prob(int index, const InferenceState& s) const;
+    // the n_top most likely tokens of the state's logits with their log-probabilities, and the
+    // log-probability and 0-based rank of `token` (xh_top_logprobs_host, the definition of
+    // XH_TOP_MAX in include/xalm_hip.h).  Throws std::invalid_argument outside its range.
+    void top_logprobs(const InferenceState& s, int n_top, int token, std::vector<int>& ids, std::vector<float>& lps,
+                      float& token_lp, int& token_rank) const;
     // temperature / top-k / top-p under the definition of xh_sampling (include/xalm_hip.h) at
     // counter `pos`, the position the token will occupy: the host restatement of the device
     // sampler, sums in double.  Throws std::invalid_argument for parameters outside it.

@@ -188,6 +188,41 @@ class Model:
         L.check(L.lib().xh_perplexity(self._ctx, L.ptr(toks), int(toks.size), int(pos0), L.ptr(out)), self._ctx)
         return out[: toks.size - 1]
 
+    def set_top_logprobs(self, n_top: int) -> None:
+        """n_top > 0: every device decode loop also records, per step, the n_top most likely tokens
+        of the raw logits with their log-probabilities and the rank of the token it emitted
+        (xh_set_top_logprobs); 0 = off, the default.  The tokens are the same either way."""
+        L.check(L.lib().xh_set_top_logprobs(self._ctx, int(n_top)), self._ctx)
+        self._n_top = int(n_top)
+
+    def top_logprobs(self, n_steps: int):
+        """(ids int32 [n_steps, n_top], log-probabilities float32 [n_steps, n_top], ranks int32
+        [n_steps]) of the first n_steps steps of the last decode call (xh_get_top_logprobs)."""
+        n_top = getattr(self, "_n_top", 0)
+        ids = np.empty((max(n_steps, 1), max(n_top, 1)), dtype=np.int32)
+        lps = np.empty((max(n_steps, 1), max(n_top, 1)), dtype=np.float32)
+        rank = np.empty(max(n_steps, 1), dtype=np.int32)
+        L.check(L.lib().xh_get_top_logprobs(self._ctx, int(n_steps), L.ptr(ids), L.ptr(lps), L.ptr(rank)), self._ctx)
+        return ids[:n_steps, :n_top], lps[:n_steps, :n_top], rank[:n_steps]
+
+    def score(self, tokens, pos0: int = 0, n_top: int = 0, echo_logits: bool = False):
+        """Prompt scoring (xh_score): forward tokens[:-1] at positions pos0..; element i of the
+        result describes tokens[i + 1] after token i.  Returns a dict: "logprobs" float32 [n - 1],
+        "ranks" int32 [n - 1] (0 = the greedy choice), with n_top > 0 "top_ids" / "top_logprobs"
+        [n - 1, n_top], with echo_logits "logits" float32 [n - 1, V], the raw logits of every row."""
+        toks = np.ascontiguousarray(np.asarray(tokens, dtype=np.int32))
+        m = max(toks.size - 1, 1)
+        out = {"logprobs": np.empty(m, dtype=np.float32), "ranks": np.empty(m, dtype=np.int32)}
+        if n_top > 0:
+            out["top_ids"] = np.empty((m, n_top), dtype=np.int32)
+            out["top_logprobs"] = np.empty((m, n_top), dtype=np.float32)
+        if echo_logits:
+            out["logits"] = np.empty((m, self.config.vocab_size), dtype=np.float32)
+        opt = lambda k: L.ptr(out[k]) if k in out else None  # noqa: E731
+        L.check(L.lib().xh_score(self._ctx, L.ptr(toks), int(toks.size), int(pos0), int(n_top), L.ptr(out["logprobs"]),
+                                 L.ptr(out["ranks"]), opt("top_ids"), opt("top_logprobs"), opt("logits")), self._ctx)
+        return out
+
     def debug_trace(self, enable: int = -1) -> np.ndarray:
         """Timeline of the last traced attention + Wo launch, [workgroup][8] device-clock stamps
         (100 MHz, attn_wo.h); `enable` 2/0 switches tracing for later launches."""
