@@ -500,6 +500,27 @@ int xh_op_mha(float* xout, const uint16_t* kb, const uint16_t* vb, const float* 
 int xh_op_prompt_gemm(float* y, const uint16_t* w, const uint16_t* xh, const uint16_t* xl, int rows, int K, int n,
                       int ks);
 
+/* The causal attention of a prompt pass (XH_OPT_PREFILL_ATTN 1 / 2; src/infer.cpp:279-301, :338) on
+ * host buffers, through the launch code of the passes: q and out [n][n_heads * head_dim] f32, k and v
+ * [pos0 + n][n_kv_heads * head_dim] fp16 bits with the pass's own rows in place; row t attends over
+ * slots [0, pos0 + t].  mode 1: the shared-tile kernel at head_dim 128, the per-wave kernel at 64 /
+ * 16 (as XH_OPT_PREFILL_ATTN 1); mode 2: the per-wave kernel.  nsplit 0: the passes' own number of
+ * history splits on this device; k >= 1 forces k splits (the merge kernel behind them when k > 1):
+ * mode 1 at head_dim 128 only, k <= max(1, pos0 / 64 / 4).  Head shapes: head_dim 128 / 64 with 1, 2,
+ * 4 or 8 q heads per KV head, head_dim 16 with 2; anything else is XH_E_INVALID before any launch. */
+int xh_op_prompt_attn(float* out, const float* q, const uint16_t* k, const uint16_t* v, int n, int pos0, int head_dim,
+                      int n_heads, int n_kv_heads, int mode, int nsplit);
+/* The attention of a ring pass (XH_OPT_PREFILL_RING; src/infer.cpp:608-613) at head_dim 128 on host
+ * buffers: m tokens at positions p0.. >= max_seq_len, 3 <= m <= W = max_seq_len - 2.  k_ring / v_ring
+ * [max_seq_len][kv_dim] fp16 bits: the ring as the pass finds it, and on return as the pass leaves
+ * it (staging row t in slot 2 + (p0 - 2 + t) % W, sink_ver[m - 1] in K rows 0 and 1); ks / vs [m][kv_dim]
+ * the pass's own rows; sink_ver [m][2][kv_dim] the sink K rows token t scores against; q and out
+ * [m][n_heads * 128].  nsplit as in xh_op_prompt_attn with pos0 = W.  Launches: the window walk, the
+ * merge that adds the sinks, the commit. */
+int xh_op_prompt_attn_ring(float* out, uint16_t* k_ring, uint16_t* v_ring, const float* q, const uint16_t* ks,
+                           const uint16_t* vs, const uint16_t* sink_ver, int m, int p0, int max_seq_len, int n_heads,
+                           int n_kv_heads, int nsplit);
+
 /* The sampler of xh_decode_sample (the same device function) on host logits[vocab], no model and
  * no context: draw d = 0 .. n_draws-1 at counter pos0 + d writes tokens_out[d] and n_kept_out[d],
  * the size of the kept set (greedy: 1; no finite logit: 0).  n_draws <= 65536. */

@@ -197,6 +197,8 @@ _SIGNATURES = {
     "xh_op_rope": (_I, [_P, _I, _I, _I, ctypes.c_float, _I]),
     "xh_op_mha": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I]),
     "xh_op_prompt_gemm": (_I, [_P, _P, _P, _P, _I, _I, _I, _I]),
+    "xh_op_prompt_attn": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I]),
+    "xh_op_prompt_attn_ring": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I]),
     "xh_time_kernel": (_I, [_P, _I, _I, _FP]),
     "xh_kernel_bytes": (_SZ, [_P, _I, _I]),
 }
@@ -424,3 +426,41 @@ def op_prompt_gemm(w: np.ndarray, xh: np.ndarray, xl: np.ndarray, ks: int = 0) -
     out = np.empty((n, rows), dtype=np.float32)
     check(lib().xh_op_prompt_gemm(ptr(out), ptr(w), ptr(xh), ptr(xl), rows, K, n, ks))
     return out
+
+
+def op_prompt_attn(q: np.ndarray, k: np.ndarray, v: np.ndarray, pos0: int, head_dim: int, n_heads: int, n_kv_heads: int,
+                   mode: int = 1, nsplit: int = 0) -> np.ndarray:
+    """The causal attention of a prompt pass (xh_op_prompt_attn): q f32 [n][n_heads * head_dim]; k, v
+    f16 bit patterns (uint16) [pos0 + n][n_kv_heads * head_dim]; row t attends over slots
+    [0, pos0 + t].  mode / nsplit as in include/xalm_hip.h.  Returns f32 [n][n_heads * head_dim]."""
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    k = np.ascontiguousarray(k, dtype=np.uint16)
+    v = np.ascontiguousarray(v, dtype=np.uint16)
+    n = q.shape[0]
+    assert q.shape == (n, n_heads * head_dim)
+    assert k.shape == (pos0 + n, n_kv_heads * head_dim) and v.shape == k.shape
+    out = np.empty_like(q)
+    check(lib().xh_op_prompt_attn(ptr(out), ptr(q), ptr(k), ptr(v), n, pos0, head_dim, n_heads, n_kv_heads, mode, nsplit))
+    return out
+
+
+def op_prompt_attn_ring(q: np.ndarray, k_ring: np.ndarray, v_ring: np.ndarray, ks: np.ndarray, vs: np.ndarray,
+                        sink_ver: np.ndarray, p0: int, n_heads: int, n_kv_heads: int, nsplit: int = 0):
+    """The attention of a ring pass at head_dim 128 (xh_op_prompt_attn_ring): q f32 [m][n_heads * 128];
+    k_ring, v_ring uint16 [max_seq_len][kv_dim]; ks, vs uint16 [m][kv_dim]; sink_ver uint16
+    [m][2][kv_dim].  Returns (out f32 [m][n_heads * 128], the K ring and the V ring after the commit);
+    the arguments are left as they were."""
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    kr = np.array(k_ring, dtype=np.uint16, order="C", copy=True)
+    vr = np.array(v_ring, dtype=np.uint16, order="C", copy=True)
+    ks = np.ascontiguousarray(ks, dtype=np.uint16)
+    vs = np.ascontiguousarray(vs, dtype=np.uint16)
+    sv = np.ascontiguousarray(sink_ver, dtype=np.uint16)
+    m, kv_dim = ks.shape
+    L = kr.shape[0]
+    assert kv_dim == n_kv_heads * 128 and q.shape == (m, n_heads * 128)
+    assert kr.shape == (L, kv_dim) and vr.shape == kr.shape and vs.shape == ks.shape and sv.shape == (m, 2, kv_dim)
+    out = np.empty_like(q)
+    check(lib().xh_op_prompt_attn_ring(ptr(out), ptr(kr), ptr(vr), ptr(q), ptr(ks), ptr(vs), ptr(sv), m, p0, L, n_heads,
+                                       n_kv_heads, nsplit))
+    return out, kr, vr

@@ -341,6 +341,26 @@ void pf_free(xh_ctx* ctx);
 int mm_op_ks(int rows, int K, int n, int* ks);
 void mm_op_launch(const uint16_t* w, const uint16_t* xh, const uint16_t* xl, float* out, int rows, int K, int n, int ks,
                   int n_cu);
+// prefill.hip: the prompt attention's launch bodies on device pointers, shared by the passes and
+// by xh_op_prompt_attn / xh_op_prompt_attn_ring.  -1: no instantiation for the head shape.
+struct PfAttnDims { int head_dim, n_heads, n_kv_heads; };
+// floats of the split partials of n rows: O [nsplit][n][q_dim], then (m, l) [nsplit][n][n_heads]
+inline size_t pf_fa_part_floats(const PfAttnDims& d, int nsplit, int n) {
+    return (size_t)nsplit * n * ((size_t)d.n_heads * d.head_dim + 2 * d.n_heads);
+}
+bool pf_attn_shape_ok(int hd, int qpk);
+// history splits: the most a walk over pos0 slots may take, and the passes' choice for n rows at
+// n_cu CUs within part_floats of partials
+int pf_fa_split_max(int pos0);
+int pf_fa_pick_nsplit(const PfAttnDims& d, int n_cu, int n, int pos0, size_t part_floats);
+// causal rows [pos0, pos0 + n) over kc / vc; shared: the shared-tile kernel (head_dim 128) over
+// nsplit >= 1 splits, part (pf_fa_part_floats) when nsplit > 1; else the per-wave kernel
+int pf_fa_launch(const PfAttnDims& d, bool shared, const float* q, const uint16_t* kc, const uint16_t* vc, float* out,
+                 int n, int pos0, int nsplit, float* part, hipStream_t s);
+// a ring pass's walk, merge with the sinks (sinkv [m][2][kv_dim]) and commit; part always
+int pf_ring_launch(const PfAttnDims& d, const float* q, uint16_t* kc, uint16_t* vc, const uint16_t* ks, const uint16_t* vs,
+                   const uint16_t* sinkv, float* out, int m, int p0, int max_seq_len, int nsplit, float* part,
+                   hipStream_t s);
 
 // prefill_blas.hip (XH_OPT_PREFILL 4).  blas_ok: 0 unprobed, 1 every GEMM shape of the model has
 // an f16 plan, -1 not.  blas_has_plan: *have = hipBLASLt has an algorithm for the shape.

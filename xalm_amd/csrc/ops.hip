@@ -2,7 +2,9 @@
 // of bench.py (xh_time_kernel, xh_kernel_bytes).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <vector>
 
 #include "ctx.h"
@@ -143,6 +145,83 @@ int xh_op_prompt_gemm(float* y, const uint16_t* w, const uint16_t* xh, const uin
         for (int s = 0; s < ks; s++) v += part[(size_t)s * n * rows + i];  // slice order, as prefill_epi_kernel
         y[i] = v;
     }
+    return 0;
+}
+
+namespace {
+int op_n_cu(int* n_cu) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+        return set_err(nullptr, XH_E_HIP, "no device");
+    return 0;
+}
+// a forced split count against the bound the passes obey over pos0 slots of history
+// (and the grid's z extent)
+bool op_split_ok(int nsplit, int pos0) { return nsplit <= std::min(pf_fa_split_max(pos0), 65535); }
+}  // namespace
+
+int xh_op_prompt_attn(float* out, const float* q, const uint16_t* k, const uint16_t* v, int n, int pos0, int head_dim,
+                      int n_heads, int n_kv_heads, int mode, int nsplit) {
+    if (!out || !q || !k || !v || n <= 0 || pos0 < 0 || pos0 > (1 << 28) || n > (1 << 20) || nsplit < 0)
+        return set_err(nullptr, XH_E_INVALID, "bad prompt_attn args");
+    if (n_kv_heads <= 0 || n_heads <= 0 || n_heads > 1024 || n_heads % n_kv_heads ||
+        !pf_attn_shape_ok(head_dim, n_heads / n_kv_heads))
+        return set_err(nullptr, XH_E_INVALID, "prompt_attn: no prompt attention for head_dim %d, %d / %d heads", head_dim,
+                       n_heads, n_kv_heads);
+    if (mode != 1 && mode != 2) return set_err(nullptr, XH_E_INVALID, "prompt_attn: mode %d (1 or 2)", mode);
+    const bool shared = mode == 1 && head_dim == 128;
+    if (nsplit > 0 && !shared)
+        return set_err(nullptr, XH_E_INVALID, "prompt_attn: splits are forced under mode 1 at head_dim 128 only");
+    if (nsplit > 0 && !op_split_ok(nsplit, pos0))
+        return set_err(nullptr, XH_E_INVALID, "prompt_attn: %d splits over %d slots (at most %d)", nsplit, pos0,
+                       pf_fa_split_max(pos0));
+    const PfAttnDims d{head_dim, n_heads, n_kv_heads};
+    int rc, n_cu = 0;
+    if ((rc = op_n_cu(&n_cu))) return rc;
+    if (nsplit == 0) nsplit = shared ? pf_fa_pick_nsplit(d, n_cu, n, pos0, SIZE_MAX) : 1;
+    DevBuf bq, bk, bv, bo, bp;
+    const size_t qe = (size_t)n * n_heads * head_dim, kve = (size_t)(pos0 + n) * n_kv_heads * head_dim;
+    if ((rc = op_alloc(bq, qe * 4, q)) || (rc = op_alloc(bk, kve * 2, k)) || (rc = op_alloc(bv, kve * 2, v)) ||
+        (rc = op_alloc(bo, qe * 4, nullptr)) || (rc = op_alloc(bp, nsplit > 1 ? pf_fa_part_floats(d, nsplit, n) * 4 : 0, nullptr)))
+        return rc;
+    if (pf_fa_launch(d, shared, (const float*)bq.p, (const uint16_t*)bk.p, (const uint16_t*)bv.p, (float*)bo.p, n, pos0, nsplit,
+                     (float*)bp.p, nullptr) < 0)
+        return set_err(nullptr, XH_E_INVALID, "prompt_attn: head shape not instantiated");
+    return op_finish(out, bo, qe * 4);
+}
+
+int xh_op_prompt_attn_ring(float* out, uint16_t* k_ring, uint16_t* v_ring, const float* q, const uint16_t* ks,
+                           const uint16_t* vs, const uint16_t* sink_ver, int m, int p0, int max_seq_len, int n_heads,
+                           int n_kv_heads, int nsplit) {
+    if (!out || !k_ring || !v_ring || !q || !ks || !vs || !sink_ver || nsplit < 0)
+        return set_err(nullptr, XH_E_INVALID, "bad prompt_attn_ring args");
+    if (n_kv_heads <= 0 || n_heads <= 0 || n_heads > 1024 || n_heads % n_kv_heads || !pf_attn_shape_ok(128, n_heads / n_kv_heads))
+        return set_err(nullptr, XH_E_INVALID, "prompt_attn_ring: no ring attention for %d / %d heads", n_heads, n_kv_heads);
+    const int W = max_seq_len - 2;
+    if (max_seq_len > (1 << 24) || W < 2 || p0 < max_seq_len || m < 3 || m > W)
+        return set_err(nullptr, XH_E_INVALID, "prompt_attn_ring: m %d at p0 %d over a ring of %d (3 <= m <= %d, p0 >= %d)", m,
+                       p0, max_seq_len, W, max_seq_len);
+    if (nsplit > 0 && !op_split_ok(nsplit, W))
+        return set_err(nullptr, XH_E_INVALID, "prompt_attn_ring: %d splits over %d slots (at most %d)", nsplit, W,
+                       pf_fa_split_max(W));
+    const PfAttnDims d{128, n_heads, n_kv_heads};
+    int rc, n_cu = 0;
+    if ((rc = op_n_cu(&n_cu))) return rc;
+    if (nsplit == 0) nsplit = pf_fa_pick_nsplit(d, n_cu, m, W, SIZE_MAX);
+    DevBuf bq, bk, bv, bks, bvs, bsv, bo, bp;
+    const size_t kv_dim = (size_t)n_kv_heads * 128, qe = (size_t)m * n_heads * 128, ring = (size_t)max_seq_len * kv_dim;
+    if ((rc = op_alloc(bq, qe * 4, q)) || (rc = op_alloc(bk, ring * 2, k_ring)) || (rc = op_alloc(bv, ring * 2, v_ring)) ||
+        (rc = op_alloc(bks, m * kv_dim * 2, ks)) || (rc = op_alloc(bvs, m * kv_dim * 2, vs)) ||
+        (rc = op_alloc(bsv, 2 * m * kv_dim * 2, sink_ver)) || (rc = op_alloc(bo, qe * 4, nullptr)) ||
+        (rc = op_alloc(bp, pf_fa_part_floats(d, nsplit, m) * 4, nullptr)))
+        return rc;
+    if (pf_ring_launch(d, (const float*)bq.p, (uint16_t*)bk.p, (uint16_t*)bv.p, (const uint16_t*)bks.p, (const uint16_t*)bvs.p,
+                       (const uint16_t*)bsv.p, (float*)bo.p, m, p0, max_seq_len, nsplit, (float*)bp.p, nullptr) < 0)
+        return set_err(nullptr, XH_E_INVALID, "prompt_attn_ring: head shape not instantiated");
+    if ((rc = op_finish(out, bo, qe * 4))) return rc;
+    if (hipMemcpy(k_ring, bk.p, ring * 2, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(v_ring, bv.p, ring * 2, hipMemcpyDeviceToHost) != hipSuccess)
+        return set_err(nullptr, XH_E_HIP, "hipMemcpy D2H failed");
     return 0;
 }
 

@@ -629,14 +629,22 @@ __global__ __launch_bounds__(ATTN_THREADS) void prefill_attn_kernel(AttnArgs a, 
 // One 32-slot tile of the prompt attention's online softmax (both kernels below): scores
 // s = st * (1 / row scale) * (1/sqrtf(hd)) (the first factor a power of two: one rounding), masked
 // past each row's pos on the diagonal tiles only (diag: wave-uniform), running max m over the
-// lane pair (l, l ^ 32), p = e^(s - m) split into exact f16 hi + lo (|p - hi - lo| <= 2^-25), O and
-// the running sum rescaled by e^(m_old - m) — skipped when it is 1 in every lane (exact: x * 1 = x).
-// e^x by v_exp_f32 of x log2(e) (__expf: <= 2e-6 relative at the x > -20 that carry weight).
+// lane pair (l, l ^ 32), p = 2^15 e^(s - m) split into exact f16 hi + lo, O and the running sum
+// rescaled by e^(m_old - m) — skipped when it is 1 in every lane (exact: x * 1 = x).  The factor
+// 2^15 (FA_P_EXP, added to the exponent inside the one fma that forms v_exp_f32's argument) keeps
+// hi a normal f16 down to p = 2^-29 and lo down to 2^-18 p: |p - hi - lo| <= 2^-22 p there.  Without
+// it lo is subnormal below p = 1/8 and the split is good to 2^-25 absolute only, which under a
+// peaked softmax sums to 5e-7 |V| over 2400 keys that weigh 1e-5 together.  O and the sum carry
+// the factor; it cancels in O / l, and the split partials are written without it (FA_P_UNSCALE).
+// e^x by v_exp_f32 of x log2(e) (<= 2e-6 relative at the x > -20 that carry weight).
 // LOW (the ring pass, prefill_fa2_ring_kernel): a row also has a first visible key `lo`, masked
 // below it on the tiles where lowdiag (wave-uniform) says some row's `lo` lies inside or past the
 // tile.  A row may then see nothing of a tile, or nothing so far: its running max stays -inf,
 // and the exponentials are taken against 0 instead, so that nothing forms e^(-inf - (-inf)); p
 // and alpha come out 0 and (m, l, O) stay (-inf, 0, 0).
+constexpr float FA_LOG2E = 1.4426950408889634f;
+constexpr float FA_P_EXP = 15.f;
+constexpr float FA_P_UNSCALE = 0x1p-15f;
 template <int NDT, bool LOW = false>
 __device__ __forceinline__ void fa_softmax_tile(const f32x16& st, const int b, const int pos, const int h,
                                                 const float sc, const bool diag, float& m, float& lsum,
@@ -662,7 +670,7 @@ __device__ __forceinline__ void fa_softmax_tile(const f32x16& st, const int b, c
     float ps = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-        const float p = __expf(sv[r] - mn);
+        const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sv[r] - mn, FA_LOG2E, FA_P_EXP));
         ps += p;
         const _Float16 hi = (_Float16)p;
         ph[r >> 3][r & 7] = hi;
@@ -1049,9 +1057,9 @@ __device__ __forceinline__ void fa2_body(const float* q, const uint16_t* kc, con
     const float l = lsum + __shfl_xor(lsum, 32);
     if (tq >= n) return;
     const bool split = RING || nsplit > 1;
-    const float inv_l = split ? 1.f : 1.f / l;
+    const float inv_l = split ? FA_P_UNSCALE : 1.f / l;  // O and l carry fa_softmax_tile's 2^15
     float* orow = (split ? part_o + (size_t)z * n * q_stride : out) + (size_t)tq * q_stride + (size_t)head * HD;
-    if (split && h == 0) part_ml[((size_t)z * n + tq) * (q_stride / HD) + head] = float2{m, l};
+    if (split && h == 0) part_ml[((size_t)z * n + tq) * (q_stride / HD) + head] = float2{m, l * FA_P_UNSCALE};
 #pragma unroll
     for (int dt = 0; dt < NDT; dt++)
 #pragma unroll

@@ -447,54 +447,134 @@ void pf_attn_t(xh_ctx* ctx, const AttnArgs& a, int n) {
 // walks its history in up to that many splits of >= FA_MIN_SPLIT_STAGES ring stages each (the
 // split partials live in pf.part, free between the qkv epilogue and the Wo GEMM).
 constexpr int FA_MIN_SPLIT_STAGES = 4;
-int pf_fa_nsplit(const xh_ctx* ctx, int nqt, int n, int pos0) {
-    if (!ctx->pf_fa_split) return 1;
-    const int wg = ctx->c.n_kv_heads * nqt;
-    int ns = std::min((2 * ctx->n_cu + wg - 1) / wg, pos0 / (32 * FA_TPS) / FA_MIN_SPLIT_STAGES);
-    const size_t per = (size_t)n * (ctx->q_dim + 2 * ctx->c.n_heads);
-    ns = (int)std::min<size_t>((size_t)ns, pf_part_floats(ctx, ctx->pf.cap[PfBufs::PASS]) / per);
-    return std::max(ns, 1);
-}
-template <int HD, int QPK>
-void pf_fa_t(xh_ctx* ctx, const AttnArgs& a, int n, int pos0) {
-    constexpr int TPW = 32 / QPK;
-    if constexpr (HD == 128) {
-        if (ctx->pf_attn_mode == 1) {
-            constexpr int NW = PF_FA_WAVES;
-            auto k = prefill_fa2_kernel<QPK, NW>;
-            ensure_lds((const void*)k);
-            const int nqt = (n + NW * TPW - 1) / (NW * TPW);
-            const int nsplit = pf_fa_nsplit(ctx, nqt, n, pos0);
-            float* po = nsplit > 1 ? ctx->pf.part : nullptr;
-            float2* pml = nsplit > 1 ? (float2*)(ctx->pf.part + (size_t)nsplit * n * ctx->q_dim) : nullptr;
-            hipLaunchKernelGGL(k, dim3(ctx->c.n_kv_heads, nqt, nsplit), dim3(64 * NW), fa_lds_bytes(), ctx->stream, a.q,
-                               a.kc, a.vc, a.out, n, pos0, ctx->q_dim, ctx->kv_dim, po, pml);
-            if (nsplit > 1)
-                hipLaunchKernelGGL(prefill_fa_merge_kernel<false>, dim3(ctx->c.n_heads, n), dim3(256), 0, ctx->stream,
-                                   (const float*)po, (const float2*)pml, a.out, n, nsplit, ctx->q_dim, FaSinks{});
-            return;
-        }
-    }
-    hipLaunchKernelGGL((prefill_fa_kernel<HD, QPK>), dim3(ctx->c.n_kv_heads, (n + TPW - 1) / TPW), dim3(64), 0,
-                       ctx->stream, a.q, a.kc, a.vc, a.out, n, pos0, ctx->q_dim, ctx->kv_dim);
+// query tiles of the shared-tile kernels: PF_FA_WAVES waves of 32 / qpk tokens each
+int fa2_query_tiles(int n, int qpk) {
+    const int per = PF_FA_WAVES * (32 / qpk);
+    return (n + per - 1) / per;
 }
 // head shapes of the batched path's attention: head_dim 128 / 64 with 1, 2, 4 or 8 q heads per KV
 // head (MHA through GQA), and the test fixtures' head_dim 16 x 2
 constexpr bool pf_attn_shape(int hd, int qpk) {
     return ((hd == 128 || hd == 64) && (qpk == 1 || qpk == 2 || qpk == 4 || qpk == 8)) || (hd == 16 && qpk == 2);
 }
-// the shapes of pf_attn_shape are the only instantiations; -1 for another one
+// One causal prompt attention on device pointers, the launch body of the passes and of
+// xh_op_prompt_attn: the shared-tile kernel (shared: head_dim 128 only) over nsplit history splits
+// with the merge behind it when nsplit > 1 (partials in `part`), else the per-wave kernel.
+template <int HD, int QPK>
+void pf_fa_t(const PfAttnDims& d, bool shared, const float* q, const uint16_t* kc, const uint16_t* vc, float* out, int n,
+             int pos0, int nsplit, float* part, hipStream_t s) {
+    constexpr int TPW = 32 / QPK;
+    const int q_dim = d.n_heads * HD, kv_dim = d.n_kv_heads * HD;
+    if constexpr (HD == 128) {
+        if (shared) {
+            constexpr int NW = PF_FA_WAVES;
+            auto k = prefill_fa2_kernel<QPK, NW>;
+            ensure_lds((const void*)k);
+            const int nqt = fa2_query_tiles(n, QPK);
+            float* po = nsplit > 1 ? part : nullptr;
+            float2* pml = nsplit > 1 ? (float2*)(part + (size_t)nsplit * n * q_dim) : nullptr;
+            hipLaunchKernelGGL(k, dim3(d.n_kv_heads, nqt, nsplit), dim3(64 * NW), fa_lds_bytes(), s, q, kc, vc, out, n, pos0,
+                               q_dim, kv_dim, po, pml);
+            if (nsplit > 1)
+                hipLaunchKernelGGL(prefill_fa_merge_kernel<false>, dim3(d.n_heads, n), dim3(256), 0, s, (const float*)po,
+                                   (const float2*)pml, out, n, nsplit, q_dim, FaSinks{});
+            return;
+        }
+    }
+    hipLaunchKernelGGL((prefill_fa_kernel<HD, QPK>), dim3(d.n_kv_heads, (n + TPW - 1) / TPW), dim3(64), 0, s, q, kc, vc, out,
+                       n, pos0, q_dim, kv_dim);
+}
 template <int HD>
-int pf_attn_hd(xh_ctx* ctx, const AttnArgs& a, int n, int pos0) {
-    return for_qpk(ctx->qpk, [&](auto Q) {
+int pf_fa_hd(const PfAttnDims& d, bool shared, const float* q, const uint16_t* kc, const uint16_t* vc, float* out, int n,
+             int pos0, int nsplit, float* part, hipStream_t s) {
+    return for_qpk(d.n_heads / d.n_kv_heads, [&](auto Q) {
         constexpr int QPK = decltype(Q)::value;
         if constexpr (pf_attn_shape(HD, QPK)) {
-            if (ctx->pf_attn_mode != 0) pf_fa_t<HD, QPK>(ctx, a, n, pos0);
-            else pf_attn_t<HD, QPK>(ctx, a, n);
+            pf_fa_t<HD, QPK>(d, shared, q, kc, vc, out, n, pos0, nsplit, part, s);
             return 0;
         }
         return -1;
     });
+}
+// The attention of a ring pass after its sink versions, on device pointers (head_dim 128): the
+// window walk into split partials, the merge that adds the sinks, the commit to the ring.
+template <int QPK>
+int pf_ring_t(const PfAttnDims& d, const float* q, uint16_t* kc, uint16_t* vc, const uint16_t* ks, const uint16_t* vs,
+              const uint16_t* sinkv, float* out, int m, int p0, int max_seq_len, int nsplit, float* part, hipStream_t s) {
+    constexpr int NW = PF_FA_WAVES;
+    const int W = max_seq_len - 2;
+    const int q_dim = d.n_heads * 128, kv_dim = d.n_kv_heads * 128;
+    FaRing rg{ks, vs, W, (p0 - 2) % W};
+    const int nqt = fa2_query_tiles(m, QPK);
+    float* po = part;
+    float2* pml = (float2*)(part + (size_t)nsplit * m * q_dim);
+    auto k = prefill_fa2_ring_kernel<QPK, NW>;
+    ensure_lds((const void*)k);
+    hipLaunchKernelGGL(k, dim3(d.n_kv_heads, nqt, nsplit), dim3(64 * NW), fa_lds_bytes(), s, q, (const uint16_t*)kc,
+                       (const uint16_t*)vc, rg, m, q_dim, kv_dim, po, pml);
+    const FaSinks sk{q, sinkv, vc, kv_dim, QPK};
+    hipLaunchKernelGGL(prefill_fa_merge_kernel<true>, dim3(d.n_heads, m), dim3(256), 0, s, (const float*)po,
+                       (const float2*)pml, out, m, nsplit, q_dim, sk);
+    hipLaunchKernelGGL(prefill_ring_commit_kernel, dim3(m + 1), dim3(256), 0, s, rg, sinkv, kc, vc, m, kv_dim);
+    return 0;
+}
+
+}  // namespace
+
+bool xalm::pf_attn_shape_ok(int hd, int qpk) { return pf_attn_shape(hd, qpk); }
+int xalm::pf_fa_split_max(int pos0) { return std::max(1, pos0 / (32 * FA_TPS) / FA_MIN_SPLIT_STAGES); }
+int xalm::pf_fa_pick_nsplit(const PfAttnDims& d, int n_cu, int n, int pos0, size_t part_floats) {
+    const int wg = d.n_kv_heads * fa2_query_tiles(n, d.n_heads / d.n_kv_heads);
+    int ns = std::min((2 * n_cu + wg - 1) / wg, pos0 / (32 * FA_TPS) / FA_MIN_SPLIT_STAGES);
+    ns = (int)std::min<size_t>((size_t)ns, part_floats / pf_fa_part_floats(d, 1, n));
+    return std::max(ns, 1);
+}
+int xalm::pf_fa_launch(const PfAttnDims& d, bool shared, const float* q, const uint16_t* kc, const uint16_t* vc, float* out,
+                       int n, int pos0, int nsplit, float* part, hipStream_t s) {
+    if (d.n_kv_heads <= 0 || d.n_heads % d.n_kv_heads) return -1;
+    return d.head_dim == 128  ? pf_fa_hd<128>(d, shared, q, kc, vc, out, n, pos0, nsplit, part, s)
+           : d.head_dim == 64 ? pf_fa_hd<64>(d, shared, q, kc, vc, out, n, pos0, nsplit, part, s)
+           : d.head_dim == 16 ? pf_fa_hd<16>(d, shared, q, kc, vc, out, n, pos0, nsplit, part, s)
+                              : -1;
+}
+int xalm::pf_ring_launch(const PfAttnDims& d, const float* q, uint16_t* kc, uint16_t* vc, const uint16_t* ks,
+                         const uint16_t* vs, const uint16_t* sinkv, float* out, int m, int p0, int max_seq_len, int nsplit,
+                         float* part, hipStream_t s) {
+    if (d.head_dim != 128 || d.n_kv_heads <= 0 || d.n_heads % d.n_kv_heads) return -1;
+    return for_qpk(d.n_heads / d.n_kv_heads, [&](auto Q) {
+        return pf_ring_t<decltype(Q)::value>(d, q, kc, vc, ks, vs, sinkv, out, m, p0, max_seq_len, nsplit, part, s);
+    });
+}
+
+namespace {
+
+PfAttnDims pf_dims(const xh_ctx* ctx) { return {ctx->c.head_dim, ctx->c.n_heads, ctx->c.n_kv_heads}; }
+// the splits of a pass of n tokens over pos0 slots of history, within the partials buffer
+int pf_fa_nsplit(const xh_ctx* ctx, int n, int pos0) {
+    if (!ctx->pf_fa_split) return 1;
+    return pf_fa_pick_nsplit(pf_dims(ctx), ctx->n_cu, n, pos0, pf_part_floats(ctx, ctx->pf.cap[PfBufs::PASS]));
+}
+// the shapes of pf_attn_shape are the only instantiations; -1 for another one
+int pf_attn_any(xh_ctx* ctx, const AttnArgs& a, int n, int pos0) {
+    const int hd = ctx->c.head_dim;
+    if (ctx->pf_attn_mode != 0) {
+        const bool shared = ctx->pf_attn_mode == 1 && hd == 128;
+        return pf_fa_launch(pf_dims(ctx), shared, a.q, a.kc, a.vc, a.out, n, pos0, shared ? pf_fa_nsplit(ctx, n, pos0) : 1,
+                            ctx->pf.part, ctx->stream);
+    }
+    auto go = [&](auto H) {
+        constexpr int HD = decltype(H)::value;
+        return for_qpk(ctx->qpk, [&](auto Q) {
+            constexpr int QPK = decltype(Q)::value;
+            if constexpr (pf_attn_shape(HD, QPK)) {
+                pf_attn_t<HD, QPK>(ctx, a, n);
+                return 0;
+            }
+            return -1;
+        });
+    };
+    return hd == 128 ? go(std::integral_constant<int, 128>{}) : hd == 64 ? go(std::integral_constant<int, 64>{})
+           : hd == 16 ? go(std::integral_constant<int, 16>{}) : -1;
 }
 // 0, XH_E_INVALID for a head shape with no prompt attention, or the split buffers' allocation error
 int pf_attn(xh_ctx* ctx, const AttnArgs& a, int n, int pos0) {
@@ -505,8 +585,7 @@ int pf_attn(xh_ctx* ctx, const AttnArgs& a, int n, int pos0) {
         if (rc) return rc;
         b.part_o = ctx->pf.po; b.part_ml = ctx->pf.pml; b.counters = ctx->pf.cnt;
     }
-    const int rc = hd == 128 ? pf_attn_hd<128>(ctx, b, n, pos0) : hd == 64 ? pf_attn_hd<64>(ctx, b, n, pos0)
-                   : hd == 16 ? pf_attn_hd<16>(ctx, b, n, pos0) : -1;
+    const int rc = pf_attn_any(ctx, b, n, pos0);
     return rc < 0 ? set_err(ctx, XH_E_INVALID, "prefill: head shape not instantiated") : 0;
 }
 
@@ -515,35 +594,17 @@ int pf_attn(xh_ctx* ctx, const AttnArgs& a, int n, int pos0) {
 // sink K versions, the window walk into split partials (pf.part: free between the qkv epilogue
 // and the Wo GEMM), the merge that adds the sinks, and the commit of the staged rows and the last
 // sink version to the ring.
-template <int QPK>
-int pf_attn_ring_t(xh_ctx* ctx, int l, int m, int p0) {
-    constexpr int NW = PF_FA_WAVES, TPW = 32 / QPK;
-    const int W = ctx->c.max_seq_len - 2;
-    FaRing rg{ctx->pf.ks, ctx->pf.vs, W, (p0 - 2) % W};
-    const int nqt = (m + NW * TPW - 1) / (NW * TPW);
-    const int nsplit = pf_fa_nsplit(ctx, nqt, m, W);
-    if ((size_t)nsplit * m * (ctx->q_dim + 2 * ctx->c.n_heads) > pf_part_floats(ctx, ctx->pf.cap[PfBufs::PASS]))
-        return set_err(ctx, XH_E_INVALID, "prefill: the ring pass's attention partials do not fit");
-    float* po = ctx->pf.part;
-    float2* pml = (float2*)(ctx->pf.part + (size_t)nsplit * m * ctx->q_dim);
-    uint16_t *kc = ctx->kcache(l), *vc = ctx->vcache(l);
-    hipStream_t s = ctx->stream;
-    hipLaunchKernelGGL(prefill_sink_versions_kernel, dim3((ctx->kv_dim + 255) / 256), dim3(256), 0, s, (const uint16_t*)kc,
-                       (const float*)ctx->sink_cos, (const float*)ctx->sink_sin, ctx->kv_dim, ctx->c.head_dim, m,
-                       ctx->pf.sinkv);
-    auto k = prefill_fa2_ring_kernel<QPK, NW>;
-    ensure_lds((const void*)k);
-    hipLaunchKernelGGL(k, dim3(ctx->c.n_kv_heads, nqt, nsplit), dim3(64 * NW), fa_lds_bytes(), s, (const float*)ctx->pf.q,
-                       (const uint16_t*)kc, (const uint16_t*)vc, rg, m, ctx->q_dim, ctx->kv_dim, po, pml);
-    const FaSinks sk{ctx->pf.q, ctx->pf.sinkv, vc, ctx->kv_dim, QPK};
-    hipLaunchKernelGGL(prefill_fa_merge_kernel<true>, dim3(ctx->c.n_heads, m), dim3(256), 0, s, (const float*)po,
-                       (const float2*)pml, ctx->pf.att, m, nsplit, ctx->q_dim, sk);
-    hipLaunchKernelGGL(prefill_ring_commit_kernel, dim3(m + 1), dim3(256), 0, s, rg, (const uint16_t*)ctx->pf.sinkv, kc, vc,
-                       m, ctx->kv_dim);
-    return 0;
-}
 int pf_attn_ring(xh_ctx* ctx, int l, int m, int p0) {
-    const int rc = for_qpk(ctx->qpk, [&](auto Q) { return pf_attn_ring_t<decltype(Q)::value>(ctx, l, m, p0); });
+    const PfAttnDims d = pf_dims(ctx);
+    const int nsplit = pf_fa_nsplit(ctx, m, ctx->c.max_seq_len - 2);
+    if (pf_fa_part_floats(d, nsplit, m) > pf_part_floats(ctx, ctx->pf.cap[PfBufs::PASS]))
+        return set_err(ctx, XH_E_INVALID, "prefill: the ring pass's attention partials do not fit");
+    uint16_t *kc = ctx->kcache(l), *vc = ctx->vcache(l);
+    hipLaunchKernelGGL(prefill_sink_versions_kernel, dim3((ctx->kv_dim + 255) / 256), dim3(256), 0, ctx->stream,
+                       (const uint16_t*)kc, (const float*)ctx->sink_cos, (const float*)ctx->sink_sin, ctx->kv_dim,
+                       ctx->c.head_dim, m, ctx->pf.sinkv);
+    const int rc = pf_ring_launch(d, ctx->pf.q, kc, vc, ctx->pf.ks, ctx->pf.vs, ctx->pf.sinkv, ctx->pf.att, m, p0,
+                                  ctx->c.max_seq_len, nsplit, ctx->pf.part, ctx->stream);
     return rc < 0 ? set_err(ctx, XH_E_INVALID, "prefill: head shape not instantiated") : rc;
 }
 
