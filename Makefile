@@ -44,7 +44,11 @@ $(OBJ)/constraint.o: xalm_amd/csrc/constraint.cpp
 $(OBJ)/top_logprobs.o: xalm_amd/csrc/top_logprobs.cpp
 	@mkdir -p $(OBJ)
 	$(CXX) $(HOSTFLAGS) -MMD -MP -c -o $@ $<
-HIP_OBJS += $(OBJ)/constraint.o $(OBJ)/top_logprobs.o
+# the host mirror of the adaptive truncation: plain C++, every f32 operation rounded on its own
+$(OBJ)/truncate.o: xalm_amd/csrc/truncate.cpp
+	@mkdir -p $(OBJ)
+	$(CXX) $(HOSTFLAGS) -ffp-contract=off -MMD -MP -c -o $@ $<
+HIP_OBJS += $(OBJ)/constraint.o $(OBJ)/top_logprobs.o $(OBJ)/truncate.o
 $(LIB)/libxalm_hip.so: $(HIP_OBJS)
 	@mkdir -p $(LIB)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $^

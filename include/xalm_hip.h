@@ -307,6 +307,79 @@ int xh_decode_sample_dfa(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* s
                          const int* history, int n_history, uint32_t state_in, int stop_token_a, int stop_token_b,
                          int* tokens_out, float* logprobs_out, uint32_t* state_out, int* n_done);
 
+/* ---- truncation that adapts to the distribution: top-n-sigma, locally typical, Mirostat v2 ---- */
+typedef struct xh_trunc_ctl {
+    float typical_p;     /* in (0, 1]; 1 = off                         */
+    float top_n_sigma;   /* >= 0, finite; 0 = off                      */
+    float mirostat_tau;  /* >= 0, finite; 0 = Mirostat off             */
+    float mirostat_eta;  /* > 0, finite when Mirostat is on; else ignored */
+} xh_trunc_ctl;
+/* The adaptive draw: xh_logit_ctl's definition with three more cuts between min-p and top-p.
+ * - Input.  The logits l'': xh_logit_ctl's adjusted logits l', masked exactly as in
+ *   xh_decode_sample_dfa when constrain != 0 (the state advance, the stuck rule and the end-token
+ *   rule are that loop's too).  constrain != 0 without both uploads is XH_E_INVALID.
+ * - Greedy.  temperature == 0 gives that loop's greedy choice (constrain == 0: xh_decode_sample_ext's,
+ *   constrain != 0: xh_decode_sample_dfa's); xh_trunc_ctl takes no part and mu_out = mu_in.
+ * - Masses.  Otherwise m = max l'', w_i = expf((l''_i - m) / temperature) and M_i = trunc(w_i * 2^40)
+ *   as an unsigned 64-bit integer (the masses of xh_sampling's device evaluation; -inf has 0).
+ * - Prefix stage.  top-k and min-p as xh_logit_ctl.  With top_n_sigma > 0, sigma is the population
+ *   standard deviation of the finite l''_i, accumulated in double in two passes (the mean, then the
+ *   squared deviations) in a fixed order; thr = (float)((double)m - (double)top_n_sigma * sigma);
+ *   n_sigma = #{i : l''_i >= thr}, compared in f32 (the maximum always qualifies).  That set is a
+ *   prefix of the order; the stage keeps the first min(top_k or V, n_minp, n_sigma) tokens.  It is
+ *   taken on the logits before the temperature, as the method is defined.
+ * - Typical stage (typical_p < 1), over the prefix set C.  S = sum_C M_i, an exact integer.  p_i =
+ *   (float)M_i / (float)S, s_i = -logf(p_i), H = sum_C p_i s_i (a token with M_i = 0 contributes 0 and
+ *   has s = +inf), d_i = |s_i - H|, all f32, the sum in a fixed order.  Order C by d ascending, ties
+ *   by d's f32 bits being equal then index ascending; keep the shortest prefix of that order whose
+ *   integer mass reaches ceil(typical_p * S), at least one token.  The most probable token may be
+ *   dropped; a token without mass never is kept.  Which tokens are kept is decided on integers: the
+ *   keys of d, the indices and the masses.
+ * - top-p and the draw.  The dropped tokens become -inf in a context-owned working copy (the logits
+ *   xh_get_logits returns are never written), and xh_sampling's definition runs on it with top_k
+ *   off: the maximum and the masses are those of the survivors, Philox at counter pos + i.  With
+ *   typical_p == 1 the draw is bit for bit xh_decode_sample_ext's / _dfa's under the effective
+ *   top-k; with top_n_sigma == 0 and Mirostat off as well the loop emits exactly their tokens.
+ * - Mirostat v2 (mirostat_tau > 0).  Requires top_k == 0, top_p == 1, min_p == 0 (or a null ctl),
+ *   typical_p == 1 and top_n_sigma == 0 (at any temperature), else XH_E_INVALID; penalties, biases
+ *   and the DFA mask apply.  S = sum M_i over all tokens, cut = (u64)ceil((double)S * exp2(-(double)mu)),
+ *   n_mu = max(1, #{i : M_i >= cut}): a prefix of the order, the effective top-k.  After the draw, K
+ *   the kept mass: obs = (float)(log2((double)K) - log2((double)M_tok)), mu' = mu - eta * (obs - tau),
+ *   the three f32 operations rounded separately (no fused multiply-add).  mu lives in a device word
+ *   the head reads and writes every step.  mu_in is finite and >= 0; the caller starts at 2 * tau (the
+ *   host mirror does when none is given).  mu_out is the value after the last emitted token, mu_in
+ *   when n_steps is 0.  A stuck step, XH_DFA_DEAD and a step with no finite logit leave mu unchanged.
+ * - One call equals two.  Tokens, DFA states and the bits of mu are identical whether a run is one
+ *   call or split anywhere; the second call is given history ++ the first call's tokens, state_out
+ *   and mu_out.
+ * - Invalid arguments.  A field outside its range or NaN, a null xh_trunc_ctl, mu_in negative or
+ *   non-finite under Mirostat, and every invalid argument of xh_decode_sample_ext and, when
+ *   constrain != 0, of xh_decode_sample_dfa: XH_E_INVALID before the device is touched.
+ * - Log-probabilities stay over the raw logits; xh_set_top_logprobs records for this loop too.
+ * How the device evaluates it (xalm_amd/csrc/sample_adapt.h): one 1024-thread workgroup runs the
+ * adjustment, the mask, the sigma passes, the prefix selection, the typical stage (-d_i into a second
+ * context-owned buffer, a mass-weighted radix selection over its keys, -inf over the dropped
+ * entries), the sampler of xh_sampling and Mirostat's update.  The parameters, mu and the DFA state
+ * sit in device words copied before the first step: changing them captures no new graph. */
+
+/* xh_decode_sample_dfa's loop with the adaptive draw (its own step head and graph; the other four
+ * heads are untouched).  constrain == 0: no mask, state_in is ignored and returned in state_out.
+ * state_out and mu_out may be NULL. */
+int xh_decode_sample_adapt(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* sampling, const xh_logit_ctl* ctl,
+                           const xh_trunc_ctl* trunc, const int* history, int n_history, int constrain,
+                           uint32_t state_in, float mu_in, int stop_token_a, int stop_token_b, int* tokens_out,
+                           float* logprobs_out, uint32_t* state_out, float* mu_out, int* n_done);
+/* Host only, plain C++, no device (also what the host Sampler uses): the kept set of the adaptive
+ * draw on l''[vocab] (already adjusted and masked) at temperature > 0, with the masses computed as
+ * above by the host's expf.  kept_out[vocab] (may be NULL) = 1 for the tokens left after the typical
+ * stage and before top-p (under Mirostat: the first n_mu tokens), *n_kept_out their number (0 when no
+ * logit is finite), *thr_out the n-sigma threshold (-inf when off); any may be NULL.  With
+ * Mirostat on and token >= 0, *mu_out = mu' had `token` been drawn from that set (mu when it is not in
+ * it or has no mass); otherwise *mu_out = mu.  temperature == 0 is XH_E_INVALID: greedy truncates
+ * nothing. */
+int xh_truncate_host(const float* logits, int vocab, const xh_sampling* sampling, float min_p, const xh_trunc_ctl* trunc,
+                     float mu, int token, uint8_t* kept_out, int* n_kept_out, float* thr_out, float* mu_out);
+
 /* ---- top-N alternative log-probabilities and ranks ------------------------------------------ */
 #define XH_TOP_MAX 32
 /* The top list of a logits row l[0..V), and the log-probability and rank of one of its tokens.
@@ -337,7 +410,7 @@ int xh_top_logprobs_host(const float* logits, int vocab, int n_rows, int n_top, 
  * pointers, no model and no context. */
 int xh_op_top_logprobs(const float* logits, int vocab, int n_rows, int n_top, const int* targets, int* ids_out,
                        float* lps_out, float* target_lp_out, int* target_rank_out);
-/* n_top > 0: every device decode loop (xh_decode_greedy, _sample, _sample_ext, _sample_dfa) also
+/* n_top > 0: every device decode loop (xh_decode_greedy, _sample, _sample_ext, _sample_dfa, _sample_adapt) also
  * records, per step, the top list of the raw logits its token was chosen from and that token's
  * rank, in context-owned buffers (one launch of the row kernel beside the step head, which itself
  * is unchanged: the tokens are those of n_top = 0).  0 (the default) = off: the steps are exactly
@@ -547,6 +620,18 @@ int xh_op_sample_dfa(const float* logits, int vocab, const xh_sampling* sampling
                      const uint32_t* offsets, uint32_t state, int stop_token_a, int stop_token_b, uint64_t pos0,
                      int n_draws, int* tokens_out, int* n_kept_out, float* masked_out, uint32_t* next_state_out,
                      float* logprob_out);
+/* The adaptive draw (xh_trunc_ctl above; the same device functions as xh_decode_sample_adapt) on host
+ * logits[vocab], no model and no context: draw d at counter pos0 + d, every draw from `state` and `mu`
+ * over the same window.  dfa NULL = unconstrained (bytes, offsets, state and the stop tokens are
+ * ignored; next_state_out receives `state`).  tokens_out, n_kept_out (the final kept set's size),
+ * next_state_out and mu_out hold n_draws entries each; kept_out[vocab] (may be NULL) is the 0/1 map
+ * of the set after the typical stage and before top-p (all 0 for a greedy or stuck draw, or with no
+ * finite logit), thr_out (may be NULL) the f32 n-sigma threshold (-inf when off). */
+int xh_op_sample_adapt(const float* logits, int vocab, const xh_sampling* sampling, const xh_logit_ctl* ctl,
+                       const xh_trunc_ctl* trunc, const int* window, int n_window, const xh_byte_dfa* dfa,
+                       const uint8_t* bytes, const uint32_t* offsets, uint32_t state, float mu, int stop_token_a,
+                       int stop_token_b, uint64_t pos0, int n_draws, int* tokens_out, int* n_kept_out,
+                       uint32_t* next_state_out, float* mu_out, uint8_t* kept_out, float* thr_out);
 /* Host only, no device, plain C++ (also what the host Sampler uses): allowed_out[t] = 1 if token t
  * is allowed in `state`, else 0, and next_state_out[t] its successor state (XH_DFA_DEAD when
  * forbidden); nothing is allowed in XH_DFA_DEAD. */
@@ -573,10 +658,11 @@ int xh_philox4x32(uint64_t seed, uint64_t pos, uint32_t out[4]);
  * head of xh_decode_sample under its last parameters, 7 = the extended step head of
  * xh_decode_sample_ext under its last parameters, 8 = the constrained step head of
  * xh_decode_sample_dfa under its last parameters, 9 = the top-N row kernel on the context's logits
- * under the current xh_set_top_logprobs width, XH_E_STATE when that is 0) over `iters` back-to-back launches with
+ * under the current xh_set_top_logprobs width, XH_E_STATE when that is 0, 10 = the adaptive step head
+ * of xh_decode_sample_adapt under its last parameters, XH_E_STATE before such a call) over `iters` back-to-back launches with
  * the current step parameters (layers rotate, so the Infinity Cache never serves a repeat).
  * 6, 7 and 8 advance the decode loop's position with every launch (7 and 8 also append to their
- * window, 8 also advances the DFA state): reset or re-hydrate afterwards.  8 needs an xh_decode_sample_dfa
+ * window, 8 also advances the DFA state; 10 advances what 7 and 8 do, and mu): reset or re-hydrate afterwards.  8 needs an xh_decode_sample_dfa
  * call since the last xh_constraint_set / xh_constraint_set_vocab, else XH_E_STATE. */
 int xh_time_kernel(xh_ctx* ctx, int which, int iters, float* avg_us);
 /* Bytes one launch of that kernel must move (algorithmic). */

@@ -21,6 +21,11 @@ out): the top-N row kernel alone (xh_time_kernel 9) at n_top 1, 5 and 32; the ex
 ms/step under xh_set_top_logprobs 0, 5 and 32, the three in turn within every round; and xh_score
 (n_top 0 and 5) against xh_perplexity over 2048 tokens, from a reset context each.
 
+With --adapt 1 (profiles/sample_adapt_time.txt; --only-adapt 1 leaves the sections above out): the
+adaptive step head (xh_time_kernel 10, xh_decode_sample_adapt) next to the extended head (7) of the
+same process under the same sampling parameters, with the truncation off, top-n-sigma 1.0, typical_p
+0.9, and Mirostat v2 (tau 5, eta 0.1; top_k 0 and top_p 1 as it requires, for both heads).
+
 Run under a time limit:  timeout -k 10 600 python tools/sample_time.py
 """
 import argparse
@@ -152,6 +157,21 @@ def top_logprobs_rows(m, c, n, args, prompt, st):
     m.prefill(prompt, 0, st)
 
 
+ADAPT_SETS = [("off", PARAMS, {}), ("n-sigma 1.0", PARAMS, dict(top_n_sigma=1.0)),
+              ("typical 0.9", PARAMS, dict(typical_p=0.9)),
+              ("Mirostat tau 5 eta 0.1", (0.8, 0, 1.0), dict(mirostat_tau=5.0, mirostat_eta=0.1))]
+
+
+def adapt_rows(m, n, args):
+    for label, (t, k, p), trunc in ADAPT_SETS:
+        m.decode_sample_ext(n, 1, t, k, p, seed=3)
+        ext_us = m.time_kernel(7, args.head_iters)
+        m.decode_sample_adapt(n, 1, t, k, p, seed=3, **trunc)
+        adp_us = m.time_kernel(10, args.head_iters)
+        print(f"  heads alone, t {t} k {k} p {p}, {label:<22}: extended (7) {ext_us:8.2f} us   adaptive (10) {adp_us:8.2f} us"
+              f"   ({adp_us - ext_us:+.2f} us)", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=128)
@@ -161,6 +181,8 @@ def main():
     ap.add_argument("--top-logprobs", type=int, default=0, help="also time the top-N row kernel, loop and xh_score")
     ap.add_argument("--only-top", type=int, default=0, help="with --top-logprobs: nothing else")
     ap.add_argument("--score-tokens", type=int, default=2048)
+    ap.add_argument("--adapt", type=int, default=0, help="also time the adaptive head against the extended head")
+    ap.add_argument("--only-adapt", type=int, default=0, help="with --adapt: nothing else")
     args = ap.parse_args()
     for name in ("mistral-7b-f16", "llama3-8b-f16"):
         w = bench.WORKLOADS[name]
@@ -175,6 +197,11 @@ def main():
         if args.top_logprobs and args.only_top:
             print(f"{name} (V = {c.vocab_size}), {args.steps} steps per call")
             top_logprobs_rows(m, c, n, args, prompt, st)
+            m.close()
+            continue
+        if args.adapt and args.only_adapt:
+            print(f"{name} (V = {c.vocab_size}), {args.head_iters} launches per figure")
+            adapt_rows(m, n, args)
             m.close()
             continue
         m.decode_greedy(n, 8)  # capture both graphs and warm up before timing
@@ -208,6 +235,9 @@ def main():
         if args.top_logprobs:
             m.prefill(prompt, 0, st)
             top_logprobs_rows(m, c, n, args, prompt, st)
+        if args.adapt:
+            m.prefill(prompt, 0, st)
+            adapt_rows(m, n, args)
         m.close()
 
 

@@ -4,8 +4,8 @@ Product: libxalm_hip.so (HIP kernels + C ABI, include/xalm_hip.h), the C++ host
 (libxalm_host.so, bin/xalm) and this thin Python mirror of Model / InferenceState.
 """
 from . import _lib
-from ._lib import XhError
+from ._lib import XhError, op_sample_adapt
 from .model import InferenceState, Model
 from .xalm_file import XalmFile
 
-__all__ = ["Model", "InferenceState", "XalmFile", "XhError", "_lib"]
+__all__ = ["Model", "InferenceState", "XalmFile", "XhError", "_lib", "op_sample_adapt"]

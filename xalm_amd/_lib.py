@@ -86,6 +86,13 @@ def logit_ctl(repeat_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, l
     return c, (btok, bval)
 
 
+class XhTruncCtl(ctypes.Structure):
+    """xh_trunc_ctl (include/xalm_hip.h): typical_p (1 = off), top_n_sigma (0 = off), Mirostat v2's
+    tau (0 = off) and eta."""
+    _fields_ = [("typical_p", ctypes.c_float), ("top_n_sigma", ctypes.c_float), ("mirostat_tau", ctypes.c_float),
+                ("mirostat_eta", ctypes.c_float)]
+
+
 DFA_DEAD, DFA_MAX_STATES = 0xFFFF, 65535
 
 
@@ -168,6 +175,14 @@ _SIGNATURES = {
     "xh_op_sample_dfa": (_I, [_P, _I, ctypes.POINTER(XhSampling), ctypes.POINTER(XhLogitCtl), _P, _I,
                               ctypes.POINTER(XhByteDfa), _P, _P, ctypes.c_uint32, _I, _I, ctypes.c_uint64, _I, _P, _P, _P,
                               _P, _P]),
+    "xh_decode_sample_adapt": (_I, [_P, _I, _I, ctypes.POINTER(XhSampling), ctypes.POINTER(XhLogitCtl),
+                                    ctypes.POINTER(XhTruncCtl), _P, _I, _I, ctypes.c_uint32, ctypes.c_float, _I, _I, _P, _P,
+                                    ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_I)]),
+    "xh_op_sample_adapt": (_I, [_P, _I, ctypes.POINTER(XhSampling), ctypes.POINTER(XhLogitCtl), ctypes.POINTER(XhTruncCtl),
+                                _P, _I, ctypes.POINTER(XhByteDfa), _P, _P, ctypes.c_uint32, ctypes.c_float, _I, _I,
+                                ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _FP]),
+    "xh_truncate_host": (_I, [_P, _I, ctypes.POINTER(XhSampling), ctypes.c_float, ctypes.POINTER(XhTruncCtl),
+                              ctypes.c_float, _I, _P, ctypes.POINTER(_I), _FP, _FP]),
     "xh_constraint_mask": (_I, [ctypes.POINTER(XhByteDfa), _P, _P, _I, ctypes.c_uint32, _I, _I, _P, _P]),
     "xh_regex_compile": (_I, [ctypes.c_char_p, _P, _P, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "xh_adjust_logits": (_I, [_P, _I, ctypes.POINTER(XhLogitCtl), _P, _I, _P]),
@@ -346,6 +361,55 @@ def op_sample_dfa(logits: np.ndarray, temperature: float, top_k: int, top_p: flo
                                  int(stop[1]), pos0, n_draws, ptr(toks), ptr(kept), ptr(masked), ptr(states), ptr(lp)))
     del keep
     return toks[:n_draws], kept[:n_draws], masked, states[:n_draws], lp[:n_draws]
+
+
+def op_sample_adapt(logits: np.ndarray, temperature: float, top_k: int, top_p: float, seed: int, pos0: int, n_draws: int,
+                    typical_p: float = 1.0, top_n_sigma: float = 0.0, mirostat_tau: float = 0.0, mirostat_eta: float = 0.1,
+                    mu: float = 0.0, dfa: "ByteDfa | None" = None, blob=None, offsets=None, state: int = 0, stop=(-1, -1),
+                    window=(), **controls):
+    """The adaptive draw on a logits vector (xh_op_sample_adapt; xh_trunc_ctl's fields by name, controls
+    as `logit_ctl`): every draw from `state` and `mu`, masked by `dfa` over the pieces (blob, offsets)
+    when given.  Returns a dict: "tokens", "n_kept" int32 [n_draws], "states" uint32 [n_draws], "mu"
+    float32 [n_draws], "kept" uint8 [V] (the set after the typical stage, before top-p), "thr" (the
+    n-sigma threshold, -inf when off)."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    s = XhSampling(temperature, top_k, top_p, seed)
+    c, keep = logit_ctl(**controls)
+    t = XhTruncCtl(typical_p, top_n_sigma, mirostat_tau, mirostat_eta)
+    win = np.ascontiguousarray(np.asarray(window, dtype=np.int32))
+    n = max(n_draws, 1)
+    out = {"tokens": np.empty(n, dtype=np.int32), "n_kept": np.empty(n, dtype=np.int32),
+           "states": np.empty(n, dtype=np.uint32), "mu": np.empty(n, dtype=np.float32),
+           "kept": np.empty(lg.size, dtype=np.uint8)}
+    thr = ctypes.c_float(0)
+    d = dfa.abi() if dfa is not None else None
+    check(lib().xh_op_sample_adapt(ptr(lg), lg.size, ctypes.byref(s), ctypes.byref(c), ctypes.byref(t),
+                                   ptr(win) if win.size else None, win.size, ctypes.byref(d) if d is not None else None,
+                                   ptr(blob) if d is not None else None, ptr(offsets) if d is not None else None,
+                                   int(state), float(mu), int(stop[0]), int(stop[1]), pos0, n_draws, ptr(out["tokens"]),
+                                   ptr(out["n_kept"]), ptr(out["states"]), ptr(out["mu"]), ptr(out["kept"]),
+                                   ctypes.byref(thr)))
+    del keep
+    for k in ("tokens", "n_kept", "states", "mu"):
+        out[k] = out[k][:n_draws]
+    out["thr"] = float(thr.value)
+    return out
+
+
+def truncate_host(logits: np.ndarray, temperature: float, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0,
+                  typical_p: float = 1.0, top_n_sigma: float = 0.0, mirostat_tau: float = 0.0, mirostat_eta: float = 0.1,
+                  mu: float = 0.0, token: int = -1):
+    """The kept set of the adaptive draw on l'' [V] on the host (xh_truncate_host): (kept uint8 [V], the
+    set after the typical stage and before top-p; its size; the n-sigma threshold; mu after `token`,
+    mu itself with token < 0 or Mirostat off).  No device needed."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    s = XhSampling(temperature, top_k, top_p, 0)
+    t = XhTruncCtl(typical_p, top_n_sigma, mirostat_tau, mirostat_eta)
+    kept = np.empty(lg.size, dtype=np.uint8)
+    n, thr, mu_out = ctypes.c_int(0), ctypes.c_float(0), ctypes.c_float(0)
+    check(lib().xh_truncate_host(ptr(lg), lg.size, ctypes.byref(s), float(min_p), ctypes.byref(t), float(mu), int(token),
+                                 ptr(kept), ctypes.byref(n), ctypes.byref(thr), ctypes.byref(mu_out)))
+    return kept, int(n.value), float(thr.value), float(mu_out.value)
 
 
 TOP_MAX = 32

@@ -80,6 +80,14 @@ struct DfaCtl {
     int stop_a, stop_b;
 };
 
+// xh_decode_sample_adapt's device block (sample_adapt.h): the fields of xh_trunc_ctl, Mirostat's mu,
+// which the step head reads and writes every step, and whether the DFA mask runs
+struct AdaptCtl {
+    float typical_p, top_n_sigma, tau, eta;
+    float mu;
+    int constrain;
+};
+
 constexpr int ARGMAX_CANDS = 1024;  // the lm_head workgroups' argmax keys (argmax_embed_kernel's block size)
 
 // The batched prefill's device buffers (prefill.hip), in growth groups.  T = cap[PASS] tokens, the
@@ -169,6 +177,11 @@ struct xh_ctx {
     int dfa_n_states = 0;
     bool dfa_block_valid = false;  // the block's pointers are the current tables' (a decode call wrote it since)
     uint32_t* dec_states = nullptr;
+    // xh_decode_sample_adapt (sample_adapt.h): parameter block, the typical stage's keys [vocab];
+    // adapt_valid: a call has written the block (with adapt_constrain under the current constraint)
+    xalm::AdaptCtl* adapt = nullptr;
+    float* adapt_negd = nullptr;
+    bool adapt_valid = false, adapt_constrain = false;
     int dec_cap = 0;
     // xh_set_top_logprobs (top_logprobs.h): the width on the host and in a device word the row
     // kernel reads, per-step top lists [dec_cap][XH_TOP_MAX] and ranks / log-probabilities of the
@@ -208,7 +221,7 @@ struct xh_ctx {
     int t_max_aw = 16;
     bool use_graphs = true;
     hipGraphExec_t g_logits = nullptr, g_hydrate = nullptr, g_decode = nullptr, g_sample = nullptr,
-                   g_sample_ext = nullptr, g_sample_dfa = nullptr;
+                   g_sample_ext = nullptr, g_sample_dfa = nullptr, g_sample_adapt = nullptr;
     int max_gemv_waves = 4096;  // 16 waves per CU
     // the qkv launch: its whole matrix is one round at 16 waves per CU (every wave one group,
     // requested at once); at 8 waves per CU each wave streams two groups back to back
@@ -328,6 +341,7 @@ int run_step(xh_ctx* ctx, bool with_logits);
 void time_sample_head(xh_ctx* ctx);  // one sample_embed_kernel launch on ctx->stream (xh_time_kernel 6)
 void time_sample_ext_head(xh_ctx* ctx);  // one sample_ext_embed_kernel launch (xh_time_kernel 7)
 void time_sample_dfa_head(xh_ctx* ctx);  // one sample_dfa_embed_kernel launch (xh_time_kernel 8)
+void time_sample_adapt_head(xh_ctx* ctx);  // one sample_adapt_embed_kernel launch (xh_time_kernel 10)
 // top_logprobs_kernel (top_logprobs.h; defined in decode.hip) over n_rows rows on stream s: the
 // kernel's arguments in its order
 void launch_top_logprobs(const float* logits, int vocab, size_t stride, int n_rows, const int* n_top_dev, int n_top,

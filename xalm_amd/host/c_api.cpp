@@ -47,6 +47,18 @@ int xalm_sample(const float* logits, int vocab, const xh_sampling* sampling, uin
     });
 }
 
+// the host Sampler's adaptive draw without a constraint (controls off: ctl may be NULL); *mu in and out
+int xalm_sample_adapt(const float* logits, int vocab, const xh_sampling* sampling, const xh_logit_ctl* ctl,
+                      const xh_trunc_ctl* trunc, const int* history, int n_history, int pos, float* mu, int* token) {
+    return guard([&] {
+        if (!sampling || !trunc || !mu || !token || n_history < 0) throw std::invalid_argument("xalm_sample_adapt: bad argument");
+        const xh_logit_ctl off{1.f, 0.f, 0.f, 0, 0.f, 0, nullptr, nullptr};
+        uint32_t state = 0;
+        *token = xalm::sample_adapt_logits(logits, vocab, *sampling, ctl ? *ctl : off, *trunc,
+                                           std::vector<int>(history, history + n_history), pos, nullptr, state, *mu, -1, -1);
+    });
+}
+
 int xalm_load_model(const char* path, int context, int device_ordinal, xh_ctx** out) {
     // the Model releases its context on destruction; detach it for the C caller
     return guard([&] {

@@ -4,7 +4,7 @@
 //   xalm <checkpoint.xalm> [-m completion|perplexity] [-d hip|cpu] [-i prompt | -f file]
 //                          [-T context] [-n steps] [-g 0|1] [-t temperature] [-k top_k] [-p top_p] [-s seed]
 //                          [-r repeat_penalty] [-w window] [-P presence] [-F frequency] [-M min_p] [-R regex]
-//                          [-L top_logprobs]
+//                          [-L top_logprobs] [-y typical_p] [-S n_sigma] [-U mirostat_tau] [-E mirostat_eta]
 //
 // -d selects the device as in the reference (src/main.cpp:465-477); this build ships the HIP
 // device.  -g 1 runs the greedy loop on the device (no host round trip per token); -g 0
@@ -20,6 +20,9 @@
 // with their log-probabilities (XH_TOP_MAX, include/xalm_hip.h): xh_set_top_logprobs with -g 1, the
 // host Sampler over xh_top_logprobs_host with -g 0; in perplexity mode, how often the scored token
 // had rank 0 (xh_score).
+// -y / -S / -U / -E (xh_trunc_ctl) cut by local typicality, by n standard deviations below the
+// maximum logit, or by Mirostat v2's running target: xh_decode_sample_adapt with -g 1, the host
+// Sampler over xh_truncate_host with -g 0.
 // Stats are wall clock (the reference divides by user+sys CPU time, src/profiler.h:124-129).
 #include <chrono>
 #include <cmath>
@@ -60,6 +63,10 @@ static void error_usage() {
     fprintf(stderr, "  -R <regex> constrain the generated text to this regular expression (whole match, bytes)\n");
     fprintf(stderr, "  -L <int> per generated token, print its rank and the 1 .. 32 most likely tokens with their\n");
     fprintf(stderr, "     log-probabilities; in perplexity mode, how often the scored token had rank 0 (default 0 - off)\n");
+    fprintf(stderr, "  -y <float> locally typical sampling: typical-p in (0, 1], 1 = off (default 1)\n");
+    fprintf(stderr, "  -S <float> top-n-sigma: keep logits within n standard deviations of the maximum, 0 = off (default 0)\n");
+    fprintf(stderr, "  -U <float> Mirostat v2 target surprise tau in bits, 0 = off (default 0); takes -k 0 -p 1 -M 0 -y 1 -S 0\n");
+    fprintf(stderr, "  -E <float> Mirostat v2 learning rate eta > 0 (default 0.1)\n");
     fprintf(stderr, "  Choose one:\n");
     fprintf(stderr, "    -i <string> input prompt\n");
     fprintf(stderr, "    -f <filepath> input file with prompt\n");
@@ -83,7 +90,7 @@ static void print_top(int token, int rank, const int* ids, const float* lps, int
 
 static void run_completion(const std::string& path, Device dev, const std::string& prompt, int context, int num_steps,
                            bool device_loop, const xh_sampling& sampling, const xh_logit_ctl& ctl,
-                           const std::string& regex, int top_n) {
+                           const xh_trunc_ctl& trunc, const std::string& regex, int top_n) {
     const XalmFile file = XalmFile::load(path);
     const Model model = Model::from_xalm(file, context, dev);
     InferenceState state(model.config);
@@ -104,6 +111,9 @@ static void run_completion(const std::string& path, Device dev, const std::strin
     // any control on: the extended draw on both routes, prompt + output as the history
     const bool ext = ctl.repeat_penalty != 1.f || ctl.presence_penalty != 0.f || ctl.frequency_penalty != 0.f ||
                      ctl.min_p != 0.f;
+    // any truncation on: the adaptive draw on both routes
+    const bool adapt = trunc.typical_p != 1.f || trunc.top_n_sigma != 0.f || trunc.mirostat_tau != 0.f;
+    float mu = 2.f * trunc.mirostat_tau;
     Constraint constraint;
     uint32_t dfa_state = 0;
     if (!regex.empty()) {
@@ -117,7 +127,9 @@ static void run_completion(const std::string& path, Device dev, const std::strin
     if (device_loop && num_steps > 0) {
         if (top_n > 0) model.set_top_logprobs(top_n);
         const std::vector<int> gen =
-            !regex.empty() ? model.decode_sample_dfa((int)encoding.size(), num_steps, sampling, ctl, encoding, dfa_state,
+            adapt ? model.decode_sample_adapt((int)encoding.size(), num_steps, sampling, ctl, trunc, encoding,
+                                              !regex.empty(), dfa_state, mu, tokenizer.eos_id, tokenizer.eot_id)
+            : !regex.empty() ? model.decode_sample_dfa((int)encoding.size(), num_steps, sampling, ctl, encoding, dfa_state,
                                                      tokenizer.eos_id, tokenizer.eot_id)
             : ext ? model.decode_sample_ext((int)encoding.size(), num_steps, sampling, ctl, encoding, tokenizer.eos_id,
                                           tokenizer.eot_id)
@@ -132,7 +144,10 @@ static void run_completion(const std::string& path, Device dev, const std::strin
         }
     } else {
         for (int i = 0; i < num_steps || num_steps == -1; i++) {
-            const int token_id = !regex.empty() ? sampler.sample(state, sampling, ctl, encoding, (int)encoding.size(),
+            const int token_id = adapt ? sampler.sample(state, sampling, ctl, trunc, encoding, (int)encoding.size(),
+                                                        regex.empty() ? nullptr : &constraint, dfa_state, mu,
+                                                        tokenizer.eos_id, tokenizer.eot_id)
+                                 : !regex.empty() ? sampler.sample(state, sampling, ctl, encoding, (int)encoding.size(),
                                                                  constraint, dfa_state, tokenizer.eos_id, tokenizer.eot_id)
                                  : ext ? sampler.sample(state, sampling, ctl, encoding, (int)encoding.size())
                                  : sampling.temperature > 0.f ? sampler.sample(state, sampling, (int)encoding.size())
@@ -207,6 +222,7 @@ int main(int argc, char** argv) {
     int context = 0, num_steps = 128, device_loop = 0, top_n = 0;
     xh_sampling sampling{0.f, 0, 1.f, 0};
     xh_logit_ctl ctl{1.f, 0.f, 0.f, 64, 0.f, 0, nullptr, nullptr};
+    xh_trunc_ctl trunc{1.f, 0.f, 0.f, 0.1f};
     if (argc >= 2) path = argv[1];
     else error_usage();
     for (int i = 2; i < argc;) {
@@ -237,6 +253,10 @@ int main(int argc, char** argv) {
         else if (f == 'M') ctl.min_p = std::stof(v);
         else if (f == 'R') regex = v;
         else if (f == 'L') top_n = std::stoi(v);
+        else if (f == 'y') trunc.typical_p = std::stof(v);
+        else if (f == 'S') trunc.top_n_sigma = std::stof(v);
+        else if (f == 'U') trunc.mirostat_tau = std::stof(v);
+        else if (f == 'E') trunc.mirostat_eta = std::stof(v);
         else error_usage();
         i += 2;
     }
@@ -256,7 +276,7 @@ int main(int argc, char** argv) {
     }
     const Device dev = device == "cpu" ? Device::CPU : Device::HIP;
     try {
-        if (mode == "completion") run_completion(path, dev, prompt, context, num_steps, device_loop != 0, sampling, ctl, regex, top_n);
+        if (mode == "completion") run_completion(path, dev, prompt, context, num_steps, device_loop != 0, sampling, ctl, trunc, regex, top_n);
         else run_perplexity(path, dev, prompt, context, top_n);
     } catch (const std::exception& e) {
         fprintf(stderr, "error: %s\n", e.what());

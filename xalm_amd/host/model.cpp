@@ -136,6 +136,24 @@ std::vector<int> Model::decode_sample_dfa(const int pos, const int n_steps, cons
     return toks;
 }
 
+std::vector<int> Model::decode_sample_adapt(const int pos, const int n_steps, const xh_sampling& sampling,
+                                            const xh_logit_ctl& ctl, const xh_trunc_ctl& trunc,
+                                            const std::vector<int>& history, const bool constrain,
+                                            const uint32_t state_in, const float mu_in, const int stop_a, const int stop_b,
+                                            uint32_t* state_out, float* mu_out, std::vector<float>* logprobs) const {
+    std::vector<int> toks((size_t)std::max(n_steps, 1));
+    std::vector<float> lp((size_t)std::max(n_steps, 1));
+    int done = 0;
+    check(xh_decode_sample_adapt(_ctx, pos, n_steps, &sampling, &ctl, &trunc, history.data(), (int)history.size(),
+                                 constrain ? 1 : 0, state_in, mu_in, stop_a, stop_b, toks.data(), lp.data(), state_out,
+                                 mu_out, &done),
+          _ctx, "xh_decode_sample_adapt");
+    toks.resize((size_t)done);
+    lp.resize((size_t)done);
+    if (logprobs) *logprobs = lp;
+    return toks;
+}
+
 Constraint Constraint::compile(const std::string& regex, const Tokenizer& tokenizer) {
     Constraint c;
     int rc = xh_regex_compile(regex.c_str(), nullptr, nullptr, 0, &c.n_states, &c.start);
@@ -451,6 +469,69 @@ int Sampler::sample(const InferenceState& s, const xh_sampling& sampling, const 
                           ? first
                           : sample_logits(adj.data(), vocab_size, sampling, (uint64_t)pos, nullptr, ctl.min_p);
     state = succ[(size_t)token];
+    return token;
+}
+
+int Sampler::sample(const InferenceState& s, const xh_sampling& sampling, const xh_logit_ctl& ctl,
+                    const xh_trunc_ctl& trunc, const std::vector<int>& history, const int pos,
+                    const Constraint* constraint, uint32_t& state, float& mu, const int stop_a, const int stop_b) const {
+    return sample_adapt_logits(s.logits(), vocab_size, sampling, ctl, trunc, history, pos, constraint, state, mu, stop_a,
+                               stop_b);
+}
+
+int sample_adapt_logits(const float* logits, const int vocab_size, const xh_sampling& sampling, const xh_logit_ctl& ctl,
+                        const xh_trunc_ctl& trunc, const std::vector<int>& history, const int pos,
+                        const Constraint* constraint, uint32_t& state, float& mu, const int stop_a, const int stop_b) {
+    if (!logits || vocab_size <= 0) throw std::invalid_argument("sample: no logits");
+    constexpr float NEG_INF = -std::numeric_limits<float>::infinity();
+    if (mu < 0.f) mu = 2.f * trunc.mirostat_tau;
+    const int stuck = stop_a >= 0 ? stop_a : stop_b >= 0 ? stop_b : 0;
+    if (constraint && state == XH_DFA_DEAD) return stuck;
+    std::vector<float> adj((size_t)vocab_size);
+    const size_t n_win = std::min(history.size(), (size_t)XH_CTL_MAX_WINDOW);
+    if (xh_adjust_logits(logits, vocab_size, &ctl, history.data() + (history.size() - n_win), (int)n_win, adj.data()))
+        throw std::invalid_argument(std::string("sample: ") + xh_last_error(nullptr));
+    std::vector<uint16_t> succ;
+    int first = -1;  // the first allowed token of the order
+    if (constraint) {
+        std::vector<uint8_t> allowed((size_t)vocab_size);
+        succ.resize((size_t)vocab_size);
+        const xh_byte_dfa d = constraint->dfa();
+        if (xh_constraint_mask(&d, constraint->bytes.data(), constraint->offsets.data(), vocab_size, state, stop_a, stop_b,
+                               allowed.data(), succ.data()))
+            throw std::invalid_argument("sample: bad constraint or state");
+        const auto key = [&](const int i) {
+            uint32_t u;
+            memcpy(&u, &adj[(size_t)i], 4);
+            return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+        };
+        for (int i = 0; i < vocab_size; ++i) {
+            if (!allowed[(size_t)i]) adj[(size_t)i] = NEG_INF;
+            else if (first < 0 || key(i) > key(first)) first = i;
+        }
+        if (first < 0) {
+            state = XH_DFA_DEAD;
+            return stuck;
+        }
+    }
+    int token;
+    if (sampling.temperature == 0.f) {
+        token = constraint ? first : sample_logits(adj.data(), vocab_size, sampling, (uint64_t)pos, nullptr, 0.f);
+    } else {
+        std::vector<uint8_t> kept((size_t)vocab_size);
+        if (xh_truncate_host(adj.data(), vocab_size, &sampling, ctl.min_p, &trunc, mu, -1, kept.data(), nullptr, nullptr,
+                             nullptr))
+            throw std::invalid_argument("sample: xh_trunc_ctl outside its definition");
+        std::vector<float> cut(adj);
+        for (int i = 0; i < vocab_size; ++i)
+            if (!kept[(size_t)i]) cut[(size_t)i] = NEG_INF;
+        xh_sampling rest = sampling;  // top-p and the draw over the survivors
+        rest.top_k = 0;
+        token = sample_logits(cut.data(), vocab_size, rest, (uint64_t)pos, nullptr, 0.f);
+        if (trunc.mirostat_tau > 0.f)
+            xh_truncate_host(adj.data(), vocab_size, &sampling, ctl.min_p, &trunc, mu, token, nullptr, nullptr, nullptr, &mu);
+    }
+    if (constraint) state = succ[(size_t)token];
     return token;
 }
 

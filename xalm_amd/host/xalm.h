@@ -131,6 +131,14 @@ public:
                                        const std::vector<int>& history, uint32_t state_in, int stop_a = -1,
                                        int stop_b = -1, uint32_t* state_out = nullptr,
                                        std::vector<float>* logprobs = nullptr) const;
+    // decode_sample_dfa with the adaptive truncation of xh_trunc_ctl (xh_decode_sample_adapt):
+    // constrain = mask with the uploaded constraint; mu_in = Mirostat's mu (2 * tau at the start) or
+    // an earlier call's *mu_out
+    std::vector<int> decode_sample_adapt(int pos, int n_steps, const xh_sampling& sampling, const xh_logit_ctl& ctl,
+                                         const xh_trunc_ctl& trunc, const std::vector<int>& history, bool constrain,
+                                         uint32_t state_in, float mu_in, int stop_a = -1, int stop_b = -1,
+                                         uint32_t* state_out = nullptr, float* mu_out = nullptr,
+                                         std::vector<float>* logprobs = nullptr) const;
     // n_top > 0: the device decode loops also record each step's top list and the emitted token's
     // rank (xh_set_top_logprobs); 0 = off
     void set_top_logprobs(int n_top) const;
@@ -209,10 +217,21 @@ struct Sampler {
     int sample(const InferenceState& s, const xh_sampling& sampling, const xh_logit_ctl& ctl,
                const std::vector<int>& history, int pos, const Constraint& constraint, uint32_t& state, int stop_a,
                int stop_b) const;
+    // the adaptive draw (the definition of xh_trunc_ctl, through xh_truncate_host): n-sigma, typical
+    // and Mirostat cuts over the adjusted and, with a constraint (may be null), masked logits, then
+    // top-p and the draw over the survivors; `mu` is Mirostat's state before the token and is
+    // updated by it (negative = none yet: 2 * tau)
+    int sample(const InferenceState& s, const xh_sampling& sampling, const xh_logit_ctl& ctl, const xh_trunc_ctl& trunc,
+               const std::vector<int>& history, int pos, const Constraint* constraint, uint32_t& state, float& mu,
+               int stop_a, int stop_b) const;
 };
 // the same on a bare logits vector; *n_kept (may be null) = size of the kept set
 // min_p > 0 (xh_logit_ctl): the top-k stage keeps at most the tokens of weight >= min_p
 int sample_logits(const float* logits, int vocab, const xh_sampling& sampling, uint64_t pos, int* n_kept,
                   float min_p = 0.f);
+// the adaptive draw of Sampler::sample on a bare logits vector (raw: the adjustment is applied here)
+int sample_adapt_logits(const float* logits, int vocab, const xh_sampling& sampling, const xh_logit_ctl& ctl,
+                        const xh_trunc_ctl& trunc, const std::vector<int>& history, int pos, const Constraint* constraint,
+                        uint32_t& state, float& mu, int stop_a, int stop_b);
 
 }  // namespace xalm

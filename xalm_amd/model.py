@@ -164,6 +164,34 @@ class Model:
         del keep
         return toks[: done.value].tolist(), lps[: done.value].copy(), int(state_out.value)
 
+    def decode_sample_adapt(self, pos: int, n_steps: int, temperature: float, top_k: int = 0, top_p: float = 1.0,
+                            seed: int = 0, typical_p: float = 1.0, top_n_sigma: float = 0.0, mirostat_tau: float = 0.0,
+                            mirostat_eta: float = 0.1, mu: float | None = None, constrain: bool = False, state: int = 0,
+                            repeat_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+                            last_n: int = 0, min_p: float = 0.0, logit_bias=None, history=(), stop=(-1, -1)):
+        """decode_sample_dfa with the adaptive truncation of xh_trunc_ctl (include/xalm_hip.h):
+        top-n-sigma, locally typical sampling, or Mirostat v2, whose `mu` is carried on the device
+        between steps (None = 2 * mirostat_tau, the start; else the mu a previous call returned).
+        `constrain` masks with the uploaded constraint from `state`.  Returns (tokens,
+        log-probabilities, state after the last token, mu after the last token)."""
+        toks = np.zeros(max(n_steps, 1), dtype=np.int32)
+        lps = np.zeros(max(n_steps, 1), dtype=np.float32)
+        done = ctypes.c_int(0)
+        state_out = ctypes.c_uint32(0)
+        mu_out = ctypes.c_float(0)
+        s = L.XhSampling(temperature, top_k, top_p, seed)
+        c, keep = L.logit_ctl(repeat_penalty, presence_penalty, frequency_penalty, last_n, min_p, logit_bias)
+        t = L.XhTruncCtl(typical_p, top_n_sigma, mirostat_tau, mirostat_eta)
+        hist = np.ascontiguousarray(np.asarray(history, dtype=np.int32))
+        mu_in = 2.0 * mirostat_tau if mu is None else mu
+        L.check(L.lib().xh_decode_sample_adapt(self._ctx, int(pos), int(n_steps), ctypes.byref(s), ctypes.byref(c),
+                                               ctypes.byref(t), L.ptr(hist) if hist.size else None, int(hist.size),
+                                               int(bool(constrain)), int(state), float(mu_in), int(stop[0]), int(stop[1]),
+                                               L.ptr(toks), L.ptr(lps), ctypes.byref(state_out), ctypes.byref(mu_out),
+                                               ctypes.byref(done)), self._ctx)
+        del keep
+        return toks[: done.value].tolist(), lps[: done.value].copy(), int(state_out.value), float(mu_out.value)
+
     def prefill(self, tokens, pos0: int, s: InferenceState | None = None) -> None:
         """Hydrate tokens[0..n) at positions pos0.. (the prompt loop of run_completion,
         src/main.cpp:94-100); the last token's logits land in `s` when given."""
