@@ -48,7 +48,11 @@ $(OBJ)/top_logprobs.o: xalm_amd/csrc/top_logprobs.cpp
 $(OBJ)/truncate.o: xalm_amd/csrc/truncate.cpp
 	@mkdir -p $(OBJ)
 	$(CXX) $(HOSTFLAGS) -ffp-contract=off -MMD -MP -c -o $@ $<
-HIP_OBJS += $(OBJ)/constraint.o $(OBJ)/top_logprobs.o $(OBJ)/truncate.o
+# the host mirror of DRY, the n-gram ban and XTC: plain C++ likewise
+$(OBJ)/seq_host.o: xalm_amd/csrc/seq_host.cpp
+	@mkdir -p $(OBJ)
+	$(CXX) $(HOSTFLAGS) -ffp-contract=off -MMD -MP -c -o $@ $<
+HIP_OBJS += $(OBJ)/constraint.o $(OBJ)/top_logprobs.o $(OBJ)/truncate.o $(OBJ)/seq_host.o
 $(LIB)/libxalm_hip.so: $(HIP_OBJS)
 	@mkdir -p $(LIB)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $^

@@ -380,6 +380,90 @@ int xh_decode_sample_adapt(xh_ctx* ctx, int pos, int n_steps, const xh_sampling*
 int xh_truncate_host(const float* logits, int vocab, const xh_sampling* sampling, float min_p, const xh_trunc_ctl* trunc,
                      float mu, int token, uint8_t* kept_out, int* n_kept_out, float* thr_out, float* mu_out);
 
+/* ---- sequence-aware sampling: DRY, no-repeat-n-gram, XTC ------------------------------------- */
+#define XH_SEQ_MAX_MATCH    64     /* longest repeat DRY measures / largest n-gram */
+#define XH_SEQ_MAX_BREAKERS 1024
+typedef struct xh_seq_ctl {
+    float   dry_multiplier;     /* >= 0, finite; 0 = DRY off                         */
+    float   dry_base;           /* >= 1, finite                                      */
+    int32_t dry_allowed_length; /* 1 .. XH_SEQ_MAX_MATCH                             */
+    int32_t no_repeat_ngram;    /* 0 = off, else 2 .. XH_SEQ_MAX_MATCH               */
+    int32_t seq_last_n;         /* 0 .. XH_CTL_MAX_WINDOW; 0 = DRY and n-gram off    */
+    int32_t n_breakers;         /* 0 .. XH_SEQ_MAX_BREAKERS                          */
+    const int32_t* breaker_token; /* distinct ids in [0, vocab), any order           */
+    float   xtc_probability;    /* in [0, 1]; 0 = XTC off                            */
+    float   xtc_threshold;      /* in (0, 1]                                         */
+} xh_seq_ctl;
+/* The sequence-aware draw: xh_trunc_ctl's definition with two more stages on the logits (DRY and the
+ * n-gram ban) and one more cut (XTC).
+ * - Window.  At step i the sequence window w[0..n) is the last min(seq_last_n, n_history + i) entries
+ *   of history ++ generated[0..i): the ring of xh_logit_ctl and the same history argument.  last_n of
+ *   xh_logit_ctl and seq_last_n are independent lengths over the one ring.
+ * - Match length.  For a position j in [0, n-1) with w[j] == w[n-1], raw_j is the largest k with
+ *   1 <= k <= min(j + 1, XH_SEQ_MAX_MATCH) and w[j-t] == w[n-1-t] for all t < k.  The match may overlap
+ *   the suffix: a a a a matches itself shifted by one.  dry_j is the same with one more condition: no
+ *   w[n-1-t], t < k, is a breaker (so dry_j = 0 when w[n-1] itself is one, and a breaker inside the
+ *   suffix cuts dry_j there but not raw_j).  For every other j both are 0.  The token after the match
+ *   is c = w[j+1]; rep_c = max_j dry_j and ng_c = max_j raw_j over the j with w[j+1] == c, 0 when
+ *   there is none.
+ * - DRY (dry_multiplier > 0).  For every c with rep_c >= dry_allowed_length: p = dry_multiplier, then
+ *   p = p * dry_base exactly rep_c - dry_allowed_length times, each product one f32 rounding (no powf,
+ *   no contraction), then l'_c = l'_c - p, one f32 subtraction.  A p that overflows to +inf gives
+ *   -inf: a ban, inside the contract.
+ * - no-repeat-n-gram (g = no_repeat_ngram >= 2).  Every c with ng_c >= g - 1 gets l'_c = -inf.
+ *   Breakers play no part in it.
+ * - Order.  Both stages run after xh_logit_ctl's adjustment (bias, then the three penalties) and
+ *   before the DFA mask; DRY before the ban.  A token neither stage touches keeps its bits; -inf
+ *   stays -inf.  With every token at -inf the rule "no finite logit: the token is 0" holds.
+ * - Greedy.  Under temperature == 0 DRY and the ban apply as the penalties do; XTC takes no part.
+ * - XTC (xtc_probability > 0, temperature > 0).  It runs after xh_trunc_ctl's typical stage and
+ *   before top-p, over the set C that stage left (typical off: the prefix set).  Masses as there: m
+ *   the maximum of l'', M_i = trunc(expf((l''_i - m) / T) * 2^40), S_C = sum_C M_i.  The coin: Philox
+ *   under the draw's key at the draw's counter (pos + i, 0, 0, 0), word x1 (the draw keeps x0);
+ *   u_x = (x1 >> 8) * 2^-24 and XTC fires iff u_x < xtc_probability, compared in f32.  When it fires,
+ *   cut = (u64)ceil((double)xtc_threshold * (double)S_C) and A = {i in C : M_i >= cut}; mass is
+ *   monotone in the key, so A is the first |A| tokens of C in the sampler's order.  If |A| >= 2 every
+ *   token of A except its last in that order (the lowest key, and among equal keys the highest
+ *   index) becomes -inf in the working copy, as does every token outside C.  top-p and the draw then
+ *   run on the survivors as after the typical stage: the maximum and the masses are the survivors',
+ *   and n_kept without top-p is |C| - (|A| - 1).  |C| is counted as xh_trunc_ctl's loop reports it:
+ *   without top-k, min-p, n-sigma and the typical stage C is every token and |C| = vocab, the -inf
+ *   entries of l'' (a DFA mask, a -inf bias, a ban) included; they carry no mass, are never in A and
+ *   are never drawn.  Everything is decided on integers: keys, indices, masses.
+ * - Mirostat requires xtc_probability == 0, else XH_E_INVALID, in line with its other exclusions.
+ * - One call equals two.  Tokens, DFA states and mu are identical however a run is split; the second
+ *   call is given history ++ the first call's tokens.
+ * - Everything off.  With dry_multiplier == 0, no_repeat_ngram == 0 and xtc_probability == 0 the
+ *   loop emits exactly xh_decode_sample_adapt's tokens, log-probabilities, states and mu bits.
+ * - Invalid arguments.  A field outside its range or NaN (checked whether or not its stage is on), a
+ *   breaker id out of range or duplicated, n_breakers > 0 with a null array, a null xh_seq_ctl, and
+ *   everything xh_decode_sample_adapt rejects: XH_E_INVALID before the device is touched.
+ * - Log-probabilities stay over the raw logits; xh_set_top_logprobs records for this loop too.
+ * How the device evaluates it (xalm_amd/csrc/sample_seq.h): thread j of the 1024-thread workgroup
+ * holds w[j] in LDS and its breaker flag (a binary search in a sorted LDS copy of the breakers),
+ * walks its match back at most XH_SEQ_MAX_MATCH steps, and the lowest j of every distinct c takes
+ * the maxima and writes l'_c; a barrier, then the DFA mask.  XTC sums C's masses, counts A, finds
+ * its lowest key and that key's highest index in C, and writes -inf in one pass each. */
+
+/* xh_decode_sample_adapt's loop with the sequence-aware stages (its own step head and graph; the
+ * other five heads are untouched).  Arguments as there. */
+int xh_decode_sample_seq(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* sampling, const xh_logit_ctl* ctl,
+                         const xh_trunc_ctl* trunc, const xh_seq_ctl* seq, const int* history, int n_history,
+                         int constrain, uint32_t state_in, float mu_in, int stop_token_a, int stop_token_b,
+                         int* tokens_out, float* logprobs_out, uint32_t* state_out, float* mu_out, int* n_done);
+/* Host only, plain C++, no device (also what the host Sampler uses): DRY and the ban on
+ * adjusted_in[vocab] (l' after xh_logit_ctl) under the window's last min(seq_last_n, n_window)
+ * tokens.  out[vocab] = l' after both stages, rep_out / ng_out [vocab] = rep_c / ng_c; any of the
+ * three may be NULL. */
+int xh_seq_adjust_host(const float* adjusted_in, int vocab, const xh_seq_ctl* seq, const int* window, int n_window,
+                       float* out, int* rep_out, int* ng_out);
+/* Host only, plain C++: XTC on logits[vocab] (l'' as it was before the typical stage) at
+ * temperature > 0 for the draw at counter pos.  kept_io[vocab]: in = the 0/1 map of C, out = C after
+ * XTC; m is the maximum of logits[0..vocab) and the masses come from the host's expf.  *n_kept_out =
+ * the survivors' number, *fired_out = 1 when the coin fired (whatever |A|); either may be NULL. */
+int xh_xtc_host(const float* logits, int vocab, float temperature, const xh_seq_ctl* seq, uint64_t seed, uint64_t pos,
+                uint8_t* kept_io, int* n_kept_out, int* fired_out);
+
 /* ---- top-N alternative log-probabilities and ranks ------------------------------------------ */
 #define XH_TOP_MAX 32
 /* The top list of a logits row l[0..V), and the log-probability and rank of one of its tokens.
@@ -410,7 +494,7 @@ int xh_top_logprobs_host(const float* logits, int vocab, int n_rows, int n_top, 
  * pointers, no model and no context. */
 int xh_op_top_logprobs(const float* logits, int vocab, int n_rows, int n_top, const int* targets, int* ids_out,
                        float* lps_out, float* target_lp_out, int* target_rank_out);
-/* n_top > 0: every device decode loop (xh_decode_greedy, _sample, _sample_ext, _sample_dfa, _sample_adapt) also
+/* n_top > 0: every device decode loop (xh_decode_greedy, _sample, _sample_ext, _sample_dfa, _sample_adapt, _sample_seq) also
  * records, per step, the top list of the raw logits its token was chosen from and that token's
  * rank, in context-owned buffers (one launch of the row kernel beside the step head, which itself
  * is unchanged: the tokens are those of n_top = 0).  0 (the default) = off: the steps are exactly
@@ -632,6 +716,19 @@ int xh_op_sample_adapt(const float* logits, int vocab, const xh_sampling* sampli
                        const uint8_t* bytes, const uint32_t* offsets, uint32_t state, float mu, int stop_token_a,
                        int stop_token_b, uint64_t pos0, int n_draws, int* tokens_out, int* n_kept_out,
                        uint32_t* next_state_out, float* mu_out, uint8_t* kept_out, float* thr_out);
+/* The sequence-aware draw (xh_seq_ctl above; the same device functions as xh_decode_sample_seq) on host
+ * logits[vocab], no model and no context; arguments as xh_op_sample_adapt, the window serving
+ * xh_logit_ctl's last_n and xh_seq_ctl's seq_last_n alike.  adjusted_out [vocab] = l' after DRY and
+ * the ban, before the mask; rep_out / ng_out [vocab] = rep_c / ng_c (0 for a token that follows no
+ * match); kept_out [n_draws][vocab] = each draw's 0/1 map after XTC and before top-p (without a
+ * removal: xh_op_sample_adapt's kept_out); xtc_fired_out [n_draws] = 1 where the coin fired, whatever
+ * |A| (0 for a greedy or stuck draw).  All five may be NULL. */
+int xh_op_sample_seq(const float* logits, int vocab, const xh_sampling* sampling, const xh_logit_ctl* ctl,
+                     const xh_trunc_ctl* trunc, const xh_seq_ctl* seq, const int* window, int n_window,
+                     const xh_byte_dfa* dfa, const uint8_t* bytes, const uint32_t* offsets, uint32_t state, float mu,
+                     int stop_token_a, int stop_token_b, uint64_t pos0, int n_draws, int* tokens_out, int* n_kept_out,
+                     uint32_t* next_state_out, float* mu_out, float* adjusted_out, int* rep_out, int* ng_out,
+                     uint8_t* kept_out, int* xtc_fired_out);
 /* Host only, no device, plain C++ (also what the host Sampler uses): allowed_out[t] = 1 if token t
  * is allowed in `state`, else 0, and next_state_out[t] its successor state (XH_DFA_DEAD when
  * forbidden); nothing is allowed in XH_DFA_DEAD. */
@@ -659,10 +756,11 @@ int xh_philox4x32(uint64_t seed, uint64_t pos, uint32_t out[4]);
  * xh_decode_sample_ext under its last parameters, 8 = the constrained step head of
  * xh_decode_sample_dfa under its last parameters, 9 = the top-N row kernel on the context's logits
  * under the current xh_set_top_logprobs width, XH_E_STATE when that is 0, 10 = the adaptive step head
- * of xh_decode_sample_adapt under its last parameters, XH_E_STATE before such a call) over `iters` back-to-back launches with
+ * of xh_decode_sample_adapt under its last parameters, XH_E_STATE before such a call, 11 = the
+ * sequence-aware step head of xh_decode_sample_seq likewise) over `iters` back-to-back launches with
  * the current step parameters (layers rotate, so the Infinity Cache never serves a repeat).
  * 6, 7 and 8 advance the decode loop's position with every launch (7 and 8 also append to their
- * window, 8 also advances the DFA state; 10 advances what 7 and 8 do, and mu): reset or re-hydrate afterwards.  8 needs an xh_decode_sample_dfa
+ * window, 8 also advances the DFA state; 10 and 11 advance what 7 and 8 do, and mu): reset or re-hydrate afterwards.  8 needs an xh_decode_sample_dfa
  * call since the last xh_constraint_set / xh_constraint_set_vocab, else XH_E_STATE. */
 int xh_time_kernel(xh_ctx* ctx, int which, int iters, float* avg_us);
 /* Bytes one launch of that kernel must move (algorithmic). */

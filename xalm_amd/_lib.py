@@ -93,6 +93,29 @@ class XhTruncCtl(ctypes.Structure):
                 ("mirostat_eta", ctypes.c_float)]
 
 
+SEQ_MAX_MATCH, SEQ_MAX_BREAKERS = 64, 1024
+
+
+class XhSeqCtl(ctypes.Structure):
+    """xh_seq_ctl (include/xalm_hip.h): DRY (multiplier 0 = off, base, allowed length), the n-gram ban
+    (0 = off), the sequence window, the breaker ids, XTC (probability 0 = off, threshold)."""
+    _fields_ = [("dry_multiplier", ctypes.c_float), ("dry_base", ctypes.c_float), ("dry_allowed_length", ctypes.c_int32),
+                ("no_repeat_ngram", ctypes.c_int32), ("seq_last_n", ctypes.c_int32), ("n_breakers", ctypes.c_int32),
+                ("breaker_token", ctypes.c_void_p), ("xtc_probability", ctypes.c_float), ("xtc_threshold", ctypes.c_float)]
+
+
+def seq_ctl(dry_multiplier=0.0, dry_base=1.75, dry_allowed_length=2, no_repeat_ngram=0, seq_last_n=0, breakers=(),
+            xtc_probability=0.0, xtc_threshold=0.1):
+    """(XhSeqCtl, the array it points to: keep it alive for the call)."""
+    brk = np.ascontiguousarray([int(t) for t in breakers], dtype=np.int32)
+    q = XhSeqCtl(dry_multiplier, dry_base, dry_allowed_length, no_repeat_ngram, seq_last_n, int(brk.size),
+                 brk.ctypes.data if brk.size else None, xtc_probability, xtc_threshold)
+    return q, brk
+
+
+SEQ_KEYS = ("dry_multiplier", "dry_base", "dry_allowed_length", "no_repeat_ngram", "seq_last_n", "breakers",
+            "xtc_probability", "xtc_threshold")
+
 DFA_DEAD, DFA_MAX_STATES = 0xFFFF, 65535
 
 
@@ -181,6 +204,16 @@ _SIGNATURES = {
     "xh_op_sample_adapt": (_I, [_P, _I, ctypes.POINTER(XhSampling), ctypes.POINTER(XhLogitCtl), ctypes.POINTER(XhTruncCtl),
                                 _P, _I, ctypes.POINTER(XhByteDfa), _P, _P, ctypes.c_uint32, ctypes.c_float, _I, _I,
                                 ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _FP]),
+    "xh_decode_sample_seq": (_I, [_P, _I, _I, ctypes.POINTER(XhSampling), ctypes.POINTER(XhLogitCtl),
+                                  ctypes.POINTER(XhTruncCtl), ctypes.POINTER(XhSeqCtl), _P, _I, _I, ctypes.c_uint32,
+                                  ctypes.c_float, _I, _I, _P, _P, ctypes.POINTER(ctypes.c_uint32),
+                                  ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_I)]),
+    "xh_op_sample_seq": (_I, [_P, _I, ctypes.POINTER(XhSampling), ctypes.POINTER(XhLogitCtl), ctypes.POINTER(XhTruncCtl),
+                              ctypes.POINTER(XhSeqCtl), _P, _I, ctypes.POINTER(XhByteDfa), _P, _P, ctypes.c_uint32,
+                              ctypes.c_float, _I, _I, ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "xh_seq_adjust_host": (_I, [_P, _I, ctypes.POINTER(XhSeqCtl), _P, _I, _P, _P, _P]),
+    "xh_xtc_host": (_I, [_P, _I, ctypes.c_float, ctypes.POINTER(XhSeqCtl), ctypes.c_uint64, ctypes.c_uint64, _P,
+                         ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "xh_truncate_host": (_I, [_P, _I, ctypes.POINTER(XhSampling), ctypes.c_float, ctypes.POINTER(XhTruncCtl),
                               ctypes.c_float, _I, _P, ctypes.POINTER(_I), _FP, _FP]),
     "xh_constraint_mask": (_I, [ctypes.POINTER(XhByteDfa), _P, _P, _I, ctypes.c_uint32, _I, _I, _P, _P]),
@@ -410,6 +443,68 @@ def truncate_host(logits: np.ndarray, temperature: float, top_k: int = 0, top_p:
     check(lib().xh_truncate_host(ptr(lg), lg.size, ctypes.byref(s), float(min_p), ctypes.byref(t), float(mu), int(token),
                                  ptr(kept), ctypes.byref(n), ctypes.byref(thr), ctypes.byref(mu_out)))
     return kept, int(n.value), float(thr.value), float(mu_out.value)
+
+
+def op_sample_seq(logits: np.ndarray, temperature: float, top_k: int, top_p: float, seed: int, pos0: int, n_draws: int,
+                  typical_p: float = 1.0, top_n_sigma: float = 0.0, mirostat_tau: float = 0.0, mirostat_eta: float = 0.1,
+                  mu: float = 0.0, dfa: "ByteDfa | None" = None, blob=None, offsets=None, state: int = 0, stop=(-1, -1),
+                  window=(), **controls):
+    """The sequence-aware draw on a logits vector (xh_op_sample_seq): op_sample_adapt's arguments, with
+    xh_seq_ctl's fields by name (SEQ_KEYS, as `seq_ctl`) among the controls.  Returns op_sample_adapt's
+    dict with "kept" uint8 [n_draws, V] (each draw's set after XTC, before top-p) in place of its
+    "kept" and "thr", and "adjusted" float32 [V] (l' after DRY and the ban, before the mask), "rep",
+    "ng" int32 [V] (rep_c, ng_c), "fired" int32 [n_draws] (the XTC coin)."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    s = XhSampling(temperature, top_k, top_p, seed)
+    q, keep_q = seq_ctl(**{k: controls.pop(k) for k in SEQ_KEYS if k in controls})
+    c, keep = logit_ctl(**controls)
+    t = XhTruncCtl(typical_p, top_n_sigma, mirostat_tau, mirostat_eta)
+    win = np.ascontiguousarray(np.asarray(window, dtype=np.int32))
+    n = max(n_draws, 1)
+    out = {"tokens": np.empty(n, dtype=np.int32), "n_kept": np.empty(n, dtype=np.int32),
+           "states": np.empty(n, dtype=np.uint32), "mu": np.empty(n, dtype=np.float32),
+           "kept": np.empty((n, lg.size), dtype=np.uint8), "adjusted": np.empty(lg.size, dtype=np.float32),
+           "rep": np.empty(lg.size, dtype=np.int32), "ng": np.empty(lg.size, dtype=np.int32),
+           "fired": np.empty(n, dtype=np.int32)}
+    d = dfa.abi() if dfa is not None else None
+    check(lib().xh_op_sample_seq(ptr(lg), lg.size, ctypes.byref(s), ctypes.byref(c), ctypes.byref(t), ctypes.byref(q),
+                                 ptr(win) if win.size else None, win.size, ctypes.byref(d) if d is not None else None,
+                                 ptr(blob) if d is not None else None, ptr(offsets) if d is not None else None,
+                                 int(state), float(mu), int(stop[0]), int(stop[1]), pos0, n_draws, ptr(out["tokens"]),
+                                 ptr(out["n_kept"]), ptr(out["states"]), ptr(out["mu"]), ptr(out["adjusted"]),
+                                 ptr(out["rep"]), ptr(out["ng"]), ptr(out["kept"]), ptr(out["fired"])))
+    del keep, keep_q
+    for k in ("tokens", "n_kept", "states", "mu", "kept", "fired"):
+        out[k] = out[k][:n_draws]
+    return out
+
+
+def seq_adjust_host(adjusted: np.ndarray, window=(), **seq):
+    """DRY and the n-gram ban on l' [V] on the host (xh_seq_adjust_host; xh_seq_ctl's fields as
+    `seq_ctl`): (l' after both stages float32 [V], rep_c int32 [V], ng_c int32 [V]).  No device needed."""
+    lg = np.ascontiguousarray(adjusted, dtype=np.float32)
+    q, keep_q = seq_ctl(**seq)
+    win = np.ascontiguousarray(np.asarray(window, dtype=np.int32))
+    out = np.empty(lg.size, dtype=np.float32)
+    rep = np.empty(lg.size, dtype=np.int32)
+    ng = np.empty(lg.size, dtype=np.int32)
+    check(lib().xh_seq_adjust_host(ptr(lg), lg.size, ctypes.byref(q), ptr(win) if win.size else None, win.size, ptr(out),
+                                   ptr(rep), ptr(ng)))
+    del keep_q
+    return out, rep, ng
+
+
+def xtc_host(logits: np.ndarray, temperature: float, kept: np.ndarray, seed: int, pos: int, **seq):
+    """XTC on l'' [V] over the set `kept` (uint8 [V], the set C) for the draw at counter pos on the
+    host (xh_xtc_host): (C after XTC uint8 [V], its size, whether the coin fired).  No device needed."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    q, keep_q = seq_ctl(**seq)
+    k = np.ascontiguousarray(kept, dtype=np.uint8).copy()
+    n, fired = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().xh_xtc_host(ptr(lg), lg.size, float(temperature), ctypes.byref(q), seed, pos, ptr(k), ctypes.byref(n),
+                            ctypes.byref(fired)))
+    del keep_q
+    return k, int(n.value), bool(fired.value)
 
 
 TOP_MAX = 32

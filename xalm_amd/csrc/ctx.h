@@ -88,6 +88,30 @@ struct AdaptCtl {
     int constrain;
 };
 
+// xh_decode_sample_seq's device block (sample_seq.h): the scalars of xh_seq_ctl (the breakers sit,
+// sorted, in a buffer of their own)
+struct SeqCtl {
+    float dry_multiplier, dry_base;
+    int dry_allowed, ngram, last_n, n_breakers;
+    float xtc_p, xtc_thr;
+};
+
+// What sample_seq_embed_kernel's tail needs (the outputs, the embedding, the rope table), in a device
+// block instead of eleven kernel arguments.  As arguments they sit in SGPRs from the kernel's first
+// instruction; with the sequence stage's scalars on top the head ran out of SGPRs, and the spill slots
+// the register allocator made then stayed in the frame as a 68-byte private segment even where it
+// spilled nothing in the end.  The block is read behind the draw, when the stages' scalars are dead.
+struct SeqTail {
+    int* tokens;
+    float* logprobs;
+    uint32_t* states;
+    const void* emb;
+    float* x;
+    const float* rope_freq;
+    float* rope_cs;
+    int cap, dtype, dim, half;
+};
+
 constexpr int ARGMAX_CANDS = 1024;  // the lm_head workgroups' argmax keys (argmax_embed_kernel's block size)
 
 // The batched prefill's device buffers (prefill.hip), in growth groups.  T = cap[PASS] tokens, the
@@ -182,6 +206,12 @@ struct xh_ctx {
     xalm::AdaptCtl* adapt = nullptr;
     float* adapt_negd = nullptr;
     bool adapt_valid = false, adapt_constrain = false;
+    // xh_decode_sample_seq (sample_seq.h): parameter block, the sorted breakers [XH_SEQ_MAX_BREAKERS];
+    // seq_valid / seq_constrain as adapt_valid / adapt_constrain
+    xalm::SeqCtl* seq = nullptr;
+    int* seq_brk = nullptr;
+    xalm::SeqTail* seq_tail = nullptr;  // written by every xh_decode_sample_seq call
+    bool seq_valid = false, seq_constrain = false;
     int dec_cap = 0;
     // xh_set_top_logprobs (top_logprobs.h): the width on the host and in a device word the row
     // kernel reads, per-step top lists [dec_cap][XH_TOP_MAX] and ranks / log-probabilities of the
@@ -221,7 +251,7 @@ struct xh_ctx {
     int t_max_aw = 16;
     bool use_graphs = true;
     hipGraphExec_t g_logits = nullptr, g_hydrate = nullptr, g_decode = nullptr, g_sample = nullptr,
-                   g_sample_ext = nullptr, g_sample_dfa = nullptr, g_sample_adapt = nullptr;
+                   g_sample_ext = nullptr, g_sample_dfa = nullptr, g_sample_adapt = nullptr, g_sample_seq = nullptr;
     int max_gemv_waves = 4096;  // 16 waves per CU
     // the qkv launch: its whole matrix is one round at 16 waves per CU (every wave one group,
     // requested at once); at 8 waves per CU each wave streams two groups back to back
@@ -342,6 +372,7 @@ void time_sample_head(xh_ctx* ctx);  // one sample_embed_kernel launch on ctx->s
 void time_sample_ext_head(xh_ctx* ctx);  // one sample_ext_embed_kernel launch (xh_time_kernel 7)
 void time_sample_dfa_head(xh_ctx* ctx);  // one sample_dfa_embed_kernel launch (xh_time_kernel 8)
 void time_sample_adapt_head(xh_ctx* ctx);  // one sample_adapt_embed_kernel launch (xh_time_kernel 10)
+void time_sample_seq_head(xh_ctx* ctx);    // one sample_seq_embed_kernel launch (xh_time_kernel 11)
 // top_logprobs_kernel (top_logprobs.h; defined in decode.hip) over n_rows rows on stream s: the
 // kernel's arguments in its order
 void launch_top_logprobs(const float* logits, int vocab, size_t stride, int n_rows, const int* n_top_dev, int n_top,

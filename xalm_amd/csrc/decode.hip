@@ -12,6 +12,7 @@
 #include "dt_launch.h"
 #include "sample.h"
 #include "sample_adapt.h"
+#include "sample_seq.h"
 #include "sample_dfa.h"
 #include "sample_ext.h"
 #include "top_logprobs.h"
@@ -345,16 +346,21 @@ int launch_attn_wo(xh_ctx* ctx, int l, hipStream_t s) {
 // their adjusted copy under ctx->ext (sample_ext_embed_kernel)
 // HEAD_SAMPLE_DFA = drawn from their adjusted and masked copy under ctx->ext and ctx->dfa
 // (sample_dfa_embed_kernel), HEAD_SAMPLE_ADAPT = the same under ctx->adapt's truncation stages
-// (sample_adapt_embed_kernel)
-enum StepHead { HEAD_GIVEN = 0, HEAD_GREEDY = 1, HEAD_SAMPLE = 2, HEAD_SAMPLE_EXT = 3, HEAD_SAMPLE_DFA = 4, HEAD_SAMPLE_ADAPT = 5 };
+// (sample_adapt_embed_kernel), HEAD_SAMPLE_SEQ = the same with ctx->seq's sequence stage and XTC
+// (sample_seq_embed_kernel)
+enum StepHead { HEAD_GIVEN = 0, HEAD_GREEDY = 1, HEAD_SAMPLE = 2, HEAD_SAMPLE_EXT = 3, HEAD_SAMPLE_DFA = 4, HEAD_SAMPLE_ADAPT = 5,
+                HEAD_SAMPLE_SEQ = 6 };
 void launch_sample_head(xh_ctx* ctx, hipStream_t s);
 void launch_sample_ext_head(xh_ctx* ctx, hipStream_t s);
 void launch_sample_dfa_head(xh_ctx* ctx, hipStream_t s);
 void launch_sample_adapt_head(xh_ctx* ctx, hipStream_t s);
+void launch_sample_seq_head(xh_ctx* ctx, hipStream_t s);
 int enqueue_step(xh_ctx* ctx, hipStream_t s, bool with_logits, int head = HEAD_GIVEN) {
     const xh_config& c = ctx->c;
     const int mb = ctx->max_gemv_waves;
-    if (head == HEAD_SAMPLE_ADAPT)
+    if (head == HEAD_SAMPLE_SEQ)
+        launch_sample_seq_head(ctx, s);
+    else if (head == HEAD_SAMPLE_ADAPT)
         launch_sample_adapt_head(ctx, s);
     else if (head == HEAD_SAMPLE_DFA)
         launch_sample_dfa_head(ctx, s);
@@ -437,12 +443,20 @@ void launch_sample_adapt_head(xh_ctx* ctx, hipStream_t s) {
                        ctx->x, (const float*)ctx->rope_freq, ctx->rope_cs, c.head_dim / 2);
 }
 
-// kind: 0 a step with logits, 1 without (hydrate), 2 .. 6 a decode step under the greedy, sampled,
-// extended, constrained and adaptive head
+void launch_sample_seq_head(xh_ctx* ctx, hipStream_t s) {
+    const xh_config& c = ctx->c;
+    hipLaunchKernelGGL(sample_seq_embed_kernel, dim3(1), dim3(SMP_THREADS), 0, s, (const float*)ctx->logits, c.vocab_size,
+                       ctx->ext, ctx->dfa, ctx->adapt, (const SeqCtl*)ctx->seq, ctx->ext_ring, (const int*)ctx->ext_btok,
+                       (const float*)ctx->ext_bval, (const int*)ctx->seq_brk, ctx->ext_adj, ctx->adapt_negd, ctx->sp,
+                       (const SeqTail*)ctx->seq_tail);
+}
+
+// kind: 0 a step with logits, 1 without (hydrate), 2 .. 7 a decode step under the greedy, sampled,
+// extended, constrained, adaptive and sequence-aware head
 int capture(xh_ctx* ctx, int kind, hipGraphExec_t* out) {
     hipGraph_t g = nullptr;
     HIP_TRY(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-    const int rc = enqueue_step(ctx, ctx->stream, kind != 1, kind == 2 ? HEAD_GREEDY : kind == 3 ? HEAD_SAMPLE : kind == 4 ? HEAD_SAMPLE_EXT : kind == 5 ? HEAD_SAMPLE_DFA : kind == 6 ? HEAD_SAMPLE_ADAPT : HEAD_GIVEN);
+    const int rc = enqueue_step(ctx, ctx->stream, kind != 1, kind == 2 ? HEAD_GREEDY : kind == 3 ? HEAD_SAMPLE : kind == 4 ? HEAD_SAMPLE_EXT : kind == 5 ? HEAD_SAMPLE_DFA : kind == 6 ? HEAD_SAMPLE_ADAPT : kind == 7 ? HEAD_SAMPLE_SEQ : HEAD_GIVEN);
     hipError_t e = hipStreamEndCapture(ctx->stream, &g);
     if (rc) { if (g) hipGraphDestroy(g); return rc; }
     if (e != hipSuccess) return set_err(ctx, XH_E_HIP, "graph capture failed: %s", hipGetErrorString(e));
@@ -555,6 +569,7 @@ void xalm::time_sample_head(xh_ctx* ctx) { launch_sample_head(ctx, ctx->stream);
 void xalm::time_sample_ext_head(xh_ctx* ctx) { launch_sample_ext_head(ctx, ctx->stream); }
 void xalm::time_sample_dfa_head(xh_ctx* ctx) { launch_sample_dfa_head(ctx, ctx->stream); }
 void xalm::time_sample_adapt_head(xh_ctx* ctx) { launch_sample_adapt_head(ctx, ctx->stream); }
+void xalm::time_sample_seq_head(xh_ctx* ctx) { launch_sample_seq_head(ctx, ctx->stream); }
 
 void xalm::launch_top_logprobs(const float* logits, int vocab, size_t stride, int n_rows, const int* n_top_dev, int n_top,
                                const StepParams* sp, int cap, const int* targets, int out_stride, int* ids, float* lps,
@@ -577,7 +592,8 @@ void xalm::drop_graphs(xh_ctx* ctx) {
     if (ctx->g_sample_dfa) hipGraphExecDestroy(ctx->g_sample_dfa);
     if (ctx->g_sample_adapt) hipGraphExecDestroy(ctx->g_sample_adapt);
     ctx->g_logits = ctx->g_hydrate = ctx->g_decode = ctx->g_sample = ctx->g_sample_ext = ctx->g_sample_dfa = nullptr;
-    ctx->g_sample_adapt = nullptr;
+    if (ctx->g_sample_seq) hipGraphExecDestroy(ctx->g_sample_seq);
+    ctx->g_sample_adapt = ctx->g_sample_seq = nullptr;
 }
 
 
@@ -1312,6 +1328,205 @@ int xh_op_sample_adapt(const float* logits, int vocab, const xh_sampling* sampli
         if (e == hipSuccess) *thr_out = hp.ap.thr;
     }
     if (e != hipSuccess) return set_err(nullptr, XH_E_HIP, "sample_adapt op failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+namespace {
+// the device block of xh_seq_ctl and its breakers in ascending order (what the head's binary search needs)
+SeqCtl seq_block(const xh_seq_ctl& q, std::vector<int>* sorted) {
+    sorted->assign(q.breaker_token, q.breaker_token + q.n_breakers);
+    std::sort(sorted->begin(), sorted->end());
+    return SeqCtl{q.dry_multiplier, q.dry_base, q.dry_allowed_length, q.no_repeat_ngram, q.seq_last_n, q.n_breakers,
+                  q.xtc_probability, q.xtc_threshold};
+}
+}  // namespace
+
+int xh_decode_sample_seq(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* sampling, const xh_logit_ctl* ctl,
+                         const xh_trunc_ctl* trunc, const xh_seq_ctl* seq, const int* history, int n_history, int constrain,
+                         uint32_t state_in, float mu_in, int stop_a, int stop_b, int* tokens_out, float* logprobs_out,
+                         uint32_t* state_out, float* mu_out, int* n_done) {
+    if (n_done) *n_done = 0;
+    if (!sampling_ok(sampling)) return set_err(ctx, XH_E_INVALID, "bad sampling parameters");
+    if (const char* why = ctl_error(ctl, history, n_history, ctx ? ctx->c.vocab_size : 0))
+        return set_err(ctx, XH_E_INVALID, "%s", why);
+    if (const char* why = trunc_error(trunc, sampling, ctl ? ctl->min_p : 0.f, mu_in))
+        return set_err(ctx, XH_E_INVALID, "%s", why);
+    if (const char* why = seq_error(seq, trunc, ctx ? ctx->c.vocab_size : 0)) return set_err(ctx, XH_E_INVALID, "%s", why);
+    if (!ctx || n_steps < 0) return XH_E_INVALID;
+    if (pos < 0) return set_err(ctx, XH_E_INVALID, "negative pos");
+    if (ctx->c.vocab_size > SMP_MAX_VOCAB) return set_err(ctx, XH_E_INVALID, "vocab_size > %d", SMP_MAX_VOCAB);
+    if (n_steps > ctx->dec_cap) return set_err(ctx, XH_E_INVALID, "n_steps > %d", ctx->dec_cap);
+    if (constrain) {
+        if (!ctx->dfa_vocab_set || !ctx->dfa_n_states)
+            return set_err(ctx, XH_E_INVALID, "constrained decode before xh_constraint_set_vocab and xh_constraint_set");
+        if (state_in != XH_DFA_DEAD && state_in >= (uint32_t)ctx->dfa_n_states)
+            return set_err(ctx, XH_E_INVALID, "state_in %u out of range", state_in);
+        if (stop_a >= ctx->c.vocab_size || stop_b >= ctx->c.vocab_size)
+            return set_err(ctx, XH_E_INVALID, "stop token out of range");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    int rc = check_ready(ctx);
+    if (rc) return rc;
+    const xh_logit_ctl& c = ctl ? *ctl : CTL_OFF;
+    StepParams* h = ctx->sp_host;
+    h->step = 0;
+    h->pos_next = pos;
+    h->max_seq_len = ctx->c.max_seq_len;
+    HIP_TRY(ctx, hipMemcpyAsync(&ctx->sp->step, &h->step, 3 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    // the four blocks (mu and the state in them), the bias table, the breakers and the history's tail
+    const int n_hist = std::min(n_history, XH_CTL_MAX_WINDOW);
+    const ExtCtl blk = ext_block(*sampling, c, n_hist);
+    const AdaptCtl ablk = {trunc->typical_p, trunc->top_n_sigma, trunc->mirostat_tau, trunc->mirostat_eta, mu_in,
+                           constrain ? 1 : 0};
+    std::vector<int> brk;
+    const SeqCtl sblk = seq_block(*seq, &brk);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->ext, &blk, sizeof blk, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->adapt, &ablk, sizeof ablk, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->seq, &sblk, sizeof sblk, hipMemcpyHostToDevice, ctx->stream));
+    const SeqTail tblk = {ctx->dec_tokens, ctx->dec_logprobs, ctx->dec_states, (const void*)ctx->embed, ctx->x,
+                          (const float*)ctx->rope_freq, ctx->rope_cs, ctx->dec_cap, ctx->embed_dt, ctx->c.dim,
+                          ctx->c.head_dim / 2};
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->seq_tail, &tblk, sizeof tblk, hipMemcpyHostToDevice, ctx->stream));
+    if (!brk.empty())
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->seq_brk, brk.data(), brk.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    if (constrain) {
+        const DfaCtl dblk = {ctx->dfa_next, ctx->dfa_accept, ctx->dfa_bytes, ctx->dfa_offsets, ctx->dfa_n_states, state_in,
+                             stop_a < 0 ? -1 : stop_a, stop_b < 0 ? -1 : stop_b};
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->dfa, &dblk, sizeof dblk, hipMemcpyHostToDevice, ctx->stream));
+        ctx->dfa_block_valid = true;
+    }
+    // the adaptive head's timing hook reads ctx->adapt too: it holds this call's parameters now
+    ctx->adapt_valid = true;
+    ctx->adapt_constrain = constrain != 0;
+    ctx->seq_valid = true;
+    ctx->seq_constrain = constrain != 0;
+    if (c.n_bias > 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_btok, c.bias_token, (size_t)c.n_bias * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_bval, c.bias_value, (size_t)c.n_bias * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (n_hist > 0)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_ring, history + (n_history - n_hist), (size_t)n_hist * sizeof(int),
+                                    hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->use_graphs && n_steps > 0 && !ctx->g_sample_seq) {
+        rc = capture(ctx, 7, &ctx->g_sample_seq);
+        if (rc) return rc;
+    }
+    const bool stops = stop_a >= 0 || stop_b >= 0;
+    int done = 0;
+    for (int i = 0; i < n_steps; i++) {
+        if (ctx->use_graphs) {
+            HIP_TRY(ctx, hipGraphLaunch(ctx->g_sample_seq, ctx->stream));
+        } else {
+            rc = eager_step(ctx, true, HEAD_SAMPLE_SEQ);
+            if (rc) return rc;
+        }
+        ctx->cand_valid = true;
+        done = i + 1;
+        if (stops) {
+            int tok = -1;
+            HIP_TRY(ctx, hipMemcpyAsync(&tok, ctx->dec_tokens + i, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (tok == stop_a || tok == stop_b) break;
+        }
+    }
+    if (tokens_out && done)
+        HIP_TRY(ctx, hipMemcpyAsync(tokens_out, ctx->dec_tokens, (size_t)done * sizeof(int), hipMemcpyDeviceToHost,
+                                    ctx->stream));
+    if (logprobs_out && done)
+        HIP_TRY(ctx, hipMemcpyAsync(logprobs_out, ctx->dec_logprobs, (size_t)done * sizeof(float), hipMemcpyDeviceToHost,
+                                    ctx->stream));
+    uint32_t st = state_in;
+    float mu = mu_in;
+    if (done && constrain)
+        HIP_TRY(ctx, hipMemcpyAsync(&st, ctx->dec_states + (done - 1), sizeof st, hipMemcpyDeviceToHost, ctx->stream));
+    if (done) HIP_TRY(ctx, hipMemcpyAsync(&mu, &ctx->adapt->mu, sizeof mu, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (state_out) *state_out = st;
+    if (mu_out) *mu_out = mu;
+    if (n_done) *n_done = done;
+    ctx->top_steps = ctx->top_n > 0 ? done : -1;
+    return check_aw(ctx);
+}
+
+int xh_op_sample_seq(const float* logits, int vocab, const xh_sampling* sampling, const xh_logit_ctl* ctl,
+                     const xh_trunc_ctl* trunc, const xh_seq_ctl* seq, const int* window, int n_window,
+                     const xh_byte_dfa* dfa, const uint8_t* bytes, const uint32_t* offsets, uint32_t state, float mu,
+                     int stop_a, int stop_b, uint64_t pos0, int n_draws, int* tokens_out, int* n_kept_out,
+                     uint32_t* next_state_out, float* mu_out, float* adjusted_out, int* rep_out, int* ng_out,
+                     uint8_t* kept_out, int* xtc_fired_out) {
+    if (!sampling_ok(sampling)) return set_err(nullptr, XH_E_INVALID, "bad sampling parameters");
+    if (!logits || !tokens_out || !n_kept_out || !next_state_out || !mu_out || vocab <= 0 || vocab > SMP_MAX_VOCAB ||
+        n_draws <= 0 || n_draws > 65536)
+        return set_err(nullptr, XH_E_INVALID, "bad sample args");
+    if (const char* why = ctl_error(ctl, window, n_window, vocab)) return set_err(nullptr, XH_E_INVALID, "%s", why);
+    if (const char* why = trunc_error(trunc, sampling, ctl ? ctl->min_p : 0.f, mu)) return set_err(nullptr, XH_E_INVALID, "%s", why);
+    if (const char* why = seq_error(seq, trunc, vocab)) return set_err(nullptr, XH_E_INVALID, "%s", why);
+    if (dfa) {
+        if (const char* why = dfa_error(dfa)) return set_err(nullptr, XH_E_INVALID, "%s", why);
+        if (const char* why = pieces_error(bytes, offsets, vocab)) return set_err(nullptr, XH_E_INVALID, "%s", why);
+        if (const char* why = dfa_state_error(dfa, state)) return set_err(nullptr, XH_E_INVALID, "%s", why);
+        if (stop_a >= vocab || stop_b >= vocab) return set_err(nullptr, XH_E_INVALID, "stop token out of range");
+    }
+    const xh_logit_ctl& c = ctl ? *ctl : CTL_OFF;
+    const int n_win = std::min(n_window, XH_CTL_MAX_WINDOW);
+    const ExtCtl blk = ext_block(*sampling, c, n_win);
+    const AdaptCtl ablk = {trunc->typical_p, trunc->top_n_sigma, trunc->mirostat_tau, trunc->mirostat_eta, mu, dfa ? 1 : 0};
+    std::vector<int> brk;
+    const SeqCtl sblk = seq_block(*seq, &brk);
+    struct Buf {
+        void* p = nullptr;
+        ~Buf() { if (p) hipFree(p); }
+        bool alloc(size_t bytes, const void* src, size_t src_bytes) {
+            if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return false;
+            return !src_bytes || hipMemcpy(p, src, src_bytes, hipMemcpyHostToDevice) == hipSuccess;
+        }
+    } d_logits, d_adj, d_negd, d_snap, d_rep, d_kept, d_rows, d_krows, d_blk, d_ablk, d_sblk, d_brk, d_dfa, d_ring, d_btok,
+        d_bval, d_prep, d_out, d_mu, d_next, d_acc, d_bytes, d_offs;
+    const size_t ns = dfa ? (size_t)dfa->n_states : 0, V = (size_t)vocab, nd = (size_t)n_draws;
+    if (!d_logits.alloc(V * 4, logits, V * 4) || !d_adj.alloc(V * 4, nullptr, 0) || !d_negd.alloc(V * 4, nullptr, 0) ||
+        !d_snap.alloc(V * 4, nullptr, 0) || !d_rep.alloc(2 * V * sizeof(int), nullptr, 0) || !d_kept.alloc(V, nullptr, 0) ||
+        !d_rows.alloc(nd * V * 4, nullptr, 0) || !d_krows.alloc(nd * V, nullptr, 0) ||
+        !d_blk.alloc(sizeof blk, &blk, sizeof blk) || !d_ablk.alloc(sizeof ablk, &ablk, sizeof ablk) ||
+        !d_sblk.alloc(sizeof sblk, &sblk, sizeof sblk) ||
+        !d_brk.alloc(XH_SEQ_MAX_BREAKERS * sizeof(int), brk.data(), brk.size() * sizeof(int)) ||
+        !d_ring.alloc(XH_CTL_MAX_WINDOW * sizeof(int), n_win ? window + (n_window - n_win) : nullptr, (size_t)n_win * sizeof(int)) ||
+        !d_btok.alloc(XH_CTL_MAX_BIAS * sizeof(int), c.bias_token, (size_t)c.n_bias * sizeof(int)) ||
+        !d_bval.alloc(XH_CTL_MAX_BIAS * sizeof(float), c.bias_value, (size_t)c.n_bias * sizeof(float)) ||
+        !d_prep.alloc(sizeof(AdaptOpPrep), nullptr, 0) || !d_out.alloc(4 * nd * sizeof(int), nullptr, 0) ||
+        !d_mu.alloc(nd * sizeof(float), nullptr, 0) ||
+        (dfa && (!d_next.alloc(ns * 512, dfa->next, ns * 512) || !d_acc.alloc(ns, dfa->accept, ns) ||
+                 !d_bytes.alloc(offsets[vocab], bytes, offsets[vocab]) ||
+                 !d_offs.alloc((V + 1) * 4, offsets, (V + 1) * 4))))
+        return set_err(nullptr, XH_E_HIP, "hipMalloc / hipMemcpy failed");
+    if (hipMemset(d_rep.p, 0, 2 * V * sizeof(int)) != hipSuccess) return set_err(nullptr, XH_E_HIP, "hipMemset failed");
+    const DfaCtl dblk = {(const uint16_t*)d_next.p, (const uint8_t*)d_acc.p, (const uint8_t*)d_bytes.p,
+                         (const uint32_t*)d_offs.p, dfa ? dfa->n_states : 0, state, stop_a < 0 ? -1 : stop_a,
+                         stop_b < 0 ? -1 : stop_b};
+    if (!d_dfa.alloc(sizeof dblk, &dblk, sizeof dblk)) return set_err(nullptr, XH_E_HIP, "hipMalloc / hipMemcpy failed");
+    int* d_tok = (int*)d_out.p;
+    hipLaunchKernelGGL(sample_seq_prep_kernel, dim3(1), dim3(SMP_THREADS), 0, nullptr, (const float*)d_logits.p, vocab,
+                       (const ExtCtl*)d_blk.p, (const DfaCtl*)d_dfa.p, (const AdaptCtl*)d_ablk.p, (const SeqCtl*)d_sblk.p,
+                       (const int*)d_ring.p, (const int*)d_btok.p, (const float*)d_bval.p, (const int*)d_brk.p,
+                       (float*)d_adj.p, (float*)d_negd.p, (float*)d_snap.p, (int*)d_rep.p, (int*)d_rep.p + V,
+                       (uint8_t*)d_kept.p, (AdaptOpPrep*)d_prep.p);
+    hipLaunchKernelGGL(sample_seq_op_kernel, dim3(n_draws), dim3(SMP_THREADS), 0, nullptr, (const float*)d_adj.p,
+                       (const uint8_t*)d_kept.p, (float*)d_rows.p, (uint8_t*)d_krows.p, vocab, (const ExtCtl*)d_blk.p,
+                       (const DfaCtl*)d_dfa.p, (const AdaptCtl*)d_ablk.p, (const SeqCtl*)d_sblk.p,
+                       (const AdaptOpPrep*)d_prep.p, (uint32_t)pos0, d_tok, d_tok + nd, (uint32_t*)d_tok + 2 * nd,
+                       (float*)d_mu.p, d_tok + 3 * nd);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(tokens_out, d_tok, nd * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(n_kept_out, d_tok + nd, nd * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(next_state_out, d_tok + 2 * nd, nd * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(mu_out, d_mu.p, nd * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && xtc_fired_out) e = hipMemcpy(xtc_fired_out, d_tok + 3 * nd, nd * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && adjusted_out) e = hipMemcpy(adjusted_out, d_snap.p, V * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rep_out) e = hipMemcpy(rep_out, d_rep.p, V * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && ng_out) e = hipMemcpy(ng_out, (int*)d_rep.p + V, V * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && kept_out) e = hipMemcpy(kept_out, d_krows.p, nd * V, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return set_err(nullptr, XH_E_HIP, "sample_seq op failed: %s", hipGetErrorString(e));
     return 0;
 }
 

@@ -229,7 +229,7 @@ int xh_op_prompt_attn_ring(float* out, uint16_t* k_ring, uint16_t* v_ring, const
 // timing hooks for bench.py
 // ---------------------------------------------------------------------------------------
 int xh_time_kernel(xh_ctx* ctx, int which, int iters, float* avg_us) {
-    if (!ctx || !avg_us || iters <= 0 || which < 0 || which > 10) return XH_E_INVALID;
+    if (!ctx || !avg_us || iters <= 0 || which < 0 || which > 11) return XH_E_INVALID;
     HIP_TRY(ctx, hipSetDevice(ctx->dev));
     int rc = check_ready(ctx);
     if (rc) return rc;
@@ -240,6 +240,11 @@ int xh_time_kernel(xh_ctx* ctx, int which, int iters, float* avg_us) {
     if (which == 10 && !(ctx->adapt_valid && (!ctx->adapt_constrain ||
                                               (ctx->dfa_vocab_set && ctx->dfa_n_states && ctx->dfa_block_valid))))
         return set_err(ctx, XH_E_STATE, "xh_time_kernel 10: no xh_decode_sample_adapt call under the current constraint");
+    // the sequence-aware head reads ctx->adapt and ctx->dfa too: the constraint that counts is the one
+    // last written to ctx->adapt, by either loop
+    if (which == 11 && !(ctx->seq_valid && (!(ctx->seq_constrain || ctx->adapt_constrain) ||
+                                            (ctx->dfa_vocab_set && ctx->dfa_n_states && ctx->dfa_block_valid))))
+        return set_err(ctx, XH_E_STATE, "xh_time_kernel 11: no xh_decode_sample_seq call under the current constraint");
     if (which == 9 && ctx->top_n <= 0) return set_err(ctx, XH_E_STATE, "xh_time_kernel 9: xh_set_top_logprobs is 0");
     const int mb = ctx->max_gemv_waves;
     // launches rotate over the layers, so a repeat never finds its weights in the 256 MB
@@ -259,6 +264,7 @@ int xh_time_kernel(xh_ctx* ctx, int which, int iters, float* avg_us) {
             case 8: time_sample_dfa_head(ctx); return true;
             case 9: time_top_logprobs(ctx); return true;
             case 10: time_sample_adapt_head(ctx); return true;
+            case 11: time_sample_seq_head(ctx); return true;
             default:
                 return launch_attn(attn_args(ctx, l), ctx->c.head_dim, ctx->qpk, ctx->c.n_kv_heads, ctx->t_max,
                                    ctx->stream);

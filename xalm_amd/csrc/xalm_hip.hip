@@ -157,6 +157,9 @@ int xh_create(const xh_config* cfg, int device_ordinal, xh_ctx** out) {
     CREATE_TRY(dmalloc(ctx, &ctx->dec_states, (size_t)ctx->dec_cap));
     CREATE_TRY(dmalloc(ctx, &ctx->adapt, (size_t)1));
     CREATE_TRY(dmalloc(ctx, &ctx->adapt_negd, (size_t)c.vocab_size));
+    CREATE_TRY(dmalloc(ctx, &ctx->seq, (size_t)1));
+    CREATE_TRY(dmalloc(ctx, &ctx->seq_brk, (size_t)XH_SEQ_MAX_BREAKERS));
+    CREATE_TRY(dmalloc(ctx, &ctx->seq_tail, (size_t)1));
     if (hipHostMalloc((void**)&ctx->sp_host, sizeof(StepParams), hipHostMallocDefault) != hipSuccess) {
         g_create_error = "hipHostMalloc failed";
         xh_destroy(ctx);
@@ -204,6 +207,7 @@ void xh_destroy(xh_ctx* ctx) {
     hipFree(ctx->dfa); hipFree(ctx->dfa_bytes); hipFree(ctx->dfa_offsets); hipFree(ctx->dfa_next); hipFree(ctx->dfa_accept);
     hipFree(ctx->dec_states);
     hipFree(ctx->adapt); hipFree(ctx->adapt_negd);
+    hipFree(ctx->seq); hipFree(ctx->seq_brk); hipFree(ctx->seq_tail);
     hipFree(ctx->top_n_dev); hipFree(ctx->top_ids); hipFree(ctx->top_lps); hipFree(ctx->top_rank); hipFree(ctx->top_tlp);
     pf_free(ctx);
     hipFree(ctx->pf_wdq); hipFree(ctx->ppl_tgt); hipFree(ctx->ppl_prob); hipFree(ctx->rope_freq); hipFree(ctx->rope_cs);

@@ -5,6 +5,8 @@
 //                          [-T context] [-n steps] [-g 0|1] [-t temperature] [-k top_k] [-p top_p] [-s seed]
 //                          [-r repeat_penalty] [-w window] [-P presence] [-F frequency] [-M min_p] [-R regex]
 //                          [-L top_logprobs] [-y typical_p] [-S n_sigma] [-U mirostat_tau] [-E mirostat_eta]
+//                          [-D dry_multiplier] [-B dry_base] [-A dry_allowed_length] [-N no_repeat_ngram]
+//                          [-W sequence window] [-X xtc_probability] [-x xtc_threshold]
 //
 // -d selects the device as in the reference (src/main.cpp:465-477); this build ships the HIP
 // device.  -g 1 runs the greedy loop on the device (no host round trip per token); -g 0
@@ -23,6 +25,12 @@
 // -y / -S / -U / -E (xh_trunc_ctl) cut by local typicality, by n standard deviations below the
 // maximum logit, or by Mirostat v2's running target: xh_decode_sample_adapt with -g 1, the host
 // Sampler over xh_truncate_host with -g 0.
+// -D / -B / -A / -N / -W / -X / -x (xh_seq_ctl) penalise the token that would extend a repeat of the
+// recent text (DRY), ban the token that would complete an n-gram already in it, and with probability
+// -X drop every token above probability -x but the least likely of them (XTC): xh_decode_sample_seq
+// with -g 1, the host Sampler over xh_seq_adjust_host and xh_xtc_host with -g 0.  DRY's breakers are
+// the tokens whose piece contains a newline, ':', '"' or '*'; only the 1024 (XH_SEQ_MAX_BREAKERS)
+// lowest ids of them are taken.
 // Stats are wall clock (the reference divides by user+sys CPU time, src/profiler.h:124-129).
 #include <chrono>
 #include <cmath>
@@ -67,6 +75,14 @@ static void error_usage() {
     fprintf(stderr, "  -S <float> top-n-sigma: keep logits within n standard deviations of the maximum, 0 = off (default 0)\n");
     fprintf(stderr, "  -U <float> Mirostat v2 target surprise tau in bits, 0 = off (default 0); takes -k 0 -p 1 -M 0 -y 1 -S 0\n");
     fprintf(stderr, "  -E <float> Mirostat v2 learning rate eta > 0 (default 0.1)\n");
+    fprintf(stderr, "  -D <float> DRY multiplier, 0 = off (default 0): the penalty is D * B^(repeat length - A)\n");
+    fprintf(stderr, "  -B <float> DRY base >= 1 (default 1.75)\n");
+    fprintf(stderr, "  -A <int> DRY allowed length 1 .. 64: shorter repeats are free (default 2)\n");
+    fprintf(stderr, "     breakers: the tokens holding a newline, ':', '\"' or '*', the 1024 lowest ids of them at most\n");
+    fprintf(stderr, "  -N <int> ban the token that would complete an n-gram already present, 2 .. 64, 0 = off (default 0)\n");
+    fprintf(stderr, "  -W <int> sequence window of -D and -N: the last 0 .. 1024 ids of prompt + output (default 1024)\n");
+    fprintf(stderr, "  -X <float> XTC probability in [0, 1], 0 = off (default 0); not with -U\n");
+    fprintf(stderr, "  -x <float> XTC threshold in (0, 1] (default 0.1)\n");
     fprintf(stderr, "  Choose one:\n");
     fprintf(stderr, "    -i <string> input prompt\n");
     fprintf(stderr, "    -f <filepath> input file with prompt\n");
@@ -90,7 +106,7 @@ static void print_top(int token, int rank, const int* ids, const float* lps, int
 
 static void run_completion(const std::string& path, Device dev, const std::string& prompt, int context, int num_steps,
                            bool device_loop, const xh_sampling& sampling, const xh_logit_ctl& ctl,
-                           const xh_trunc_ctl& trunc, const std::string& regex, int top_n) {
+                           const xh_trunc_ctl& trunc, xh_seq_ctl seq, const std::string& regex, int top_n) {
     const XalmFile file = XalmFile::load(path);
     const Model model = Model::from_xalm(file, context, dev);
     InferenceState state(model.config);
@@ -113,6 +129,11 @@ static void run_completion(const std::string& path, Device dev, const std::strin
                      ctl.min_p != 0.f;
     // any truncation on: the adaptive draw on both routes
     const bool adapt = trunc.typical_p != 1.f || trunc.top_n_sigma != 0.f || trunc.mirostat_tau != 0.f;
+    // any sequence stage on: the sequence-aware draw on both routes, with the default breakers
+    const bool seq_on = seq.dry_multiplier != 0.f || seq.no_repeat_ngram != 0 || seq.xtc_probability != 0.f;
+    const std::vector<int> breakers = seq_on ? tokenizer.default_breakers() : std::vector<int>();
+    seq.n_breakers = (int)breakers.size();
+    seq.breaker_token = breakers.data();
     float mu = 2.f * trunc.mirostat_tau;
     Constraint constraint;
     uint32_t dfa_state = 0;
@@ -127,7 +148,9 @@ static void run_completion(const std::string& path, Device dev, const std::strin
     if (device_loop && num_steps > 0) {
         if (top_n > 0) model.set_top_logprobs(top_n);
         const std::vector<int> gen =
-            adapt ? model.decode_sample_adapt((int)encoding.size(), num_steps, sampling, ctl, trunc, encoding,
+            seq_on ? model.decode_sample_seq((int)encoding.size(), num_steps, sampling, ctl, trunc, seq, encoding,
+                                             !regex.empty(), dfa_state, mu, tokenizer.eos_id, tokenizer.eot_id)
+            : adapt ? model.decode_sample_adapt((int)encoding.size(), num_steps, sampling, ctl, trunc, encoding,
                                               !regex.empty(), dfa_state, mu, tokenizer.eos_id, tokenizer.eot_id)
             : !regex.empty() ? model.decode_sample_dfa((int)encoding.size(), num_steps, sampling, ctl, encoding, dfa_state,
                                                      tokenizer.eos_id, tokenizer.eot_id)
@@ -144,7 +167,10 @@ static void run_completion(const std::string& path, Device dev, const std::strin
         }
     } else {
         for (int i = 0; i < num_steps || num_steps == -1; i++) {
-            const int token_id = adapt ? sampler.sample(state, sampling, ctl, trunc, encoding, (int)encoding.size(),
+            const int token_id = seq_on ? sampler.sample(state, sampling, ctl, trunc, seq, encoding, (int)encoding.size(),
+                                                         regex.empty() ? nullptr : &constraint, dfa_state, mu,
+                                                         tokenizer.eos_id, tokenizer.eot_id)
+                                 : adapt ? sampler.sample(state, sampling, ctl, trunc, encoding, (int)encoding.size(),
                                                         regex.empty() ? nullptr : &constraint, dfa_state, mu,
                                                         tokenizer.eos_id, tokenizer.eot_id)
                                  : !regex.empty() ? sampler.sample(state, sampling, ctl, encoding, (int)encoding.size(),
@@ -223,6 +249,7 @@ int main(int argc, char** argv) {
     xh_sampling sampling{0.f, 0, 1.f, 0};
     xh_logit_ctl ctl{1.f, 0.f, 0.f, 64, 0.f, 0, nullptr, nullptr};
     xh_trunc_ctl trunc{1.f, 0.f, 0.f, 0.1f};
+    xh_seq_ctl seq{0.f, 1.75f, 2, 0, XH_CTL_MAX_WINDOW, 0, nullptr, 0.f, 0.1f};
     if (argc >= 2) path = argv[1];
     else error_usage();
     for (int i = 2; i < argc;) {
@@ -257,6 +284,13 @@ int main(int argc, char** argv) {
         else if (f == 'S') trunc.top_n_sigma = std::stof(v);
         else if (f == 'U') trunc.mirostat_tau = std::stof(v);
         else if (f == 'E') trunc.mirostat_eta = std::stof(v);
+        else if (f == 'D') seq.dry_multiplier = std::stof(v);
+        else if (f == 'B') seq.dry_base = std::stof(v);
+        else if (f == 'A') seq.dry_allowed_length = std::stoi(v);
+        else if (f == 'N') seq.no_repeat_ngram = std::stoi(v);
+        else if (f == 'W') seq.seq_last_n = std::stoi(v);
+        else if (f == 'X') seq.xtc_probability = std::stof(v);
+        else if (f == 'x') seq.xtc_threshold = std::stof(v);
         else error_usage();
         i += 2;
     }
@@ -276,7 +310,7 @@ int main(int argc, char** argv) {
     }
     const Device dev = device == "cpu" ? Device::CPU : Device::HIP;
     try {
-        if (mode == "completion") run_completion(path, dev, prompt, context, num_steps, device_loop != 0, sampling, ctl, trunc, regex, top_n);
+        if (mode == "completion") run_completion(path, dev, prompt, context, num_steps, device_loop != 0, sampling, ctl, trunc, seq, regex, top_n);
         else run_perplexity(path, dev, prompt, context, top_n);
     } catch (const std::exception& e) {
         fprintf(stderr, "error: %s\n", e.what());

@@ -154,6 +154,24 @@ std::vector<int> Model::decode_sample_adapt(const int pos, const int n_steps, co
     return toks;
 }
 
+std::vector<int> Model::decode_sample_seq(const int pos, const int n_steps, const xh_sampling& sampling,
+                                          const xh_logit_ctl& ctl, const xh_trunc_ctl& trunc, const xh_seq_ctl& seq,
+                                          const std::vector<int>& history, const bool constrain, const uint32_t state_in,
+                                          const float mu_in, const int stop_a, const int stop_b, uint32_t* state_out,
+                                          float* mu_out, std::vector<float>* logprobs) const {
+    std::vector<int> toks((size_t)std::max(n_steps, 1));
+    std::vector<float> lp((size_t)std::max(n_steps, 1));
+    int done = 0;
+    check(xh_decode_sample_seq(_ctx, pos, n_steps, &sampling, &ctl, &trunc, &seq, history.data(), (int)history.size(),
+                               constrain ? 1 : 0, state_in, mu_in, stop_a, stop_b, toks.data(), lp.data(), state_out, mu_out,
+                               &done),
+          _ctx, "xh_decode_sample_seq");
+    toks.resize((size_t)done);
+    lp.resize((size_t)done);
+    if (logprobs) *logprobs = lp;
+    return toks;
+}
+
 Constraint Constraint::compile(const std::string& regex, const Tokenizer& tokenizer) {
     Constraint c;
     int rc = xh_regex_compile(regex.c_str(), nullptr, nullptr, 0, &c.n_states, &c.start);
@@ -280,6 +298,20 @@ void Tokenizer::pieces(std::vector<uint8_t>& bytes, std::vector<uint32_t>& offse
         offsets.push_back((uint32_t)bytes.size());
     }
     if (bytes.empty()) bytes.push_back(0);  // data() stays non-null
+}
+
+std::vector<int> Tokenizer::default_breakers() const {
+    std::vector<uint8_t> bytes;
+    std::vector<uint32_t> offsets;
+    pieces(bytes, offsets);
+    std::vector<int> out;
+    for (size_t t = 0; t + 1 < offsets.size() && out.size() < (size_t)XH_SEQ_MAX_BREAKERS; t++)
+        for (uint32_t i = offsets[t]; i < offsets[t + 1]; i++)
+            if (bytes[i] == '\n' || bytes[i] == ':' || bytes[i] == '"' || bytes[i] == '*') {
+                out.push_back((int)t);
+                break;
+            }
+    return out;
 }
 
 // greedy longest match over the vocab trie with byte fallback (src/tokenizer.cpp:82-119)
@@ -479,10 +511,26 @@ int Sampler::sample(const InferenceState& s, const xh_sampling& sampling, const 
                                stop_b);
 }
 
+int Sampler::sample(const InferenceState& s, const xh_sampling& sampling, const xh_logit_ctl& ctl,
+                    const xh_trunc_ctl& trunc, const xh_seq_ctl& seq, const std::vector<int>& history, const int pos,
+                    const Constraint* constraint, uint32_t& state, float& mu, const int stop_a, const int stop_b) const {
+    return sample_seq_logits(s.logits(), vocab_size, sampling, ctl, trunc, &seq, history, pos, constraint, state, mu, stop_a,
+                             stop_b);
+}
+
 int sample_adapt_logits(const float* logits, const int vocab_size, const xh_sampling& sampling, const xh_logit_ctl& ctl,
                         const xh_trunc_ctl& trunc, const std::vector<int>& history, const int pos,
                         const Constraint* constraint, uint32_t& state, float& mu, const int stop_a, const int stop_b) {
+    return sample_seq_logits(logits, vocab_size, sampling, ctl, trunc, nullptr, history, pos, constraint, state, mu, stop_a,
+                             stop_b);
+}
+
+int sample_seq_logits(const float* logits, const int vocab_size, const xh_sampling& sampling, const xh_logit_ctl& ctl,
+                      const xh_trunc_ctl& trunc, const xh_seq_ctl* seq, const std::vector<int>& history, const int pos,
+                      const Constraint* constraint, uint32_t& state, float& mu, const int stop_a, const int stop_b) {
     if (!logits || vocab_size <= 0) throw std::invalid_argument("sample: no logits");
+    if (seq && trunc.mirostat_tau > 0.f && seq->xtc_probability != 0.f)
+        throw std::invalid_argument("sample: Mirostat takes xtc_probability 0");
     constexpr float NEG_INF = -std::numeric_limits<float>::infinity();
     if (mu < 0.f) mu = 2.f * trunc.mirostat_tau;
     const int stuck = stop_a >= 0 ? stop_a : stop_b >= 0 ? stop_b : 0;
@@ -491,6 +539,10 @@ int sample_adapt_logits(const float* logits, const int vocab_size, const xh_samp
     const size_t n_win = std::min(history.size(), (size_t)XH_CTL_MAX_WINDOW);
     if (xh_adjust_logits(logits, vocab_size, &ctl, history.data() + (history.size() - n_win), (int)n_win, adj.data()))
         throw std::invalid_argument(std::string("sample: ") + xh_last_error(nullptr));
+    // DRY and the n-gram ban: behind the adjustment, in front of the mask
+    if (seq && xh_seq_adjust_host(adj.data(), vocab_size, seq, history.data() + (history.size() - n_win), (int)n_win,
+                                  adj.data(), nullptr, nullptr))
+        throw std::invalid_argument("sample: xh_seq_ctl outside its definition");
     std::vector<uint16_t> succ;
     int first = -1;  // the first allowed token of the order
     if (constraint) {
@@ -522,6 +574,11 @@ int sample_adapt_logits(const float* logits, const int vocab_size, const xh_samp
         if (xh_truncate_host(adj.data(), vocab_size, &sampling, ctl.min_p, &trunc, mu, -1, kept.data(), nullptr, nullptr,
                              nullptr))
             throw std::invalid_argument("sample: xh_trunc_ctl outside its definition");
+        // XTC over the set the typical stage left, at this draw's counter
+        if (seq && seq->xtc_probability > 0.f &&
+            xh_xtc_host(adj.data(), vocab_size, sampling.temperature, seq, sampling.seed, (uint64_t)pos, kept.data(), nullptr,
+                        nullptr))
+            throw std::invalid_argument("sample: xh_seq_ctl outside its definition");
         std::vector<float> cut(adj);
         for (int i = 0; i < vocab_size; ++i)
             if (!kept[(size_t)i]) cut[(size_t)i] = NEG_INF;

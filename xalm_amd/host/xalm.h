@@ -139,6 +139,12 @@ public:
                                          uint32_t state_in, float mu_in, int stop_a = -1, int stop_b = -1,
                                          uint32_t* state_out = nullptr, float* mu_out = nullptr,
                                          std::vector<float>* logprobs = nullptr) const;
+    // decode_sample_adapt with DRY, the n-gram ban and XTC of xh_seq_ctl (xh_decode_sample_seq)
+    std::vector<int> decode_sample_seq(int pos, int n_steps, const xh_sampling& sampling, const xh_logit_ctl& ctl,
+                                       const xh_trunc_ctl& trunc, const xh_seq_ctl& seq, const std::vector<int>& history,
+                                       bool constrain, uint32_t state_in, float mu_in, int stop_a = -1, int stop_b = -1,
+                                       uint32_t* state_out = nullptr, float* mu_out = nullptr,
+                                       std::vector<float>* logprobs = nullptr) const;
     // n_top > 0: the device decode loops also record each step's top list and the emitted token's
     // rank (xh_set_top_logprobs); 0 = off
     void set_top_logprobs(int n_top) const;
@@ -191,6 +197,9 @@ struct Tokenizer {
     // the piece table of xh_constraint_set_vocab: the vocab string of every token, the single byte
     // for a byte-fallback token; decode_one's strip of the space after BOS is not applied
     void pieces(std::vector<uint8_t>& bytes, std::vector<uint32_t>& offsets) const;
+    // DRY's default sequence breakers: every token whose piece contains a newline, ':', '"' or '*', in
+    // ascending id order; only the first XH_SEQ_MAX_BREAKERS (1024) of them are taken
+    std::vector<int> default_breakers() const;
 };
 
 struct Sampler {
@@ -224,6 +233,12 @@ struct Sampler {
     int sample(const InferenceState& s, const xh_sampling& sampling, const xh_logit_ctl& ctl, const xh_trunc_ctl& trunc,
                const std::vector<int>& history, int pos, const Constraint* constraint, uint32_t& state, float& mu,
                int stop_a, int stop_b) const;
+    // the sequence-aware draw (the definition of xh_seq_ctl, through xh_seq_adjust_host and
+    // xh_xtc_host): DRY and the n-gram ban over `history` behind the adjustment and in front of the
+    // mask, XTC behind the typical stage at this draw's counter
+    int sample(const InferenceState& s, const xh_sampling& sampling, const xh_logit_ctl& ctl, const xh_trunc_ctl& trunc,
+               const xh_seq_ctl& seq, const std::vector<int>& history, int pos, const Constraint* constraint,
+               uint32_t& state, float& mu, int stop_a, int stop_b) const;
 };
 // the same on a bare logits vector; *n_kept (may be null) = size of the kept set
 // min_p > 0 (xh_logit_ctl): the top-k stage keeps at most the tokens of weight >= min_p
@@ -233,5 +248,9 @@ int sample_logits(const float* logits, int vocab, const xh_sampling& sampling, u
 int sample_adapt_logits(const float* logits, int vocab, const xh_sampling& sampling, const xh_logit_ctl& ctl,
                         const xh_trunc_ctl& trunc, const std::vector<int>& history, int pos, const Constraint* constraint,
                         uint32_t& state, float& mu, int stop_a, int stop_b);
+// the sequence-aware draw of Sampler::sample on a bare logits vector (seq null: sample_adapt_logits)
+int sample_seq_logits(const float* logits, int vocab, const xh_sampling& sampling, const xh_logit_ctl& ctl,
+                      const xh_trunc_ctl& trunc, const xh_seq_ctl* seq, const std::vector<int>& history, int pos,
+                      const Constraint* constraint, uint32_t& state, float& mu, int stop_a, int stop_b);
 
 }  // namespace xalm

@@ -192,6 +192,39 @@ class Model:
         del keep
         return toks[: done.value].tolist(), lps[: done.value].copy(), int(state_out.value), float(mu_out.value)
 
+    def decode_sample_seq(self, pos: int, n_steps: int, temperature: float, top_k: int = 0, top_p: float = 1.0,
+                          seed: int = 0, dry_multiplier: float = 0.0, dry_base: float = 1.75, dry_allowed_length: int = 2,
+                          no_repeat_ngram: int = 0, seq_last_n: int = 0, breakers=(), xtc_probability: float = 0.0,
+                          xtc_threshold: float = 0.1, typical_p: float = 1.0, top_n_sigma: float = 0.0,
+                          mirostat_tau: float = 0.0, mirostat_eta: float = 0.1, mu: float | None = None,
+                          constrain: bool = False, state: int = 0, repeat_penalty: float = 1.0,
+                          presence_penalty: float = 0.0, frequency_penalty: float = 0.0, last_n: int = 0,
+                          min_p: float = 0.0, logit_bias=None, history=(), stop=(-1, -1)):
+        """decode_sample_adapt with the sequence-aware stages of xh_seq_ctl (include/xalm_hip.h): DRY
+        (a penalty that grows with the length of the repeat a token would extend, measured over the
+        last `seq_last_n` tokens of history + output and cut at `breakers`), the no-repeat-n-gram ban
+        and XTC (with `xtc_probability`, drop every token above `xtc_threshold` but the least likely
+        of them).  Returns what decode_sample_adapt returns."""
+        toks = np.zeros(max(n_steps, 1), dtype=np.int32)
+        lps = np.zeros(max(n_steps, 1), dtype=np.float32)
+        done = ctypes.c_int(0)
+        state_out = ctypes.c_uint32(0)
+        mu_out = ctypes.c_float(0)
+        s = L.XhSampling(temperature, top_k, top_p, seed)
+        c, keep = L.logit_ctl(repeat_penalty, presence_penalty, frequency_penalty, last_n, min_p, logit_bias)
+        t = L.XhTruncCtl(typical_p, top_n_sigma, mirostat_tau, mirostat_eta)
+        q, keep_q = L.seq_ctl(dry_multiplier, dry_base, dry_allowed_length, no_repeat_ngram, seq_last_n, breakers,
+                              xtc_probability, xtc_threshold)
+        hist = np.ascontiguousarray(np.asarray(history, dtype=np.int32))
+        mu_in = 2.0 * mirostat_tau if mu is None else mu
+        L.check(L.lib().xh_decode_sample_seq(self._ctx, int(pos), int(n_steps), ctypes.byref(s), ctypes.byref(c),
+                                             ctypes.byref(t), ctypes.byref(q), L.ptr(hist) if hist.size else None,
+                                             int(hist.size), int(bool(constrain)), int(state), float(mu_in), int(stop[0]),
+                                             int(stop[1]), L.ptr(toks), L.ptr(lps), ctypes.byref(state_out),
+                                             ctypes.byref(mu_out), ctypes.byref(done)), self._ctx)
+        del keep, keep_q
+        return toks[: done.value].tolist(), lps[: done.value].copy(), int(state_out.value), float(mu_out.value)
+
     def prefill(self, tokens, pos0: int, s: InferenceState | None = None) -> None:
         """Hydrate tokens[0..n) at positions pos0.. (the prompt loop of run_completion,
         src/main.cpp:94-100); the last token's logits land in `s` when given."""
