@@ -51,12 +51,20 @@ enum xh_dtype {
      *   Q5_0 (quants.py:353-393): 22 B = d, u32 qh, 16 bytes;         value d*(q-16), q = 0..31
      *   Q5_1 (quants.py:396-438): 24 B = d, f16 m, u32 qh, 16 bytes;  value d*q + m, q = 0..31
      * XH_OPT_FUSE_ATTN_WO 1: the fused attention + Wo kernel has no block instantiation; a
-     * layer whose Wo is any of the five block types takes the two-launch route. */
+     * layer whose Wo is any of the block types takes the two-launch route.
+     * MXFP4: OCP microscaling FP4, the 4-bit format gfx950 decodes in hardware
+     * (v_cvt_scalef32_pk_f32_fp4).  17 B = e (E8M0), 16 bytes of e2m1 codes in Q4_0's nibble order
+     * (ggml's block_mxfp4).  Code c has sign c >> 3 and magnitude {0, 0.5, 1, 1.5, 2, 3, 4, 6}[c & 7]
+     * (code 8 is -0); a weight is exactly value(c) * 2^(e - 127).  e = 255 (NaN) is invalid: every
+     * upload route answers XH_E_INVALID for a tensor that holds one; every other e, 0 and 254
+     * included, is valid (a product that overflows f32 is outside the contract).  Columns in whole
+     * 32-element blocks, header shape = bytes per row, as for the other blocks. */
     XH_Q8_0 = 20,
     XH_Q4_0 = 21,
     XH_Q4_1 = 22,
     XH_Q5_0 = 23,
-    XH_Q5_1 = 24
+    XH_Q5_1 = 24,
+    XH_MXFP4 = 25
 };
 
 /* ---- tensor kinds (names as in .xalm, src/model.cpp:83-114) ------------------------ */
@@ -137,8 +145,17 @@ int xh_upload_synthetic(xh_ctx* ctx, int tensor_kind, int layer, int dtype, uint
 /* The converter's block quantizer on the host (no context, no device): n_blocks * 32 floats ->
  * n_blocks blocks of `dtype` (any of the five XH_Q*_* block types) in the file layout, the bytes
  * quants.py `quantize` writes.  It is the quantizer of the synthetic weights
- * (include/xalm_synth.h).  XH_E_INVALID for another dtype or a null pointer. */
+ * (include/xalm_synth.h).  XH_E_INVALID for another dtype or a null pointer.
+ * XH_MXFP4: per block amax = max|v|; amax == 0 gives e = 0 and all codes 0; else
+ * E = clamp(floor(log2(amax)) - 2, -127, 127) from the f32 exponent bits (a subnormal amax exactly),
+ * e = E + 127, each code the sign plus the e2m1 magnitude nearest to |v| * 2^-E (an exact product),
+ * ties to the even code, above 6 saturating at 6.  A non-finite input: XH_E_INVALID. */
 int xh_quantize_blocks(int dtype, const float* values, size_t n_blocks, void* out);
+/* The inverse on the host: n_blocks blocks of a block dtype in the file layout -> n_blocks * 32
+ * floats, each the value the kernels decode (d*q, d*(q - bias), fmaf(d, q, m); MXFP4:
+ * ldexpf(value(c), e - 127), so e = 0 yields the f32 subnormals exactly).  XH_E_INVALID for a
+ * non-block dtype, a null pointer or an MXFP4 block with e = 255. */
+int xh_dequantize_blocks(int dtype, const void* blocks, size_t n_blocks, float* out);
 /* Fill KV ring rows [slot0, slot0+n_slots) of one layer with synthetic fp16 N(0, std)-like values. */
 int xh_kv_fill_synthetic(xh_ctx* ctx, int layer, int which, int slot0, int n_slots, uint64_t seed, float std);
 
@@ -593,7 +610,12 @@ int xh_set_graphs(xh_ctx* ctx, int enable);
  * blocks likewise through their exact f16 hi + lo images (d*q has at most 19 significant bits);
  * the affine blocks Q4_1 / Q5_1, whose fmaf(d, q, m) is a general f32 with no exact f16 pair, take
  * the f32-input MFMA kernel under every value >= 1 (lm_head of xh_perplexity included), as bf16
- * and f32 weights do; other weight dtypes
+ * and f32 weights do; MXFP4 (2 significant bits): a matrix whose recorded scale bytes all lie in
+ * 114 <= e <= 140 (0.5 * 2^(e-127) and 6 * 2^(e-127) normal f16) goes through ONE exact f16 image
+ * into gemm16.h under 1 and 4, the fp8 route, no lo half; any other MXFP4 matrix, every MXFP4
+ * matrix under 2 and 3, and the lm_head of xh_perplexity / xh_score take the f32-input MFMA
+ * kernel, which decodes the blocks in registers (xh_prefill_route plans by the same rule: one such
+ * matrix in a layer makes the passes 64 tokens long); other weight dtypes
  * on the f32-input MFMA kernel (activations exactly as the reference) in passes of 64 tokens;
  * 2 = the split-f16 register-streaming MFMA kernel wherever the weights convert exactly to f16
  * (f16, fp8), passes of 64 tokens; 3 = f32-input MFMA only; 4 = as 1 with vendor hipBLASLt in place

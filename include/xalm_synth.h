@@ -207,7 +207,47 @@ XS_FN void xs_quant_q5_1(const float* v, uint8_t* out) {
     xs_put_f16(out + 2, m);
     xs_pack_codes(q, out + 4, out + 8);
 }
-/* one block of `dtype` (20 Q8_0, 21 Q4_0, 22 Q4_1, 23 Q5_0, 24 Q5_1) from 32 floats; returns the
+/* ---- OCP microscaling FP4 (XH_MXFP4 = 25): 32 e2m1 codes under one E8M0 scale, 17 bytes: e, then
+ * 16 bytes with element j in the low and j + 16 in the high nibble of byte j.  Code c is
+ * (c >> 3 ? -1 : 1) * {0, 0.5, 1, 1.5, 2, 3, 4, 6}[c & 7], a weight value(c) * 2^(e - 127).
+ * E = clamp(floor(log2(amax)) - 2, -127, 127) from the exponent bits (a subnormal amax by its
+ * leading bit), so amax * 2^-E lies in [4, 8) unless E is clamped; every |v| * 2^-E is an exact
+ * product (a power of two; where it would underflow it is far below the first threshold), and the
+ * nearest magnitude is chosen by comparisons against the exact midpoints, ties to the even code. */
+XS_FN uint8_t xs_e2m1_code(float v, float inv) {
+    const uint32_t u = xs_f32_bits(v);
+    const float t = xs_bits_f32(u & 0x7FFFFFFFu) * inv;
+    const int c = (t > 0.25f) + (t >= 0.75f) + (t > 1.25f) + (t >= 1.75f) + (t > 2.5f) + (t >= 3.5f) + (t > 5.0f);
+    return (uint8_t)((u >> 31) << 3 | (uint32_t)c);
+}
+/* out: 17 bytes */
+XS_FN void xs_quant_mxfp4(const float* v, uint8_t* out) {
+    uint32_t amax = 0;  /* |v| orders as its bits */
+    for (int k = 0; k < 32; k++) {
+        const uint32_t a = xs_f32_bits(v[k]) & 0x7FFFFFFFu;
+        if (a > amax) amax = a;
+    }
+    if (amax == 0) {
+        for (int k = 0; k < 17; k++) out[k] = 0;
+        return;
+    }
+    int fl;  /* floor(log2(amax)) */
+    if (amax >> 23) {
+        fl = (int)(amax >> 23) - 127;
+    } else {
+        int top = 22;
+        while (!((amax >> top) & 1u)) top--;
+        fl = top - 149;
+    }
+    int E = fl - 2;
+    if (E < -127) E = -127;
+    if (E > 127) E = 127;
+    /* 2^-E: normal for E <= 126; E = 127 (unreachable: fl <= 127) would be the subnormal 2^-127 */
+    const float inv = xs_bits_f32(E <= 126 ? (uint32_t)(127 - E) << 23 : 0x00400000u);
+    out[0] = (uint8_t)(E + 127);
+    for (int j = 0; j < 16; j++) out[1 + j] = (uint8_t)(xs_e2m1_code(v[j], inv) | (xs_e2m1_code(v[j + 16], inv) << 4));
+}
+/* one block of `dtype` (20 Q8_0, 21 Q4_0, 22 Q4_1, 23 Q5_0, 24 Q5_1, 25 MXFP4) from 32 floats; returns the
  * block's bytes, 0 for another dtype */
 XS_FN int xs_quant_block(int dtype, const float* v, uint8_t* out) {
     switch (dtype) {
@@ -216,16 +256,17 @@ XS_FN int xs_quant_block(int dtype, const float* v, uint8_t* out) {
         case 22: xs_quant_q4_1(v, out); return 20;
         case 23: xs_quant_q5_0(v, out); return 22;
         case 24: xs_quant_q5_1(v, out); return 24;
+        case 25: xs_quant_mxfp4(v, out); return 17;
         default: return 0;
     }
 }
 /* synthetic block b of row r of a [rows][cols] tensor: the 32 values xs_value gives elements
- * r*cols + 32b .. +31, quantized (dtype 20 Q8_0 / 21 Q4_0 / 22 Q4_1 / 23 Q5_0 / 24 Q5_1) */
+ * r*cols + 32b .. +31, quantized (dtype 20 Q8_0 / 21 Q4_0 / 22 Q4_1 / 23 Q5_0 / 24 Q5_1 / 25 MXFP4) */
 XS_FN void xs_block(uint8_t* out, int dtype, uint64_t seed, uint64_t r, uint64_t cols, uint64_t b, float mean, float std) {
     float v[32];
     for (int k = 0; k < 32; k++) v[k] = xs_value(seed, r * cols + 32 * b + k, mean, std);
     if (dtype == 20) xs_quant_q8_0(v, out);
-    else if (dtype >= 22 && dtype <= 24) xs_quant_block(dtype, v, out);
+    else if (dtype >= 22 && dtype <= 25) xs_quant_block(dtype, v, out);
     else xs_quant_q4_0(v, out);
 }
 

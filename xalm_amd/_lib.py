@@ -18,11 +18,14 @@ HIP_LIB_PATH = os.environ.get("XALM_HIP_LIB") or os.path.join(LIB_DIR, "libxalm_
 F32, F16, BF16, F8_E4M3, F8_E5M2, U8, Q8 = 1, 2, 3, 6, 7, 8, 9
 # the converter's gguf blocks (convert.py:176-187, quants.py): this build's ids
 Q8_0, Q4_0, Q4_1, Q5_0, Q5_1 = 20, 21, 22, 23, 24
+# OCP microscaling FP4: 32 e2m1 codes under one E8M0 scale byte (include/xalm_hip.h)
+MXFP4 = 25
 DTYPE_BY_NAME = {"F32": F32, "F16": F16, "BF16": BF16, "F8_E4M3": F8_E4M3, "F8_E5M2": F8_E5M2,
-                 "U8": U8, "Q8": Q8, "Q8_0": Q8_0, "Q4_0": Q4_0, "Q4_1": Q4_1, "Q5_0": Q5_0, "Q5_1": Q5_1}
+                 "U8": U8, "Q8": Q8, "Q8_0": Q8_0, "Q4_0": Q4_0, "Q4_1": Q4_1, "Q5_0": Q5_0, "Q5_1": Q5_1,
+                 "MXFP4": MXFP4}
 DTYPE_SIZE = {F32: 4, F16: 2, BF16: 2, F8_E4M3: 1, F8_E5M2: 1, U8: 1, Q8: 1}
-# bytes per 32-element block: f16 d, [f16 m], [u32 qh], codes (quants.py)
-GQ_BLOCK_BYTES = {Q8_0: 34, Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24}
+# bytes per 32-element block: f16 d, [f16 m], [u32 qh], codes (quants.py); MXFP4: e, codes
+GQ_BLOCK_BYTES = {Q8_0: 34, Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24, MXFP4: 17}
 
 
 def row_bytes(dtype: int, n: int) -> int:
@@ -183,6 +186,7 @@ _SIGNATURES = {
     "xh_upload_file": (_I, [_P, _I, _I, _I, ctypes.c_char_p, ctypes.c_uint64, _SZ]),
     "xh_upload_synthetic": (_I, [_P, _I, _I, _I, ctypes.c_uint64, ctypes.c_float, ctypes.c_float]),
     "xh_quantize_blocks": (_I, [_I, _P, _SZ, _P]),
+    "xh_dequantize_blocks": (_I, [_I, _P, _SZ, _P]),
     "xh_kv_fill_synthetic": (_I, [_P, _I, _I, _I, _I, ctypes.c_uint64, ctypes.c_float]),
     "xh_forward": (_I, [_P, _I, _I, _I, _P]),
     "xh_decode_greedy": (_I, [_P, _I, _I, _I, _I, _P, ctypes.POINTER(_I)]),
@@ -303,6 +307,17 @@ def quantize_blocks(dtype: int, values: np.ndarray) -> np.ndarray:
         raise ValueError("quantize_blocks: a block dtype and whole 32-element blocks")
     out = np.empty(v.shape[:-1] + (v.shape[-1] // 32 * GQ_BLOCK_BYTES[dtype],), dtype=np.uint8)
     check(lib().xh_quantize_blocks(dtype, ptr(v), v.size // 32, ptr(out)))
+    return out
+
+
+def dequantize_blocks(dtype: int, blocks: np.ndarray) -> np.ndarray:
+    """The inverse on the host (xh_dequantize_blocks): uint8 [..., k * block bytes] in the file
+    layout -> float32 [..., 32 k], the values the kernels decode.  No device needed."""
+    b = np.ascontiguousarray(blocks, dtype=np.uint8)
+    if dtype not in GQ_BLOCK_BYTES or b.shape[-1] % GQ_BLOCK_BYTES[dtype]:
+        raise ValueError("dequantize_blocks: a block dtype and whole blocks")
+    out = np.empty(b.shape[:-1] + (b.shape[-1] // GQ_BLOCK_BYTES[dtype] * 32,), dtype=np.float32)
+    check(lib().xh_dequantize_blocks(dtype, ptr(b), b.size // GQ_BLOCK_BYTES[dtype], ptr(out)))
     return out
 
 

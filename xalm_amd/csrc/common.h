@@ -151,7 +151,11 @@ template <> struct WDec<XH_Q8> {
 __host__ __device__ constexpr bool gq_has_qh(const int dt) { return dt == XH_Q5_0 || dt == XH_Q5_1; }  // fifth-bit plane
 __host__ __device__ constexpr bool gq_has_m(const int dt) { return dt == XH_Q4_1 || dt == XH_Q5_1; }   // affine: d*q + m
 __host__ __device__ constexpr bool gq_ext(const int dt) { return gq_has_qh(dt) || gq_has_m(dt); }
-__host__ __device__ constexpr bool gq_dt(const int dt) { return dt == XH_Q8_0 || dt == XH_Q4_0 || gq_ext(dt); }
+// OCP microscaling FP4 (XH_MXFP4): the planar row is [e2m1 nibbles: n/2 B][e: 1 B per block], the
+// nibble order Q4_0's, the scale the E8M0 byte (2^(e - 127)) in place of an f16 d.  The hardware
+// converter decodes the codes (WDec<XH_MXFP4>); the scale multiplies in f32.
+__host__ __device__ constexpr bool gq_mx(const int dt) { return dt == XH_MXFP4; }
+__host__ __device__ constexpr bool gq_dt(const int dt) { return dt == XH_Q8_0 || dt == XH_Q4_0 || gq_ext(dt) || gq_mx(dt); }
 // the code the scale multiplies is q - gq_bias (Q8_0: the int8 itself)
 __host__ __device__ constexpr int gq_bias(const int dt) { return dt == XH_Q4_0 ? 8 : dt == XH_Q5_0 ? 16 : 0; }
 __host__ __device__ constexpr size_t gq_qbytes(const int dt, const size_t n) { return dt == XH_Q8_0 ? n : n / 2; }
@@ -161,11 +165,28 @@ __host__ __device__ constexpr size_t gq_d_off(const int dt, const size_t n) {
 }
 __host__ __device__ constexpr size_t gq_m_off(const int dt, const size_t n) { return gq_d_off(dt, n) + n / 16; }
 __host__ __device__ constexpr size_t gq_pitch(const int dt, const size_t n) {
-    return (gq_d_off(dt, n) + (gq_has_m(dt) ? n / 8 : n / 16) + 15) & ~(size_t)15;
+    return (gq_d_off(dt, n) + (gq_mx(dt) ? n / 32 : gq_has_m(dt) ? n / 8 : n / 16) + 15) & ~(size_t)15;
 }
-// bytes of one block in the file: d, m, qh, codes
+// bytes of one block in the file: d, m, qh, codes (MXFP4: e, codes)
 __host__ __device__ constexpr size_t gq_block_bytes(const int dt) {
-    return dt == XH_Q8_0 ? 34 : 18 + (gq_has_qh(dt) ? 4 : 0) + (gq_has_m(dt) ? 2 : 0);
+    return dt == XH_Q8_0 ? 34 : gq_mx(dt) ? 17 : 18 + (gq_has_qh(dt) ? 4 : 0) + (gq_has_m(dt) ? 2 : 0);
+}
+// bytes in front of a file block's codes (d, m, qh; MXFP4: e)
+__host__ __device__ constexpr size_t gq_head_bytes(const int dt) {
+    return gq_mx(dt) ? 1 : 2 + (gq_has_qh(dt) ? 4 : 0) + (gq_has_m(dt) ? 2 : 0);
+}
+// MXFP4: 2^(e - 127) as an f32, exact for every e < 255 (e = 0: the subnormal 2^-127), and the
+// e-range whose weights (0.5 .. 6 times the scale) are all normal f16
+constexpr int MX_E_F16_LO = 114, MX_E_F16_HI = 140;
+__host__ __device__ inline float mx_scale(const uint32_t e) {
+    const uint32_t u = e ? e << 23 : 0x00400000u;
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_bit_cast(float, u);
+#else
+    float f;
+    __builtin_memcpy(&f, &u, 4);
+    return f;
+#endif
 }
 // every block dtype carries one scale set per 32 elements (BLOCK: elements per scale, 0: none)
 template <int DT> struct WScale { static constexpr int BLOCK = gq_dt(DT) ? 32 : 0; };
@@ -186,6 +207,8 @@ __device__ __forceinline__ typename GqSc<DT>::T gq_ld_sc(const char* tail, const
         s.m = gq_has_m(DT) ? (float)__builtin_bit_cast(_Float16, *(const uint16_t*)(dp + 2 * nb + blk * 2)) : 0.f;
         s.qh = gq_has_qh(DT) ? *(const uint32_t*)(tail + blk * 4) : 0u;
         return s;
+    } else if constexpr (gq_mx(DT)) {
+        return mx_scale(*(const uint8_t*)(tail + blk));
     } else {
         return (float)__builtin_bit_cast(_Float16, *(const uint16_t*)(tail + blk * 2));
     }
@@ -213,6 +236,27 @@ template <> struct WDec<XH_Q4_0> {
                 f[4 * i + k] = (float)((int)(b & 15u) - 8);        // element j = 4i + k
                 f[16 + 4 * i + k] = (float)((int)(b >> 4) - 8);    // element j + 16
             }
+    }
+};
+
+// MXFP4: the 32 e2m1 values of a block by v_cvt_scalef32_pk_f32_fp4 (one byte, two codes, per
+// instruction: the low nibble is element j, the high one j + 16), under the neutral scale 1.0;
+// the block's own scale multiplies afterwards (gq_vals, gq_rows), which also covers e = 0
+template <> struct WDec<XH_MXFP4> {
+    static constexpr int E = 32;
+    __device__ __forceinline__ static void dec(const u32x4 v, float* f) {
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const f2_t p0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w[i], 1.0f, 0);
+            const f2_t p1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w[i], 1.0f, 1);
+            const f2_t p2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w[i], 1.0f, 2);
+            const f2_t p3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w[i], 1.0f, 3);
+            f[4 * i + 0] = p0.x; f[16 + 4 * i + 0] = p0.y;
+            f[4 * i + 1] = p1.x; f[16 + 4 * i + 1] = p1.y;
+            f[4 * i + 2] = p2.x; f[16 + 4 * i + 2] = p2.y;
+            f[4 * i + 3] = p3.x; f[16 + 4 * i + 3] = p3.y;
+        }
     }
 };
 
@@ -275,6 +319,12 @@ __device__ __forceinline__ float dec1(const int dtype, const void* p, const size
 __device__ __forceinline__ float dec_row(const int dtype, const void* p, const size_t row, const int n, const int i) {
     if (!gq_dt(dtype)) return dec1(dtype, p, row * (size_t)n + i);
     const uint8_t* r = (const uint8_t*)p + row * gq_pitch(dtype, n);
+    if (gq_mx(dtype)) {
+        // the same converter and the same f32 product as the matvec's decode
+        const uint32_t b = r[(i >> 5) * 16 + (i & 15)];
+        const f2_t v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(b, 1.0f, 0);
+        return ((i & 16) ? v.y : v.x) * mx_scale(r[gq_d_off(dtype, n) + (i >> 5)]);
+    }
     const float d = (float)__builtin_bit_cast(_Float16, *(const uint16_t*)(r + gq_d_off(dtype, n) + (i >> 5) * 2));
     if (dtype == XH_Q8_0) return d * (float)(int8_t)r[i];
     const uint8_t b = r[(i >> 5) * 16 + (i & 15)];

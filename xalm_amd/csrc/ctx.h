@@ -33,8 +33,8 @@ inline int elems_per_16b(int dt) { return 16 / (int)dtype_size(dt); }
 // LDS bytes of the decode matvec's x image for an n-column matrix of dt (gemv_smem_bytes); the
 // f32 image is the smallest of any dtype
 inline size_t matrix_lds_bytes(int dt, int n) {
-    const bool nib = gq_dt(dt) && dt != XH_Q8_0;
-    return gemv_lds_bytes(nib ? 32 : gq_dt(dt) ? 16 : elems_per_16b(dt), nib, n);
+    const bool nib = gq_dt(dt) && dt != XH_Q8_0 && !gq_mx(dt);  // gq4_image
+    return gemv_lds_bytes(nib || gq_mx(dt) ? 32 : gq_dt(dt) ? 16 : elems_per_16b(dt), nib, n);
 }
 // the kernel's decode form for a matrix: fp8 with NaN/Inf codes -> the exact bit decoder
 inline int kdt(int dt, bool special) {
@@ -47,8 +47,12 @@ struct LayerW {
     void* w13 = nullptr; int w13_dt = 0; unsigned w13_have = 0;   // bit0 w1, bit1 w3
     void* wo = nullptr; int wo_dt = 0;
     void* w2 = nullptr; int w2_dt = 0;
-    // fp8 matrices holding NaN/Inf codes (decoded with the exact bit form, no fused kernels)
+    // fp8 matrices holding NaN/Inf codes (decoded with the exact bit form, no fused kernels);
+    // MXFP4 matrices with a scale byte outside [MX_E_F16_LO, MX_E_F16_HI] (no exact f16 image:
+    // the prompt passes decode them in registers)
     bool qkv_x = false, w13_x = false, wo_x = false, w2_x = false;
+    // MXFP4: the least and greatest scale byte e uploaded into each matrix (255, 0: none yet)
+    uint8_t qkv_e[2] = {255, 0}, w13_e[2] = {255, 0}, wo_e[2] = {255, 0}, w2_e[2] = {255, 0};
     void* attn_norm = nullptr; int an_dt = 0;
     void* ffn_norm = nullptr; int fn_dt = 0;
 };
@@ -168,6 +172,7 @@ struct xh_ctx {
     void* embed = nullptr; int embed_dt = 0;
     void* final_norm = nullptr; int final_norm_dt = 0;
     void* wcls = nullptr; int wcls_dt = 0; bool wcls_x = false;
+    uint8_t wcls_e[2] = {255, 0};  // MXFP4: its scale bytes' range, as LayerW's
     int* scan_flag = nullptr;  // device word for the fp8 special-code scan
     int q_dim = 0, kv_dim = 0, qpk = 0;
     uint16_t* kv = nullptr;  // [n_layers][2][max_seq_len][kv_dim]
@@ -341,6 +346,7 @@ int for_dt(int dt, const F& f) {
         case XH_Q4_1: return f.template run<XH_Q4_1>();
         case XH_Q5_0: return f.template run<XH_Q5_0>();
         case XH_Q5_1: return f.template run<XH_Q5_1>();
+        case XH_MXFP4: return f.template run<XH_MXFP4>();
         default: return -1;
     }
 }
@@ -417,5 +423,7 @@ void blas_free(xh_ctx* ctx);
 
 // upload.hip
 void gq_repack(int dt, const uint8_t* src, size_t rows, size_t cols, uint8_t* dst);
+// MXFP4 blocks in the file layout: the least and greatest scale byte (lo > hi: no block)
+void mx_e_range(const uint8_t* src, size_t n_blocks, uint8_t* lo, uint8_t* hi);
 
 }  // namespace xalm

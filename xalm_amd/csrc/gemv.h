@@ -196,8 +196,9 @@ __device__ __forceinline__ float4 load_norm4_nb(const void* w, const int dtype, 
 // The affine / 5-bit blocks (Q4_1 / Q5_0 / Q5_1) share the image; what follows it is the block's
 // sum(x) times the factor their form needs: -8 (Q4_0), -16 (Q5_0: d * sum((q - 16) x)), 1 (affine:
 // the m * sum(x) term).  gq4_image: 0 = no such image, else the dtype (the factor's selector).
+// MXFP4 has none: its codes are signed values the converter decodes, so x is staged as it is.
 template <int DT>
-__device__ __host__ constexpr int gq4_image() { return gq_dt(DT) && DT != XH_Q8_0 ? DT : 0; }
+__device__ __host__ constexpr int gq4_image() { return gq_dt(DT) && DT != XH_Q8_0 && !gq_mx(DT) ? DT : 0; }
 template <int GQ4>
 __device__ __host__ constexpr float gq4_factor() { return GQ4 == XH_Q4_0 ? -8.f : GQ4 == XH_Q5_0 ? -16.f : 1.f; }
 __device__ __forceinline__ const float* gq4_nxs(const float4* xs4, const int n) {
@@ -478,6 +479,28 @@ __device__ __forceinline__ float gq_dot(const u32x4 w, const float4* xv, const u
             s = fma_mix_lo(p23, xv[i].z, s);
             s = fma_mix_hi(p23, xv[i].w, s);
         }
+    } else if constexpr (gq_mx(DT)) {
+        // MXFP4: v_cvt_scalef32_pk_f32_fp4 turns byte k of a word into the two values of its nibbles
+        // (element 4i + k and 16 + 4i + k: Q4_0's order, so the plain E = 32 image serves), scale 1.0:
+        // 0.5 converts + 1 fma per element, no integer work.  Two chains (low / high nibbles) halve
+        // the dependent fma depth.  The caller multiplies the sum by the block's 2^(e - 127).
+        float sh = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const f2_t p0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(ww[i], 1.0f, 0);
+            const f2_t p1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(ww[i], 1.0f, 1);
+            const f2_t p2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(ww[i], 1.0f, 2);
+            const f2_t p3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(ww[i], 1.0f, 3);
+            s = fmaf(p0.x, xv[i].x, s);
+            sh = fmaf(p0.y, xv[4 + i].x, sh);
+            s = fmaf(p1.x, xv[i].y, s);
+            sh = fmaf(p1.y, xv[4 + i].y, sh);
+            s = fmaf(p2.x, xv[i].z, s);
+            sh = fmaf(p2.y, xv[4 + i].z, sh);
+            s = fmaf(p3.x, xv[i].w, s);
+            sh = fmaf(p3.y, xv[4 + i].w, sh);
+        }
+        s += sh;
     } else {
         // Q4_0 (byte j = element j in the low nibble, j + 16 in the high one), denormal form: the
         // nibbles are masked into the mantissa bits of packed f16 with a zero exponent, so each
@@ -525,6 +548,8 @@ __device__ __forceinline__ float gq_dot(const u32x4 w, const float4* xv, const u
 // sum((d q + m) x) as d * sum(q x) + m * sum(x), nx = sum(x): two products per block instead of a
 // fused multiply-add per element; each rounds relative to its own term, |d| sum|q x| and
 // |m| sum|x| (the tests' magnitude), not to their possibly cancelling sum.
+// MXFP4: d = 2^(e - 127), one exact-scale fma per block on the f32 block sum (e = 0: a subnormal
+// f32 operand, which v_fma_f32 takes as it is; the kernels run with f32 denormals on).
 template <int DT, int ROWS>
 __device__ __forceinline__ void gq_rows(const u32x4 (&w)[ROWS], const typename GqSc<DT>::T (&d)[ROWS], const float4* xv,
                                         float* acc, const float nx) {

@@ -38,6 +38,10 @@ constexpr int UNROLL = 4;
 // inside the prologue (-5.7 % per decode layer); the plain shape covers every other n.
 using ShapeShort = GemvShape<512, ROWS, UNROLL, true, 4, false>;
 using ShapeLong = GemvShape<512, ROWS, UNROLL, true, 4, false>;
+// MXFP4 on the staged shapes: 2 chunks in flight.  A chunk is 32 converted values against 32 x
+// floats per row; at 4 chunks x 2 rows the instantiation needs more than the 128 VGPRs of 4 waves
+// per SIMD (hipcc: 24 - 31 spilled), at 2 it takes 106 - 126 and spills none.
+using ShapeStagedMx = GemvShape<512, ROWS, 2, true, 4, false>;
 using ShapePF2 = GemvShape<512, ROWS, UNROLL, true, 4, true, 2>;  // n <= 4096
 using ShapePF8 = GemvShape<512, ROWS, UNROLL, true, 4, true, 8>;  // n <= 16384 (W2 / Wo inputs)
 
@@ -169,9 +173,9 @@ bool launch_gemv_t(const GemvArgs& a, hipStream_t s, int max_waves) {
             if constexpr (Sel::HAS_PF8) return launch_gemv_s<DT, PRO, EPI, ShapePF8>(a, s, max_waves);
             break;
         case SH_SHORT:
-            if constexpr (Sel::HAS_SHORT) return launch_gemv_s<DT, PRO, EPI, ShapeShort>(a, s, max_waves);
+            if constexpr (Sel::HAS_SHORT) return launch_gemv_s<DT, PRO, EPI, std::conditional_t<gq_mx(DT), ShapeStagedMx, ShapeShort>>(a, s, max_waves);
             break;
-        case SH_LONG: return launch_gemv_s<DT, PRO, EPI, ShapeLong>(a, s, max_waves);
+        case SH_LONG: return launch_gemv_s<DT, PRO, EPI, std::conditional_t<gq_mx(DT), ShapeStagedMx, ShapeLong>>(a, s, max_waves);
     }
     return false;
 }

@@ -46,6 +46,11 @@ int xh_op_matmul(float* xout, const float* x, const void* w, int dtype, int n, i
     if (gq_dt(dtype) && n % 32) return set_err(nullptr, XH_E_INVALID, "bad matmul args: n %% 32");
     // gguf blocks: w in the file layout, repacked to the planar device rows
     std::vector<uint8_t> gq_tmp;
+    if (gq_mx(dtype)) {
+        uint8_t lo, hi;
+        mx_e_range((const uint8_t*)w, (size_t)d * (n / 32), &lo, &hi);
+        if (hi == 255) return set_err(nullptr, XH_E_INVALID, "bad matmul args: an MXFP4 block with e = 255 (NaN)");
+    }
     if (gq_dt(dtype)) {
         gq_tmp.resize((size_t)d * dev_row_bytes(dtype, n));
         gq_repack(dtype, (const uint8_t*)w, d, n, gq_tmp.data());

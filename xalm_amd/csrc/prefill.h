@@ -51,7 +51,7 @@ struct PfGemmArgs {
 // (the planar row's scale area) multiplies the decoded codes, w = q * d exact in f32 as
 // quants.py's dequantize (oracle xo_gq_elem), before the MFMA.  The affine / 5-bit blocks (Q4_1 /
 // Q5_0 / Q5_1) bring m and qh from their planes too: w = fmaf(d, q, m), the converter's one
-// rounding (gq_vals, common.h).
+// rounding (gq_vals, common.h).  MXFP4: the converter's e2m1 values times the block's 2^(e - 127).
 template <int DT, bool PIPE, int RT>
 __global__ __launch_bounds__(PF_THREADS) void prefill_gemm_kernel(const PfGemmArgs a) {
     constexpr int E = WDec<DT>::E;
@@ -1283,6 +1283,30 @@ __global__ __launch_bounds__(256) void pf_dequant_gq_kernel(const uint8_t* w, co
         }
         *(u32x4*)(hi + r * (size_t)K + k) = u32x4{h[0], h[1], h[2], h[3]};
         *(u32x4*)(lo + r * (size_t)K + k) = u32x4{l[0], l[1], l[2], l[3]};
+    }
+}
+
+// MXFP4 (planar device rows: e2m1 nibbles, then one scale byte e per 32 elements) -> the exact f16
+// image of every weight for the f16 GEMMs of a prompt pass.  The host sends only matrices whose
+// every e lies in [MX_E_F16_LO, MX_E_F16_HI]: 0.5 * 2^(e - 127) .. 6 * 2^(e - 127) are then normal
+// f16 with 2 significant bits, so neither the f32 product nor the conversion rounds.  One thread
+// per block: 16 B of codes through v_cvt_scalef32_pk_f32_fp4 (WDec<XH_MXFP4>), 64 B of f16 out.
+__global__ __launch_bounds__(256) void pf_dequant_mx_kernel(const uint8_t* w, const int rows, const int K, uint16_t* out) {
+    const size_t pitch = gq_pitch(XH_MXFP4, (size_t)K), e_off = gq_d_off(XH_MXFP4, (size_t)K);
+    const size_t per_row = (size_t)K / 32, total = (size_t)rows * per_row;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const size_t r = i / per_row, b = i - r * per_row;
+        const uint8_t* row = w + r * pitch;
+        const float sc = mx_scale(row[e_off + b]);
+        float f[32];
+        WDec<XH_MXFP4>::dec(*(const u32x4*)(row + 16 * b), f);
+        uint32_t h[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++)
+            h[j] = (uint32_t)f32_to_f16_bits(f[2 * j] * sc) | ((uint32_t)f32_to_f16_bits(f[2 * j + 1] * sc) << 16);
+        u32x4* o = (u32x4*)(out + r * (size_t)K + 32 * b);
+#pragma unroll
+        for (int q = 0; q < 4; q++) o[q] = u32x4{h[4 * q], h[4 * q + 1], h[4 * q + 2], h[4 * q + 3]};
     }
 }
 

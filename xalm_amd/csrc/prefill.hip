@@ -96,18 +96,20 @@ int pf_alloc_group(xh_ctx* ctx, const int g) {
 
 // The model's GEMMs: W [rows][K] of decode form dt.  A layer's four in launch order, and the
 // lm_head (all vocab_size rows; it runs in chunks of PF_CLS_CHUNK).
-struct PfMat { const char* what; int dt; const void* w; int K, rows; };
+// wide: an MXFP4 matrix that takes no f16 image (a scale byte outside [MX_E_F16_LO, MX_E_F16_HI]:
+// the upload's *_x flag; the lm_head always): the f32-input MFMA kernel decodes it in registers.
+struct PfMat { const char* what; int dt; const void* w; int K, rows; bool wide; };
 enum { PF_QKV, PF_WO, PF_W13, PF_W2 };
 std::array<PfMat, 4> pf_layer_mats(const xh_ctx* ctx, const int l) {
     const xh_config& c = ctx->c;
     const LayerW& w = ctx->L[l];
-    return {{{"qkv", kdt(w.qkv_dt, w.qkv_x), w.wqkv, c.dim, ctx->q_dim + 2 * ctx->kv_dim},
-             {"wo", kdt(w.wo_dt, w.wo_x), w.wo, ctx->q_dim, c.dim},
-             {"w1/w3", kdt(w.w13_dt, w.w13_x), w.w13, c.dim, 2 * c.hidden_dim},
-             {"w2", kdt(w.w2_dt, w.w2_x), w.w2, c.hidden_dim, c.dim}}};
+    return {{{"qkv", kdt(w.qkv_dt, w.qkv_x), w.wqkv, c.dim, ctx->q_dim + 2 * ctx->kv_dim, w.qkv_x},
+             {"wo", kdt(w.wo_dt, w.wo_x), w.wo, ctx->q_dim, c.dim, w.wo_x},
+             {"w1/w3", kdt(w.w13_dt, w.w13_x), w.w13, c.dim, 2 * c.hidden_dim, w.w13_x},
+             {"w2", kdt(w.w2_dt, w.w2_x), w.w2, c.hidden_dim, c.dim, w.w2_x}}};
 }
 PfMat pf_cls_mat(const xh_ctx* ctx) {
-    return {"lm_head", kdt(ctx->wcls_dt, ctx->wcls_x), ctx->wcls, ctx->c.dim, ctx->c.vocab_size};
+    return {"lm_head", kdt(ctx->wcls_dt, ctx->wcls_x), ctx->wcls, ctx->c.dim, ctx->c.vocab_size, true};
 }
 // every layer's GEMMs, then one lm_head chunk
 std::vector<PfMat> pf_all_mats(const xh_ctx* ctx) {
@@ -166,7 +168,15 @@ bool pf_f8(int dt) { return dt == XH_F8_E4M3 || dt == XH_F8_E5M2; }
 bool pf_f16w(int dt) { return dt == XH_F16 || pf_f8(dt); }
 // Does the GEMM over W (dtype dt, K columns) run on the row-major split input: gemm16.h
 // (XH_OPT_PREFILL 1: K in whole 64-deep steps) or hipBLASLt (4: a plan for every shape)?
-bool pf_lay0(const xh_ctx* ctx, int dt, int K) {
+bool pf_lay0(const xh_ctx* ctx, int dt, int K, bool wide) {
+    // MXFP4 (2 significant bits): ONE exact f16 image, the fp8 route (XH_OPT_PREFILL 1 and 4), when
+    // every scale byte of the matrix lies in [MX_E_F16_LO, MX_E_F16_HI]; else (wide) the f32-input
+    // MFMA kernel, as under XH_OPT_PREFILL 2 and 3
+    if (gq_mx(dt)) {
+        if (wide || K % 32) return false;
+        if (ctx->prefill_gemm == 1) return K % MM_KMULT == 0;
+        return ctx->prefill_gemm == 4 && blas_ok(ctx) > 0;
+    }
     // gguf blocks: their exact f16 hi + lo images through gemm16.h (XH_OPT_PREFILL 1); the affine
     // blocks (fmaf(d, q, m): no exact f16 pair) always take the f32-input MFMA kernel
     if (gq_has_m(dt)) return false;
@@ -184,7 +194,7 @@ int pf_prepare(xh_ctx* ctx) {
     if (ctx->prefill_gemm == 4 && !blas_ok(ctx)) {
         int ok = 1;
         for (const PfMat& g : gs) {
-            if (!pf_f16w(g.dt)) continue;
+            if (!pf_f16w(g.dt) && !(gq_mx(g.dt) && !g.wide)) continue;
             bool have = false;
             int rc = blas_has_plan(ctx, g.rows, g.K, 2 * PF_TOK_BLAS, &have);
             if (rc) return rc;
@@ -194,8 +204,8 @@ int pf_prepare(xh_ctx* ctx) {
     }
     size_t wdq = 0;  // fp8: one f16 image; gguf blocks: hi and lo images
     for (const PfMat& g : gs)
-        if ((pf_f8(g.dt) || gq_dt(g.dt)) && pf_lay0(ctx, g.dt, g.K))
-            wdq = std::max(wdq, (size_t)g.rows * g.K * (gq_dt(g.dt) ? 2 : 1));
+        if ((pf_f8(g.dt) || gq_dt(g.dt)) && pf_lay0(ctx, g.dt, g.K, g.wide))
+            wdq = std::max(wdq, (size_t)g.rows * g.K * (gq_dt(g.dt) && !gq_mx(g.dt) ? 2 : 1));
     if (wdq > ctx->pf_wdq_elems) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         hipFree(ctx->pf_wdq);
@@ -212,8 +222,8 @@ int pf_prepare(xh_ctx* ctx) {
 // (f32-input MFMA).  XH_OPT_PREFILL 1 / 4: row-major for f16 / e4m3 / e5m2 where the GEMM fits,
 // else the split kernel for fp8; 2: the split kernel for f16 and fp8; 3: never split.  The split
 // kernel also needs a K slicing.
-int pf_layout(const xh_ctx* ctx, int dt, int K, int rows) {
-    if (pf_lay0(ctx, dt, K)) return 0;
+int pf_layout(const xh_ctx* ctx, int dt, int K, int rows, bool wide) {
+    if (pf_lay0(ctx, dt, K, wide)) return 0;
     const bool f8 = pf_f8(dt);
     const int m = ctx->prefill_gemm;
     if (!(m == 2 || ((m == 1 || m == 4) && f8))) return -1;
@@ -228,14 +238,14 @@ uint16_t* pf_lo(xh_ctx* ctx, int layout, int n, int K) {
 }
 // grid of the split kernels: one workgroup per token row, fragments padded to 32-token tiles
 int pf_split_grid(int layout, int n) { return layout ? 32 * ((n + 31) / 32) : n; }
-int pf_layout(const xh_ctx* ctx, const PfMat& g) { return pf_layout(ctx, g.dt, g.K, g.rows); }
+int pf_layout(const xh_ctx* ctx, const PfMat& g) { return pf_layout(ctx, g.dt, g.K, g.rows, g.wide); }
 // Tokens per pass: PF_TOK_MM (gemm16.h) / PF_TOK_BLAS (hipBLASLt) when every layer GEMM takes the
 // row-major input (the lm_head of a perplexity pass aside: it runs on 64-token slices when it
 // cannot), else 64 (the register-streaming MFMA kernels' two token tiles)
 int pf_pass_tokens(const xh_ctx* ctx) {
     for (int l = 0; l < (int)ctx->L.size(); l++)
         for (const PfMat& g : pf_layer_mats(ctx, l))
-            if (!pf_lay0(ctx, g.dt, g.K)) return PF_TOK;
+            if (!pf_lay0(ctx, g.dt, g.K, g.wide)) return PF_TOK;
     return ctx->prefill_gemm == 4 ? PF_TOK_BLAS : PF_TOK_MM;
 }
 // One pass of prefill_batched: m tokens at positions p0.. (ring: all >= max_seq_len), and what one
@@ -304,8 +314,18 @@ int pf_gemm(xh_ctx* ctx, PfPass& ps, const PfMat& g, const float* x, int n, int&
                                    (const u32x4*)w, n16, (u32x4*)ctx->pf_wdq);
             w = ctx->pf_wdq;
         }
+        if (gq_mx(dt)) {
+            // MXFP4 in the f16 range: one exact image, as fp8 (0.53 B read, 2 B written per weight)
+            if ((size_t)rows * K > ctx->pf_wdq_elems || K % 32)
+                return set_err(ctx, XH_E_INVALID, "prefill: %s MXFP4 image does not fit", g.what);
+            const size_t chunks = (size_t)rows * K / 32;
+            const int grid = (int)std::min<size_t>((chunks + 255) / 256, 8192);
+            hipLaunchKernelGGL(pf_dequant_mx_kernel, dim3(grid), dim3(256), 0, ctx->stream, (const uint8_t*)w, rows, K,
+                               ctx->pf_wdq);
+            w = ctx->pf_wdq;
+        }
         const uint16_t* w_lo = nullptr;  // gguf blocks: the lo image, a second GEMM into more partials
-        if (gq_dt(dt)) {
+        if (gq_dt(dt) && !gq_mx(dt)) {
             if ((size_t)2 * rows * K > ctx->pf_wdq_elems || K % 32)
                 return set_err(ctx, XH_E_INVALID, "prefill: %s block image does not fit", g.what);
             const size_t chunks = (size_t)rows * K / 8;
@@ -755,7 +775,7 @@ int pf_logits_probs(xh_ctx* ctx, PfPass& ps, const int* targets, float* probs, c
     const PfMat cls = pf_cls_mat(ctx);
     const size_t cls_rb = dev_row_bytes(ctx->wcls_dt, c.dim);
     // lm_head weights off the hipBLASLt path (bf16 on the fp8 checkpoints): 64-token slices
-    const int tstep = pf_lay0(ctx, cls.dt, c.dim) ? m : PF_TOK;
+    const int tstep = pf_lay0(ctx, cls.dt, c.dim, cls.wide) ? m : PF_TOK;
     for (int r0 = 0; r0 < c.vocab_size; r0 += PF_CLS_CHUNK) {
         PfMat g = cls;
         g.w = (const char*)cls.w + (size_t)r0 * cls_rb;

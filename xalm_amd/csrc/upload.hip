@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <cerrno>
+#include <cmath>
 #include <cstring>
 #include <thread>
 #include <vector>
@@ -56,8 +57,9 @@ int tensor_slot(xh_ctx* ctx, int kind, int layer, int dtype, Slot* out) {
     out->cols = cols;
     out->pitch = rb;
     drop_graphs(ctx);
-    auto plain = [&](void** dst, int* dst_dt, bool* special = nullptr) -> int {
+    auto plain = [&](void** dst, int* dst_dt, bool* special = nullptr, uint8_t* er = nullptr) -> int {
         if (special) *special = false;  // a whole-buffer upload: rescanned after the copy
+        if (er) { er[0] = 255; er[1] = 0; }
         if (*dst && *dst_dt != dtype) {
             if (*dst == ctx->wcls && *dst != ctx->embed) ctx->wcls = nullptr;
             hipFree(*dst);
@@ -78,14 +80,14 @@ int tensor_slot(xh_ctx* ctx, int kind, int layer, int dtype, Slot* out) {
     if (kind == XH_FINAL_NORM) return plain(&ctx->final_norm, &ctx->final_norm_dt);
     if (kind == XH_WCLS) {
         if (ctx->wcls == ctx->embed) ctx->wcls = nullptr;
-        return plain(&ctx->wcls, &ctx->wcls_dt, &ctx->wcls_x);
+        return plain(&ctx->wcls, &ctx->wcls_dt, &ctx->wcls_x, ctx->wcls_e);
     }
     LayerW& w = ctx->L[layer];
     switch (kind) {
         case XH_ATTN_NORM: return plain(&w.attn_norm, &w.an_dt);
         case XH_FFN_NORM: return plain(&w.ffn_norm, &w.fn_dt);
-        case XH_WO: return plain(&w.wo, &w.wo_dt, &w.wo_x);
-        case XH_W2: return plain(&w.w2, &w.w2_dt, &w.w2_x);
+        case XH_WO: return plain(&w.wo, &w.wo_dt, &w.wo_x, w.wo_e);
+        case XH_W2: return plain(&w.w2, &w.w2_dt, &w.w2_x, w.w2_e);
         case XH_WQ: case XH_WK: case XH_WV: {
             // fused [Wq; Wk; Wv] rows, one dtype
             if (w.wqkv && w.qkv_dt != dtype) {
@@ -93,7 +95,10 @@ int tensor_slot(xh_ctx* ctx, int kind, int layer, int dtype, Slot* out) {
                     return set_err(ctx, XH_E_INVALID, "layer %d: q/k/v must share one dtype", layer);
                 hipFree(w.wqkv); w.wqkv = nullptr; w.qkv_have = 0;
             }
-            if (!(w.qkv_have & ~(1u << (kind - XH_WQ)))) w.qkv_x = false;  // no other part holds codes
+            if (!(w.qkv_have & ~(1u << (kind - XH_WQ)))) {  // no other part holds codes
+                w.qkv_x = false;
+                w.qkv_e[0] = 255; w.qkv_e[1] = 0;
+            }
             if (!w.wqkv) HIP_TRY(ctx, hipMalloc(&w.wqkv, (size_t)(ctx->q_dim + 2 * ctx->kv_dim) * rb));
             w.qkv_dt = dtype;
             const size_t row0 = kind == XH_WQ ? 0 : kind == XH_WK ? ctx->q_dim : ctx->q_dim + ctx->kv_dim;
@@ -108,7 +113,10 @@ int tensor_slot(xh_ctx* ctx, int kind, int layer, int dtype, Slot* out) {
                 if (w.w13_have & ~bit) return set_err(ctx, XH_E_INVALID, "layer %d: w1/w3 must share one dtype", layer);
                 hipFree(w.w13); w.w13 = nullptr; w.w13_have = 0;
             }
-            if (!(w.w13_have & ~bit)) w.w13_x = false;
+            if (!(w.w13_have & ~bit)) {
+                w.w13_x = false;
+                w.w13_e[0] = 255; w.w13_e[1] = 0;
+            }
             if (!w.w13) HIP_TRY(ctx, hipMalloc(&w.w13, (size_t)2 * c.hidden_dim * rb));
             w.w13_dt = dtype;
             out->base = (char*)w.w13 + (kind == XH_W3 ? rb : 0);
@@ -153,6 +161,64 @@ int scan_f8(xh_ctx* ctx, int kind, int layer, int dtype, const Slot& s) {
     return 0;
 }
 
+// MXFP4: the least and greatest scale byte of the planar rows of a slot (the e plane behind the
+// codes), into range[0] (min, preset to 255) and range[1] (max, preset to 0)
+__global__ void mx_e_scan_kernel(const uint8_t* base, size_t pitch, size_t rows, size_t cols, int* range) {
+    const size_t nb = cols / 32, off = gq_d_off(XH_MXFP4, cols);
+    int lo = 255, hi = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows * nb; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / nb;
+        const int e = base[r * pitch + off + (i - r * nb)];
+        lo = min(lo, e);
+        hi = max(hi, e);
+    }
+    if (lo <= hi) {
+        atomicMin(range, lo);
+        atomicMax(range + 1, hi);
+    }
+}
+
+// after an upload into slot s: merge the MXFP4 matrix's scale range into its record; a matrix
+// with a scale outside [MX_E_F16_LO, MX_E_F16_HI] has no exact f16 image (the *_x flag: the prompt
+// passes decode it in registers).  e = 255 (NaN) never gets here from a host route (checked before
+// the copy) and the quantizer cannot emit it; a slot that holds one all the same is refused.
+int scan_mx(xh_ctx* ctx, int kind, int layer, int dtype, const Slot& s) {
+    if (!gq_mx(dtype) || kind == XH_ATTN_NORM || kind == XH_FFN_NORM || kind == XH_FINAL_NORM) return 0;
+    const int init[2] = {255, 0};
+    int got[2] = {255, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scan_flag, init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(mx_e_scan_kernel, dim3(1024), dim3(256), 0, ctx->stream, (const uint8_t*)s.base, s.pitch, s.rows,
+                       s.cols, ctx->scan_flag);
+    HIP_TRY(ctx, hipMemcpyAsync(got, ctx->scan_flag, sizeof got, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (got[1] == 255) return set_err(ctx, XH_E_INVALID, "tensor kind %d: an MXFP4 block with e = 255 (NaN)", kind);
+    uint8_t* er = nullptr;
+    bool* x = nullptr;
+    if (kind == XH_WCLS) { er = ctx->wcls_e; x = &ctx->wcls_x; }
+    else if (kind != XH_EMBED) {
+        LayerW& w = ctx->L[layer];
+        switch (kind) {
+            case XH_WQ: case XH_WK: case XH_WV: er = w.qkv_e; x = &w.qkv_x; break;
+            case XH_W1: case XH_W3: er = w.w13_e; x = &w.w13_x; break;
+            case XH_WO: er = w.wo_e; x = &w.wo_x; break;
+            case XH_W2: er = w.w2_e; x = &w.w2_x; break;
+        }
+    }
+    if (!er) return 0;
+    er[0] = (uint8_t)std::min<int>(er[0], got[0]);
+    er[1] = (uint8_t)std::max<int>(er[1], got[1]);
+    *x = er[0] < MX_E_F16_LO || er[1] > MX_E_F16_HI;
+    return 0;
+}
+// a host tensor of MXFP4 blocks before it is copied: e = 255 refused
+int check_mx_host(xh_ctx* ctx, int kind, int dtype, const void* host, size_t bytes) {
+    if (!gq_mx(dtype)) return 0;
+    uint8_t lo, hi;
+    mx_e_range((const uint8_t*)host, bytes / gq_block_bytes(dtype), &lo, &hi);
+    if (lo <= hi && hi == 255) return set_err(ctx, XH_E_INVALID, "tensor kind %d: an MXFP4 block with e = 255 (NaN)", kind);
+    return 0;
+}
+
 __global__ void synth_fill_kernel(char* base, size_t pitch, size_t rows, size_t cols, int dtype, uint64_t seed,
                                   float mean, float std) {
     const size_t n = rows * cols;
@@ -172,16 +238,17 @@ __global__ void synth_fill_kernel(char* base, size_t pitch, size_t rows, size_t 
 void xalm::gq_repack(int dt, const uint8_t* src, size_t rows, size_t cols, uint8_t* dst) {
     const size_t nb = cols / 32, bs = gq_block_bytes(dt);
     const size_t hm = gq_has_m(dt) ? 2 : 0, hq = gq_has_qh(dt) ? 4 : 0;  // header bytes behind d
-    const size_t qb = bs - 2 - hm - hq;
+    const size_t ds = gq_mx(dt) ? 1 : 2;                                 // d (MXFP4: the scale byte e)
+    const size_t qb = bs - gq_head_bytes(dt);
     const size_t pitch = gq_pitch(dt, cols), qbytes = gq_qbytes(dt, cols);
-    const size_t d_off = gq_d_off(dt, cols), m_off = gq_m_off(dt, cols), end = m_off + hm * nb;
+    const size_t d_off = gq_d_off(dt, cols), m_off = gq_m_off(dt, cols), end = gq_mx(dt) ? d_off + nb : m_off + hm * nb;
     auto part = [&](size_t r0, size_t r1) {
         for (size_t r = r0; r < r1; r++) {
             const uint8_t* in = src + r * nb * bs;
             uint8_t* out = dst + r * pitch;
             for (size_t b = 0; b < nb; b++) {
-                memcpy(out + b * qb, in + b * bs + 2 + hm + hq, qb);
-                memcpy(out + d_off + 2 * b, in + b * bs, 2);
+                memcpy(out + b * qb, in + b * bs + ds + hm + hq, qb);
+                memcpy(out + d_off + ds * b, in + b * bs, ds);
                 if (hm) memcpy(out + m_off + 2 * b, in + b * bs + 2, 2);
                 if (hq) memcpy(out + qbytes + 4 * b, in + b * bs + 2 + hm, 4);
             }
@@ -195,6 +262,17 @@ void xalm::gq_repack(int dt, const uint8_t* src, size_t rows, size_t cols, uint8
     for (auto& x : th) x.join();
 }
 
+void xalm::mx_e_range(const uint8_t* src, size_t n_blocks, uint8_t* lo, uint8_t* hi) {
+    uint8_t l = 255, h = 0;
+    for (size_t b = 0; b < n_blocks; b++) {
+        const uint8_t e = src[b * 17];
+        l = std::min(l, e);
+        h = std::max(h, e);
+    }
+    *lo = l;
+    *hi = h;
+}
+
 namespace {
 
 // synthetic gguf blocks: one thread per block, the values and quantizer of xalm_synth.h
@@ -203,13 +281,18 @@ __global__ void synth_gq_kernel(char* base, size_t pitch, size_t rows, size_t co
                                 float std) {
     const size_t nb = cols / 32, qbytes = gq_qbytes(dtype, cols);
     const size_t hm = gq_has_m(dtype) ? 2 : 0, hq = gq_has_qh(dtype) ? 4 : 0;  // header bytes behind d
-    const size_t qb = gq_block_bytes(dtype) - 2 - hm - hq;
+    const size_t qb = gq_block_bytes(dtype) - gq_head_bytes(dtype);
     const size_t d_off = gq_d_off(dtype, cols), m_off = gq_m_off(dtype, cols);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows * nb; i += (size_t)gridDim.x * blockDim.x) {
         const size_t r = i / nb, b = i - r * nb;
         uint8_t blk[34];
         xs_block(blk, dtype, seed, r, cols, b, mean, std);
         char* row = base + r * pitch;
+        if (gq_mx(dtype)) {  // e, then the codes
+            for (size_t k = 0; k < qb; k++) row[b * qb + k] = (char)blk[1 + k];
+            row[d_off + b] = (char)blk[0];
+            continue;
+        }
         for (size_t k = 0; k < qb; k++) row[b * qb + k] = (char)blk[2 + hm + hq + k];
         row[d_off + 2 * b] = (char)blk[0];
         row[d_off + 2 * b + 1] = (char)blk[1];
@@ -249,6 +332,7 @@ int xh_upload(xh_ctx* ctx, int kind, int layer, int dtype, const void* host, siz
     HIP_TRY(ctx, hipSetDevice(ctx->dev));
     Slot s;
     int rc = check_bytes(ctx, kind, dtype, bytes);
+    if (!rc) rc = check_mx_host(ctx, kind, dtype, host, bytes);
     if (!rc) rc = tensor_slot(ctx, kind, layer, dtype, &s);
     if (rc) return rc;
     if (gq_dt(dtype)) {
@@ -256,7 +340,7 @@ int xh_upload(xh_ctx* ctx, int kind, int layer, int dtype, const void* host, siz
         std::vector<uint8_t> tmp(s.rows * rb);
         gq_repack(dtype, (const uint8_t*)host, s.rows, s.cols, tmp.data());
         HIP_TRY(ctx, copy2d_sync(ctx, s.base, s.pitch, tmp.data(), rb, rb, s.rows));
-        return 0;
+        return scan_mx(ctx, kind, layer, dtype, s);
     }
     HIP_TRY(ctx, copy2d_sync(ctx, s.base, s.pitch, host, s.cols * dtype_size(dtype), s.cols * dtype_size(dtype),
                                  s.rows));
@@ -289,7 +373,8 @@ int xh_upload_file(xh_ctx* ctx, int kind, int layer, int dtype, const char* path
     close(fd);
     if (map == MAP_FAILED) return set_err(ctx, XH_E_INVALID, "%s: mmap: %s", path, strerror(map_errno));
     Slot s;
-    rc = tensor_slot(ctx, kind, layer, dtype, &s);
+    rc = check_mx_host(ctx, kind, dtype, (const char*)map + (offset - a0), bytes);
+    if (!rc) rc = tensor_slot(ctx, kind, layer, dtype, &s);
     if (!rc && gq_dt(dtype)) {
         // gguf blocks: repacked on the host from the mapping (planar device rows)
         const size_t rb = dev_row_bytes(dtype, s.cols);
@@ -307,6 +392,7 @@ int xh_upload_file(xh_ctx* ctx, int kind, int layer, int dtype, const char* path
         if (e != hipSuccess) rc = set_err(ctx, XH_E_HIP, "%s: copy to the device: %s", path, hipGetErrorString(e));
     }
     munmap(map, len);
+    if (!rc) rc = scan_mx(ctx, kind, layer, dtype, s);
     return rc ? rc : scan_f8(ctx, kind, layer, dtype, s);
 }
 
@@ -325,13 +411,49 @@ int xh_upload_synthetic(xh_ctx* ctx, int kind, int layer, int dtype, uint64_t se
                            dtype, seed, mean, std);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = scan_mx(ctx, kind, layer, dtype, s))) return rc;
     return scan_f8(ctx, kind, layer, dtype, s);
 }
 
 int xh_quantize_blocks(int dtype, const float* values, size_t n_blocks, void* out) {
     if (!gq_dt(dtype) || !values || !out) return set_err(nullptr, XH_E_INVALID, "quantize_blocks: dtype %d is no block type, or a null pointer", dtype);
     const size_t bs = gq_block_bytes(dtype);
+    if (gq_mx(dtype))
+        for (size_t i = 0; i < 32 * n_blocks; i++)
+            if (!std::isfinite(values[i])) return set_err(nullptr, XH_E_INVALID, "quantize_blocks: value %zu is not finite", i);
     for (size_t b = 0; b < n_blocks; b++) xs_quant_block(dtype, values + 32 * b, (uint8_t*)out + b * bs);
+    return 0;
+}
+
+int xh_dequantize_blocks(int dtype, const void* blocks, size_t n_blocks, float* out) {
+    if (!gq_dt(dtype) || !blocks || !out) return set_err(nullptr, XH_E_INVALID, "dequantize_blocks: dtype %d is no block type, or a null pointer", dtype);
+    static const float E2M1[8] = {0.f, 0.5f, 1.f, 1.5f, 2.f, 3.f, 4.f, 6.f};
+    const size_t bs = gq_block_bytes(dtype);
+    auto f16 = [](const uint8_t* p) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(p[0] | p[1] << 8)); };
+    for (size_t b = 0; b < n_blocks; b++) {
+        const uint8_t* in = (const uint8_t*)blocks + b * bs;
+        float* o = out + 32 * b;
+        if (gq_mx(dtype)) {
+            if (in[0] == 255) return set_err(nullptr, XH_E_INVALID, "dequantize_blocks: block %zu has e = 255 (NaN)", b);
+            for (int j = 0; j < 32; j++) {
+                const unsigned c = j < 16 ? in[1 + j] & 15u : in[1 + j - 16] >> 4;
+                o[j] = ldexpf((c & 8u) ? -E2M1[c & 7u] : E2M1[c & 7u], (int)in[0] - 127);
+            }
+            continue;
+        }
+        const float d = f16(in), m = gq_has_m(dtype) ? f16(in + 2) : 0.f;
+        const uint8_t* qs = in + gq_head_bytes(dtype);
+        if (dtype == XH_Q8_0) {
+            for (int j = 0; j < 32; j++) o[j] = d * (float)(int8_t)qs[j];
+            continue;
+        }
+        uint32_t qh = 0;
+        if (gq_has_qh(dtype)) memcpy(&qh, in + 2 + (gq_has_m(dtype) ? 2 : 0), 4);
+        for (int j = 0; j < 32; j++) {
+            const int q = (int)(j < 16 ? qs[j] & 15u : qs[j - 16] >> 4) + (int)(((qh >> j) & 1u) << 4) - gq_bias(dtype);
+            o[j] = gq_has_m(dtype) ? fmaf(d, (float)q, m) : d * (float)q;  // d * q is exact
+        }
+    }
     return 0;
 }
 

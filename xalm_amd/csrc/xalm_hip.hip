@@ -127,7 +127,7 @@ int xh_create(const xh_config* cfg, int device_ordinal, xh_ctx** out) {
     CREATE_TRY(dmalloc(ctx, &ctx->attn_cnt, (size_t)c.n_kv_heads));
     CREATE_TRY(dmalloc(ctx, &ctx->aw_sync, (size_t)c.n_layers * AW_SYNC_WORDS));
     CREATE_TRY(dmalloc(ctx, &ctx->cand, (size_t)ARGMAX_CANDS));
-    CREATE_TRY(dmalloc(ctx, &ctx->scan_flag, (size_t)1));
+    CREATE_TRY(dmalloc(ctx, &ctx->scan_flag, (size_t)2));  // fp8: one flag; MXFP4: (min e, max e)
     CREATE_TRY(dmalloc(ctx, &ctx->samp, (size_t)1));
     CREATE_TRY(dmalloc(ctx, &ctx->ext, (size_t)1));
     CREATE_TRY(dmalloc(ctx, &ctx->ext_ring, (size_t)XH_CTL_MAX_WINDOW));

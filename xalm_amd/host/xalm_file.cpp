@@ -12,10 +12,12 @@
 
 namespace xalm {
 
-// the converter's gguf block types: name, id, bytes per 32-element block (quants.py)
+// the block types: name, id, bytes per 32-element block (the converter's gguf blocks, quants.py;
+// MXFP4: OCP microscaling FP4, written by tools/xalm_requant.py)
 struct BlockType { const char* name; int type; size_t bytes; };
 const BlockType BLOCK_TYPES[] = {{"Q8_0", XH_Q8_0, 34}, {"Q4_0", XH_Q4_0, 18}, {"Q4_1", XH_Q4_1, 20},
-                                 {"Q5_0", XH_Q5_0, 22}, {"Q5_1", XH_Q5_1, 24}};
+                                 {"Q5_0", XH_Q5_0, 22}, {"Q5_1", XH_Q5_1, 24},
+                                 {"MXFP4", XH_MXFP4, 17}};
 
 // Type::parse, src/types.h:468-499 (case-insensitive names)
 int parse_type(const std::string& s) {
