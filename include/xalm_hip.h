@@ -700,6 +700,61 @@ int xh_op_prompt_attn_ring(float* out, uint16_t* k_ring, uint16_t* v_ring, const
                            const uint16_t* vs, const uint16_t* sink_ver, int m, int p0, int max_seq_len, int n_heads,
                            int n_kv_heads, int nsplit);
 
+/* One GEMM of a prompt pass on host buffers, through the launch code of the passes: y[n][rows] = x . w^T
+ * with x f32 [n][K] and w [rows][K] of `dtype` in the file layout (repacked as xh_op_matmul does).  mode =
+ * XH_OPT_PREFILL 1, 2 or 3 picks the route as a pass does; *route_out reports it: 0 = the row-major
+ * split input of gemm16.h (f16 as stored; e4m3 / e5m2 / Q8_0 / Q4_0 / Q5_0 / MXFP4 with every scale
+ * in 114 .. 140 through their f16 image), E > 0 = the fragment kernel (prefill_gemm16_kernel, E weights
+ * per 16 bytes), -1 = the f32-input kernel (prefill_gemm_kernel).  Launches: prefill_split_kernel where
+ * the route takes split input, the image kernel if any, the GEMM, prefill_epi_kernel with EPI_STORE
+ * (times 1 / s_t on the row-major route, as a pass).  ks 0: the passes' K slicing; k >= 1 forces k slices
+ * and is XH_E_INVALID unless k obeys the route's picker: a power of two, K in k slices of whole
+ * 64-deep steps and k <= 8 (route 0), of whole 8E-deep rings (E > 0; -1 when K % 8E == 0, else of 2E),
+ * k <= 64 and k * ceil(rows / tile) <= 1024 there.  XH_E_INVALID before any launch also for: a dtype with
+ * no prompt GEMM, K % (2 * decoder chunk) != 0, n > 64 off the row-major route (n > 2048 on it), an
+ * MXFP4 block with e = 255, a NULL pointer.  No reference counterpart (src/infer.cpp:104-135 over n
+ * tokens at once). */
+int xh_op_prompt_matmul(float* y, const float* x, const void* w, int dtype, int rows, int K, int n, int mode, int ks,
+                        int* route_out);
+/* The exact f16 image(s) the row-major route multiplies, by the passes' image kernels: hi_out [rows][K]
+ * f16 bits for e4m3 / e5m2 (finite codes) / MXFP4 (scales in 114 .. 140) with lo_out NULL; hi_out and
+ * lo_out for Q8_0 / Q4_0 / Q5_0 (w = hi + lo exactly).  w in the file layout, K % 32 == 0.  max_groups 0:
+ * the passes' cap of 8192 workgroups; k >= 1 caps the grid at k, so every thread strides. */
+int xh_op_prompt_weight_image(int dtype, const void* w, int rows, int K, uint16_t* hi_out, uint16_t* lo_out,
+                              int max_groups);
+/* The producers of a prompt GEMM's split input, and the epilogue, on given partials part [ks][n][row]
+ * (summed in slice order, times part_s[t] when part_s is not NULL).  layout: 0 = row-major halves,
+ * 8 / 16 = the fragment layout for that many weights per 16 bytes.  The producers need dim % 8 == 0
+ * (layout 0) or dim % (2 * layout) == 0.
+ *   XH_STAGE_SPLIT                 x [n][dim] -> halves                         (prefill_split_kernel)
+ *   XH_STAGE_NORM_SPLIT            rmsnorm(x) * norm_w -> halves                (prefill_rmsnorm_split_kernel)
+ *   XH_STAGE_RESID_NORM_SPLIT      x += partials (row = dim), then as NORM_SPLIT, one launch
+ *   XH_STAGE_RESID_THEN_NORM_SPLIT the same in two: EPI_RESID, then prefill_rmsnorm_split_kernel
+ *   XH_STAGE_GLU_SPLIT             act(g) * u of partials (row = 2 dim, g / u interleaved) -> halves, one launch
+ *   XH_STAGE_GLU_THEN_SPLIT        the same in two: EPI_GLU, then prefill_split_kernel
+ *   XH_STAGE_STORE                 EPI_STORE of partials (row = dim, any parity) into y_out [n][out_stride]
+ *                                  (0: dim), which comes in as the rows to be overwritten
+ * The fused kinds give the bits of their two-launch kinds.  Outputs of the producers: x (the RESID kinds:
+ * updated in place), inv_s_out [n] = 1 / s_t, hi_out / lo_out [n][dim] f16 bits row-major (a fragment
+ * layout gathered back through the kernels' own offset function), *pad_out = non-zero halves in the
+ * padding rows n .. 32 ceil(n / 32) of a fragment layout (they start as 0xffff).  norm_w: dim weights of
+ * norm_dtype XH_F32 or XH_BF16.  Arguments a kind does not use may be NULL / 0. */
+enum xh_prompt_stage {
+    XH_STAGE_SPLIT = 0,
+    XH_STAGE_NORM_SPLIT = 1,
+    XH_STAGE_RESID_NORM_SPLIT = 2,
+    XH_STAGE_RESID_THEN_NORM_SPLIT = 3,
+    XH_STAGE_GLU_SPLIT = 4,
+    XH_STAGE_GLU_THEN_SPLIT = 5,
+    XH_STAGE_STORE = 6
+};
+int xh_op_prompt_stage(int kind, const float* part, int ks, const float* part_s, float* x, int n, int dim,
+                       const void* norm_w, int norm_dtype, float eps, int act, int layout, size_t out_stride, float* y_out,
+                       float* inv_s_out, uint16_t* hi_out, uint16_t* lo_out, int* pad_out);
+/* Host only, no device: weight rows per wave (route -1 or E > 0) or per workgroup (route 0) of the
+ * prompt GEMM of that route, as xh_op_prompt_matmul reports it. */
+int xh_prompt_gemm_tile(int route);
+
 /* The sampler of xh_decode_sample (the same device function) on host logits[vocab], no model and
  * no context: draw d = 0 .. n_draws-1 at counter pos0 + d writes tokens_out[d] and n_kept_out[d],
  * the size of the kept set (greedy: 1; no finite logit: 0).  n_draws <= 65536. */

@@ -12,6 +12,8 @@ import pytest
 from oracle import oracle as O
 from xalm_amd import _lib as L
 
+from prompt_gemm_ref import split16
+
 pytestmark = pytest.mark.gpu
 
 
@@ -170,16 +172,6 @@ def test_matmul_f8_hw(dtype, n, d):
     wd = decoded(w, dtype).reshape(d, n)
     mag = np.abs(wd) @ np.abs(x.astype(np.float64))
     assert np.all(np.abs(got - cpu) <= 2e-6 * mag + 1e-7), np.abs(got - cpu).max()
-
-
-def split16(x):
-    """prefill_split_kernel's exact f16 hi + lo of rows scaled into [2^14, 2^15) (float64 ref)"""
-    m = np.abs(x).max(axis=1, keepdims=True)
-    s = np.exp2(15 - np.ceil(np.log2(np.where(m > 0, m, 1.0)) + 1e-12))
-    u = (x * s).astype(np.float32)
-    hi = u.astype(np.float16)
-    lo = (u - hi.astype(np.float32)).astype(np.float16)
-    return hi.view(np.uint16), lo.view(np.uint16)
 
 
 @pytest.mark.parametrize("rows,K,n,ks", [(256, 64, 1, 1), (300, 128, 37, 0), (1000, 512, 200, 4), (6144, 4096, 512, 0),

@@ -251,6 +251,11 @@ _SIGNATURES = {
     "xh_op_prompt_gemm": (_I, [_P, _P, _P, _P, _I, _I, _I, _I]),
     "xh_op_prompt_attn": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I]),
     "xh_op_prompt_attn_ring": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I]),
+    "xh_op_prompt_matmul": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, ctypes.POINTER(_I)]),
+    "xh_op_prompt_weight_image": (_I, [_I, _P, _I, _I, _P, _P, _I]),
+    "xh_op_prompt_stage": (_I, [_I, _P, _I, _P, _P, _I, _I, _P, _I, ctypes.c_float, _I, _I, _SZ, _P, _P, _P, _P,
+                                ctypes.POINTER(_I)]),
+    "xh_prompt_gemm_tile": (_I, [_I]),
     "xh_time_kernel": (_I, [_P, _I, _I, _FP]),
     "xh_kernel_bytes": (_SZ, [_P, _I, _I]),
 }
@@ -616,6 +621,67 @@ def op_prompt_attn(q: np.ndarray, k: np.ndarray, v: np.ndarray, pos0: int, head_
     out = np.empty_like(q)
     check(lib().xh_op_prompt_attn(ptr(out), ptr(q), ptr(k), ptr(v), n, pos0, head_dim, n_heads, n_kv_heads, mode, nsplit))
     return out
+
+
+# enum xh_prompt_stage
+(STAGE_SPLIT, STAGE_NORM_SPLIT, STAGE_RESID_NORM_SPLIT, STAGE_RESID_THEN_NORM_SPLIT, STAGE_GLU_SPLIT,
+ STAGE_GLU_THEN_SPLIT, STAGE_STORE) = range(7)
+# xh_op_prompt_matmul's route_out
+ROUTE_ROWMAJOR, ROUTE_F32 = 0, -1
+
+
+def prompt_gemm_tile(route: int) -> int:
+    """Weight rows per wave (route -1 or E > 0) or workgroup (route 0) of the prompt GEMM.  No device needed."""
+    return int(lib().xh_prompt_gemm_tile(route))
+
+
+def op_prompt_matmul(x: np.ndarray, w: np.ndarray, dtype: int, rows: int, mode: int, ks: int = 0):
+    """One GEMM of a prompt pass (xh_op_prompt_matmul): x f32 [n][K], w [rows] rows of `dtype` in the file
+    layout.  Returns (y f32 [n][rows], route)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    w = np.ascontiguousarray(w)
+    n, K = x.shape
+    assert w.nbytes == rows * row_bytes(dtype, K)
+    out = np.empty((n, rows), dtype=np.float32)
+    route = ctypes.c_int(-99)
+    check(lib().xh_op_prompt_matmul(ptr(out), ptr(x), ptr(w), dtype, rows, K, n, mode, ks, ctypes.byref(route)))
+    return out, route.value
+
+
+def op_prompt_weight_image(dtype: int, w: np.ndarray, rows: int, K: int, max_groups: int = 0):
+    """The f16 image(s) of the row-major prompt GEMM (xh_op_prompt_weight_image): (hi, lo) uint16
+    [rows][K], lo None for the one-image dtypes."""
+    w = np.ascontiguousarray(w)
+    assert w.nbytes == rows * row_bytes(dtype, K)
+    hi = np.empty((rows, K), dtype=np.uint16)
+    lo = np.empty((rows, K), dtype=np.uint16) if dtype in (Q8_0, Q4_0, Q5_0) else None
+    check(lib().xh_op_prompt_weight_image(dtype, ptr(w), rows, K, ptr(hi), ptr(lo) if lo is not None else None, max_groups))
+    return hi, lo
+
+
+def op_prompt_stage(kind: int, n: int, dim: int, part=None, part_s=None, x=None, norm_w=None, norm_dtype: int = F32,
+                    eps: float = 1e-5, act: int = ACT_SILU, layout: int = 0, out_stride: int = 0, y=None):
+    """A producer or the epilogue of a prompt GEMM (xh_op_prompt_stage).  part f32 [ks][n][row].
+    STAGE_STORE: returns y [n][out_stride or dim] (y: the rows before the store).  Else returns a dict:
+    x (updated, the RESID kinds), inv_s [n], hi / lo uint16 [n][dim], pad (non-zero padding halves)."""
+    f32 = lambda a: None if a is None else np.array(a, dtype=np.float32, order="C", copy=True)
+    part, part_s, x = f32(part), f32(part_s), f32(x)
+    ks = part.shape[0] if part is not None else 1
+    nw = None if norm_w is None else np.ascontiguousarray(norm_w)
+    P = lambda a: None if a is None else ptr(a)
+    if kind == STAGE_STORE:
+        yo = np.array(y, dtype=np.float32, order="C", copy=True)
+        assert yo.shape == (n, out_stride or dim) and part.shape == (ks, n, dim)
+        check(lib().xh_op_prompt_stage(kind, P(part), ks, P(part_s), None, n, dim, None, 0, eps, act, layout, out_stride,
+                                       ptr(yo), None, None, None, None))
+        return yo
+    inv_s = np.empty(n, dtype=np.float32)
+    hi = np.empty((n, dim), dtype=np.uint16)
+    lo = np.empty((n, dim), dtype=np.uint16)
+    pad = ctypes.c_int(-1)
+    check(lib().xh_op_prompt_stage(kind, P(part), ks, P(part_s), P(x), n, dim, P(nw), norm_dtype, eps, act, layout, 0, None,
+                                   ptr(inv_s), ptr(hi), ptr(lo), ctypes.byref(pad)))
+    return {"x": x, "inv_s": inv_s, "hi": hi, "lo": lo, "pad": pad.value}
 
 
 def op_prompt_attn_ring(q: np.ndarray, k_ring: np.ndarray, v_ring: np.ndarray, ks: np.ndarray, vs: np.ndarray,

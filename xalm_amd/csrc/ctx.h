@@ -413,6 +413,61 @@ int pf_ring_launch(const PfAttnDims& d, const float* q, uint16_t* kc, uint16_t* 
                    const uint16_t* sinkv, float* out, int m, int p0, int max_seq_len, int nsplit, float* part,
                    hipStream_t s);
 
+// prefill.hip: the prompt GEMM's launch bodies on device pointers, shared by the passes (pf_gemm) and
+// by xh_op_prompt_matmul / xh_op_prompt_weight_image / xh_op_prompt_stage.  Nothing here reads a context.
+// One GEMM Y[n][rows] = X[n][K] . W[rows][K]^T of decode form dt under XH_OPT_PREFILL `mode` (blas: mode 4
+// with a hipBLASLt plan for every shape of the model).  wide: an MXFP4 matrix with no f16 image.
+// ks 0: the route's own K slicing, else that many slices (pf_gemm_ks_ok).  max_groups 0: the image
+// kernels' cap of PF_IMAGE_GROUPS workgroups.
+constexpr int PF_IMAGE_GROUPS = 8192;
+struct PfGemmPlan {
+    int mode; bool blas;
+    int dt, K, rows; bool wide;
+    int n, n_cu;
+    size_t part_floats;  // capacity of `part`
+    int ks, max_groups;
+};
+struct PfGemmIo {
+    const void* w;        // device rows of dt
+    const float* x;       // [n][K] (the f32-input route reads it; the others their split halves)
+    uint16_t *xh, *xl;    // split halves: row-major hi rows then lo rows in xh (route 0), fragments in xh / xl (E > 0)
+    float* xs;            // [n] 1 / row scale
+    uint16_t* wdq;        // f16 image(s) of w (route 0), wdq_elems f16
+    size_t wdq_elems;
+    float* part;          // [ks][n][rows]
+};
+enum { PF_GEMM_OK = 0, PF_GEMM_E_IMAGE = -1, PF_GEMM_E_FIT = -2, PF_GEMM_E_SHAPE = -3, PF_GEMM_E_DTYPE = -4 };
+// weights per 16-byte chunk of the f32-input kernel's decoder of dt (WDec<DT>::E)
+int pf_elems(int dt);
+// the route: 0 = row-major split input (gemm16.h or hipBLASLt), E > 0 = the fragment kernel, -1 = f32 input
+int pf_gemm_route(const PfGemmPlan& p);
+// rows per wave (routes -1 and E > 0) or per workgroup (route 0): the launch's row tile
+int pf_gemm_row_tile(int route);
+// may the GEMM of p run in p.ks > 0 slices on `route`: the divisibility and capacity rules of its picker
+bool pf_gemm_ks_ok(const PfGemmPlan& p, int route);
+// the split halves of x [n][K] in layout lay (0 or E): hi, lo and 1 / s_t
+void pf_split_launch(const float* x, int K, int n, int lay, uint16_t* xh, uint16_t* xl, float* inv_s, hipStream_t s);
+uint16_t* pf_split_lo(int lay, int n, int K, uint16_t* xh, uint16_t* xl);  // where lay's lo halves go
+size_t pf_split_index(int t, int k, int K, int lay);                      // split_off on the host
+// route 0: the f16 image(s) of w into io.wdq (none for f16: *w_hi = io.w); *w_lo: the gguf blocks' lo image
+int pf_gemm_images(const PfGemmPlan& p, const PfGemmIo& io, const uint16_t** w_hi, const uint16_t** w_lo, hipStream_t s);
+// route 0 on gemm16.h over w_hi (and w_lo into partials [ks, 2 ks)); *ks_out = slices the epilogue sums
+int pf_gemm_rowmajor(const PfGemmPlan& p, const PfGemmIo& io, const uint16_t* w_hi, const uint16_t* w_lo, int* ks_out,
+                     hipStream_t s);
+int pf_gemm_frag(const PfGemmPlan& p, const PfGemmIo& io, int lay, int* ks_out, hipStream_t s);
+int pf_gemm_f32(const PfGemmPlan& p, const PfGemmIo& io, int* ks_out, hipStream_t s);
+// the producers and the epilogue (prefill.h) on plain arguments
+void pf_norm_split_launch(const float* x, int dim, const void* nw, int ndt, float eps, int n, int lay, uint16_t* xh,
+                          uint16_t* xl, float* inv_s, hipStream_t s);
+void pf_norm_launch(const float* x, int dim, const void* nw, int ndt, float eps, int n, float* o, hipStream_t s);
+void pf_resid_norm_split_launch(const float* part, int ks, const float* part_s, float* x, int dim, const void* nw, int ndt,
+                                float eps, int n, int lay, uint16_t* xh, uint16_t* xl, float* inv_s, hipStream_t s);
+void pf_glu_split_launch(const float* part, int ks, const float* part_s, int n, int hidden, int act, int lay, uint16_t* xh,
+                         uint16_t* xl, float* inv_s, hipStream_t s);
+// prefill_epi_kernel with EPI_STORE / EPI_RESID / EPI_GLU (no K/V arguments)
+void pf_epi_plain_launch(const float* part, const float* part_s, int ks, int n, int rows, int epi, float* out,
+                         size_t out_stride, int act, hipStream_t s);
+
 // prefill_blas.hip (XH_OPT_PREFILL 4).  blas_ok: 0 unprobed, 1 every GEMM shape of the model has
 // an f16 plan, -1 not.  blas_has_plan: *have = hipBLASLt has an algorithm for the shape.
 int blas_ok(const xh_ctx* ctx);

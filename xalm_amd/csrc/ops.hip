@@ -230,6 +230,203 @@ int xh_op_prompt_attn_ring(float* out, uint16_t* k_ring, uint16_t* v_ring, const
     return 0;
 }
 
+namespace {
+// w in the file layout as the device rows of its decode form: the gguf blocks repacked (tmp), fp8
+// with NaN / Inf codes as the _EXACT form.  XH_E_INVALID for an MXFP4 block with e = 255.
+int op_weight_rows(const char* what, int dtype, const void* w, int rows, int K, std::vector<uint8_t>& tmp, const void** dev_rows,
+                   int* dt, bool* wide) {
+    *wide = false;
+    if (gq_mx(dtype)) {
+        uint8_t lo, hi;
+        mx_e_range((const uint8_t*)w, (size_t)rows * (K / 32), &lo, &hi);
+        if (hi == 255) return set_err(nullptr, XH_E_INVALID, "%s: an MXFP4 block with e = 255 (NaN)", what);
+        *wide = lo < MX_E_F16_LO || hi > MX_E_F16_HI;
+    }
+    *dev_rows = w;
+    if (gq_dt(dtype)) {
+        tmp.resize((size_t)rows * dev_row_bytes(dtype, K));
+        gq_repack(dtype, (const uint8_t*)w, rows, K, tmp.data());
+        *dev_rows = tmp.data();
+    }
+    bool special = false;
+    if (dtype == XH_F8_E4M3 || dtype == XH_F8_E5M2)
+        for (size_t i = 0; i < (size_t)rows * K && !special; i++) special = f8_special(((const uint8_t*)w)[i], dtype == XH_F8_E5M2);
+    *dt = kdt(dtype, special);
+    return 0;
+}
+}  // namespace
+
+int xh_op_prompt_matmul(float* y, const float* x, const void* w, int dtype, int rows, int K, int n, int mode, int ks,
+                        int* route_out) {
+    if (!y || !x || !w || !route_out || rows <= 0 || K <= 0 || n <= 0 || n > 2048 || rows > (1 << 20) || K > (1 << 20) ||
+        ks < 0 || ks > 64)
+        return set_err(nullptr, XH_E_INVALID, "bad prompt_matmul args");
+    if (mode < 1 || mode > 3) return set_err(nullptr, XH_E_INVALID, "prompt_matmul: mode %d (1, 2 or 3)", mode);
+    if (!matrix_dtype_ok(dtype)) return set_err(nullptr, XH_E_INVALID, "prompt_matmul: no prompt GEMM for dtype %d", dtype);
+    // pf_supported: every GEMM's K in whole chunk pairs of its decoder (the split kernels' 8s follow)
+    if (K % (2 * pf_elems(dtype)))
+        return set_err(nullptr, XH_E_INVALID, "prompt_matmul: K %d is not in whole chunk pairs of dtype %d", K, dtype);
+    std::vector<uint8_t> tmp;
+    PfGemmPlan p{};
+    const void* hw = nullptr;
+    int rc;
+    if ((rc = op_weight_rows("prompt_matmul", dtype, w, rows, K, tmp, &hw, &p.dt, &p.wide))) return rc;
+    p.mode = mode; p.K = K; p.rows = rows; p.n = n; p.ks = ks;
+    if ((rc = op_n_cu(&p.n_cu))) return rc;
+    const int route = pf_gemm_route(p);
+    if (route != 0 && n > 64) return set_err(nullptr, XH_E_INVALID, "prompt_matmul: %d tokens off the row-major route (at most 64)", n);
+    // room for any slicing the route's picker may take (two images of 8 slices; 64 slices)
+    p.part_floats = (size_t)(route == 0 ? 16 : 64) * n * rows;
+    if (ks > 0 && !pf_gemm_ks_ok(p, route))
+        return set_err(nullptr, XH_E_INVALID, "prompt_matmul: %d slices of K %d over %d rows on route %d", ks, K, rows, route);
+    const size_t xe = (size_t)n * K, pad = (size_t)32 * ((n + 31) / 32) * K;
+    const size_t images = route == 0 && p.dt != XH_F16 ? (gq_dt(p.dt) && !gq_mx(p.dt) ? 2 : 1) : 0;
+    DevBuf bw, bx, bxh, bxl, bxs, bq, bp, bo;
+    if ((rc = op_alloc(bw, (size_t)rows * dev_row_bytes(dtype, K), hw)) || (rc = op_alloc(bx, xe * 4, x)) ||
+        (rc = op_alloc(bxh, (route == 0 ? 2 * xe : route > 0 ? pad : 0) * 2, nullptr)) ||
+        (rc = op_alloc(bxl, (route > 0 ? pad : 0) * 2, nullptr)) || (rc = op_alloc(bxs, (size_t)n * 4, nullptr)) ||
+        (rc = op_alloc(bq, images * rows * K * 2, nullptr)) || (rc = op_alloc(bp, p.part_floats * 4, nullptr)) ||
+        (rc = op_alloc(bo, (size_t)n * rows * 4, nullptr)))
+        return rc;
+    const PfGemmIo io{bw.p, (const float*)bx.p, (uint16_t*)bxh.p, (uint16_t*)bxl.p, (float*)bxs.p, (uint16_t*)bq.p,
+                      images * rows * K, (float*)bp.p};
+    int nks = 0;
+    if (route >= 0) pf_split_launch(io.x, K, n, route, io.xh, pf_split_lo(route, n, K, io.xh, io.xl), io.xs, nullptr);
+    if (route == 0) {
+        const uint16_t *w_hi = nullptr, *w_lo = nullptr;
+        if (!(rc = pf_gemm_images(p, io, &w_hi, &w_lo, nullptr))) rc = pf_gemm_rowmajor(p, io, w_hi, w_lo, &nks, nullptr);
+    } else {
+        rc = route > 0 ? pf_gemm_frag(p, io, route, &nks, nullptr) : pf_gemm_f32(p, io, &nks, nullptr);
+    }
+    if (rc) {
+        hipDeviceSynchronize();
+        return set_err(nullptr, XH_E_INVALID, "prompt_matmul: the launch code refused the GEMM (%d)", rc);
+    }
+    // the row-major partials are unscaled: the epilogue multiplies by 1 / s_t, as a pass's
+    pf_epi_plain_launch(io.part, route == 0 ? io.xs : nullptr, nks, n, rows, EPI_STORE, (float*)bo.p, 0, 0, nullptr);
+    *route_out = route;
+    return op_finish(y, bo, (size_t)n * rows * 4);
+}
+
+int xh_op_prompt_weight_image(int dtype, const void* w, int rows, int K, uint16_t* hi_out, uint16_t* lo_out, int max_groups) {
+    const bool one = dtype == XH_F8_E4M3 || dtype == XH_F8_E5M2 || dtype == XH_MXFP4;
+    const bool two = dtype == XH_Q8_0 || dtype == XH_Q4_0 || dtype == XH_Q5_0;
+    if (!w || !hi_out || rows <= 0 || K <= 0 || K % 32 || rows > (1 << 20) || K > (1 << 20) || max_groups < 0)
+        return set_err(nullptr, XH_E_INVALID, "bad prompt_weight_image args");
+    if (!(one || two) || (two && !lo_out) || (one && lo_out))
+        return set_err(nullptr, XH_E_INVALID, "prompt_weight_image: dtype %d has %s", dtype,
+                       one ? "one image (lo_out NULL)" : two ? "two images" : "no f16 image");
+    std::vector<uint8_t> tmp;
+    PfGemmPlan p{};
+    const void* hw = nullptr;
+    int rc;
+    if ((rc = op_weight_rows("prompt_weight_image", dtype, w, rows, K, tmp, &hw, &p.dt, &p.wide))) return rc;
+    if (p.wide || p.dt != dtype)
+        return set_err(nullptr, XH_E_INVALID, "prompt_weight_image: the matrix has no exact f16 image (%s)",
+                       p.wide ? "an MXFP4 scale outside the f16 range" : "a NaN / Inf code");
+    p.mode = 1; p.K = K; p.rows = rows; p.max_groups = max_groups;
+    const size_t we = (size_t)rows * K, images = two ? 2 : 1;
+    DevBuf bw, bq;
+    if ((rc = op_alloc(bw, (size_t)rows * dev_row_bytes(dtype, K), hw)) || (rc = op_alloc(bq, images * we * 2, nullptr))) return rc;
+    const PfGemmIo io{bw.p, nullptr, nullptr, nullptr, nullptr, (uint16_t*)bq.p, images * we, nullptr};
+    const uint16_t *w_hi = nullptr, *w_lo = nullptr;
+    if ((rc = pf_gemm_images(p, io, &w_hi, &w_lo, nullptr)))
+        return set_err(nullptr, XH_E_INVALID, "prompt_weight_image: the launch code refused the image (%d)", rc);
+    if ((rc = op_finish(hi_out, bq, we * 2))) return rc;
+    if (two && hipMemcpy(lo_out, w_lo, we * 2, hipMemcpyDeviceToHost) != hipSuccess)
+        return set_err(nullptr, XH_E_HIP, "hipMemcpy D2H failed");
+    return 0;
+}
+
+int xh_op_prompt_stage(int kind, const float* part, int ks, const float* part_s, float* x, int n, int dim, const void* norm_w,
+                       int norm_dtype, float eps, int act, int layout, size_t out_stride, float* y_out, float* inv_s_out,
+                       uint16_t* hi_out, uint16_t* lo_out, int* pad_out) {
+    const bool store = kind == XH_STAGE_STORE;
+    const bool from_x = kind == XH_STAGE_SPLIT || kind == XH_STAGE_NORM_SPLIT;
+    const bool resid = kind == XH_STAGE_RESID_NORM_SPLIT || kind == XH_STAGE_RESID_THEN_NORM_SPLIT;
+    const bool glu = kind == XH_STAGE_GLU_SPLIT || kind == XH_STAGE_GLU_THEN_SPLIT;
+    const bool normed = kind == XH_STAGE_NORM_SPLIT || resid;
+    if (!(store || from_x || resid || glu) || n <= 0 || n > 2048 || dim <= 0 || dim > 16000 || ks < 1 || ks > 64)
+        return set_err(nullptr, XH_E_INVALID, "bad prompt_stage args");
+    if ((!from_x && !part) || ((from_x || resid) && !x) || (normed && !norm_w) || (store && !y_out) ||
+        (!store && (!inv_s_out || !hi_out || !lo_out || !pad_out)))
+        return set_err(nullptr, XH_E_INVALID, "prompt_stage: a buffer of kind %d is NULL", kind);
+    if (normed && !(norm_dtype == XH_F32 || norm_dtype == XH_BF16))
+        return set_err(nullptr, XH_E_INVALID, "prompt_stage: norm weight dtype %d", norm_dtype);
+    // the producers move 8 elements at a time; a fragment layout holds whole chunk pairs
+    if (!store && (!(layout == 0 || layout == 8 || layout == 16) || dim % (layout ? 2 * layout : 8)))
+        return set_err(nullptr, XH_E_INVALID, "prompt_stage: rows of %d in layout %d (0, 8 or 16; whole 8s / chunk pairs)", dim,
+                       layout);
+    if (store && out_stride && out_stride < (size_t)dim) return set_err(nullptr, XH_E_INVALID, "prompt_stage: out_stride < rows");
+    if (glu && act != XH_ACT_SILU && act != XH_ACT_GELU) return set_err(nullptr, XH_E_INVALID, "prompt_stage: act %d", act);
+    const size_t prow = glu ? 2 * (size_t)dim : (size_t)dim;  // a row of the partials
+    const size_t ne = (size_t)n * dim, stride = out_stride ? out_stride : (size_t)dim;
+    const int tpad = layout ? 32 * ((n + 31) / 32) : n;
+    const size_t he = (size_t)tpad * dim;  // f16 per half
+    DevBuf bp, bps, bx, bw, bh, bxh, bxl, bxs, by;
+    int rc;
+    if ((rc = op_alloc(bp, from_x ? 0 : (size_t)ks * n * prow * 4, from_x ? nullptr : part)) ||
+        (rc = op_alloc(bps, (size_t)n * 4, part_s)) || (rc = op_alloc(bx, ne * 4, from_x || resid ? x : nullptr)) ||
+        (rc = op_alloc(bw, normed ? (size_t)dim * dtype_size(norm_dtype) : 0, normed ? norm_w : nullptr)) ||
+        (rc = op_alloc(bh, ne * 4, nullptr)) || (rc = op_alloc(bxh, (layout ? he : 2 * he) * 2, nullptr)) ||
+        (rc = op_alloc(bxl, he * 2, nullptr)) || (rc = op_alloc(bxs, (size_t)n * 4, nullptr)) ||
+        (rc = op_alloc(by, store ? (size_t)n * stride * 4 : 0, store ? y_out : nullptr)))
+        return rc;
+    // halves start as all ones: a padding row the producer does not zero shows in *pad_out
+    if (hipMemset(bxh.p, 0xff, (layout ? he : 2 * he) * 2) != hipSuccess || hipMemset(bxl.p, 0xff, he * 2) != hipSuccess)
+        return set_err(nullptr, XH_E_HIP, "hipMemset failed");
+    const float* ps = part_s ? (const float*)bps.p : nullptr;
+    float* dx = (float*)bx.p;
+    uint16_t* xh = (uint16_t*)bxh.p;
+    uint16_t* xl = pf_split_lo(layout, n, dim, xh, (uint16_t*)bxl.p);
+    float* xs = (float*)bxs.p;
+    switch (kind) {
+        case XH_STAGE_SPLIT: pf_split_launch(dx, dim, n, layout, xh, xl, xs, nullptr); break;
+        case XH_STAGE_NORM_SPLIT: pf_norm_split_launch(dx, dim, bw.p, norm_dtype, eps, n, layout, xh, xl, xs, nullptr); break;
+        case XH_STAGE_RESID_NORM_SPLIT:
+            pf_resid_norm_split_launch((const float*)bp.p, ks, ps, dx, dim, bw.p, norm_dtype, eps, n, layout, xh, xl, xs, nullptr);
+            break;
+        case XH_STAGE_RESID_THEN_NORM_SPLIT:
+            pf_epi_plain_launch((const float*)bp.p, ps, ks, n, dim, EPI_RESID, dx, 0, 0, nullptr);
+            pf_norm_split_launch(dx, dim, bw.p, norm_dtype, eps, n, layout, xh, xl, xs, nullptr);
+            break;
+        case XH_STAGE_GLU_SPLIT:
+            pf_glu_split_launch((const float*)bp.p, ks, ps, n, dim, act, layout, xh, xl, xs, nullptr);
+            break;
+        case XH_STAGE_GLU_THEN_SPLIT:
+            pf_epi_plain_launch((const float*)bp.p, ps, ks, n, 2 * dim, EPI_GLU, (float*)bh.p, 0, act, nullptr);
+            pf_split_launch((const float*)bh.p, dim, n, layout, xh, xl, xs, nullptr);
+            break;
+        default:
+            pf_epi_plain_launch((const float*)bp.p, ps, ks, n, dim, EPI_STORE, (float*)by.p, out_stride, 0, nullptr);
+            return op_finish(y_out, by, (size_t)n * stride * 4);
+    }
+    if ((rc = op_finish(inv_s_out, bxs, (size_t)n * 4))) return rc;
+    if (resid && hipMemcpy(x, bx.p, ne * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return set_err(nullptr, XH_E_HIP, "hipMemcpy D2H failed");
+    std::vector<uint16_t> hh(he), hl(he);
+    if (hipMemcpy(hh.data(), xh, he * 2, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(hl.data(), xl, he * 2, hipMemcpyDeviceToHost) != hipSuccess)
+        return set_err(nullptr, XH_E_HIP, "hipMemcpy D2H failed");
+    int padnz = 0;
+    for (int t = 0; t < tpad; t++)
+        for (int k = 0; k < dim; k += 8) {
+            const size_t o = pf_split_index(t, k, dim, layout);
+            for (int j = 0; j < 8; j++) {
+                if (t < n) {
+                    hi_out[(size_t)t * dim + k + j] = hh[o + j];
+                    lo_out[(size_t)t * dim + k + j] = hl[o + j];
+                } else {
+                    padnz += (hh[o + j] != 0) + (hl[o + j] != 0);
+                }
+            }
+        }
+    *pad_out = padnz;
+    return 0;
+}
+
+int xh_prompt_gemm_tile(int route) { return pf_gemm_row_tile(route); }
+
 // ---------------------------------------------------------------------------------------
 // timing hooks for bench.py
 // ---------------------------------------------------------------------------------------

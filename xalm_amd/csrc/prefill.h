@@ -190,7 +190,7 @@ __host__ __device__ inline size_t frag_off(const int tt, const int c, const int 
 }
 // offset (f16 elements) of X[t][k .. k+8) in the split layout: E > 0 the fragment layout above,
 // E == 0 plain row-major [t][K] (the hipBLASLt GEMM's B operand)
-__device__ __forceinline__ size_t split_off(const int t, const int k, const int K, const int E) {
+__host__ __device__ __forceinline__ size_t split_off(const int t, const int k, const int K, const int E) {
     if (E == 0) return (size_t)t * K + k;
     const int M = E / 8, n_c = K / (2 * E);
     const int c = k / (2 * E), r = k - c * 2 * E, hh = r / E, m = (r - hh * E) / 8;

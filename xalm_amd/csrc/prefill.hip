@@ -157,35 +157,41 @@ void pf_gemm16_t(const PfGemm16Args& a, hipStream_t s) {
     hipLaunchKernelGGL((prefill_gemm16_kernel<DT, PF_RT16>), dim3((waves + PF_WAVES - 1) / PF_WAVES), dim3(PF_THREADS),
                        0, s, a);
 }
-// weights per 16-byte chunk of the f32-input MFMA kernel's decoders (WDec<DT>::E)
-int pf_elems(int dt) {
-    if (dt == XH_F8_E4M3_EXACT || dt == XH_F8_E5M2_EXACT || dt == XH_Q8_0) return 16;
-    return gq_dt(dt) ? 32 : elems_per_16b(dt);  // the nibble blocks (Q8_0 above)
-}
 // weights the f16 GEMMs take: f16 as stored, e4m3 / e5m2 through their exact f16 image (kdt
 // keeps the _EXACT dtypes, whose NaN / Inf codes the reference decodes to finite values, off it)
 bool pf_f8(int dt) { return dt == XH_F8_E4M3 || dt == XH_F8_E5M2; }
 bool pf_f16w(int dt) { return dt == XH_F16 || pf_f8(dt); }
-// Does the GEMM over W (dtype dt, K columns) run on the row-major split input: gemm16.h
-// (XH_OPT_PREFILL 1: K in whole 64-deep steps) or hipBLASLt (4: a plan for every shape)?
-bool pf_lay0(const xh_ctx* ctx, int dt, int K, bool wide) {
+// Does the GEMM of p run on the row-major split input: gemm16.h (XH_OPT_PREFILL 1: K in whole
+// 64-deep steps) or hipBLASLt (4: a plan for every shape)?
+bool pf_lay0(const PfGemmPlan& p) {
+    const int dt = p.dt, K = p.K;
     // MXFP4 (2 significant bits): ONE exact f16 image, the fp8 route (XH_OPT_PREFILL 1 and 4), when
     // every scale byte of the matrix lies in [MX_E_F16_LO, MX_E_F16_HI]; else (wide) the f32-input
     // MFMA kernel, as under XH_OPT_PREFILL 2 and 3
     if (gq_mx(dt)) {
-        if (wide || K % 32) return false;
-        if (ctx->prefill_gemm == 1) return K % MM_KMULT == 0;
-        return ctx->prefill_gemm == 4 && blas_ok(ctx) > 0;
+        if (p.wide || K % 32) return false;
+        if (p.mode == 1) return K % MM_KMULT == 0;
+        return p.mode == 4 && p.blas;
     }
     // gguf blocks: their exact f16 hi + lo images through gemm16.h (XH_OPT_PREFILL 1); the affine
     // blocks (fmaf(d, q, m): no exact f16 pair) always take the f32-input MFMA kernel
     if (gq_has_m(dt)) return false;
-    if (gq_dt(dt)) return ctx->prefill_gemm == 1 && K % MM_KMULT == 0;
+    if (gq_dt(dt)) return p.mode == 1 && K % MM_KMULT == 0;
     if (!pf_f16w(dt)) return false;
-    if (ctx->prefill_gemm == 1) return K % MM_KMULT == 0;
-    if (ctx->prefill_gemm == 4) return blas_ok(ctx) > 0;
+    if (p.mode == 1) return K % MM_KMULT == 0;
+    if (p.mode == 4) return p.blas;
     return false;
 }
+// the plan of a GEMM of this context (n, the partials and a forced slicing left to the caller)
+PfGemmPlan pf_plan_of(const xh_ctx* ctx, int dt, int K, int rows, bool wide) {
+    PfGemmPlan p{};
+    p.mode = ctx->prefill_gemm;
+    p.blas = p.mode == 4 && blas_ok(ctx) > 0;
+    p.dt = dt; p.K = K; p.rows = rows; p.wide = wide;
+    p.n_cu = ctx->n_cu;
+    return p;
+}
+bool pf_lay0(const xh_ctx* ctx, int dt, int K, bool wide) { return pf_lay0(pf_plan_of(ctx, dt, K, 0, wide)); }
 // Once per prefill: (XH_OPT_PREFILL 4, once per context) does hipBLASLt have an f16 plan for every
 // full-pass GEMM of the model (if not, every dtype keeps the MFMA kernels); and the f16 image
 // buffer of the largest fp8 matrix that goes to the f16 GEMMs.
@@ -217,25 +223,13 @@ int pf_prepare(xh_ctx* ctx) {
     }
     return 0;
 }
-// Layout of the split-f16 input of the GEMM over W (dtype dt, [rows][K]): 0 = row-major (gemm16.h
-// or hipBLASLt), E > 0 = the split-f16 register-streaming kernel's fragments, -1 = no split
-// (f32-input MFMA).  XH_OPT_PREFILL 1 / 4: row-major for f16 / e4m3 / e5m2 where the GEMM fits,
-// else the split kernel for fp8; 2: the split kernel for f16 and fp8; 3: never split.  The split
-// kernel also needs a K slicing.
+// Layout of the split-f16 input of the GEMM over W (dtype dt, [rows][K]): pf_gemm_route of its plan
 int pf_layout(const xh_ctx* ctx, int dt, int K, int rows, bool wide) {
-    if (pf_lay0(ctx, dt, K, wide)) return 0;
-    const bool f8 = pf_f8(dt);
-    const int m = ctx->prefill_gemm;
-    if (!(m == 2 || ((m == 1 || m == 4) && f8))) return -1;
-    if (dt != XH_F16 && !f8) return -1;
-    const int E = elems_per_16b(dt);
-    return pf_ks16(rows, K, E) ? E : -1;
+    return pf_gemm_route(pf_plan_of(ctx, dt, K, rows, wide));
 }
 // split-f16 halves of a pass's rows: hi into pf.xh; lo into pf.xl (fragments) or right after
 // the hi rows (row-major)
-uint16_t* pf_lo(xh_ctx* ctx, int layout, int n, int K) {
-    return layout ? ctx->pf.xl : ctx->pf.xh + (size_t)n * K;
-}
+uint16_t* pf_lo(xh_ctx* ctx, int layout, int n, int K) { return pf_split_lo(layout, n, K, ctx->pf.xh, ctx->pf.xl); }
 // grid of the split kernels: one workgroup per token row, fragments padded to 32-token tiles
 int pf_split_grid(int layout, int n) { return layout ? 32 * ((n + 31) / 32) : n; }
 int pf_layout(const xh_ctx* ctx, const PfMat& g) { return pf_layout(ctx, g.dt, g.K, g.rows, g.wide); }
@@ -259,13 +253,11 @@ void pf_norm(xh_ctx* ctx, PfPass& ps, const void* nw, int ndt, const PfMat& g) {
     PfBufs& b = ctx->pf;
     const int lay = pf_layout(ctx, g);
     if (lay >= 0) {
-        hipLaunchKernelGGL(prefill_rmsnorm_split_kernel, dim3(pf_split_grid(lay, ps.m)), dim3(256), 0, ctx->stream,
-                           (const float*)b.x, c.dim, nw, ndt, c.norm_eps, ps.m, lay, b.xh, pf_lo(ctx, lay, ps.m, c.dim),
-                           b.xs);
+        pf_norm_split_launch(b.x, c.dim, nw, ndt, c.norm_eps, ps.m, lay, b.xh, pf_lo(ctx, lay, ps.m, c.dim), b.xs,
+                             ctx->stream);
         ps.split_ready = true;
     } else {
-        hipLaunchKernelGGL(prefill_rmsnorm_kernel, dim3(ps.m), dim3(256), 0, ctx->stream, (const float*)b.x, c.dim, nw,
-                           ndt, c.norm_eps, b.xn);
+        pf_norm_launch(b.x, c.dim, nw, ndt, c.norm_eps, ps.m, b.xn, ctx->stream);
     }
 }
 // one prompt GEMM launch (gemm16.h): the 4-wave instantiation when the launch has at least
@@ -284,127 +276,66 @@ struct PfGemmF32 {  // for_dt: the f32-input MFMA kernel of a dtype
     const PfGemmArgs& a; hipStream_t s;
     template <int DT> int run() const { pf_gemm_t<DT>(a, s); return 0; }
 };
+// a launch body's refusal (PF_GEMM_E_*) as the pass's error
+int pf_gemm_err(xh_ctx* ctx, int rc, const PfMat& g, int n) {
+    switch (rc) {
+        case PF_GEMM_E_IMAGE: return set_err(ctx, XH_E_INVALID, "prefill: %s weight image does not fit", g.what);
+        case PF_GEMM_E_FIT:
+            return set_err(ctx, XH_E_INVALID, "prefill: %s GEMM %d x %d over %d tokens does not fit", g.what, g.rows, g.K, n);
+        case PF_GEMM_E_DTYPE: return set_err(ctx, XH_E_INVALID, "prefill: %s dtype %d not supported", g.what, g.dt);
+        default: return set_err(ctx, XH_E_INVALID, "prefill: %s shape not supported", g.what);
+    }
+}
 // Y partials of g's W[rows][K] . X[n][K] into pf.part ([ks][n][rows]).  Split-f16 paths convert x
-// first unless ps.split_ready says its halves are there already.  0 or an error code.
+// first unless ps.split_ready says its halves are there already.  0 or an error code.  The launches
+// are the context-free bodies below (pf_gemm_*); hipBLASLt (XH_OPT_PREFILL 4) alone needs the context.
 int pf_gemm(xh_ctx* ctx, PfPass& ps, const PfMat& g, const float* x, int n, int& ks) {
     PfBufs& b = ctx->pf;
-    const int dt = g.dt, K = g.K, rows = g.rows;
-    const void* w = g.w;
-    const int lay = pf_layout(ctx, g);
+    PfGemmPlan p = pf_plan_of(ctx, g.dt, g.K, g.rows, g.wide);
+    p.n = n;
+    p.part_floats = pf_part_floats(ctx, b.cap[PfBufs::PASS]);
+    const PfGemmIo io{g.w, x, b.xh, b.xl, b.xs, ctx->pf_wdq, ctx->pf_wdq_elems, b.part};
+    const int lay = pf_gemm_route(p);
     ps.scaled = false;
     if (lay >= 0) {
-        if (!ps.split_ready)
-            hipLaunchKernelGGL(prefill_split_kernel, dim3(pf_split_grid(lay, n)), dim3(256), 0, ctx->stream, x, K, n,
-                               lay, b.xh, pf_lo(ctx, lay, n, K), b.xs);
+        if (!ps.split_ready) pf_split_launch(x, g.K, n, lay, b.xh, pf_lo(ctx, lay, n, g.K), b.xs, ctx->stream);
         ps.split_ready = false;
     }
+    int rc;
     if (lay == 0) {
         // row-major hi rows then lo rows; partials unscaled, the epilogue multiplies by 1 / s_t
-        if (pf_f8(dt)) {
-            // the matrix's exact f16 image first (one streaming pass: 1 B read, 2 B written per weight)
-            const size_t n16 = (size_t)rows * K / 16;
-            if ((size_t)rows * K > ctx->pf_wdq_elems || K % 16)
-                return set_err(ctx, XH_E_INVALID, "prefill: %s fp8 image does not fit", g.what);
-            const int grid = (int)std::min<size_t>((n16 + 255) / 256, 8192);
-            if (dt == XH_F8_E4M3)
-                hipLaunchKernelGGL(pf_dequant_f16_kernel<XH_F8_E4M3>, dim3(grid), dim3(256), 0, ctx->stream,
-                                   (const u32x4*)w, n16, (u32x4*)ctx->pf_wdq);
-            else
-                hipLaunchKernelGGL(pf_dequant_f16_kernel<XH_F8_E5M2>, dim3(grid), dim3(256), 0, ctx->stream,
-                                   (const u32x4*)w, n16, (u32x4*)ctx->pf_wdq);
-            w = ctx->pf_wdq;
-        }
-        if (gq_mx(dt)) {
-            // MXFP4 in the f16 range: one exact image, as fp8 (0.53 B read, 2 B written per weight)
-            if ((size_t)rows * K > ctx->pf_wdq_elems || K % 32)
-                return set_err(ctx, XH_E_INVALID, "prefill: %s MXFP4 image does not fit", g.what);
-            const size_t chunks = (size_t)rows * K / 32;
-            const int grid = (int)std::min<size_t>((chunks + 255) / 256, 8192);
-            hipLaunchKernelGGL(pf_dequant_mx_kernel, dim3(grid), dim3(256), 0, ctx->stream, (const uint8_t*)w, rows, K,
-                               ctx->pf_wdq);
-            w = ctx->pf_wdq;
-        }
-        const uint16_t* w_lo = nullptr;  // gguf blocks: the lo image, a second GEMM into more partials
-        if (gq_dt(dt) && !gq_mx(dt)) {
-            if ((size_t)2 * rows * K > ctx->pf_wdq_elems || K % 32)
-                return set_err(ctx, XH_E_INVALID, "prefill: %s block image does not fit", g.what);
-            const size_t chunks = (size_t)rows * K / 8;
-            const int grid = (int)std::min<size_t>((chunks + 255) / 256, 8192);
-            uint16_t* hi = ctx->pf_wdq;
-            uint16_t* lo = ctx->pf_wdq + (size_t)rows * K;
-            if (dt == XH_Q8_0)
-                hipLaunchKernelGGL(pf_dequant_gq_kernel<XH_Q8_0>, dim3(grid), dim3(256), 0, ctx->stream,
-                                   (const uint8_t*)w, rows, K, hi, lo);
-            else if (dt == XH_Q5_0)
-                hipLaunchKernelGGL(pf_dequant_gq_kernel<XH_Q5_0>, dim3(grid), dim3(256), 0, ctx->stream,
-                                   (const uint8_t*)w, rows, K, hi, lo);
-            else
-                hipLaunchKernelGGL(pf_dequant_gq_kernel<XH_Q4_0>, dim3(grid), dim3(256), 0, ctx->stream,
-                                   (const uint8_t*)w, rows, K, hi, lo);
-            w = hi;
-            w_lo = lo;
-        }
+        const uint16_t *w_hi = nullptr, *w_lo = nullptr;
+        if ((rc = pf_gemm_images(p, io, &w_hi, &w_lo, ctx->stream))) return pf_gemm_err(ctx, rc, g, n);
         ps.scaled = true;
         if (ctx->prefill_gemm == 4) {
             // hi and lo rows as one B operand of 2n columns: partials [2][n][rows]; a pass length
             // hipBLASLt has no algorithm for runs on gemm16.h instead (same layout, same bound)
             bool have = false;
-            int rc = blas_has_plan(ctx, rows, K, 2 * n, &have);
+            rc = blas_has_plan(ctx, g.rows, g.K, 2 * n, &have);
             if (rc) return rc;
-            if (have || K % MM_KMULT) {
-                rc = blas_gemm(ctx, w, K, rows, b.xh, 2 * n, b.part);
+            if (have || g.K % MM_KMULT) {
+                rc = blas_gemm(ctx, w_hi, g.K, g.rows, b.xh, 2 * n, b.part);
                 if (rc) return rc;
                 ks = 2;
                 return 0;
             }
         }
-        const int images = w_lo ? 2 : 1;
-        const size_t cap = pf_part_floats(ctx, b.cap[PfBufs::PASS]);
-        MmArgs a{};
-        a.w = (const uint16_t*)w; a.xh = b.xh; a.xl = b.xh + (size_t)n * K; a.out = b.part;
-        a.rows = rows; a.K = K; a.n = n; a.ks = mm_pick_ks(rows, K, n, cap / images, ctx->n_cu);
-        a.n_rt = mm_row_tiles(rows); a.n_tt = mm_tok_tiles(n);
-        if (a.ks <= 0 || (size_t)images * a.ks * n * rows > cap)
-            return set_err(ctx, XH_E_INVALID, "prefill: %s GEMM %d x %d over %d tokens does not fit", g.what, rows, K, n);
-        mm_launch(a, ctx->n_cu, ctx->stream);
-        if (w_lo) {  // partials [ks, 2 ks): W_lo . X, summed after W_hi's by the epilogue
-            a.w = w_lo;
-            a.out = b.part + (size_t)a.ks * n * rows;
-            mm_launch(a, ctx->n_cu, ctx->stream);
-        }
-        ks = images * a.ks;
-        return 0;
+        rc = pf_gemm_rowmajor(p, io, w_hi, w_lo, &ks, ctx->stream);
+    } else if (lay > 0) {
+        rc = pf_gemm_frag(p, io, lay, &ks, ctx->stream);
+    } else {
+        rc = pf_gemm_f32(p, io, &ks, ctx->stream);
     }
-    if (lay > 0) {
-        PfGemm16Args a{};
-        a.w = w; a.row_bytes = (size_t)K * (16 / lay); a.K = K; a.rows = rows;
-        a.xh = b.xh; a.xl = b.xl; a.inv_s = b.xs; a.n = n; a.ks = pf_ks16(rows, K, lay);
-        a.part = b.part;
-        switch (dt) {
-            case XH_F16: pf_gemm16_t<XH_F16>(a, ctx->stream); break;
-            case XH_F8_E4M3: pf_gemm16_t<XH_F8_E4M3>(a, ctx->stream); break;
-            default: pf_gemm16_t<XH_F8_E5M2>(a, ctx->stream); break;
-        }
-        ks = a.ks;
-        return 0;
-    }
-    const int E = pf_elems(dt);
-    if (K % (2 * E) || n > PF_TOK) return set_err(ctx, XH_E_INVALID, "prefill: %s shape not supported", g.what);
-    PfGemmArgs a{};
-    a.w = w; a.K = K; a.rows = rows; a.x = x; a.n = n; a.part = b.part;
-    a.row_bytes = gq_dt(dt) ? gq_pitch(dt, K) : (size_t)K * (16 / E);
-    a.ks = pf_ks(rows, K, E);
-    if ((size_t)a.ks * rows > PF_PART_ROWS) return set_err(ctx, XH_E_INVALID, "prefill: %s shape not supported", g.what);
-    if (for_dt(dt, PfGemmF32{a, ctx->stream}) < 0)
-        return set_err(ctx, XH_E_INVALID, "prefill: %s dtype %d not supported", g.what, dt);
-    ks = a.ks;
-    return 0;
+    return rc ? pf_gemm_err(ctx, rc, g, n) : 0;
+}
+void pf_epi_launch(const PfEpiArgs& e, hipStream_t s) {
+    const int threads = e.n * ((e.rows + 1) / 2);
+    hipLaunchKernelGGL(prefill_epi_kernel, dim3((threads + 255) / 256), dim3(256), 0, s, e);
 }
 void pf_epi(xh_ctx* ctx, const PfPass& ps, PfEpiArgs e) {
     e.part = ctx->pf.part;
     e.part_s = ps.scaled ? ctx->pf.xs : nullptr;
-    const int threads = e.n * ((e.rows + 1) / 2);
-    hipLaunchKernelGGL(prefill_epi_kernel, dim3((threads + 255) / 256), dim3(256), 0, ctx->stream, e);
+    pf_epi_launch(e, ctx->stream);
 }
 // x += the last GEMM's partials (EPI_RESID), then the rmsnorm of the updated rows as the input of
 // the GEMM g (K = dim): one launch when that GEMM takes the split input and the rows fit the
@@ -416,9 +347,8 @@ int pf_resid_norm(xh_ctx* ctx, PfPass& ps, int ks, const void* nw, int ndt, cons
     const size_t lds = (size_t)c.dim * sizeof(float);  // + the kernel's static red[4]
     if (lay >= 0 && ctx->pf_resid_norm && c.dim % 8 == 0 && lds + 4 * sizeof(float) <= 64 * 1024) {
         HIP_TRY(ctx, hipGetLastError());  // an earlier launch's error is reported as such
-        hipLaunchKernelGGL(prefill_resid_norm_split_kernel, dim3(pf_split_grid(lay, ps.m)), dim3(256), lds, ctx->stream,
-                           (const float*)b.part, ks, (const float*)(ps.scaled ? b.xs : nullptr), b.x, c.dim, nw, ndt,
-                           c.norm_eps, ps.m, lay, b.xh, pf_lo(ctx, lay, ps.m, c.dim), b.xs);
+        pf_resid_norm_split_launch(b.part, ks, ps.scaled ? b.xs : nullptr, b.x, c.dim, nw, ndt, c.norm_eps, ps.m, lay, b.xh,
+                                   pf_lo(ctx, lay, ps.m, c.dim), b.xs, ctx->stream);
         HIP_TRY(ctx, hipGetLastError());
         ps.split_ready = true;
         return 0;
@@ -442,9 +372,8 @@ int pf_glu(xh_ctx* ctx, PfPass& ps, int ks, const PfMat& w2) {
         // part_s and inv_s are both pf.xs: a workgroup reads its token's factor before the
         // barrier and writes the new one after it
         HIP_TRY(ctx, hipGetLastError());  // an earlier launch's error is reported as such
-        hipLaunchKernelGGL(prefill_glu_split_kernel, dim3(pf_split_grid(lay, ps.m)), dim3(1024), lds, ctx->stream,
-                           (const float*)b.part, ks, ps.m, c.hidden_dim, c.act, lay, b.xh,
-                           pf_lo(ctx, lay, ps.m, c.hidden_dim), b.xs, (const float*)(ps.scaled ? b.xs : nullptr));
+        pf_glu_split_launch(b.part, ks, ps.scaled ? b.xs : nullptr, ps.m, c.hidden_dim, c.act, lay, b.xh,
+                            pf_lo(ctx, lay, ps.m, c.hidden_dim), b.xs, ctx->stream);
         HIP_TRY(ctx, hipGetLastError());
         ps.split_ready = true;
         return 0;
@@ -540,6 +469,171 @@ int pf_ring_t(const PfAttnDims& d, const float* q, uint16_t* kc, uint16_t* vc, c
 }
 
 }  // namespace
+
+// ---- the prompt GEMM's launch bodies (ctx.h): what pf_gemm and the test ops both run ----------
+// weights per 16-byte chunk of the f32-input MFMA kernel's decoders (WDec<DT>::E)
+int xalm::pf_elems(int dt) {
+    if (dt == XH_F8_E4M3_EXACT || dt == XH_F8_E5M2_EXACT || dt == XH_Q8_0) return 16;
+    return gq_dt(dt) ? 32 : elems_per_16b(dt);  // the nibble blocks (Q8_0 above)
+}
+// 0 = row-major (gemm16.h or hipBLASLt), E > 0 = the split-f16 register-streaming kernel's
+// fragments, -1 = no split (f32-input MFMA).  XH_OPT_PREFILL 1 / 4: row-major for f16 / e4m3 / e5m2
+// where the GEMM fits, else the split kernel for fp8; 2: the split kernel for f16 and fp8; 3: never
+// split.  The split kernel also needs a K slicing.
+int xalm::pf_gemm_route(const PfGemmPlan& p) {
+    if (pf_lay0(p)) return 0;
+    const bool f8 = pf_f8(p.dt);
+    const int m = p.mode;
+    if (!(m == 2 || ((m == 1 || m == 4) && f8))) return -1;
+    if (p.dt != XH_F16 && !f8) return -1;
+    const int E = elems_per_16b(p.dt);
+    return pf_ks16(p.rows, p.K, E) ? E : -1;
+}
+int xalm::pf_gemm_row_tile(int route) { return route == 0 ? MM_BR : 32 * (route > 0 ? PF_RT16 : PF_RT); }
+bool xalm::pf_gemm_ks_ok(const PfGemmPlan& p, int route) {
+    const int ks = p.ks, K = p.K;
+    if (ks <= 0 || (ks & (ks - 1))) return false;  // every picker doubles
+    if (route == 0) {                              // mm_pick_ks
+        const int images = gq_dt(p.dt) && !gq_mx(p.dt) ? 2 : 1;
+        return ks <= 8 && K % (ks * MM_KMULT) == 0 && (size_t)images * ks * p.n * p.rows <= p.part_floats;
+    }
+    const int E = route > 0 ? route : pf_elems(p.dt);
+    const int rt = route > 0 ? PF_RT16 : PF_RT;
+    const int n_rt = (p.rows + 32 * rt - 1) / (32 * rt);
+    // pf_ks16: slices of whole rings; pf_ks: of whole rings where K allows, else of chunk pairs
+    const int unit = route > 0 || K % (8 * E) == 0 ? 8 * E : 2 * E;
+    if (ks > 64 || K % (ks * unit) || (ks > 1 && (size_t)ks * n_rt > PF_WAVE_TARGET)) return false;
+    return (size_t)ks * p.rows <= PF_PART_ROWS && (size_t)ks * p.n * p.rows <= p.part_floats;
+}
+uint16_t* xalm::pf_split_lo(int lay, int n, int K, uint16_t* xh, uint16_t* xl) { return lay ? xl : xh + (size_t)n * K; }
+size_t xalm::pf_split_index(int t, int k, int K, int lay) { return split_off(t, k, K, lay); }
+void xalm::pf_split_launch(const float* x, int K, int n, int lay, uint16_t* xh, uint16_t* xl, float* inv_s, hipStream_t s) {
+    hipLaunchKernelGGL(prefill_split_kernel, dim3(pf_split_grid(lay, n)), dim3(256), 0, s, x, K, n, lay, xh, xl, inv_s);
+}
+int xalm::pf_gemm_images(const PfGemmPlan& p, const PfGemmIo& io, const uint16_t** w_hi, const uint16_t** w_lo,
+                         hipStream_t s) {
+    const int dt = p.dt, rows = p.rows, K = p.K;
+    const size_t cap = (size_t)(p.max_groups > 0 ? p.max_groups : PF_IMAGE_GROUPS);
+    *w_hi = (const uint16_t*)io.w;
+    *w_lo = nullptr;  // gguf blocks: the lo image, a second GEMM into more partials
+    if (pf_f8(dt)) {
+        // the matrix's exact f16 image first (one streaming pass: 1 B read, 2 B written per weight)
+        const size_t n16 = (size_t)rows * K / 16;
+        if ((size_t)rows * K > io.wdq_elems || K % 16) return PF_GEMM_E_IMAGE;
+        const int grid = (int)std::min<size_t>((n16 + 255) / 256, cap);
+        if (dt == XH_F8_E4M3)
+            hipLaunchKernelGGL(pf_dequant_f16_kernel<XH_F8_E4M3>, dim3(grid), dim3(256), 0, s, (const u32x4*)io.w, n16,
+                               (u32x4*)io.wdq);
+        else
+            hipLaunchKernelGGL(pf_dequant_f16_kernel<XH_F8_E5M2>, dim3(grid), dim3(256), 0, s, (const u32x4*)io.w, n16,
+                               (u32x4*)io.wdq);
+        *w_hi = io.wdq;
+    }
+    if (gq_mx(dt)) {
+        // MXFP4 in the f16 range: one exact image, as fp8 (0.53 B read, 2 B written per weight)
+        if ((size_t)rows * K > io.wdq_elems || K % 32) return PF_GEMM_E_IMAGE;
+        const size_t chunks = (size_t)rows * K / 32;
+        const int grid = (int)std::min<size_t>((chunks + 255) / 256, cap);
+        hipLaunchKernelGGL(pf_dequant_mx_kernel, dim3(grid), dim3(256), 0, s, (const uint8_t*)io.w, rows, K, io.wdq);
+        *w_hi = io.wdq;
+    }
+    if (gq_dt(dt) && !gq_mx(dt)) {
+        if ((size_t)2 * rows * K > io.wdq_elems || K % 32) return PF_GEMM_E_IMAGE;
+        const size_t chunks = (size_t)rows * K / 8;
+        const int grid = (int)std::min<size_t>((chunks + 255) / 256, cap);
+        uint16_t* hi = io.wdq;
+        uint16_t* lo = io.wdq + (size_t)rows * K;
+        if (dt == XH_Q8_0)
+            hipLaunchKernelGGL(pf_dequant_gq_kernel<XH_Q8_0>, dim3(grid), dim3(256), 0, s, (const uint8_t*)io.w, rows, K, hi, lo);
+        else if (dt == XH_Q5_0)
+            hipLaunchKernelGGL(pf_dequant_gq_kernel<XH_Q5_0>, dim3(grid), dim3(256), 0, s, (const uint8_t*)io.w, rows, K, hi, lo);
+        else if (dt == XH_Q4_0)
+            hipLaunchKernelGGL(pf_dequant_gq_kernel<XH_Q4_0>, dim3(grid), dim3(256), 0, s, (const uint8_t*)io.w, rows, K, hi, lo);
+        else
+            return PF_GEMM_E_DTYPE;  // the affine blocks have no exact f16 pair
+        *w_hi = hi;
+        *w_lo = lo;
+    }
+    return PF_GEMM_OK;
+}
+int xalm::pf_gemm_rowmajor(const PfGemmPlan& p, const PfGemmIo& io, const uint16_t* w_hi, const uint16_t* w_lo, int* ks_out,
+                           hipStream_t s) {
+    const int rows = p.rows, K = p.K, n = p.n;
+    const int images = w_lo ? 2 : 1;
+    const size_t cap = p.part_floats;
+    MmArgs a{};
+    a.w = w_hi; a.xh = io.xh; a.xl = io.xh + (size_t)n * K; a.out = io.part;
+    a.rows = rows; a.K = K; a.n = n; a.ks = p.ks > 0 ? p.ks : mm_pick_ks(rows, K, n, cap / images, p.n_cu);
+    a.n_rt = mm_row_tiles(rows); a.n_tt = mm_tok_tiles(n);
+    if (a.ks <= 0 || K % (a.ks * MM_KMULT) || (size_t)images * a.ks * n * rows > cap) return PF_GEMM_E_FIT;
+    mm_launch(a, p.n_cu, s);
+    if (w_lo) {  // partials [ks, 2 ks): W_lo . X, summed after W_hi's by the epilogue
+        a.w = w_lo;
+        a.out = io.part + (size_t)a.ks * n * rows;
+        mm_launch(a, p.n_cu, s);
+    }
+    *ks_out = images * a.ks;
+    return PF_GEMM_OK;
+}
+int xalm::pf_gemm_frag(const PfGemmPlan& p, const PfGemmIo& io, int lay, int* ks_out, hipStream_t s) {
+    PfGemm16Args a{};
+    a.w = io.w; a.row_bytes = (size_t)p.K * (16 / lay); a.K = p.K; a.rows = p.rows;
+    a.xh = io.xh; a.xl = io.xl; a.inv_s = io.xs; a.n = p.n; a.ks = p.ks > 0 ? p.ks : pf_ks16(p.rows, p.K, lay);
+    a.part = io.part;
+    if (p.n > PF_TOK || a.ks <= 0 || p.K % (a.ks * 8 * lay)) return PF_GEMM_E_SHAPE;
+    if ((size_t)a.ks * p.n * p.rows > p.part_floats) return PF_GEMM_E_FIT;
+    switch (p.dt) {
+        case XH_F16: pf_gemm16_t<XH_F16>(a, s); break;
+        case XH_F8_E4M3: pf_gemm16_t<XH_F8_E4M3>(a, s); break;
+        case XH_F8_E5M2: pf_gemm16_t<XH_F8_E5M2>(a, s); break;
+        default: return PF_GEMM_E_DTYPE;
+    }
+    *ks_out = a.ks;
+    return PF_GEMM_OK;
+}
+int xalm::pf_gemm_f32(const PfGemmPlan& p, const PfGemmIo& io, int* ks_out, hipStream_t s) {
+    const int dt = p.dt, K = p.K, rows = p.rows;
+    const int E = pf_elems(dt);
+    if (K % (2 * E) || p.n > PF_TOK) return PF_GEMM_E_SHAPE;
+    PfGemmArgs a{};
+    a.w = io.w; a.K = K; a.rows = rows; a.x = io.x; a.n = p.n; a.part = io.part;
+    a.row_bytes = gq_dt(dt) ? gq_pitch(dt, K) : (size_t)K * (16 / E);
+    a.ks = p.ks > 0 ? p.ks : pf_ks(rows, K, E);
+    if ((size_t)a.ks * rows > PF_PART_ROWS || K % (a.ks * 2 * E)) return PF_GEMM_E_SHAPE;
+    if ((size_t)a.ks * p.n * rows > p.part_floats) return PF_GEMM_E_FIT;
+    if (for_dt(dt, PfGemmF32{a, s}) < 0) return PF_GEMM_E_DTYPE;
+    *ks_out = a.ks;
+    return PF_GEMM_OK;
+}
+void xalm::pf_norm_split_launch(const float* x, int dim, const void* nw, int ndt, float eps, int n, int lay, uint16_t* xh,
+                                uint16_t* xl, float* inv_s, hipStream_t s) {
+    hipLaunchKernelGGL(prefill_rmsnorm_split_kernel, dim3(pf_split_grid(lay, n)), dim3(256), 0, s, x, dim, nw, ndt, eps, n, lay,
+                       xh, xl, inv_s);
+}
+void xalm::pf_norm_launch(const float* x, int dim, const void* nw, int ndt, float eps, int n, float* o, hipStream_t s) {
+    hipLaunchKernelGGL(prefill_rmsnorm_kernel, dim3(n), dim3(256), 0, s, x, dim, nw, ndt, eps, o);
+}
+void xalm::pf_resid_norm_split_launch(const float* part, int ks, const float* part_s, float* x, int dim, const void* nw,
+                                      int ndt, float eps, int n, int lay, uint16_t* xh, uint16_t* xl, float* inv_s,
+                                      hipStream_t s) {
+    const size_t lds = (size_t)dim * sizeof(float);  // + the kernel's static red[4]
+    hipLaunchKernelGGL(prefill_resid_norm_split_kernel, dim3(pf_split_grid(lay, n)), dim3(256), lds, s, part, ks, part_s, x, dim,
+                       nw, ndt, eps, n, lay, xh, xl, inv_s);
+}
+void xalm::pf_glu_split_launch(const float* part, int ks, const float* part_s, int n, int hidden, int act, int lay,
+                               uint16_t* xh, uint16_t* xl, float* inv_s, hipStream_t s) {
+    // dynamic LDS = one f32 row of h; the kernel adds a static 16-float reduction array
+    const size_t lds = (size_t)hidden * sizeof(float);
+    hipLaunchKernelGGL(prefill_glu_split_kernel, dim3(pf_split_grid(lay, n)), dim3(1024), lds, s, part, ks, n, hidden, act, lay,
+                       xh, xl, inv_s, part_s);
+}
+void xalm::pf_epi_plain_launch(const float* part, const float* part_s, int ks, int n, int rows, int epi, float* out,
+                               size_t out_stride, int act, hipStream_t s) {
+    PfEpiArgs e{};
+    e.part = part; e.part_s = part_s; e.ks = ks; e.n = n; e.rows = rows; e.epi = epi; e.out = out;
+    e.out_stride = out_stride; e.act = act;
+    pf_epi_launch(e, s);
+}
 
 bool xalm::pf_attn_shape_ok(int hd, int qpk) { return pf_attn_shape(hd, qpk); }
 int xalm::pf_fa_split_max(int pos0) { return std::max(1, pos0 / (32 * FA_TPS) / FA_MIN_SPLIT_STAGES); }
