@@ -52,7 +52,11 @@ $(OBJ)/truncate.o: xalm_amd/csrc/truncate.cpp
 $(OBJ)/seq_host.o: xalm_amd/csrc/seq_host.cpp
 	@mkdir -p $(OBJ)
 	$(CXX) $(HOSTFLAGS) -ffp-contract=off -MMD -MP -c -o $@ $<
-HIP_OBJS += $(OBJ)/constraint.o $(OBJ)/top_logprobs.o $(OBJ)/truncate.o $(OBJ)/seq_host.o
+# the host definition of the fp8 KV ring's element: plain C++, integer arithmetic
+$(OBJ)/kv8.o: xalm_amd/csrc/kv8.cpp
+	@mkdir -p $(OBJ)
+	$(CXX) $(HOSTFLAGS) -MMD -MP -c -o $@ $<
+HIP_OBJS += $(OBJ)/constraint.o $(OBJ)/top_logprobs.o $(OBJ)/truncate.o $(OBJ)/seq_host.o $(OBJ)/kv8.o
 $(LIB)/libxalm_hip.so: $(HIP_OBJS)
 	@mkdir -p $(LIB)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $^

@@ -120,6 +120,28 @@ typedef struct xh_ctx xh_ctx;
 /* Create a device context on HIP device `device_ordinal`: allocates the fp16 KV rings
  * (2 * n_layers * max_seq_len * n_kv_heads*head_dim) and the device InferenceState. */
 int xh_create(const xh_config* cfg, int device_ordinal, xh_ctx** out);
+
+/* xh_create with the KV rings' element type: XH_F16 (exactly xh_create) or XH_F8_E4M3, anything else
+ * XH_E_INVALID.  An fp8 (e4m3) context keeps one byte per element in rings of the same
+ * [slot][kv_dim] shape: half the bytes the attention streams per step, twice the context in the
+ * same memory.  head_dim must be a multiple of 16.  Every K/V writer stores
+ * xh_f8_e4m3_from_f32 of the value the fp16 ring would round to fp16; the attention decodes the
+ * codes with the gfx950 converter and computes in f32 as ever.
+ * The two sink rows of K (slots 0 and 1), which the reference re-rotates every step past the ring
+ * wrap, are kept per layer in an fp16 master [2][kv_dim]: the rotation reads and writes the master
+ * (the fp16 ring's arithmetic exactly) and ring slot r is rewritten as the e4m3 rounding of master
+ * row r, so the fp8 rounding does not accumulate over the rotations.  At all times ring K slot r
+ * equals f8(master[r]).
+ * Routing on an fp8 context (the stored xh_option values are untouched and read back as set):
+ *   decode:  every layer takes the two-launch route (attention, then Wo), as a layer with a
+ *            block-type Wo does; the fused attention + Wo launch has no fp8 instantiation.
+ *   prompts: the GEMMs as ever; the attention as under XH_OPT_PREFILL_ATTN 0 (the per-token
+ *            split kernel); no ring passes: a prompt that reaches past the ring is batched
+ *            below max_seq_len and takes the per-token loop from the cut (xh_prefill_route
+ *            answers accordingly). */
+int xh_create_kv(const xh_config* cfg, int device_ordinal, int kv_dtype, xh_ctx** out);
+/* The context's KV element type: XH_F16 or XH_F8_E4M3. */
+int xh_kv_dtype(const xh_ctx* ctx);
 void xh_destroy(xh_ctx* ctx);
 const char* xh_last_error(const xh_ctx* ctx); /* ctx may be NULL: last create error */
 
@@ -592,6 +614,26 @@ int xh_reset(xh_ctx* ctx);
  * which: 0 = key cache, 1 = value cache.  Rows are [slot][n_kv_heads*head_dim] fp16 bits. */
 int xh_kv_write(xh_ctx* ctx, int layer, int which, int slot0, int n_slots, const uint16_t* host);
 int xh_kv_read(xh_ctx* ctx, int layer, int which, int slot0, int n_slots, uint16_t* host);
+/* The same on an fp8 context (xh_create_kv): rows of raw e4m3 codes, one byte per element.  A NaN
+ * code (0x7F, 0xFF) in a write is XH_E_INVALID and nothing is written.  Writing K slots 0 or 1 also
+ * sets the sink master to the exact fp16 image of the codes.  xh_kv_write / xh_kv_read return
+ * XH_E_INVALID on an fp8 context, this pair on an fp16 one.  xh_kv_fill_synthetic on an fp8 context
+ * stores the e4m3 rounding of the fp16 value it would have stored, and sets the master likewise. */
+int xh_kv_write8(xh_ctx* ctx, int layer, int which, int slot0, int n_slots, const uint8_t* host);
+int xh_kv_read8(xh_ctx* ctx, int layer, int which, int slot0, int n_slots, uint8_t* host);
+/* Test hook: the layer's sink master, fp16 bits [2][kv_dim].  XH_E_INVALID on an fp16 context. */
+int xh_kv_sink_read(xh_ctx* ctx, int layer, uint16_t* out);
+
+/* The element of the fp8 KV ring, on the host in plain C++: clamp v to [-448, 448] with f32 min /
+ * max, then the nearest e4m3fn value, ties to the even mantissa, subnormals down to 2^-9;
+ * magnitudes below 2^-10 and the tie at 2^-10 give a zero; the sign is kept (-0 is 0x80).  NaN is
+ * outside the contract.  This is the definition of what every K/V writer stores. */
+int xh_f8_e4m3_from_f32(const float* in, size_t n, uint8_t* out);
+/* The same through the device function the K/V writers call (the clamp, then v_cvt_pk_fp8_f32);
+ * needs a device, no context.  Bit-identical to xh_f8_e4m3_from_f32 on every finite input class
+ * the tests cover (all f16 values, the midpoints of adjacent codes and their neighbours, the
+ * clamp's edges, the zero threshold): the converter needs no integer fallback. */
+int xh_op_kv_quantize(const float* in, size_t n, uint8_t* out);
 
 /* Bytes the forward pass reads per token: Model::active_bytes(pos), src/model.cpp:12-35. */
 size_t xh_active_bytes(const xh_ctx* ctx, size_t pos);
@@ -670,6 +712,10 @@ int xh_op_rope(float* vec, int d, int head_dim, int pos, float theta, int rotary
 /* mha_cuda (src/model.h:308-313): xout[n_heads*head_dim]; kb/vb fp16 [max_seq_len][n_kv_heads*head_dim]. */
 int xh_op_mha(float* xout, const uint16_t* kb, const uint16_t* vb, const float* q, int head_dim,
               int kv_len, int max_seq_len, int n_heads, int n_kv_heads);
+/* The same over fp8 rings (e4m3 codes, [max_seq_len][n_kv_heads*head_dim] bytes; head_dim % 16 == 0),
+ * through the launch code of an fp8 context's decode step. */
+int xh_op_mha8(float* xout, const uint8_t* kb, const uint8_t* vb, const float* q, int head_dim,
+               int kv_len, int max_seq_len, int n_heads, int n_kv_heads);
 
 /* The prompt-pass GEMM of XH_OPT_PREFILL 1 (gemm16.h): y[t][r] = sum_k w[r][k] * (xh[t][k] + xl[t][k])
  * with f16 w [rows][K], f16 xh / xl [n][K] and f32 y [n][rows] (the K slices' partials summed in

@@ -180,6 +180,8 @@ _FP = ctypes.POINTER(ctypes.c_float)
 
 _SIGNATURES = {
     "xh_create": (_I, [ctypes.POINTER(XhConfig), _I, ctypes.POINTER(_P)]),
+    "xh_create_kv": (_I, [ctypes.POINTER(XhConfig), _I, _I, ctypes.POINTER(_P)]),
+    "xh_kv_dtype": (_I, [_P]),
     "xh_destroy": (None, [_P]),
     "xh_last_error": (ctypes.c_char_p, [_P]),
     "xh_upload": (_I, [_P, _I, _I, _I, _P, _SZ]),
@@ -240,6 +242,12 @@ _SIGNATURES = {
     "xh_reset": (_I, [_P]),
     "xh_kv_write": (_I, [_P, _I, _I, _I, _I, _P]),
     "xh_kv_read": (_I, [_P, _I, _I, _I, _I, _P]),
+    "xh_kv_write8": (_I, [_P, _I, _I, _I, _I, _P]),
+    "xh_kv_read8": (_I, [_P, _I, _I, _I, _I, _P]),
+    "xh_kv_sink_read": (_I, [_P, _I, _P]),
+    "xh_f8_e4m3_from_f32": (_I, [_P, _SZ, _P]),
+    "xh_op_kv_quantize": (_I, [_P, _SZ, _P]),
+    "xh_op_mha8": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I]),
     "xh_active_bytes": (_SZ, [_P, _SZ]),
     "xh_set_graphs": (_I, [_P, _I]),
     "xh_set_option": (_I, [_P, _I, _I]),
@@ -581,6 +589,34 @@ def op_rope(vec: np.ndarray, head_dim: int, pos: int, theta: float, rotary_dim: 
     v = np.array(vec, dtype=np.float32, copy=True)
     check(lib().xh_op_rope(ptr(v), v.size, head_dim, pos, theta, rotary_dim))
     return v
+
+
+def f8_e4m3_from_f32(values: np.ndarray) -> np.ndarray:
+    """The element of the fp8 KV ring (xh_f8_e4m3_from_f32): float32 -> e4m3 codes, uint8 of the
+    same shape.  The host definition; no device needed."""
+    v = np.ascontiguousarray(values, dtype=np.float32)
+    out = np.empty(v.shape, dtype=np.uint8)
+    check(lib().xh_f8_e4m3_from_f32(ptr(v), v.size, ptr(out)))
+    return out
+
+
+def op_kv_quantize(values: np.ndarray) -> np.ndarray:
+    """The same through the device function the K/V writers call (xh_op_kv_quantize)."""
+    v = np.ascontiguousarray(values, dtype=np.float32)
+    out = np.empty(v.shape, dtype=np.uint8)
+    check(lib().xh_op_kv_quantize(ptr(v), v.size, ptr(out)))
+    return out
+
+
+def op_mha8(kb: np.ndarray, vb: np.ndarray, q: np.ndarray, head_dim: int, kv_len: int, max_seq_len: int,
+            n_heads: int, n_kv_heads: int) -> np.ndarray:
+    """op_mha over fp8 rings: kb / vb e4m3 codes, uint8 [max_seq_len][n_kv_heads * head_dim]."""
+    kb = np.ascontiguousarray(kb, dtype=np.uint8)
+    vb = np.ascontiguousarray(vb, dtype=np.uint8)
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    out = np.empty(n_heads * head_dim, dtype=np.float32)
+    check(lib().xh_op_mha8(ptr(out), ptr(kb), ptr(vb), ptr(q), head_dim, kv_len, max_seq_len, n_heads, n_kv_heads))
+    return out
 
 
 def op_mha(kb: np.ndarray, vb: np.ndarray, q: np.ndarray, head_dim: int, kv_len: int, max_seq_len: int,

@@ -1,4 +1,6 @@
-// attention.h — single-token GQA attention over the fp16 KV ring (split-KV "flash decoding").
+// attention.h — single-token GQA attention over the KV ring (split-KV "flash decoding"): fp16
+// elements, or e4m3 codes (template argument KV of attn_block; the scores, the softmax, the
+// partials and the merge are f32 either way).
 //
 // Replaces the head loop of Block::_block_cpu (jubruckne/Xalm src/infer.cpp:434-444) and
 // `attn` (src/infer.cpp:325-359) + `softmax` (:280-297):
@@ -39,7 +41,7 @@ constexpr int ATTN_MIN_T = 256;  // minimum slots per split
 
 struct AttnArgs {
     const float* q;          // [n_heads * HD], roped
-    const uint16_t* kc;      // [max_seq_len][kv_dim] fp16 bits
+    const uint16_t* kc;      // [max_seq_len][kv_dim] fp16 bits (KV = XH_F8_E4M3: one e4m3 code per element)
     const uint16_t* vc;
     int kv_dim;
     int n_heads;
@@ -59,12 +61,56 @@ __device__ __host__ __forceinline__ int attn_split_len(const int kv_len, const i
     return t < min_t ? min_t : t;
 }
 // one round of K/V rows per block: the split floor of a THREADS-thread block
-__device__ __host__ constexpr int attn_min_t(const int hd, const int threads) { return ATTN_MIN_ROUNDS * threads / (hd / 8); }
+// (e: K/V elements per lane, attn_kv_elems)
+__device__ __host__ constexpr int attn_min_t(const int hd, const int threads, const int e = 8) {
+    return ATTN_MIN_ROUNDS * threads / (hd / e);
+}
 // the fused launch's floor: half a round (each split block pulls half the bytes: a block's
 // K/V fetch is bound by its CU's ~60 GB/s, so more, smaller splits shorten the chain)
-__device__ __host__ constexpr int attn_min_t_partials(const int hd, const int threads) {
-    return attn_min_t(hd, threads) / 2;
+__device__ __host__ constexpr int attn_min_t_partials(const int hd, const int threads, const int e = 8) {
+    return attn_min_t(hd, threads, e) / 2;
 }
+
+// K/V elements one lane holds per row.  fp16: a 16-byte load's 8, so a row takes HD / 8 lanes.
+// e4m3: a 16-byte load holds 16, and a row then takes HD / 16 lanes (1 at head_dim 16) — but a lane
+// keeps E values of q and E of the output for each of its QPK q heads, and a 1024-thread block has
+// 128 registers per lane: at QPK * E = 64 the compiler spills (the e4m3 form at 4 q heads per KV
+// head: 216 bytes of scratch; the fp16 form does at 8).  So the e4m3 forms keep QPK * E <= 32: 16
+// elements up to 2 q heads per KV head, 8 (an 8-byte load) at 4, 4 (a 4-byte load) at 8, and
+// hold proportionally more passes per round (attn_pref_long), so that a round requests as many
+// bytes as the fp16 form's.
+__device__ __host__ constexpr int attn_kv_elems(const int kv, const int qpk) {
+    return kv == XH_F8_E4M3 ? (qpk <= 2 ? 16 : qpk <= 4 ? 8 : 4) : 8;
+}
+// one lane's chunk of a row: V its registers, dec() the E values
+template <int KV, int E> struct AttnKv;
+template <> struct AttnKv<XH_F16, 8> {
+    typedef u32x4 V;
+    __device__ __forceinline__ static void dec(const V v, float* f) { WDec<XH_F16>::dec(v, f); }
+};
+template <> struct AttnKv<XH_F8_E4M3, 16> {
+    typedef u32x4 V;
+    __device__ __forceinline__ static void dec(const V v, float* f) { WDec<XH_F8_E4M3>::dec(v, f); }
+};
+// 4 codes of one word (v_cvt_pk_f32_fp8, as dec_f8_hw)
+__device__ __forceinline__ void dec_f8_e4m3_word(const uint32_t w, float* f) {
+    const f2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8(w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(w, true);
+    f[0] = lo.x; f[1] = lo.y; f[2] = hi.x; f[3] = hi.y;
+}
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+template <> struct AttnKv<XH_F8_E4M3, 8> {
+    typedef u32x2 V;
+    __device__ __forceinline__ static void dec(const V v, float* f) {
+        dec_f8_e4m3_word(v.x, f);
+        dec_f8_e4m3_word(v.y, f + 4);
+    }
+};
+template <> struct AttnKv<XH_F8_E4M3, 4> {
+    typedef uint32_t V;
+    __device__ __forceinline__ static void dec(const V v, float* f) { dec_f8_e4m3_word(v, f); }
+};
+// passes per round of a long split for a lane chunk of `bytes`: ATTN_PREF_LONG 16-byte chunks' worth
+__device__ __host__ constexpr int attn_pref_long(const int bytes) { return ATTN_PREF_LONG * 16 / bytes; }
 
 __device__ __forceinline__ float ld_sc1(const float* p) {
     return __builtin_bit_cast(float, __hip_atomic_load((const uint32_t*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -100,16 +146,21 @@ struct AddArrive {
 // split, or the last split to arrive, which merges) stores the head's output write-through,
 // drains and calls arrive(done): the consumer waits for n_kv_heads arrivals and reads the
 // merged output, instead of merging n_active partials itself.
+// KV: the ring's element type, XH_F16 or XH_F8_E4M3.
 template <int HD, int QPK, int THREADS, bool PARTIALS, int MINT = 0, class Wait = NoWait,
-          class Arrive = AddArrive, bool SIGNAL = false>
+          class Arrive = AddArrive, bool SIGNAL = false, int KV = XH_F16>
 __device__ __forceinline__ void attn_block(const AttnArgs& a, const int g, const int s, char* smem, unsigned* done,
                                            unsigned long long* dbg = nullptr, const Wait& wait = Wait(),
                                            const Arrive& arrive = Arrive()) {
 #define ATTN_STAMP(k) \
     do { if (dbg && threadIdx.x == 0) dbg[k] = __builtin_amdgcn_s_memrealtime(); } while (0)
     constexpr int WAVES = THREADS / 64;
-    constexpr int PREF = PARTIALS ? ATTN_PREF : ATTN_PREF_LONG;
-    constexpr int LPR = HD / 8;               // lanes per K/V row (16 B = 8 fp16 each)
+    constexpr int PREF = PARTIALS ? ATTN_PREF : attn_pref_long(KV == XH_F16 ? 16 : attn_kv_elems(KV, QPK));
+    constexpr int E = attn_kv_elems(KV, QPK);  // K/V elements per lane
+    typedef AttnKv<KV, E> Kv;
+    typedef typename Kv::V kvec;
+    constexpr int LPR = HD / E;               // lanes per K/V row (16 B = 8 fp16 / 16 e4m3 each)
+    constexpr size_t ESZ = KV == XH_F16 ? 2 : 1;  // bytes per element
     constexpr int RPP = THREADS / LPR;        // rows per pass
     constexpr int NO = QPK * HD;              // outputs of this block
     float* red = (float*)smem;                               // [WAVES][NO]
@@ -119,7 +170,7 @@ __device__ __forceinline__ void attn_block(const AttnArgs& a, const int g, const
     int* flag = (int*)(ml + 2 * QPK);
 
     const int kv_len = a.sp->kv_len;
-    constexpr int MIN_T = MINT ? MINT : PARTIALS ? attn_min_t_partials(HD, THREADS) : ATTN_MIN_T;
+    constexpr int MIN_T = MINT ? MINT : PARTIALS ? attn_min_t_partials(HD, THREADS, E) : ATTN_MIN_T;
     const int T = attn_split_len(kv_len, a.nsplit, MIN_T);
     const int t0 = s * T;
     if (t0 >= kv_len) return;
@@ -129,15 +180,15 @@ __device__ __forceinline__ void attn_block(const AttnArgs& a, const int g, const
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int sub = tid % LPR, rr = tid / LPR;
     const float scale = 1.0f / sqrtf((float)HD);  // src/infer.cpp:338
-    const size_t col = (size_t)g * HD + sub * 8;
+    const size_t col = (size_t)g * HD + sub * E;
     auto ld_kv = [&](const uint16_t* base, const int t) {
-        const __attribute__((address_space(1))) u32x4* p =
-            (const __attribute__((address_space(1))) u32x4*)((const char*)base + ((size_t)t * a.kv_dim + col) * 2);
+        const __attribute__((address_space(1))) kvec* p =
+            (const __attribute__((address_space(1))) kvec*)((const char*)base + ((size_t)t * a.kv_dim + col) * ESZ);
         return PARTIALS ? *p : __builtin_nontemporal_load(p);
     };
 
     // ---- first round of K and V rows, requested before anything else ----
-    u32x4 kr[PREF], vr[PREF];
+    kvec kr[PREF], vr[PREF];
 #pragma unroll
     for (int p = 0; p < PREF; p++) {
         const int t = t0 + rr + p * RPP;
@@ -147,25 +198,29 @@ __device__ __forceinline__ void attn_block(const AttnArgs& a, const int g, const
         }
     }
     wait();
-    float qv[QPK][8];
+    float qv[QPK][E];
 #pragma unroll
     for (int h = 0; h < QPK; h++) {
-        const size_t qo = (size_t)(g * QPK + h) * HD + sub * 8;
+        const size_t qo = (size_t)(g * QPK + h) * HD + sub * E;
         const float4* qp = (const float4*)(a.q + qo);
-        const float4 q0 = qp[0], q1 = qp[1];
-        qv[h][0] = q0.x; qv[h][1] = q0.y; qv[h][2] = q0.z; qv[h][3] = q0.w;
-        qv[h][4] = q1.x; qv[h][5] = q1.y; qv[h][6] = q1.z; qv[h][7] = q1.w;
+        float4 q4[E / 4];
+#pragma unroll
+        for (int j = 0; j < E / 4; j++) q4[j] = qp[j];
+#pragma unroll
+        for (int j = 0; j < E / 4; j++) {
+            qv[h][4 * j + 0] = q4[j].x; qv[h][4 * j + 1] = q4[j].y; qv[h][4 * j + 2] = q4[j].z; qv[h][4 * j + 3] = q4[j].w;
+        }
     }
 
     // ---- scores ----
-    auto score_row = [&](const u32x4 kw, const int t) {
-        float kf[8];
-        WDec<XH_F16>::dec(kw, kf);
+    auto score_row = [&](const kvec kw, const int t) {
+        float kf[E];
+        Kv::dec(kw, kf);
 #pragma unroll
         for (int h = 0; h < QPK; h++) {
             float p = 0.f;
 #pragma unroll
-            for (int i = 0; i < 8; i++) p = fmaf(qv[h][i], kf[i], p);
+            for (int i = 0; i < E; i++) p = fmaf(qv[h][i], kf[i], p);
             p = group_reduce<LPR>(p);
             if (sub == 0) sc[h * T + (t - t0)] = p * scale;
         }
@@ -177,11 +232,11 @@ __device__ __forceinline__ void attn_block(const AttnArgs& a, const int g, const
     // wait is counted.  (One round in flight per wave left the passes latency-bound at long
     // contexts.)
     constexpr int STEP = PREF * RPP;
-    auto ld_round = [&](u32x4 (&v)[PREF], const uint16_t* base_p, const int base) {
+    auto ld_round = [&](kvec (&v)[PREF], const uint16_t* base_p, const int base) {
 #pragma unroll
         for (int p = 0; p < PREF; p++) v[p] = ld_kv(base_p, min(base + rr + p * RPP, t1 - 1));
     };
-    auto score_round = [&](const u32x4 (&v)[PREF], const int base) {
+    auto score_round = [&](const kvec (&v)[PREF], const int base) {
 #pragma unroll
         for (int p = 0; p < PREF; p++) {
             const int t = base + rr + p * RPP;
@@ -189,7 +244,7 @@ __device__ __forceinline__ void attn_block(const AttnArgs& a, const int g, const
         }
     };
     {
-        u32x4 rb[PREF];
+        kvec rb[PREF];
         int base = t0;
         for (;;) {
             if (base + STEP >= t1) { score_round(kr, base); break; }
@@ -205,7 +260,7 @@ __device__ __forceinline__ void attn_block(const AttnArgs& a, const int g, const
     // V round 1 is requested before the softmax (its loads do not depend on it), so the CU's
     // memory pipe is not empty across the two barriers between the K and V passes (clamped:
     // a split of one round re-reads its last row, unused)
-    u32x4 vn[PREF];
+    kvec vn[PREF];
     ld_round(vn, a.vc, t0 + STEP);
     lds_barrier();  // the scores are in LDS; the V loads stay in flight across the softmax
     ATTN_STAMP(3);
@@ -278,23 +333,23 @@ __device__ __forceinline__ void attn_block(const AttnArgs& a, const int g, const
     ATTN_STAMP(6);
 
     // ---- p . V ----
-    float acc[QPK][8];
+    float acc[QPK][E];
 #pragma unroll
     for (int h = 0; h < QPK; h++)
 #pragma unroll
-        for (int i = 0; i < 8; i++) acc[h][i] = 0.f;
-    auto pv_row = [&](const u32x4 vw, const int t) {
-        float vf[8];
-        WDec<XH_F16>::dec(vw, vf);
+        for (int i = 0; i < E; i++) acc[h][i] = 0.f;
+    auto pv_row = [&](const kvec vw, const int t) {
+        float vf[E];
+        Kv::dec(vw, vf);
 #pragma unroll
         for (int h = 0; h < QPK; h++) {
             const float e = sc[h * T + (t - t0)];
 #pragma unroll
-            for (int i = 0; i < 8; i++) acc[h][i] = fmaf(e, vf[i], acc[h][i]);
+            for (int i = 0; i < E; i++) acc[h][i] = fmaf(e, vf[i], acc[h][i]);
         }
     };
     {
-        auto pv_round = [&](const u32x4 (&v)[PREF], const int base) {
+        auto pv_round = [&](const kvec (&v)[PREF], const int base) {
 #pragma unroll
             for (int p = 0; p < PREF; p++) {
                 const int t = base + rr + p * RPP;
@@ -317,21 +372,21 @@ __device__ __forceinline__ void attn_block(const AttnArgs& a, const int g, const
     }
     ATTN_STAMP(7);
     // reduce over the row slots of this wave (lanes sharing `sub`), then over waves (fixed order)
-    if constexpr (LPR <= 16 && QPK * 8 >= 4) {
+    if constexpr (LPR <= 16 && QPK * E >= 4) {
         // slots inside a 16-lane row first (DPP), then a reduce-scatter over the 4 rows: each
-        // row ends with a quarter of the QPK*8 values, written by its first LPR lanes
-        constexpr int N = QPK * 8;
+        // row ends with a quarter of the QPK*E values, written by its first LPR lanes
+        constexpr int N = QPK * E;
         float v[N];
 #pragma unroll
         for (int h = 0; h < QPK; h++)
 #pragma unroll
-            for (int i = 0; i < 8; i++) {
+            for (int i = 0; i < E; i++) {
                 float x = acc[h][i];
                 if (LPR <= 1) x += dpp<DPP_ROW_ROR + 1>(x);
                 if (LPR <= 2) x += dpp<DPP_ROW_ROR + 2>(x);
                 if (LPR <= 4) x += dpp<DPP_ROW_ROR + 4>(x);
                 if (LPR <= 8) x += dpp<DPP_ROW_ROR + 8>(x);
-                v[h * 8 + i] = x;
+                v[h * E + i] = x;
             }
         rows_reduce_scatter<N>(v);
         const int r = lane >> 4;
@@ -340,20 +395,20 @@ __device__ __forceinline__ void attn_block(const AttnArgs& a, const int g, const
 #pragma unroll
             for (int k = 0; k < N / 4; k++) {
                 const int vi = vb + k;
-                red[wid * NO + (vi >> 3) * HD + sub * 8 + (vi & 7)] = v[k];
+                red[wid * NO + (vi / E) * HD + sub * E + (vi % E)] = v[k];
             }
         }
     } else {
 #pragma unroll
         for (int h = 0; h < QPK; h++)
 #pragma unroll
-            for (int i = 0; i < 8; i++)
-                acc[h][i] = strided_reduce<LPR>(acc[h][i]);
+            for (int i = 0; i < E; i++)
+                if constexpr (LPR < 64) acc[h][i] = strided_reduce<LPR>(acc[h][i]);  // 64: one row per wave
         if (lane < LPR) {
 #pragma unroll
             for (int h = 0; h < QPK; h++)
 #pragma unroll
-                for (int i = 0; i < 8; i++) red[wid * NO + h * HD + sub * 8 + i] = acc[h][i];
+                for (int i = 0; i < E; i++) red[wid * NO + h * HD + sub * E + i] = acc[h][i];
         }
     }
     __syncthreads();
@@ -500,13 +555,14 @@ __device__ __forceinline__ void attn_block(const AttnArgs& a, const int g, const
 
 #undef ATTN_STAMP
 
-template <int HD, int QPK>
+template <int HD, int QPK, int KV = XH_F16>
 __global__ __launch_bounds__(ATTN_THREADS) void attn_split_kernel(const AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    attn_block<HD, QPK, ATTN_THREADS, false>(a, blockIdx.x, blockIdx.y, smem, nullptr);
+    attn_block<HD, QPK, ATTN_THREADS, false, 0, NoWait, AddArrive, false, KV>(a, blockIdx.x, blockIdx.y, smem, nullptr);
 }
 
-// shared-memory bytes of attn_block<HD,QPK,threads> for a given max split length
+// shared-memory bytes of attn_block<HD,QPK,threads> for a given max split length (the same for
+// every KV element type: nothing in it is per lane of a row)
 inline size_t attn_smem_bytes(const int hd, const int qpk, const int t_max, const int nsplit,
                               const int threads = ATTN_THREADS) {
     const size_t scn = (size_t)qpk * (t_max > nsplit ? t_max : nsplit);

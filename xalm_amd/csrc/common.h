@@ -343,6 +343,23 @@ __device__ __forceinline__ float f16_bits_to_f32(const uint16_t h) {
     return (float)__builtin_bit_cast(_Float16, h);
 }
 
+// ---- the fp8 (e4m3) KV ring's element: what every K/V writer of an fp8 context stores ----
+// The definition is xh_f8_e4m3_from_f32 (kv8.cpp, plain C++): clamp to [-448, 448] with f32
+// min / max, then the nearest e4m3fn value, ties to the even mantissa, subnormals down to 2^-9,
+// the sign kept.  On the device: the same clamp, then the gfx950 converter (v_cvt_pk_fp8_f32
+// rounds to nearest even and keeps subnormals; without the clamp a magnitude past 448 would
+// come out as the NaN code).  The pair (v0, v1) as two codes, v0's in the low byte.
+__device__ __forceinline__ uint32_t kv8_pack(const float v0, const float v1) {
+    const float c0 = fminf(fmaxf(v0, -448.f), 448.f), c1 = fminf(fmaxf(v1, -448.f), 448.f);
+    return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(c0, c1, 0, false) & 0xffffu;
+}
+// the two codes of kv8_pack's result as their fp16 images (every e4m3 value is exact in fp16),
+// the low code's in the low half
+__device__ __forceinline__ uint32_t kv8_image_f16x2(const uint32_t codes) {
+    const f2_t f = __builtin_amdgcn_cvt_pk_f32_fp8(codes, false);
+    return (uint32_t)f32_to_f16_bits(f.x) | ((uint32_t)f32_to_f16_bits(f.y) << 16);
+}
+
 // ---- cross-lane reductions without LDS: DPP within 16-lane rows, permlane swaps across rows
 // (v_permlane16/32_swap, gfx950; hipcc inserts the VALU->permlane wait states).  Every lane of
 // the reduced group ends with the same value.

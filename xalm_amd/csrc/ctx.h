@@ -175,7 +175,15 @@ struct xh_ctx {
     uint8_t wcls_e[2] = {255, 0};  // MXFP4: its scale bytes' range, as LayerW's
     int* scan_flag = nullptr;  // device word for the fp8 special-code scan
     int q_dim = 0, kv_dim = 0, qpk = 0;
-    uint16_t* kv = nullptr;  // [n_layers][2][max_seq_len][kv_dim]
+    uint16_t* kv = nullptr;  // [n_layers][2][max_seq_len][kv_dim]: fp16 bits, or one e4m3 code each (kv_dt)
+    int kv_dt = XH_F16;      // xh_create_kv: XH_F16 or XH_F8_E4M3
+    // fp8 KV only: the fp16 master of K slots 0 and 1 [n_layers][2][kv_dim] (what rotate_sinks
+    // rotates; ring K slot r is its e4m3 rounding at all times)
+    uint16_t* sink_master = nullptr;
+    bool kv8() const { return kv_dt == XH_F8_E4M3; }
+    size_t kv_esz() const { return kv8() ? 1 : 2; }
+    size_t kv_bytes() const { return (size_t)c.n_layers * 2 * c.max_seq_len * kv_dim * kv_esz(); }
+    uint16_t* master(int l) { return sink_master + (size_t)l * 2 * kv_dim; }
     float *x = nullptr, *q = nullptr, *attn_out = nullptr, *hb = nullptr, *logits = nullptr;
     float *part_o = nullptr, *part_ml = nullptr;
     int* attn_cnt = nullptr;        // [n_kv_heads] split arrival tickets
@@ -271,8 +279,9 @@ struct xh_ctx {
     // the last layer's launches and the lm_head each write their own region (LT_*): the step's
     // timeline, kernel boundaries included (tools/layer_trace.py)
     bool layer_trace_on = false;
-    uint16_t* kcache(int l) { return kv + (size_t)l * 2 * c.max_seq_len * kv_dim; }
-    uint16_t* vcache(int l) { return kcache(l) + (size_t)c.max_seq_len * kv_dim; }
+    // (typed as the fp16 ring; an fp8 ring's rows are kv_dim bytes: address it through kv_esz())
+    uint16_t* kcache(int l) { return (uint16_t*)((char*)kv + (size_t)l * 2 * c.max_seq_len * kv_dim * kv_esz()); }
+    uint16_t* vcache(int l) { return (uint16_t*)((char*)kcache(l) + (size_t)c.max_seq_len * kv_dim * kv_esz()); }
 };
 
 namespace xalm {
@@ -317,11 +326,14 @@ constexpr size_t LT_QKV = 0, LT_AW = 8192, LT_W13 = 16384, LT_W2 = 20480, LT_CLS
 
 // launch.hip: the only unit that instantiates gemv_kernel and attn_split_kernel.  A role is one
 // (prologue, epilogue) pair of gemv.h; false = no instantiation for the dtype / head shape.
-enum GemvRole { GEMV_QKV, GEMV_GLU, GEMV_RESID, GEMV_LOGITS, GEMV_STORE };
+// GEMV_QKV8: GEMV_QKV writing an fp8 KV ring (EPI_QKV8).
+enum GemvRole { GEMV_QKV, GEMV_GLU, GEMV_RESID, GEMV_LOGITS, GEMV_STORE, GEMV_QKV8 };
+inline GemvRole qkv_role(const xh_ctx* ctx) { return ctx->kv8() ? GEMV_QKV8 : GEMV_QKV; }
 bool launch_gemv(GemvRole role, int dt, const GemvArgs& a, hipStream_t s, int max_waves);
 // the shape launch_gemv takes for (role, dt) at input length n (xh_gemv_shape), -1 = none
 int gemv_shape(int role, int dt, int n);
-bool launch_attn(const AttnArgs& a, int hd, int qpk, int n_kv_heads, int t_max, hipStream_t s);
+// kv_dt: the rings' element type behind a.kc / a.vc (XH_F16, XH_F8_E4M3)
+bool launch_attn(const AttnArgs& a, int hd, int qpk, int n_kv_heads, int t_max, hipStream_t s, int kv_dt = XH_F16);
 int attn_nsplit(int n_kv_heads, int max_seq_len);
 // The dynamic-LDS limit of a kernel above 64 KiB (up to the CU's 160 KiB), set once per (kernel,
 // device); false when it could not be set.

@@ -319,6 +319,7 @@ __global__ void argmax_advance_kernel(const float* logits, int vocab, StepParams
 bool use_attn_wo(const xh_ctx* ctx, int l) {
     const int dt = ctx->L[l].wo_dt;
     if (ctx->L[l].wo_x) return false;  // exact fp8 decode: the separate launches
+    if (ctx->kv8()) return false;      // fp8 KV ring: attn_wo.h has no instantiation for it
     return ctx->fuse_attn_wo && aw_instantiated(ctx->c.head_dim, ctx->qpk) &&
            (dt == XH_F32 || dt == XH_F16 || dt == XH_BF16 || dt == XH_F8_E4M3 || dt == XH_F8_E5M2 || dt == XH_Q8);
 }
@@ -383,7 +384,7 @@ int enqueue_step(xh_ctx* ctx, hipStream_t s, bool with_logits, int head = HEAD_G
                             XH_TOP_MAX, ctx->top_ids, ctx->top_lps, ctx->top_tlp, ctx->top_rank, s);
     for (int l = 0; l < c.n_layers; l++) {
         const LayerW& w = ctx->L[l];
-        if (!launch_gemv(GEMV_QKV, kdt(w.qkv_dt, w.qkv_x), qkv_args(ctx, l), s, qkv_launch_waves(ctx, l)))
+        if (!launch_gemv(qkv_role(ctx), kdt(w.qkv_dt, w.qkv_x), qkv_args(ctx, l), s, qkv_launch_waves(ctx, l)))
             return set_err(ctx, XH_E_INVALID, "layer %d: unsupported qkv dtype %d", l, w.qkv_dt);
         GemvArgs a13 = w13_args(ctx, l);
         if (use_attn_wo(ctx, l)) {
@@ -392,7 +393,7 @@ int enqueue_step(xh_ctx* ctx, hipStream_t s, bool with_logits, int head = HEAD_G
             // W1/W3 right behind it zeroes its hand-off words for the next step
             a13.aw_reset = ctx->aw_sync + (size_t)AW_SYNC_WORDS * l;
         } else {
-            if (!launch_attn(attn_args(ctx, l), c.head_dim, ctx->qpk, c.n_kv_heads, ctx->t_max, s))
+            if (!launch_attn(attn_args(ctx, l), c.head_dim, ctx->qpk, c.n_kv_heads, ctx->t_max, s, ctx->kv_dt))
                 return set_err(ctx, XH_E_INVALID, "unsupported head_dim %d / q-per-kv %d", c.head_dim, ctx->qpk);
             if (!launch_gemv(GEMV_RESID, kdt(w.wo_dt, w.wo_x), wo_args(ctx, l), s, mb))
                 return set_err(ctx, XH_E_INVALID, "layer %d: unsupported wo dtype", l);
@@ -485,6 +486,7 @@ GemvArgs xalm::qkv_args(xh_ctx* ctx, int l) {
     a.q_dim = ctx->q_dim; a.kv_dim = ctx->kv_dim; a.head_dim = ctx->c.head_dim;
     a.rope_freq = ctx->rope_freq; a.rope_cs = ctx->rope_cs; a.sink_cos = ctx->sink_cos; a.sink_sin = ctx->sink_sin;
     a.qkv_clip = ctx->c.qkv_clip; a.sp = ctx->sp;
+    if (ctx->kv8()) a.sink_master = ctx->master(l);
     if (layer_traced(ctx, l)) a.trace = ctx->aw_trace + LT_QKV;
     return a;
 }

@@ -26,7 +26,10 @@
 namespace xalm {
 
 enum { PRO_PLAIN = 0, PRO_RMSNORM = 1 };
-enum { EPI_STORE = 0, EPI_RESID = 1, EPI_QKV = 2, EPI_GLU = 3, EPI_LOGITS = 4 };
+// EPI_QKV8: EPI_QKV on an fp8 (e4m3) KV ring: the K/V pair stored as two codes (kv8_pack), the
+// sinks kept through an fp16 master (rotate_sinks)
+enum { EPI_STORE = 0, EPI_RESID = 1, EPI_QKV = 2, EPI_GLU = 3, EPI_LOGITS = 4, EPI_QKV8 = 5 };
+__device__ __host__ constexpr bool epi_qkv(const int epi) { return epi == EPI_QKV || epi == EPI_QKV8; }
 
 constexpr int LDS_HEAD_BYTES = 64;
 #ifndef GEMV_BAL_CU
@@ -82,6 +85,8 @@ struct GemvArgs {
     unsigned long long* trace;  // debug (null = off): per workgroup [4] start, x staged, rows done
     unsigned long long* cand;   // EPI_LOGITS: [gridDim.x] argmax_key of the workgroup's best logit
     unsigned* aw_reset;         // workgroup 0 zeroes words 0, 32, ..., 32 (AW_RESET_WORDS - 1) (attn_wo.h sync)
+    // EPI_QKV8: kcache / vcache hold one e4m3 code per element (same [slot][kv_dim] shape)
+    uint16_t* sink_master;      // this layer's fp16 master of K slots 0 and 1 [2][kv_dim]
 };
 
 // agent-scope relaxed (sc1: L1-bypassing, write-through) accesses for data handed between
@@ -252,10 +257,13 @@ __device__ __forceinline__ void stage_x(const GemvArgs& a, float4* xs4, float* r
 }
 
 // StreamingLLM sink re-rotation (src/infer.cpp:421-431): K[r] = f16(rope(f32(K[r]), pos=1)).
-template <int THREADS>
+// KV8 (an fp8 ring): the rows rotate in their fp16 master, exactly as above, so the rounding does
+// not accumulate beyond the fp16 drift of the rotation itself; ring slot r is rewritten as the
+// e4m3 rounding of the new master row (ring K slot r == f8(master[r]) at all times).
+template <int THREADS, bool KV8 = false>
 __device__ __forceinline__ void rotate_sinks(const GemvArgs& a, const int kv_sink) {
     for (int r = 0; r < kv_sink; r++) {
-        uint16_t* krow = a.kcache + (size_t)r * a.kv_dim;
+        uint16_t* krow = (KV8 ? a.sink_master : a.kcache) + (size_t)r * a.kv_dim;
         for (int p = threadIdx.x; p < (a.kv_dim >> 1); p += THREADS) {
             const int i = p << 1;
             const int jh = (i % a.head_dim) >> 1;
@@ -263,6 +271,9 @@ __device__ __forceinline__ void rotate_sinks(const GemvArgs& a, const int kv_sin
             const float fcr = a.sink_cos[jh], fci = a.sink_sin[jh];
             krow[i] = f32_to_f16_bits(k0 * fcr - k1 * fci);
             krow[i + 1] = f32_to_f16_bits(k0 * fci + k1 * fcr);
+            if constexpr (KV8)
+                *(uint16_t*)((uint8_t*)a.kcache + (size_t)r * a.kv_dim + i) =
+                    (uint16_t)kv8_pack(f16_bits_to_f32(krow[i]), f16_bits_to_f32(krow[i + 1]));
         }
     }
 }
@@ -324,7 +335,7 @@ __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, const int row0,
     } else if (EPI == EPI_GLU) {
 #pragma unroll
         for (int p = 0; p < ROWS; p += 2) epi_st<SC1>(a.out + ((row0 + p) >> 1), act_fn(a.act, acc[p]) * acc[p + 1]);
-    } else {  // EPI_QKV
+    } else {  // EPI_QKV / EPI_QKV8
         const int kv_pos = pre ? pre->kv_pos : a.sp->kv_pos;
 #pragma unroll
         for (int p = 0; p < ROWS; p += 2) {
@@ -341,6 +352,16 @@ __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, const int row0,
                 if (isk) {
                     if (pre) rope_pair_cs(v0, v1, pre->cs[p], pre->cs[p + 1]);  // q_dim % head_dim == 0
                     else rope_pair_tab(v0, v1, kr, a.head_dim, a.rope_cs);
+                }
+                if constexpr (EPI == EPI_QKV8) {
+                    // the pair as two codes in one 2-byte store (kr is even); the K rows of slots 0
+                    // and 1 also as their fp16 image in the master
+                    const uint32_t pk8 = kv8_pack(v0, v1);
+                    uint16_t* dst8 = (uint16_t*)((uint8_t*)(isk ? a.kcache : a.vcache) + (size_t)kv_pos * a.kv_dim + kr);
+                    if (SC1) __hip_atomic_store(dst8, (uint16_t)pk8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    else *dst8 = (uint16_t)pk8;
+                    if (isk && kv_pos < 2) *(uint32_t*)(a.sink_master + (size_t)kv_pos * a.kv_dim + kr) = kv8_image_f16x2(pk8);
+                    continue;
                 }
                 uint16_t* dst = (isk ? a.kcache : a.vcache) + (size_t)kv_pos * a.kv_dim + kr;
                 // the pair as one 4-byte store (kr is even)
@@ -732,7 +753,7 @@ __device__ __forceinline__ void gemv_rows_pipe(const GemvArgs& a, const int g0, 
     // QKV: requested with the weights, ahead of the epilogue that uses them.  One-byte weights
     // only: fp8 decode 596 -> 603 tok/s, while the 2-byte qkv launch measured 0.5 % slower with it
     // (same-box A/B, two pairs each; again with the rope table: 393.3 vs 391.2 tok/s, 3 pairs)
-    constexpr bool QKV = EPI == EPI_QKV && E >= 16;
+    constexpr bool QKV = epi_qkv(EPI) && E >= 16;
     QkvPre<ROWS> qp{};
     if constexpr (QKV) {
         qp.pos = a.sp->pos;
@@ -945,7 +966,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, const int block, co
             gq_load_scales<DT, S::ROWS, S::U>(pre_d, wrow, rs, gq_qbytes(DT, (size_t)a.n), 0, lane);
         }
         stage_x_finish<E, PRO, S, gq4_image<DT>()>(a, xv, nw, xs4, red);
-        if (EPI == EPI_QKV && block == 0) rotate_sinks<S::THREADS>(a, a.sp->kv_sink);
+        if (epi_qkv(EPI) && block == 0) rotate_sinks<S::THREADS, EPI == EPI_QKV8>(a, a.sp->kv_sink);
         __syncthreads();
         if (a.trace && threadIdx.x == 0) a.trace[4 * block + 1] = __builtin_amdgcn_s_memrealtime();
         if constexpr (S::PIPE == 2) {
@@ -956,7 +977,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, const int block, co
         }
     } else {
         stage_x<E, PRO, S::THREADS, false, gq4_image<DT>()>(a, xs4, red);
-        if (EPI == EPI_QKV && block == 0) rotate_sinks<S::THREADS>(a, a.sp->kv_sink);
+        if (epi_qkv(EPI) && block == 0) rotate_sinks<S::THREADS, EPI == EPI_QKV8>(a, a.sp->kv_sink);
         __syncthreads();
         if (a.trace && threadIdx.x == 0) a.trace[4 * block + 1] = __builtin_amdgcn_s_memrealtime();
         u32x4 none[S::U][S::ROWS];

@@ -93,9 +93,9 @@ template <int DT, int PRO, int EPI>
 struct ShapeSel {
     static constexpr int E = WDec<DT>::E;
     static constexpr bool GQ = gq_dt(DT);
-    static constexpr bool HAS_PF2P = (EPI == EPI_QKV || EPI == EPI_GLU) && !GQ;
-    static constexpr bool HAS_Q384 = HAS_PF2P && EPI == EPI_QKV && E <= 8 && QKV_T384;
-    static constexpr bool HAS_PF2PB = HAS_PF2P && EPI == EPI_QKV && E >= 16 && GEMV_BAL_FP8_QKV;
+    static constexpr bool HAS_PF2P = (epi_qkv(EPI) || EPI == EPI_GLU) && !GQ;
+    static constexpr bool HAS_Q384 = HAS_PF2P && epi_qkv(EPI) && E <= 8 && QKV_T384;
+    static constexpr bool HAS_PF2PB = HAS_PF2P && epi_qkv(EPI) && E >= 16 && GEMV_BAL_FP8_QKV;
     static constexpr bool HAS_GQL = GQ && PRO == PRO_PLAIN;
     static constexpr bool HAS_W2K = PRO == PRO_PLAIN && EPI == EPI_RESID && E >= 16 && W2_T1024;
     static constexpr bool HAS_PF8 = PRO == PRO_PLAIN && !HAS_W2K;
@@ -204,6 +204,7 @@ int for_role(int role, int dt, A... args) {
         case GEMV_RESID: return for_dt(dt, F<PRO_PLAIN, EPI_RESID>{args...});
         case GEMV_LOGITS: return for_dt(dt, F<PRO_RMSNORM, EPI_LOGITS>{args...});
         case GEMV_STORE: return for_dt(dt, F<PRO_PLAIN, EPI_STORE>{args...});
+        case GEMV_QKV8: return for_dt(dt, F<PRO_RMSNORM, EPI_QKV8>{args...});
     }
     return -1;
 }
@@ -224,33 +225,38 @@ namespace {
 // ---------------------------------------------------------------------------------------
 // attention launch dispatch
 // ---------------------------------------------------------------------------------------
-template <int HD, int QPK>
+template <int HD, int QPK, int KV>
 void launch_attn_t(const AttnArgs& a, int n_kv_heads, int t_max, hipStream_t s) {
     const size_t smem = attn_smem_bytes(HD, QPK, t_max, a.nsplit);
-    auto k = attn_split_kernel<HD, QPK>;
+    auto k = attn_split_kernel<HD, QPK, KV>;
     if (smem > 64 * 1024) ensure_lds((const void*)k);
     hipLaunchKernelGGL(k, dim3(n_kv_heads, a.nsplit), dim3(ATTN_THREADS), smem, s, a);
 }
 
-template <int HD>
+template <int HD, int KV>
 bool launch_attn_hd(const AttnArgs& a, int qpk, int n_kv_heads, int t_max, hipStream_t s) {
     return for_qpk(qpk, [&](auto Q) {
-        launch_attn_t<HD, decltype(Q)::value>(a, n_kv_heads, t_max, s);
+        launch_attn_t<HD, decltype(Q)::value, KV>(a, n_kv_heads, t_max, s);
         return 0;
     }) == 0;
+}
+template <int KV>
+bool launch_attn_kv(const AttnArgs& a, int hd, int qpk, int n_kv_heads, int t_max, hipStream_t s) {
+    switch (hd) {
+        case 16: return launch_attn_hd<16, KV>(a, qpk, n_kv_heads, t_max, s);
+        case 32: return launch_attn_hd<32, KV>(a, qpk, n_kv_heads, t_max, s);
+        case 64: return launch_attn_hd<64, KV>(a, qpk, n_kv_heads, t_max, s);
+        case 128: return launch_attn_hd<128, KV>(a, qpk, n_kv_heads, t_max, s);
+        case 256: return launch_attn_hd<256, KV>(a, qpk, n_kv_heads, t_max, s);
+        default: return false;
+    }
 }
 
 }  // namespace
 
-bool xalm::launch_attn(const AttnArgs& a, int hd, int qpk, int n_kv_heads, int t_max, hipStream_t s) {
-    switch (hd) {
-        case 16: return launch_attn_hd<16>(a, qpk, n_kv_heads, t_max, s);
-        case 32: return launch_attn_hd<32>(a, qpk, n_kv_heads, t_max, s);
-        case 64: return launch_attn_hd<64>(a, qpk, n_kv_heads, t_max, s);
-        case 128: return launch_attn_hd<128>(a, qpk, n_kv_heads, t_max, s);
-        case 256: return launch_attn_hd<256>(a, qpk, n_kv_heads, t_max, s);
-        default: return false;
-    }
+bool xalm::launch_attn(const AttnArgs& a, int hd, int qpk, int n_kv_heads, int t_max, hipStream_t s, int kv_dt) {
+    return kv_dt == XH_F8_E4M3 ? launch_attn_kv<XH_F8_E4M3>(a, hd, qpk, n_kv_heads, t_max, s)
+                               : launch_attn_kv<XH_F16>(a, hd, qpk, n_kv_heads, t_max, s);
 }
 
 int xalm::attn_nsplit(int n_kv_heads, int max_seq_len) {

@@ -36,6 +36,16 @@ int op_finish(void* dst, const DevBuf& b, size_t bytes) {
         return set_err(nullptr, XH_E_HIP, "hipMemcpy D2H failed");
     return 0;
 }
+// xh_op_kv_quantize: pairs through kv8_pack, the K/V writers' device function (an odd tail with 0)
+__global__ __launch_bounds__(256) void kv_quantize_kernel(const float* in, size_t n, uint8_t* out) {
+    const size_t pairs = (n + 1) / 2;
+    for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < pairs; p += (size_t)gridDim.x * 256) {
+        const bool two = 2 * p + 1 < n;
+        const uint32_t pk = kv8_pack(in[2 * p], two ? in[2 * p + 1] : 0.f);
+        out[2 * p] = (uint8_t)(pk & 0xffu);
+        if (two) out[2 * p + 1] = (uint8_t)(pk >> 8);
+    }
+}
 }  // namespace
 
 int xh_op_matmul(float* xout, const float* x, const void* w, int dtype, int n, int d) {
@@ -95,10 +105,13 @@ int xh_op_rope(float* vec, int d, int head_dim, int pos, float theta, int rotary
     return op_finish(vec, bv, (size_t)d * 4);
 }
 
-int xh_op_mha(float* xout, const uint16_t* kb, const uint16_t* vb, const float* q, int head_dim, int kv_len,
-              int max_seq_len, int n_heads, int n_kv_heads) {
+// xh_op_mha / xh_op_mha8: rings of esz bytes per element through launch_attn, as the decode step
+static int op_mha_any(float* xout, const void* kb, const void* vb, const float* q, int head_dim, int kv_len,
+                      int max_seq_len, int n_heads, int n_kv_heads, int kv_dt) {
     if (!xout || !kb || !vb || !q || kv_len <= 0 || kv_len > max_seq_len || n_kv_heads <= 0 || n_heads % n_kv_heads)
         return set_err(nullptr, XH_E_INVALID, "bad mha args");
+    if (kv_dt == XH_F8_E4M3 && (head_dim <= 0 || head_dim % 16))
+        return set_err(nullptr, XH_E_INVALID, "mha8: head_dim %d is no multiple of 16", head_dim);
     const int qpk = n_heads / n_kv_heads, kv_dim = n_kv_heads * head_dim;
     const int nsplit = attn_nsplit(n_kv_heads, max_seq_len);
     const int t_max = attn_split_len(max_seq_len, nsplit);
@@ -108,7 +121,7 @@ int xh_op_mha(float* xout, const uint16_t* kb, const uint16_t* vb, const float* 
     sp.kv_len = kv_len;
     sp.max_seq_len = max_seq_len;
     int rc;
-    const size_t kvb = (size_t)max_seq_len * kv_dim * 2;
+    const size_t kvb = (size_t)max_seq_len * kv_dim * (kv_dt == XH_F8_E4M3 ? 1 : 2);
     if ((rc = op_alloc(bk, kvb, kb)) || (rc = op_alloc(bv, kvb, vb)) || (rc = op_alloc(bq, (size_t)n_heads * head_dim * 4, q)) ||
         (rc = op_alloc(bo, (size_t)n_heads * head_dim * 4, nullptr)) ||
         (rc = op_alloc(bpo, (size_t)nsplit * n_heads * head_dim * 4, nullptr)) ||
@@ -119,9 +132,30 @@ int xh_op_mha(float* xout, const uint16_t* kb, const uint16_t* vb, const float* 
     a.q = (const float*)bq.p; a.kc = (const uint16_t*)bk.p; a.vc = (const uint16_t*)bv.p; a.kv_dim = kv_dim;
     a.n_heads = n_heads; a.nsplit = nsplit; a.out = (float*)bo.p; a.part_o = (float*)bpo.p;
     a.part_ml = (float*)bpm.p; a.counters = (int*)bcnt.p; a.sp = (const StepParams*)bsp.p;
-    if (!launch_attn(a, head_dim, qpk, n_kv_heads, t_max, nullptr))
+    if (!launch_attn(a, head_dim, qpk, n_kv_heads, t_max, nullptr, kv_dt))
         return set_err(nullptr, XH_E_INVALID, "unsupported head_dim %d / qpk %d", head_dim, qpk);
     return op_finish(xout, bo, (size_t)n_heads * head_dim * 4);
+}
+
+int xh_op_mha(float* xout, const uint16_t* kb, const uint16_t* vb, const float* q, int head_dim, int kv_len,
+              int max_seq_len, int n_heads, int n_kv_heads) {
+    return op_mha_any(xout, kb, vb, q, head_dim, kv_len, max_seq_len, n_heads, n_kv_heads, XH_F16);
+}
+
+int xh_op_mha8(float* xout, const uint8_t* kb, const uint8_t* vb, const float* q, int head_dim, int kv_len,
+               int max_seq_len, int n_heads, int n_kv_heads) {
+    return op_mha_any(xout, kb, vb, q, head_dim, kv_len, max_seq_len, n_heads, n_kv_heads, XH_F8_E4M3);
+}
+
+int xh_op_kv_quantize(const float* in, size_t n, uint8_t* out) {
+    if (!in || !out) return set_err(nullptr, XH_E_INVALID, "bad kv_quantize args");
+    if (!n) return 0;
+    DevBuf bi, bo;
+    int rc;
+    if ((rc = op_alloc(bi, n * 4, in)) || (rc = op_alloc(bo, n, nullptr))) return rc;
+    hipLaunchKernelGGL(kv_quantize_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, nullptr,
+                       (const float*)bi.p, n, (uint8_t*)bo.p);
+    return op_finish(out, bo, n);
 }
 
 int xh_op_prompt_gemm(float* y, const uint16_t* w, const uint16_t* xh, const uint16_t* xl, int rows, int K, int n,
@@ -456,7 +490,7 @@ int xh_time_kernel(xh_ctx* ctx, int which, int iters, float* avg_us) {
         const int l = rot++ % ctx->c.n_layers;
         switch (which) {
             case 0: return launch_gemv(GEMV_GLU, kdt(ctx->L[l].w13_dt, ctx->L[l].w13_x), w13_args(ctx, l), ctx->stream, mb);
-            case 1: return launch_gemv(GEMV_QKV, kdt(ctx->L[l].qkv_dt, ctx->L[l].qkv_x), qkv_args(ctx, l), ctx->stream,
+            case 1: return launch_gemv(qkv_role(ctx), kdt(ctx->L[l].qkv_dt, ctx->L[l].qkv_x), qkv_args(ctx, l), ctx->stream,
                                                              qkv_launch_waves(ctx, l));
             case 2: return launch_gemv(GEMV_RESID, kdt(ctx->L[l].wo_dt, ctx->L[l].wo_x), wo_args(ctx, l), ctx->stream, mb);
             case 3: return launch_gemv(GEMV_RESID, kdt(ctx->L[l].w2_dt, ctx->L[l].w2_x), w2_args(ctx, l), ctx->stream, mb);
@@ -469,7 +503,7 @@ int xh_time_kernel(xh_ctx* ctx, int which, int iters, float* avg_us) {
             case 11: time_sample_seq_head(ctx); return true;
             default:
                 return launch_attn(attn_args(ctx, l), ctx->c.head_dim, ctx->qpk, ctx->c.n_kv_heads, ctx->t_max,
-                                   ctx->stream);
+                                   ctx->stream, ctx->kv_dt);
         }
     };
     hipEvent_t e0, e1;
@@ -498,7 +532,7 @@ size_t xh_kernel_bytes(const xh_ctx* ctx, int which, int kv_len) {
         case 0: return (size_t)2 * c.hidden_dim * file_row_bytes(w.w13_dt, c.dim) + c.dim * (vec + dtype_size(w.fn_dt)) +
                        (size_t)c.hidden_dim * vec;
         case 1: return (size_t)(ctx->q_dim + 2 * ctx->kv_dim) * file_row_bytes(w.qkv_dt, c.dim) +
-                       c.dim * (vec + dtype_size(w.an_dt)) + (size_t)ctx->q_dim * vec + 2 * ctx->kv_dim * 2;
+                       c.dim * (vec + dtype_size(w.an_dt)) + (size_t)ctx->q_dim * vec + 2 * ctx->kv_dim * ctx->kv_esz();
         case 2: return (size_t)c.dim * file_row_bytes(w.wo_dt, ctx->q_dim) + ctx->q_dim * vec + 2 * c.dim * vec;
         case 3: return (size_t)c.dim * file_row_bytes(w.w2_dt, c.hidden_dim) + c.hidden_dim * vec + 2 * c.dim * vec;
         case 4: return (size_t)c.vocab_size * file_row_bytes(ctx->wcls ? ctx->wcls_dt : ctx->embed_dt, c.dim) +
@@ -506,7 +540,7 @@ size_t xh_kernel_bytes(const xh_ctx* ctx, int which, int kv_len) {
         case 6: return (size_t)c.vocab_size * vec + file_row_bytes(ctx->embed_dt, c.dim) + c.dim * vec;
         case 7: return (size_t)2 * c.vocab_size * vec + file_row_bytes(ctx->embed_dt, c.dim) + c.dim * vec;
         case 9: return (size_t)c.vocab_size * vec + (size_t)2 * ctx->top_n * vec;
-        default: return (size_t)2 * kv_len * ctx->kv_dim * 2 + 2 * (size_t)ctx->q_dim * vec;
+        default: return (size_t)2 * kv_len * ctx->kv_dim * ctx->kv_esz() + 2 * (size_t)ctx->q_dim * vec;
     }
 }
 

@@ -523,7 +523,7 @@ struct PfEpiArgs {
     const float* part;  // [ks][n][rows]
     const float* part_s;  // nullable: [n] factor of token t's summed partials (hipBLASLt: 1 / s_t)
     int ks, n, rows;
-    int epi;            // EPI_QKV / EPI_RESID / EPI_GLU / EPI_STORE
+    int epi;            // EPI_QKV / EPI_QKV8 / EPI_RESID / EPI_GLU / EPI_STORE
     float* out;         // RESID: X [n][rows] (+=); GLU: H [n][rows/2]; STORE: [n][out_stride]
     size_t out_stride;  // STORE row stride (0: rows)
     // EPI_QKV
@@ -539,6 +539,9 @@ struct PfEpiArgs {
     // [n][kv_dim] instead of the ring, which its attention still reads as it stood (null: the ring)
     uint16_t* kstage;
     uint16_t* vstage;
+    // EPI_QKV8 (an fp8 KV ring: kcache / vcache rows of kv_dim codes; no ring passes): the fp16
+    // master of K slots 0 and 1 [2][kv_dim]
+    uint16_t* sink_master;
 };
 
 __global__ __launch_bounds__(256) void prefill_epi_kernel(const PfEpiArgs a) {
@@ -569,7 +572,7 @@ __global__ __launch_bounds__(256) void prefill_epi_kernel(const PfEpiArgs a) {
         if (r + 1 < a.rows) o[1] = v1;
     } else if (a.epi == EPI_GLU) {
         a.out[(size_t)t * (a.rows / 2) + r / 2] = act_fn(a.act, v0) * v1;
-    } else {  // EPI_QKV: src/infer.cpp:392-414 at pos = pos0 + t
+    } else {  // EPI_QKV / EPI_QKV8: src/infer.cpp:392-414 at pos = pos0 + t
         const int pos = a.pos0 + t;
         v0 = clipf(v0, a.qkv_clip);
         v1 = clipf(v1, a.qkv_clip);
@@ -581,6 +584,12 @@ __global__ __launch_bounds__(256) void prefill_epi_kernel(const PfEpiArgs a) {
             const bool isk = r < a.q_dim + a.kv_dim;
             const int kr = isk ? r - a.q_dim : r - a.q_dim - a.kv_dim;
             if (isk) rope_pair(v0, v1, kr, a.head_dim, pos, a.rope_freq);
+            if (a.epi == EPI_QKV8) {  // two codes in one 2-byte store, as gemv_epilogue
+                const uint32_t pk8 = kv8_pack(v0, v1);
+                *(uint16_t*)((uint8_t*)(isk ? a.kcache : a.vcache) + (size_t)pos * a.kv_dim + kr) = (uint16_t)pk8;
+                if (isk && pos < 2) *(uint32_t*)(a.sink_master + (size_t)pos * a.kv_dim + kr) = kv8_image_f16x2(pk8);
+                return;
+            }
             uint16_t* dst = a.kstage ? (isk ? a.kstage : a.vstage) + (size_t)t * a.kv_dim + kr
                                      : (isk ? a.kcache : a.vcache) + (size_t)pos * a.kv_dim + kr;
             *(uint32_t*)dst = (uint32_t)f32_to_f16_bits(v0) | ((uint32_t)f32_to_f16_bits(v1) << 16);
@@ -612,7 +621,7 @@ __global__ __launch_bounds__(256) void prefill_embed_kernel(const int* tokens, c
 
 // attention of the pass's tokens: grid (n_kv_heads, nsplit, n); token t attends to slots
 // [0, pos0 + t] (its own K/V row included), per-token StepParams in sps[t]
-template <int HD, int QPK>
+template <int HD, int QPK, int KV = XH_F16>
 __global__ __launch_bounds__(ATTN_THREADS) void prefill_attn_kernel(AttnArgs a, const StepParams* sps, int q_stride,
                                                                     int n_kv_heads) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -623,7 +632,7 @@ __global__ __launch_bounds__(ATTN_THREADS) void prefill_attn_kernel(AttnArgs a, 
     a.part_ml += (size_t)t * a.nsplit * a.n_heads * 2;
     a.counters += t * n_kv_heads;
     a.sp = sps + t;
-    attn_block<HD, QPK, ATTN_THREADS, false>(a, blockIdx.x, blockIdx.y, smem, nullptr);
+    attn_block<HD, QPK, ATTN_THREADS, false, 0, NoWait, AddArrive, false, KV>(a, blockIdx.x, blockIdx.y, smem, nullptr);
 }
 
 // One 32-slot tile of the prompt attention's online softmax (both kernels below): scores

@@ -383,10 +383,10 @@ int pf_glu(xh_ctx* ctx, PfPass& ps, int ks, const PfMat& w2) {
     pf_epi(ctx, ps, e);
     return 0;
 }
-template <int HD, int QPK>
+template <int HD, int QPK, int KV>
 void pf_attn_t(xh_ctx* ctx, const AttnArgs& a, int n) {
     const size_t smem = attn_smem_bytes(HD, QPK, ctx->t_max, a.nsplit);
-    auto k = prefill_attn_kernel<HD, QPK>;
+    auto k = prefill_attn_kernel<HD, QPK, KV>;
     if (smem > 64 * 1024) ensure_lds((const void*)k);
     hipLaunchKernelGGL(k, dim3(ctx->c.n_kv_heads, a.nsplit, n), dim3(ATTN_THREADS), smem, ctx->stream, a,
                        (const StepParams*)ctx->pf.sp, ctx->q_dim, ctx->c.n_kv_heads);
@@ -663,6 +663,9 @@ int xalm::pf_ring_launch(const PfAttnDims& d, const float* q, uint16_t* kc, uint
 namespace {
 
 PfAttnDims pf_dims(const xh_ctx* ctx) { return {ctx->c.head_dim, ctx->c.n_heads, ctx->c.n_kv_heads}; }
+// the prompt attention in force: XH_OPT_PREFILL_ATTN, but 0 (prefill_attn_kernel, the decode
+// blocks) on an fp8 KV ring, which the MFMA kernels have no tiles for; the stored option is untouched
+int pf_attn_mode_of(const xh_ctx* ctx) { return ctx->kv8() ? 0 : ctx->pf_attn_mode; }
 // the splits of a pass of n tokens over pos0 slots of history, within the partials buffer
 int pf_fa_nsplit(const xh_ctx* ctx, int n, int pos0) {
     if (!ctx->pf_fa_split) return 1;
@@ -671,7 +674,7 @@ int pf_fa_nsplit(const xh_ctx* ctx, int n, int pos0) {
 // the shapes of pf_attn_shape are the only instantiations; -1 for another one
 int pf_attn_any(xh_ctx* ctx, const AttnArgs& a, int n, int pos0) {
     const int hd = ctx->c.head_dim;
-    if (ctx->pf_attn_mode != 0) {
+    if (pf_attn_mode_of(ctx) != 0) {
         const bool shared = ctx->pf_attn_mode == 1 && hd == 128;
         return pf_fa_launch(pf_dims(ctx), shared, a.q, a.kc, a.vc, a.out, n, pos0, shared ? pf_fa_nsplit(ctx, n, pos0) : 1,
                             ctx->pf.part, ctx->stream);
@@ -681,7 +684,8 @@ int pf_attn_any(xh_ctx* ctx, const AttnArgs& a, int n, int pos0) {
         return for_qpk(ctx->qpk, [&](auto Q) {
             constexpr int QPK = decltype(Q)::value;
             if constexpr (pf_attn_shape(HD, QPK)) {
-                pf_attn_t<HD, QPK>(ctx, a, n);
+                if (ctx->kv8()) pf_attn_t<HD, QPK, XH_F8_E4M3>(ctx, a, n);
+                else pf_attn_t<HD, QPK, XH_F16>(ctx, a, n);
                 return 0;
             }
             return -1;
@@ -694,7 +698,7 @@ int pf_attn_any(xh_ctx* ctx, const AttnArgs& a, int n, int pos0) {
 int pf_attn(xh_ctx* ctx, const AttnArgs& a, int n, int pos0) {
     const int hd = ctx->c.head_dim;
     AttnArgs b = a;
-    if (pf_attn_shape(hd, ctx->qpk) && ctx->pf_attn_mode == 0) {
+    if (pf_attn_shape(hd, ctx->qpk) && pf_attn_mode_of(ctx) == 0) {
         const int rc = pf_alloc_group(ctx, PfBufs::ATTN0);
         if (rc) return rc;
         b.part_o = ctx->pf.po; b.part_ml = ctx->pf.pml; b.counters = ctx->pf.cnt;
@@ -734,8 +738,9 @@ bool pf_supported(const xh_ctx* ctx) {
 }
 // Ring passes (positions >= max_seq_len): the shared-tile attention's head shape only
 // (prefill_fa2_ring_kernel is head_dim 128), and a ring with at least two slots behind the sinks
+// An fp8 KV ring has none: the pass would need the sinks' master versions and fp8 staging rows.
 bool pf_ring_ok(const xh_ctx* ctx) {
-    return ctx->pf_ring && ctx->c.head_dim == 128 && ctx->pf_attn_mode == 1 && ctx->c.max_seq_len - 2 >= 2;
+    return ctx->pf_ring && !ctx->kv8() && ctx->c.head_dim == 128 && ctx->pf_attn_mode == 1 && ctx->c.max_seq_len - 2 >= 2;
 }
 
 // How a prompt of n tokens at pos0 runs: pieces in order, each batched (PF_RING: ring passes of at
@@ -754,14 +759,17 @@ void pf_plan(const xh_ctx* ctx, int n, int pos0, int min_n, std::vector<PfPiece>
     const int L = ctx->c.max_seq_len;
     out.clear();
     const bool wraps = pos0 > L - n;  // pos0 + n > L
-    if (!pf_supported(ctx) || (wraps && !pf_ring_ok(ctx))) {
+    // an fp8 KV ring batches the part below L and takes the loop from the cut
+    if (!pf_supported(ctx) || (wraps && !pf_ring_ok(ctx) && !ctx->kv8())) {
         out.push_back({0, n, PF_LOOP, 0});
         return;
     }
     const int pass = pf_pass_tokens(ctx);
     const int na = wraps ? std::max(0, L - pos0) : n, nb = n - na;
     if (na > 0) out.push_back({0, na, na >= min_n ? PF_BATCH : PF_LOOP, na >= min_n ? (na + pass - 1) / pass : 0});
-    if (nb > 0) {
+    if (nb > 0 && !pf_ring_ok(ctx)) {
+        out.push_back({na, nb, PF_LOOP, 0});
+    } else if (nb > 0) {
         const int rp = std::min(pass, L - 2);
         const int rem = nb % rp, tail = rem > 0 && rem < PF_RING_MIN ? rem : 0;
         if (nb > tail) out.push_back({na, nb - tail, PF_RING, (nb - tail + rp - 1) / rp});
@@ -803,7 +811,8 @@ int pf_layer(xh_ctx* ctx, PfPass& ps, int l) {
     if (l == 0) pf_norm(ctx, ps, w.attn_norm, w.an_dt, mats[PF_QKV]);
     if ((rc = pf_gemm(ctx, ps, mats[PF_QKV], b.xn, m, ks))) return rc;
     PfEpiArgs e{};
-    e.ks = ks; e.n = m; e.rows = mats[PF_QKV].rows; e.epi = EPI_QKV; e.q = b.q;
+    e.ks = ks; e.n = m; e.rows = mats[PF_QKV].rows; e.epi = ctx->kv8() ? EPI_QKV8 : EPI_QKV; e.q = b.q;
+    if (ctx->kv8()) e.sink_master = ctx->master(l);
     e.kcache = ctx->kcache(l); e.vcache = ctx->vcache(l); e.q_dim = ctx->q_dim; e.kv_dim = ctx->kv_dim;
     e.head_dim = c.head_dim; e.rope_freq = ctx->rope_freq; e.qkv_clip = c.qkv_clip; e.pos0 = ps.p0; e.act = c.act;
     if (ps.ring) { e.kstage = b.ks; e.vstage = b.vs; }

@@ -230,6 +230,26 @@ __global__ void synth_fill_kernel(char* base, size_t pitch, size_t rows, size_t 
     }
 }
 
+// xh_kv_fill_synthetic on an fp8 KV ring: the e4m3 rounding (kv8_pack) of the value the fp16 fill
+// stores, f16(xs_value); master (K rows, null otherwise): rows of slots < 2 also as their fp16 image
+__global__ void synth_fill_kv8_kernel(uint8_t* base, size_t rows, size_t cols, int slot0, uint16_t* master,
+                                      uint64_t seed, float std) {
+    const size_t n = rows * cols;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t code = kv8_pack(f16_bits_to_f32(xs_to_f16(xs_value(seed, i, 0.0f, std))), 0.f) & 0xffu;
+        base[i] = (uint8_t)code;
+        const size_t slot = slot0 + i / cols;
+        if (master && slot < 2) master[slot * cols + i % cols] = (uint16_t)kv8_image_f16x2(code);
+    }
+}
+
+// the fp16 bits of an e4m3 code (finite codes; exact)
+uint16_t f8_e4m3_f16_bits(const uint8_t b) {
+    const int e = (b >> 3) & 15, m = b & 7;
+    const float v = e ? ldexpf((float)(8 + m), e - 10) : ldexpf((float)m, -9);
+    return __builtin_bit_cast(uint16_t, (_Float16)((b & 0x80) ? -v : v));
+}
+
 }  // namespace
 
 // gguf blocks: file layout ([rows][cols/32 blocks: f16 d, f16 m (affine), u32 qh (5-bit), codes])
@@ -462,6 +482,14 @@ int xh_kv_fill_synthetic(xh_ctx* ctx, int layer, int which, int slot0, int n_slo
         slot0 + n_slots > ctx->c.max_seq_len)
         return set_err(ctx, XH_E_INVALID, "bad kv_fill_synthetic arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    if (ctx->kv8()) {
+        uint8_t* base8 = (uint8_t*)(which ? ctx->vcache(layer) : ctx->kcache(layer)) + (size_t)slot0 * ctx->kv_dim;
+        hipLaunchKernelGGL(synth_fill_kv8_kernel, dim3(2048), dim3(256), 0, ctx->stream, base8, (size_t)n_slots,
+                           (size_t)ctx->kv_dim, slot0, which ? (uint16_t*)nullptr : ctx->master(layer), seed, std);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return 0;
+    }
     char* base = (char*)((which ? ctx->vcache(layer) : ctx->kcache(layer)) + (size_t)slot0 * ctx->kv_dim);
     hipLaunchKernelGGL(synth_fill_kernel, dim3(2048), dim3(256), 0, ctx->stream, base, (size_t)ctx->kv_dim * 2,
                        (size_t)n_slots, (size_t)ctx->kv_dim, (int)XH_F16, seed, 0.0f, std);
@@ -474,6 +502,7 @@ int xh_kv_write(xh_ctx* ctx, int layer, int which, int slot0, int n_slots, const
     if (!ctx || !host || layer < 0 || layer >= ctx->c.n_layers || (which != 0 && which != 1) || slot0 < 0 ||
         n_slots < 0 || slot0 + n_slots > ctx->c.max_seq_len)
         return set_err(ctx, XH_E_INVALID, "bad kv_write arguments");
+    if (ctx->kv8()) return set_err(ctx, XH_E_INVALID, "kv_write: the context's KV ring is fp8 (xh_kv_write8)");
     HIP_TRY(ctx, hipSetDevice(ctx->dev));
     uint16_t* base = (which ? ctx->vcache(layer) : ctx->kcache(layer)) + (size_t)slot0 * ctx->kv_dim;
     HIP_TRY(ctx, copy_sync(ctx, base, host, (size_t)n_slots * ctx->kv_dim * 2, hipMemcpyHostToDevice));
@@ -484,10 +513,53 @@ int xh_kv_read(xh_ctx* ctx, int layer, int which, int slot0, int n_slots, uint16
     if (!ctx || !host || layer < 0 || layer >= ctx->c.n_layers || (which != 0 && which != 1) || slot0 < 0 ||
         n_slots < 0 || slot0 + n_slots > ctx->c.max_seq_len)
         return set_err(ctx, XH_E_INVALID, "bad kv_read arguments");
+    if (ctx->kv8()) return set_err(ctx, XH_E_INVALID, "kv_read: the context's KV ring is fp8 (xh_kv_read8)");
     HIP_TRY(ctx, hipSetDevice(ctx->dev));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const uint16_t* base = (which ? ctx->vcache(layer) : ctx->kcache(layer)) + (size_t)slot0 * ctx->kv_dim;
     HIP_TRY(ctx, copy_sync(ctx, host, base, (size_t)n_slots * ctx->kv_dim * 2, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int xh_kv_write8(xh_ctx* ctx, int layer, int which, int slot0, int n_slots, const uint8_t* host) {
+    if (!ctx || !host || layer < 0 || layer >= ctx->c.n_layers || (which != 0 && which != 1) || slot0 < 0 ||
+        n_slots < 0 || slot0 + n_slots > ctx->c.max_seq_len)
+        return set_err(ctx, XH_E_INVALID, "bad kv_write8 arguments");
+    if (!ctx->kv8()) return set_err(ctx, XH_E_INVALID, "kv_write8: the context's KV ring is fp16 (xh_kv_write)");
+    const size_t kd = (size_t)ctx->kv_dim, n = (size_t)n_slots * kd;
+    for (size_t i = 0; i < n; i++)
+        if (f8_special(host[i], false)) return set_err(ctx, XH_E_INVALID, "kv_write8: element %zu is the NaN code", i);
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    uint8_t* base = (uint8_t*)(which ? ctx->vcache(layer) : ctx->kcache(layer)) + (size_t)slot0 * kd;
+    HIP_TRY(ctx, copy_sync(ctx, base, host, n, hipMemcpyHostToDevice));
+    if (which == 0 && slot0 < 2 && n_slots > 0) {  // the sinks' master: the exact fp16 image
+        const size_t rows = std::min<size_t>((size_t)n_slots, (size_t)(2 - slot0));
+        std::vector<uint16_t> img(rows * kd);
+        for (size_t i = 0; i < img.size(); i++) img[i] = f8_e4m3_f16_bits(host[i]);
+        HIP_TRY(ctx, copy_sync(ctx, ctx->master(layer) + (size_t)slot0 * kd, img.data(), img.size() * 2, hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
+int xh_kv_read8(xh_ctx* ctx, int layer, int which, int slot0, int n_slots, uint8_t* host) {
+    if (!ctx || !host || layer < 0 || layer >= ctx->c.n_layers || (which != 0 && which != 1) || slot0 < 0 ||
+        n_slots < 0 || slot0 + n_slots > ctx->c.max_seq_len)
+        return set_err(ctx, XH_E_INVALID, "bad kv_read8 arguments");
+    if (!ctx->kv8()) return set_err(ctx, XH_E_INVALID, "kv_read8: the context's KV ring is fp16 (xh_kv_read)");
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const uint8_t* base = (const uint8_t*)(which ? ctx->vcache(layer) : ctx->kcache(layer)) + (size_t)slot0 * ctx->kv_dim;
+    HIP_TRY(ctx, copy_sync(ctx, host, base, (size_t)n_slots * ctx->kv_dim, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int xh_kv_sink_read(xh_ctx* ctx, int layer, uint16_t* out) {
+    if (!ctx || !out || layer < 0 || layer >= ctx->c.n_layers) return set_err(ctx, XH_E_INVALID, "bad kv_sink_read arguments");
+    if (!ctx->kv8()) return set_err(ctx, XH_E_INVALID, "kv_sink_read: the context's KV ring is fp16 (no sink master)");
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, copy_sync(ctx, out, ctx->master(layer), (size_t)2 * ctx->kv_dim * 2, hipMemcpyDeviceToHost));
     return 0;
 }
 }  // extern "C"

@@ -59,9 +59,19 @@ extern "C" {
 const char* xh_last_error(const xh_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
 int xh_create(const xh_config* cfg, int device_ordinal, xh_ctx** out) {
+    return xh_create_kv(cfg, device_ordinal, XH_F16, out);
+}
+
+int xh_kv_dtype(const xh_ctx* ctx) { return ctx ? ctx->kv_dt : XH_E_INVALID; }
+
+int xh_create_kv(const xh_config* cfg, int device_ordinal, int kv_dtype, xh_ctx** out) {
     if (!cfg || !out) return set_err(nullptr, XH_E_INVALID, "null argument");
     *out = nullptr;
     const xh_config& c = *cfg;
+    if (kv_dtype != XH_F16 && kv_dtype != XH_F8_E4M3)
+        return set_err(nullptr, XH_E_INVALID, "kv_dtype %d is neither XH_F16 nor XH_F8_E4M3", kv_dtype);
+    if (kv_dtype == XH_F8_E4M3 && (c.head_dim <= 0 || c.head_dim % 16))
+        return set_err(nullptr, XH_E_INVALID, "an fp8 KV ring needs head_dim %% 16 == 0 (got %d)", c.head_dim);
     if (c.dim <= 0 || c.hidden_dim <= 0 || c.head_dim <= 0 || c.n_layers <= 0 || c.n_heads <= 0 ||
         c.n_kv_heads <= 0 || c.vocab_size <= 0 || c.max_seq_len <= 2)
         return set_err(nullptr, XH_E_INVALID, "bad config dims");
@@ -106,6 +116,7 @@ int xh_create(const xh_config* cfg, int device_ordinal, xh_ctx** out) {
     ctx->q_dim = c.n_heads * c.head_dim;
     ctx->kv_dim = c.n_kv_heads * c.head_dim;
     ctx->qpk = qpk;
+    ctx->kv_dt = kv_dtype;
     ctx->nsplit = attn_nsplit(c.n_kv_heads, c.max_seq_len);
     ctx->t_max = attn_split_len(c.max_seq_len, ctx->nsplit);
     ctx->t_max_aw = attn_split_len(c.max_seq_len, ctx->nsplit, attn_min_t_partials(c.head_dim, AW_THREADS));
@@ -116,7 +127,9 @@ int xh_create(const xh_config* cfg, int device_ordinal, xh_ctx** out) {
         delete ctx;
         return set_err(nullptr, XH_E_HIP, "stream create failed");
     }
-    CREATE_TRY(dmalloc(ctx, &ctx->kv, (size_t)c.n_layers * 2 * c.max_seq_len * ctx->kv_dim));
+    // (dmalloc counts uint16_t: an fp8 ring is half of them; kv_dim is even)
+    CREATE_TRY(dmalloc(ctx, &ctx->kv, ctx->kv_bytes() / 2));
+    if (ctx->kv8()) CREATE_TRY(dmalloc(ctx, &ctx->sink_master, (size_t)c.n_layers * 2 * ctx->kv_dim));
     CREATE_TRY(dmalloc(ctx, &ctx->x, (size_t)c.dim));
     CREATE_TRY(dmalloc(ctx, &ctx->q, (size_t)ctx->q_dim));
     CREATE_TRY(dmalloc(ctx, &ctx->attn_out, (size_t)ctx->q_dim));
@@ -199,7 +212,7 @@ void xh_destroy(xh_ctx* ctx) {
     }
     if (ctx->wcls && ctx->wcls != ctx->embed) hipFree(ctx->wcls);
     hipFree(ctx->embed); hipFree(ctx->final_norm);
-    hipFree(ctx->kv); hipFree(ctx->x); hipFree(ctx->q); hipFree(ctx->attn_out); hipFree(ctx->hb);
+    hipFree(ctx->kv); hipFree(ctx->sink_master); hipFree(ctx->x); hipFree(ctx->q); hipFree(ctx->attn_out); hipFree(ctx->hb);
     hipFree(ctx->logits); hipFree(ctx->part_o); hipFree(ctx->part_ml); hipFree(ctx->attn_cnt); hipFree(ctx->aw_sync); hipFree(ctx->cand); hipFree(ctx->scan_flag);
     hipFree(ctx->samp);
     hipFree(ctx->ext); hipFree(ctx->ext_ring); hipFree(ctx->ext_btok); hipFree(ctx->ext_bval); hipFree(ctx->ext_adj);
@@ -223,7 +236,8 @@ int xh_reset(xh_ctx* ctx) {
     if (!ctx) return XH_E_INVALID;
     HIP_TRY(ctx, hipSetDevice(ctx->dev));
     const xh_config& c = ctx->c;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->kv, 0, (size_t)c.n_layers * 2 * c.max_seq_len * ctx->kv_dim * 2, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->kv, 0, ctx->kv_bytes(), ctx->stream));
+    if (ctx->kv8()) HIP_TRY(ctx, hipMemsetAsync(ctx->sink_master, 0, (size_t)c.n_layers * 2 * ctx->kv_dim * 2, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(ctx->x, 0, (size_t)c.dim * 4, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(ctx->logits, 0, (size_t)c.vocab_size * 4, ctx->stream));
     // the attention + Wo hand-off words (normally zeroed by each layer's W1/W3 launch): a step
@@ -251,7 +265,7 @@ size_t xh_active_bytes(const xh_ctx* ctx, size_t pos) {
         bytes += (size_t)c.dim * file_row_bytes(w.wo_dt, ctx->q_dim);
         bytes += (size_t)2 * c.hidden_dim * file_row_bytes(w.w13_dt, c.dim);
         bytes += (size_t)c.dim * file_row_bytes(w.w2_dt, c.hidden_dim);
-        bytes += 2 * kv_len * ctx->kv_dim * 2;
+        bytes += 2 * kv_len * ctx->kv_dim * ctx->kv_esz();
     }
     return bytes;
 }

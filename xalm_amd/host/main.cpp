@@ -48,6 +48,8 @@
 using namespace xalm;
 using clk = std::chrono::steady_clock;
 
+static int g_kv_dtype = XH_F16;  // -K: the KV rings' element type
+
 static void error_usage() {
     fprintf(stderr, "Usage:   xalm <checkpoint> [options]\n");
     fprintf(stderr, "Example: xalm model.xalm -i \"Q: What is the meaning of life?\"\n");
@@ -58,6 +60,7 @@ static void error_usage() {
     fprintf(stderr, "  -T <int> sliding window context length (0 - max)\n");
     fprintf(stderr, "  -n <int> number of steps in completion mode, default 128. 0 = max_seq_len, -1 = infinite\n");
     fprintf(stderr, "  -g <0|1> decode loop on the device (default 0)\n");
+    fprintf(stderr, "  -K [f16,f8] KV ring element type (default f16; f8 = e4m3, hip only)\n");
     fprintf(stderr, "  -t <float> sampling temperature (default 0 - greedy)\n");
     fprintf(stderr, "  -k <int> top-k, 0 = off (default 0)\n");
     fprintf(stderr, "  -p <float> top-p in (0, 1], 1 = off (default 1)\n");
@@ -108,7 +111,7 @@ static void run_completion(const std::string& path, Device dev, const std::strin
                            bool device_loop, const xh_sampling& sampling, const xh_logit_ctl& ctl,
                            const xh_trunc_ctl& trunc, xh_seq_ctl seq, const std::string& regex, int top_n) {
     const XalmFile file = XalmFile::load(path);
-    const Model model = Model::from_xalm(file, context, dev);
+    const Model model = Model::from_xalm(file, context, dev, 0, g_kv_dtype);
     InferenceState state(model.config);
     const Sampler sampler(model.config);
     const Tokenizer tokenizer(file);
@@ -212,7 +215,7 @@ static void run_completion(const std::string& path, Device dev, const std::strin
 // run_perplexity, src/main.cpp:198-268
 static void run_perplexity(const std::string& path, Device dev, const std::string& prompt, int context, int top_n) {
     const XalmFile file = XalmFile::load(path);
-    const Model model = Model::from_xalm(file, context, dev);
+    const Model model = Model::from_xalm(file, context, dev, 0, g_kv_dtype);
     InferenceState state(model.config);
     const Tokenizer tokenizer(file);
     model.forward(state, 0, 0);
@@ -269,6 +272,11 @@ int main(int argc, char** argv) {
         else if (f == 'T') context = std::stoi(v);
         else if (f == 'n') num_steps = std::stoi(v);
         else if (f == 'g') device_loop = std::stoi(v);
+        else if (f == 'K') {
+            if (v == "f16") g_kv_dtype = XH_F16;
+            else if (v == "f8") g_kv_dtype = XH_F8_E4M3;
+            else error_usage();
+        }
         else if (f == 't') sampling.temperature = std::stof(v);
         else if (f == 'k') sampling.top_k = std::stoi(v);
         else if (f == 'p') sampling.top_p = std::stof(v);
@@ -308,6 +316,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "error: -L takes 0 .. %d\n", XH_TOP_MAX);
         return 1;
     }
+    if (g_kv_dtype != XH_F16 && device == "cpu") error_usage();  // the fp8 KV ring is the HIP device's
     const Device dev = device == "cpu" ? Device::CPU : Device::HIP;
     try {
         if (mode == "completion") run_completion(path, dev, prompt, context, num_steps, device_loop != 0, sampling, ctl, trunc, seq, regex, top_n);

@@ -22,7 +22,8 @@ void check(int rc, xh_ctx* ctx, const char* what) {
 // Model::from_xalm, src/model.cpp:48-118: the same tensor names and shape checks; the weights
 // stream from the file into device memory through xh_upload_file (mapped, pinned and DMAd; no host
 // Tensor buffers).
-Model Model::from_xalm(const XalmFile& xalm, const int context, const Device device, const int ordinal) {
+Model Model::from_xalm(const XalmFile& xalm, const int context, const Device device, const int ordinal,
+                       const int kv_dtype) {
     if (device != Device::HIP)
         throw std::invalid_argument(
             "-d cpu: the reference CPU forward is not part of this build (its restatement is the test oracle, "
@@ -30,7 +31,7 @@ Model Model::from_xalm(const XalmFile& xalm, const int context, const Device dev
     const Config c = Config::from_xalm(xalm, context);
     xh_config abi = c.to_abi();
     xh_ctx* ctx = nullptr;
-    check(xh_create(&abi, ordinal, &ctx), nullptr, "xh_create");
+    check(xh_create_kv(&abi, ordinal, kv_dtype, &ctx), nullptr, "xh_create_kv");
     Model m(c, ctx);
     auto load = [&](const std::string& name, int kind, int layer, std::vector<int> shape) {
         const TensorInfo& ti = xalm.tensors.at(name);

@@ -99,7 +99,9 @@ struct Constraint {
 
 class Model {
 public:
-    static Model from_xalm(const XalmFile& xalm, int context = 0, Device device = Device::HIP, int ordinal = 0);
+    // kv_dtype: the KV rings' element type, XH_F16 or XH_F8_E4M3 (xh_create_kv)
+    static Model from_xalm(const XalmFile& xalm, int context = 0, Device device = Device::HIP, int ordinal = 0,
+                           int kv_dtype = XH_F16);
     Model(Model&& o) noexcept;
     Model& operator=(Model&&) = delete;
     Model(const Model&) = delete;

@@ -29,18 +29,20 @@ class InferenceState:
 
 
 class Model:
-    def __init__(self, config: L.XhConfig, device: int = 0):
+    def __init__(self, config: L.XhConfig, device: int = 0, kv_dtype: int = L.F16):
+        """`kv_dtype`: the KV rings' element type, L.F16 or L.F8_E4M3 (xh_create_kv)."""
         self.config = config
         self._ctx = ctypes.c_void_p()
-        L.check(L.lib().xh_create(ctypes.byref(config), device, ctypes.byref(self._ctx)))
+        L.check(L.lib().xh_create_kv(ctypes.byref(config), device, int(kv_dtype), ctypes.byref(self._ctx)))
 
     # -- construction ----------------------------------------------------------------
     @classmethod
-    def from_xalm(cls, xf: XalmFile, context: int = 0, device: int = 0, direct: bool = True) -> "Model":
+    def from_xalm(cls, xf: XalmFile, context: int = 0, device: int = 0, direct: bool = True,
+                  kv_dtype: int = L.F16) -> "Model":
         """`direct`: tensors stream from the file into device memory (xh_upload_file);
         otherwise each one is read on the host and copied (xh_upload)."""
         cfg = xf.config(context)
-        m = cls(cfg, device)
+        m = cls(cfg, device, kv_dtype)
         c = cfg
         shapes = {L.EMBED: (c.vocab_size, c.dim), L.FINAL_NORM: (c.dim,), L.WCLS: (c.vocab_size, c.dim)}
         for kind, name in xf.global_tensors(bool(c.tie_word_embeddings)).items():
@@ -331,6 +333,28 @@ class Model:
         kv_dim = self.config.n_kv_heads * self.config.head_dim
         out = np.empty((n_slots, kv_dim), dtype=np.uint16)
         L.check(L.lib().xh_kv_read(self._ctx, layer, which, slot0, n_slots, L.ptr(out)), self._ctx)
+        return out
+
+    @property
+    def kv_dtype(self) -> int:
+        return int(L.lib().xh_kv_dtype(self._ctx))
+
+    def kv_write8(self, layer: int, which: int, slot0: int, rows: np.ndarray):
+        """Rows of raw e4m3 codes into an fp8 KV ring (xh_kv_write8)."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        L.check(L.lib().xh_kv_write8(self._ctx, layer, which, slot0, rows.shape[0], L.ptr(rows)), self._ctx)
+
+    def kv_read8(self, layer: int, which: int, slot0: int, n_slots: int) -> np.ndarray:
+        kv_dim = self.config.n_kv_heads * self.config.head_dim
+        out = np.empty((n_slots, kv_dim), dtype=np.uint8)
+        L.check(L.lib().xh_kv_read8(self._ctx, layer, which, slot0, n_slots, L.ptr(out)), self._ctx)
+        return out
+
+    def kv_sink_read(self, layer: int) -> np.ndarray:
+        """The layer's fp16 master of K slots 0 and 1, uint16 [2][kv_dim] (fp8 KV contexts)."""
+        kv_dim = self.config.n_kv_heads * self.config.head_dim
+        out = np.empty((2, kv_dim), dtype=np.uint16)
+        L.check(L.lib().xh_kv_sink_read(self._ctx, layer, L.ptr(out)), self._ctx)
         return out
 
     def time_kernel(self, which: int, iters: int) -> float:
