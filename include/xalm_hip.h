@@ -58,13 +58,29 @@ enum xh_dtype {
      * (code 8 is -0); a weight is exactly value(c) * 2^(e - 127).  e = 255 (NaN) is invalid: every
      * upload route answers XH_E_INVALID for a tensor that holds one; every other e, 0 and 254
      * included, is valid (a product that overflows f32 is outside the contract).  Columns in whole
-     * 32-element blocks, header shape = bytes per row, as for the other blocks. */
+     * 32-element blocks, header shape = bytes per row, as for the other blocks.
+     * gguf K-quants: super-blocks of 256 consecutive elements of a row (little-endian; columns in
+     * whole super-blocks, header shape = bytes per row).
+     *   Q4_K (quants.py Q4_K.dequantize_blocks): 144 B = f16 d, f16 dmin, s[12], qs[128].  Sub-block
+     *     j (0..7, elements 32j..32j+31) has the 6-bit fields
+     *       j < 4:  sc = s[j] & 63,                           mn = s[j+4] & 63
+     *       j >= 4: sc = (s[j+4] & 15) | (s[j-4] >> 6) << 4,  mn = (s[j+4] >> 4) | (s[j] >> 6) << 4
+     *     element 64g + l (l 0..31) the low nibble q of qs[32g + l], element 64g + 32 + l the high
+     *     one; a weight is fmaf(d*sc, q, -(dmin*mn)): both products exact, ONE f32 rounding.
+     *   Q6_K (quants.py Q6_K.dequantize_blocks): 210 B = ql[128], qh[64], int8 sc[16], f16 d.
+     *     Element e = 128h + 32k + l (h 0..1, k 0..3, l 0..31) has the code q = nibble k >> 1 of
+     *     ql[64h + 32(k & 1) + l] | (bits 2k..2k+1 of qh[32h + l]) << 4; a weight is
+     *     (d*sc[e / 16]) * (q - 32), exact in f32.
+     * The decode matvecs, the embedding gather and the prompt passes (the f32-input MFMA kernel, as
+     * Q4_1 / Q5_1) run both; a Wo of either takes the two-launch route like every block type. */
     XH_Q8_0 = 20,
     XH_Q4_0 = 21,
     XH_Q4_1 = 22,
     XH_Q5_0 = 23,
     XH_Q5_1 = 24,
-    XH_MXFP4 = 25
+    XH_MXFP4 = 25,
+    XH_Q4_K = 26,
+    XH_Q6_K = 27
 };
 
 /* ---- tensor kinds (names as in .xalm, src/model.cpp:83-114) ------------------------ */
@@ -171,12 +187,31 @@ int xh_upload_synthetic(xh_ctx* ctx, int tensor_kind, int layer, int dtype, uint
  * XH_MXFP4: per block amax = max|v|; amax == 0 gives e = 0 and all codes 0; else
  * E = clamp(floor(log2(amax)) - 2, -127, 127) from the f32 exponent bits (a subnormal amax exactly),
  * e = E + 127, each code the sign plus the e2m1 magnitude nearest to |v| * 2^-E (an exact product),
- * ties to the even code, above 6 saturating at 6.  A non-finite input: XH_E_INVALID. */
+ * ties to the even code, above 6 saturating at 6.  A non-finite input: XH_E_INVALID.
+ * XH_Q4_K / XH_Q6_K: n_blocks counts SUPER-blocks (256 floats in, 144 / 210 bytes out each).  The
+ * reference ships no quantizer for them; this one (xs_quant_q4_k / xs_quant_q6_k, xalm_synth.h) is a
+ * plain min / max quantizer, every f32 operation rounded on its own, f16 by round-to-nearest-even
+ * saturating at 65504, rnd(t) = floorf(t + 0.5f):
+ *   Q4_K: per sub-block j  lo_j = min(0, min v), a_j = (max v - lo_j) / 15, b_j = 0 - lo_j;
+ *         d = f16(max_j a_j / 63), dmin = f16(max_j b_j / 63);  sc_j = min(63, rnd(a_j / d)) (0 when
+ *         d == 0), mn_j = min(63, rnd(b_j / dmin)) likewise;  with D = d*sc_j, M = dmin*mn_j:
+ *         q = clamp(rnd((v + M) / D), 0, 15), 0 when D == 0.  So dmin*mn >= 0, as ggml has it.
+ *         Error of element v of sub-block j against its decoded weight w:
+ *           |v - w| <= max(d*sc_j / 2, 8*d + dmin) * (1 + 2^-16) + 2^-14
+ *         (half a step of the sub-block's grid; or, where q or a 6-bit field clamps, the roundings
+ *         of sc_j (15 * d/2), of mn_j (dmin/2) and of d / dmin to f16: 2^-12 relative, 2^-25 absolute).
+ *   Q6_K: per 16-element group g  a_g = max|v| / 31;  d = f16(max_g a_g / 127);
+ *         sc_g = min(127, rnd(a_g / d)) (0 when d == 0);  with D = d*sc_g:
+ *         q = clamp(floorf(v / D + 32.5f), 0, 63), 0 when D == 0 (the weight is 0 whatever q is).
+ *           |v - w| <= max(d*sc_g / 2, 17*d) * (1 + 2^-16) + 2^-13
+ *   Both: every output field is in range and d / dmin are finite; 256 zeros give an all-zero
+ *   super-block; a non-finite input: XH_E_INVALID. */
 int xh_quantize_blocks(int dtype, const float* values, size_t n_blocks, void* out);
 /* The inverse on the host: n_blocks blocks of a block dtype in the file layout -> n_blocks * 32
  * floats, each the value the kernels decode (d*q, d*(q - bias), fmaf(d, q, m); MXFP4:
  * ldexpf(value(c), e - 127), so e = 0 yields the f32 subnormals exactly).  XH_E_INVALID for a
- * non-block dtype, a null pointer or an MXFP4 block with e = 255. */
+ * non-block dtype, a null pointer or an MXFP4 block with e = 255.  XH_Q4_K / XH_Q6_K: n_blocks counts
+ * super-blocks (n_blocks * 256 floats out), the values as defined at the enum. */
 int xh_dequantize_blocks(int dtype, const void* blocks, size_t n_blocks, float* out);
 /* Fill KV ring rows [slot0, slot0+n_slots) of one layer with synthetic fp16 N(0, std)-like values. */
 int xh_kv_fill_synthetic(xh_ctx* ctx, int layer, int which, int slot0, int n_slots, uint64_t seed, float std);

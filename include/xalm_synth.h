@@ -270,6 +270,130 @@ XS_FN void xs_block(uint8_t* out, int dtype, uint64_t seed, uint64_t r, uint64_t
     else xs_quant_q4_0(v, out);
 }
 
+/* ---- gguf K-quants (XH_Q4_K = 26, XH_Q6_K = 27): one super-block from 256 floats.  The reference
+ * ships only their decoders (quants.py Q4_K / Q6_K dequantize_blocks); the quantizers are this
+ * project's, defined in xalm_hip.h at xh_quantize_blocks: min / max per sub-block, the 6-bit / int8
+ * sub-block scales against the super-block's largest.  Every f32 operation below stands alone (a
+ * division or an addition behind a division: nothing a compiler can contract), so gcc, hipcc and
+ * numpy agree byte for byte. */
+XS_FN float xs_from_f16(uint16_t h) {
+    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
+    const uint32_t e = (h >> 10) & 31u, m = h & 0x3FFu;
+    if (e == 0) return xs_bits_f32(sign | xs_f32_bits((float)m * (1.0f / 16777216.0f)));  /* m * 2^-24 */
+    return xs_bits_f32(sign | ((e + 112u) << 23) | (m << 13));                          /* finite (e < 31) */
+}
+/* min(cap, floorf(a / d + 0.5f)), 0 when d == 0 (a >= 0) */
+XS_FN int xs_kq_field(float a, float d, int cap) {
+    if (d == 0.0f) return 0;
+    const float t = a / d;
+    const float r = floorf(t + 0.5f);
+    return r > (float)cap ? cap : (int)r;
+}
+/* out: 144 bytes, f16 d, f16 dmin, s[12], qs[128] */
+XS_FN void xs_quant_q4_k(const float* v, uint8_t* out) {
+    float a[8], b[8], amax = 0.0f, bmax = 0.0f;
+    for (int j = 0; j < 8; j++) {
+        float mx = v[32 * j], lo = fminf(v[32 * j], 0.0f);
+        for (int k = 1; k < 32; k++) { mx = fmaxf(mx, v[32 * j + k]); lo = fminf(lo, v[32 * j + k]); }
+        a[j] = (mx - lo) / 15.0f;
+        b[j] = 0.0f - lo;  /* +0 for lo == 0 */
+        amax = fmaxf(amax, a[j]);
+        bmax = fmaxf(bmax, b[j]);
+    }
+    const uint16_t dh = xs_to_f16(amax / 63.0f), mh = xs_to_f16(bmax / 63.0f);
+    const float d = xs_from_f16(dh), dmin = xs_from_f16(mh);
+    out[0] = (uint8_t)(dh & 0xFFu); out[1] = (uint8_t)(dh >> 8);
+    out[2] = (uint8_t)(mh & 0xFFu); out[3] = (uint8_t)(mh >> 8);
+    uint8_t sc[8], mn[8], q[256];
+    for (int j = 0; j < 8; j++) {
+        sc[j] = (uint8_t)xs_kq_field(a[j], d, 63);
+        mn[j] = (uint8_t)xs_kq_field(b[j], dmin, 63);
+        const float D = d * (float)sc[j], M = dmin * (float)mn[j];  /* exact: 11 + 6 bits */
+        for (int k = 0; k < 32; k++) {
+            float r = 0.0f;
+            if (D != 0.0f) {
+                const float t = (v[32 * j + k] + M) / D;
+                r = floorf(t + 0.5f);
+            }
+            q[32 * j + k] = (uint8_t)(r < 0.0f ? 0.0f : (r > 15.0f ? 15.0f : r));
+        }
+    }
+    uint8_t* s = out + 4;
+    for (int j = 0; j < 4; j++) {
+        s[j] = (uint8_t)(sc[j] | ((sc[j + 4] >> 4) << 6));
+        s[j + 4] = (uint8_t)(mn[j] | ((mn[j + 4] >> 4) << 6));
+        s[j + 8] = (uint8_t)((sc[j + 4] & 15u) | ((mn[j + 4] & 15u) << 4));
+    }
+    for (int g = 0; g < 4; g++)
+        for (int l = 0; l < 32; l++) out[16 + 32 * g + l] = (uint8_t)(q[64 * g + l] | (q[64 * g + 32 + l] << 4));
+}
+/* out: 210 bytes, ql[128], qh[64], int8 sc[16], f16 d */
+XS_FN void xs_quant_q6_k(const float* v, uint8_t* out) {
+    float a[16], amax = 0.0f;
+    for (int g = 0; g < 16; g++) {
+        float m = 0.0f;
+        for (int k = 0; k < 16; k++) m = fmaxf(m, fabsf(v[16 * g + k]));
+        a[g] = m / 31.0f;
+        amax = fmaxf(amax, a[g]);
+    }
+    const uint16_t dh = xs_to_f16(amax / 127.0f);
+    const float d = xs_from_f16(dh);
+    uint8_t q[256];
+    for (int g = 0; g < 16; g++) {
+        const int sc = xs_kq_field(a[g], d, 127);
+        out[192 + g] = (uint8_t)sc;
+        const float D = d * (float)sc;  /* exact: 11 + 7 bits */
+        for (int k = 0; k < 16; k++) {
+            float r = 0.0f;
+            if (D != 0.0f) {
+                const float t = v[16 * g + k] / D;
+                r = floorf(t + 32.5f);
+            }
+            q[16 * g + k] = (uint8_t)(r < 0.0f ? 0.0f : (r > 63.0f ? 63.0f : r));
+        }
+    }
+    for (int h = 0; h < 2; h++)
+        for (int l = 0; l < 32; l++) {
+            const uint8_t* e = q + 128 * h + l;  /* e[32 k]: element 128h + 32k + l */
+            out[64 * h + l] = (uint8_t)((e[0] & 15u) | ((e[64] & 15u) << 4));
+            out[64 * h + 32 + l] = (uint8_t)((e[32] & 15u) | ((e[96] & 15u) << 4));
+            out[128 + 32 * h + l] = (uint8_t)((e[0] >> 4) | ((e[32] >> 4) << 2) | ((e[64] >> 4) << 4) | ((e[96] >> 4) << 6));
+        }
+    out[208] = (uint8_t)(dh & 0xFFu);
+    out[209] = (uint8_t)(dh >> 8);
+}
+/* the decoders (the definition in xalm_hip.h): 256 floats from one super-block */
+XS_FN void xs_dequant_q4_k(const uint8_t* in, float* o) {
+    const float d = xs_from_f16((uint16_t)(in[0] | in[1] << 8)), dmin = xs_from_f16((uint16_t)(in[2] | in[3] << 8));
+    const uint8_t* s = in + 4;
+    for (int j = 0; j < 8; j++) {
+        const int sc = j < 4 ? s[j] & 63 : (s[j + 4] & 15) | ((s[j - 4] >> 6) << 4);
+        const int mn = j < 4 ? s[j + 4] & 63 : (s[j + 4] >> 4) | ((s[j] >> 6) << 4);
+        const float D = d * (float)sc, M = dmin * (float)mn;
+        for (int l = 0; l < 32; l++) {
+            const uint8_t b = in[16 + 32 * (j >> 1) + l];
+            o[32 * j + l] = fmaf(D, (float)((j & 1) ? b >> 4 : b & 15u), -M);
+        }
+    }
+}
+XS_FN void xs_dequant_q6_k(const uint8_t* in, float* o) {
+    const float d = xs_from_f16((uint16_t)(in[208] | in[209] << 8));
+    for (int e = 0; e < 256; e++) {
+        const int h = e >> 7, k = (e >> 5) & 3, l = e & 31;
+        const int lo = (in[64 * h + 32 * (k & 1) + l] >> (4 * (k >> 1))) & 15;
+        const int hi = (in[128 + 32 * h + l] >> (2 * k)) & 3;
+        o[e] = (d * (float)(int8_t)in[192 + (e >> 4)]) * (float)((lo | (hi << 4)) - 32);
+    }
+}
+/* synthetic super-block b of row r of a [rows][cols] tensor (dtype 26 Q4_K / 27 Q6_K): the 256 values
+ * xs_value gives elements r*cols + 256b .. +255, quantized; out: 144 / 210 bytes */
+XS_FN void xs_superblock(uint8_t* out, int dtype, uint64_t seed, uint64_t r, uint64_t cols, uint64_t b, float mean, float std) {
+    float v[256];
+    for (int k = 0; k < 256; k++) v[k] = xs_value(seed, r * cols + 256 * b + k, mean, std);
+    if (dtype == 26) xs_quant_q4_k(v, out);
+    else xs_quant_q6_k(v, out);
+}
+
 /* dtype ids as in xalm_hip.h: 1 F32, 2 F16, 3 BF16, 6 F8_E4M3, 7 F8_E5M2 */
 XS_FN void xs_store(void* dst, uint64_t idx, int dtype, float v) {
     switch (dtype) {

@@ -20,17 +20,31 @@ F32, F16, BF16, F8_E4M3, F8_E5M2, U8, Q8 = 1, 2, 3, 6, 7, 8, 9
 Q8_0, Q4_0, Q4_1, Q5_0, Q5_1 = 20, 21, 22, 23, 24
 # OCP microscaling FP4: 32 e2m1 codes under one E8M0 scale byte (include/xalm_hip.h)
 MXFP4 = 25
+# gguf K-quants: super-blocks of 256 elements (include/xalm_hip.h)
+Q4_K, Q6_K = 26, 27
 DTYPE_BY_NAME = {"F32": F32, "F16": F16, "BF16": BF16, "F8_E4M3": F8_E4M3, "F8_E5M2": F8_E5M2,
                  "U8": U8, "Q8": Q8, "Q8_0": Q8_0, "Q4_0": Q4_0, "Q4_1": Q4_1, "Q5_0": Q5_0, "Q5_1": Q5_1,
-                 "MXFP4": MXFP4}
+                 "MXFP4": MXFP4, "Q4_K": Q4_K, "Q6_K": Q6_K}
 DTYPE_SIZE = {F32: 4, F16: 2, BF16: 2, F8_E4M3: 1, F8_E5M2: 1, U8: 1, Q8: 1}
 # bytes per 32-element block: f16 d, [f16 m], [u32 qh], codes (quants.py); MXFP4: e, codes
 GQ_BLOCK_BYTES = {Q8_0: 34, Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24, MXFP4: 17}
+# bytes per 256-element super-block of the K-quants
+KQ_BLOCK_BYTES = {Q4_K: 144, Q6_K: 210}
+
+
+def block_geometry(dtype: int):
+    """(elements, bytes) of one block of a block dtype in the file layout, None for any other."""
+    if dtype in GQ_BLOCK_BYTES:
+        return 32, GQ_BLOCK_BYTES[dtype]
+    if dtype in KQ_BLOCK_BYTES:
+        return 256, KQ_BLOCK_BYTES[dtype]
+    return None
 
 
 def row_bytes(dtype: int, n: int) -> int:
-    """Bytes of one n-element row as uploaded (gguf blocks: n/32 blocks)."""
-    return n // 32 * GQ_BLOCK_BYTES[dtype] if dtype in GQ_BLOCK_BYTES else n * DTYPE_SIZE[dtype]
+    """Bytes of one n-element row as uploaded (gguf blocks: n/32 blocks, K-quants: n/256 super-blocks)."""
+    g = block_geometry(dtype)
+    return n // g[0] * g[1] if g else n * DTYPE_SIZE[dtype]
 # enum xh_option
 OPT_FUSE_ATTN_WO = 1
 OPT_PREFILL = 2
@@ -314,12 +328,14 @@ def gemv_shape(role: int, dtype: int, n: int) -> int:
 
 def quantize_blocks(dtype: int, values: np.ndarray) -> np.ndarray:
     """The converter's block quantizer (quants.py `quantize`) on the host: float32 [..., n] with
-    n % 32 == 0 -> uint8 [..., n / 32 * block bytes] in the file layout.  No device needed."""
+    n % 32 == 0 -> uint8 [..., n / 32 * block bytes] in the file layout (Q4_K / Q6_K: n % 256 == 0,
+    the project's own quantizer, xalm_hip.h).  No device needed."""
     v = np.ascontiguousarray(values, dtype=np.float32)
-    if dtype not in GQ_BLOCK_BYTES or v.shape[-1] % 32:
-        raise ValueError("quantize_blocks: a block dtype and whole 32-element blocks")
-    out = np.empty(v.shape[:-1] + (v.shape[-1] // 32 * GQ_BLOCK_BYTES[dtype],), dtype=np.uint8)
-    check(lib().xh_quantize_blocks(dtype, ptr(v), v.size // 32, ptr(out)))
+    g = block_geometry(dtype)
+    if g is None or v.shape[-1] % g[0]:
+        raise ValueError("quantize_blocks: a block dtype and whole blocks (32 elements, K-quants 256)")
+    out = np.empty(v.shape[:-1] + (v.shape[-1] // g[0] * g[1],), dtype=np.uint8)
+    check(lib().xh_quantize_blocks(dtype, ptr(v), v.size // g[0], ptr(out)))
     return out
 
 
@@ -327,10 +343,11 @@ def dequantize_blocks(dtype: int, blocks: np.ndarray) -> np.ndarray:
     """The inverse on the host (xh_dequantize_blocks): uint8 [..., k * block bytes] in the file
     layout -> float32 [..., 32 k], the values the kernels decode.  No device needed."""
     b = np.ascontiguousarray(blocks, dtype=np.uint8)
-    if dtype not in GQ_BLOCK_BYTES or b.shape[-1] % GQ_BLOCK_BYTES[dtype]:
+    g = block_geometry(dtype)
+    if g is None or b.shape[-1] % g[1]:
         raise ValueError("dequantize_blocks: a block dtype and whole blocks")
-    out = np.empty(b.shape[:-1] + (b.shape[-1] // GQ_BLOCK_BYTES[dtype] * 32,), dtype=np.float32)
-    check(lib().xh_dequantize_blocks(dtype, ptr(b), b.size // GQ_BLOCK_BYTES[dtype], ptr(out)))
+    out = np.empty(b.shape[:-1] + (b.shape[-1] // g[1] * g[0],), dtype=np.float32)
+    check(lib().xh_dequantize_blocks(dtype, ptr(b), b.size // g[1], ptr(out)))
     return out
 
 

@@ -150,12 +150,28 @@ template <> struct WDec<XH_Q8> {
 // coalesced reads.  A weight's value is fmaf(d, q, m) (one f32 rounding, m = 0 without the plane).
 __host__ __device__ constexpr bool gq_has_qh(const int dt) { return dt == XH_Q5_0 || dt == XH_Q5_1; }  // fifth-bit plane
 __host__ __device__ constexpr bool gq_has_m(const int dt) { return dt == XH_Q4_1 || dt == XH_Q5_1; }   // affine: d*q + m
-__host__ __device__ constexpr bool gq_ext(const int dt) { return gq_has_qh(dt) || gq_has_m(dt); }
+// gguf K-quants (XH_Q4_K / XH_Q6_K): super-blocks of 256 elements, still streamed as 32-element
+// chunks of Q4_0-ordered nibbles, so every launch shape of the nibble blocks serves.  Planar rows:
+//   Q4_K [nibbles: n/2 B][16 B per super-block: f16 d, f16 dmin, s[12] as in the file]
+//        a chunk's lane reads its super-block's 16 B in one load (the eight lanes of a super-block
+//        the same address) and unpacks sub-block j = blk & 7 to {d*sc, -(dmin*mn)}: from there on
+//        the Q4_1 form, fmaf(d_eff, q, m_eff).
+//   Q6_K [nibbles: n/2 B][2-bit plane: 8 B per chunk][int8 sc: 2 B per chunk][f16 d per super-block]
+//        the low nibbles of a chunk are one 16-element scale group and the high nibbles the next;
+//        the 2-bit plane holds, per chunk, one u32 for each: element 4w + k of the group at bits
+//        8k + 2w, so (u32 >> 2w) & 0x03030303 lines the high bits of word w's four codes up with
+//        its bytes.  A weight is (d*sc) * (q - 32), exact.
+__host__ __device__ constexpr bool gq_k(const int dt) { return dt == XH_Q4_K || dt == XH_Q6_K; }
+// affine in the matvec: d_eff * sum(q x) + m_eff * sum(x) per chunk (gq_rows)
+__host__ __device__ constexpr bool gq_affine(const int dt) { return gq_has_m(dt) || dt == XH_Q4_K; }
+__host__ __device__ constexpr bool gq_ext(const int dt) { return gq_has_qh(dt) || gq_has_m(dt) || dt == XH_Q4_K; }
 // OCP microscaling FP4 (XH_MXFP4): the planar row is [e2m1 nibbles: n/2 B][e: 1 B per block], the
 // nibble order Q4_0's, the scale the E8M0 byte (2^(e - 127)) in place of an f16 d.  The hardware
 // converter decodes the codes (WDec<XH_MXFP4>); the scale multiplies in f32.
 __host__ __device__ constexpr bool gq_mx(const int dt) { return dt == XH_MXFP4; }
-__host__ __device__ constexpr bool gq_dt(const int dt) { return dt == XH_Q8_0 || dt == XH_Q4_0 || gq_ext(dt) || gq_mx(dt); }
+__host__ __device__ constexpr bool gq_dt(const int dt) { return dt == XH_Q8_0 || dt == XH_Q4_0 || gq_ext(dt) || gq_mx(dt) || gq_k(dt); }
+// elements a row must hold whole multiples of
+__host__ __device__ constexpr int gq_group(const int dt) { return gq_k(dt) ? 256 : 32; }
 // the code the scale multiplies is q - gq_bias (Q8_0: the int8 itself)
 __host__ __device__ constexpr int gq_bias(const int dt) { return dt == XH_Q4_0 ? 8 : dt == XH_Q5_0 ? 16 : 0; }
 __host__ __device__ constexpr size_t gq_qbytes(const int dt, const size_t n) { return dt == XH_Q8_0 ? n : n / 2; }
@@ -164,11 +180,41 @@ __host__ __device__ constexpr size_t gq_d_off(const int dt, const size_t n) {
     return gq_qbytes(dt, n) + (gq_has_qh(dt) ? n / 8 : 0);
 }
 __host__ __device__ constexpr size_t gq_m_off(const int dt, const size_t n) { return gq_d_off(dt, n) + n / 16; }
+// Q6_K: the planes behind the 2-bit plane (the int8 scales, then d per super-block)
+__host__ __device__ constexpr size_t kq6_sc_off(const size_t n) { return n / 2 + n / 4; }
+__host__ __device__ constexpr size_t kq6_d_off(const size_t n) { return n / 2 + n / 4 + n / 16; }
 __host__ __device__ constexpr size_t gq_pitch(const int dt, const size_t n) {
+    if (dt == XH_Q4_K) return n / 2 + n / 16;  // 144 B per super-block
+    if (dt == XH_Q6_K) return (kq6_d_off(n) + n / 128 + 15) & ~(size_t)15;
     return (gq_d_off(dt, n) + (gq_mx(dt) ? n / 32 : gq_has_m(dt) ? n / 8 : n / 16) + 15) & ~(size_t)15;
+}
+// K-quants: one file super-block `in` into the planar row `out` (n columns) at super-block index sb:
+// the one statement of the device layout, for the host repack and the synthetic fill kernel
+__host__ __device__ inline void kq_repack_sb(const int dt, const uint8_t* in, uint8_t* out, const size_t n, const size_t sb) {
+    uint8_t q[256];
+    if (dt == XH_Q4_K) {
+        for (int e = 0; e < 256; e++) q[e] = (in[16 + 32 * (e >> 6) + (e & 31)] >> (4 * ((e >> 5) & 1))) & 15u;
+        for (int k = 0; k < 16; k++) out[n / 2 + 16 * sb + k] = in[k];  // d, dmin, s[12]
+    } else {
+        for (int e = 0; e < 256; e++) {
+            const int h = e >> 7, k = (e >> 5) & 3, l = e & 31;
+            q[e] = (uint8_t)(((in[64 * h + 32 * (k & 1) + l] >> (4 * (k >> 1))) & 15u) | (((in[128 + 32 * h + l] >> (2 * k)) & 3u) << 4));
+        }
+        for (int j = 0; j < 8; j++) {  // the chunk's two plane words: element 4w + k at bits 8k + 2w
+            uint32_t pl[2] = {0u, 0u};
+            for (int i = 0; i < 32; i++) pl[i >> 4] |= (uint32_t)(q[32 * j + i] >> 4) << (8 * (i & 3) + 2 * ((i >> 2) & 3));
+            for (int k = 0; k < 8; k++) out[n / 2 + 8 * (8 * sb + j) + k] = (uint8_t)(pl[k >> 2] >> (8 * (k & 3)));
+        }
+        for (int k = 0; k < 16; k++) out[kq6_sc_off(n) + 16 * sb + k] = in[192 + k];
+        out[kq6_d_off(n) + 2 * sb] = in[208];
+        out[kq6_d_off(n) + 2 * sb + 1] = in[209];
+    }
+    for (int j = 0; j < 8; j++)
+        for (int i = 0; i < 16; i++) out[128 * sb + 16 * j + i] = (uint8_t)((q[32 * j + i] & 15u) | ((q[32 * j + 16 + i] & 15u) << 4));
 }
 // bytes of one block in the file: d, m, qh, codes (MXFP4: e, codes)
 __host__ __device__ constexpr size_t gq_block_bytes(const int dt) {
+    if (gq_k(dt)) return dt == XH_Q4_K ? 144 : 210;  // per super-block (gq_group elements)
     return dt == XH_Q8_0 ? 34 : gq_mx(dt) ? 17 : 18 + (gq_has_qh(dt) ? 4 : 0) + (gq_has_m(dt) ? 2 : 0);
 }
 // bytes in front of a file block's codes (d, m, qh; MXFP4: e)
@@ -193,13 +239,39 @@ template <int DT> struct WScale { static constexpr int BLOCK = gq_dt(DT) ? 32 : 
 // What the matvec holds per chunk beside the codes: the block's d, and for the affine / 5-bit
 // blocks m and qh too (a field the dtype lacks is never read and costs no register)
 struct GqScX { float d, m; uint32_t qh; };
+// Q6_K: d*sc of the chunk's two 16-element groups and their high-bit words
+struct GqSc6 { float d0, d1; uint32_t qa, qb; };
 template <int DT, bool X = gq_ext(DT)> struct GqSc { typedef float T; };
 template <int DT> struct GqSc<DT, true> { typedef GqScX T; };
+template <> struct GqSc<XH_Q6_K, false> { typedef GqSc6 T; };
 // ... read from a row's planes (tail: the row's first byte behind the codes, qbytes: the codes'
 // bytes, n / 2 for the nibble types, so a row has qbytes / 16 blocks)
 template <int DT>
 __device__ __forceinline__ typename GqSc<DT>::T gq_ld_sc(const char* tail, const size_t qbytes, const int blk) {
-    if constexpr (gq_ext(DT)) {
+    if constexpr (DT == XH_Q4_K) {
+        // the super-block's {d, dmin, s[12]}: word 1 = s[0..3], 2 = s[4..7], 3 = s[8..11]
+        const u32x4 t = *(const u32x4*)(tail + (size_t)(blk >> 3) * 16);
+        const int j = blk & 7, sh = 8 * (j & 3);
+        const uint32_t a = t.y >> sh, b = t.z >> sh, c = t.w >> sh;
+        const uint32_t sc = j < 4 ? a & 63u : (c & 15u) | ((a >> 2) & 0x30u);
+        const uint32_t mn = j < 4 ? b & 63u : ((c >> 4) & 15u) | ((b >> 2) & 0x30u);
+        GqScX s;
+        s.d = (float)__builtin_bit_cast(_Float16, (uint16_t)(t.x & 0xffffu)) * (float)sc;
+        s.m = -((float)__builtin_bit_cast(_Float16, (uint16_t)(t.x >> 16)) * (float)mn);
+        s.qh = 0u;
+        return s;
+    } else if constexpr (DT == XH_Q6_K) {
+        const size_t nb = qbytes / 16;
+        const uint2 q = *(const uint2*)(tail + (size_t)blk * 8);
+        const uint32_t s2 = *(const uint16_t*)(tail + 8 * nb + (size_t)blk * 2);
+        const float d = (float)__builtin_bit_cast(_Float16, *(const uint16_t*)(tail + 10 * nb + (size_t)(blk >> 3) * 2));
+        GqSc6 s;
+        s.d0 = d * (float)(int8_t)(s2 & 0xffu);
+        s.d1 = d * (float)(int8_t)(s2 >> 8);
+        s.qa = q.x;
+        s.qb = q.y;
+        return s;
+    } else if constexpr (gq_ext(DT)) {
         const size_t nb = qbytes / 16;
         const char* dp = tail + (gq_has_qh(DT) ? 4 * nb : 0);
         GqScX s;
@@ -280,11 +352,21 @@ template <int DT> struct WDecNib {
 template <> struct WDec<XH_Q4_1> : WDecNib<XH_Q4_1> {};
 template <> struct WDec<XH_Q5_0> : WDecNib<XH_Q5_0> {};
 template <> struct WDec<XH_Q5_1> : WDecNib<XH_Q5_1> {};
+template <> struct WDec<XH_Q4_K> : WDecNib<XH_Q4_K> {};
+template <> struct WDec<XH_Q6_K> : WDecNib<XH_Q6_K> {};
+// the two high bits of element e (0..31) of a Q6_K chunk (GqSc6's plane words)
+__device__ __forceinline__ uint32_t kq6_hi(const uint32_t qa, const uint32_t qb, const int e) {
+    return (((e & 16) ? qb : qa) >> (8 * (e & 3) + 2 * ((e >> 2) & 3))) & 3u;
+}
 // the weights of one chunk of a block dtype from its codes and scale set (sc: GqSc<DT>::T)
 template <int DT, class SC>
 __device__ __forceinline__ void gq_vals(const u32x4 v, const SC& sc, float* f) {
     WDec<DT>::dec(v, f);
-    if constexpr (gq_ext(DT)) {
+    if constexpr (DT == XH_Q6_K) {
+#pragma unroll
+        for (int e = 0; e < 32; e++)
+            f[e] = (e < 16 ? sc.d0 : sc.d1) * (f[e] + (float)(int)(kq6_hi(sc.qa, sc.qb, e) * 16u) - 32.f);  // exact
+    } else if constexpr (gq_ext(DT)) {
 #pragma unroll
         for (int e = 0; e < 32; e++) {
             const float q = f[e] + (float)(int)((gq_has_qh(DT) ? ((sc.qh >> e) & 1u) * 16u : 0u)) - (float)gq_bias(DT);
@@ -324,6 +406,18 @@ __device__ __forceinline__ float dec_row(const int dtype, const void* p, const s
         const uint32_t b = r[(i >> 5) * 16 + (i & 15)];
         const f2_t v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(b, 1.0f, 0);
         return ((i & 16) ? v.y : v.x) * mx_scale(r[gq_d_off(dtype, n) + (i >> 5)]);
+    }
+    if (gq_k(dtype)) {
+        // the chunk's scale set as the matvec reads it, then the one element
+        const uint8_t b = r[(i >> 5) * 16 + (i & 15)];
+        const float nib = (float)((i & 16) ? (b >> 4) : (b & 15u));
+        const char* tail = (const char*)r + n / 2;
+        if (dtype == XH_Q4_K) {
+            const GqScX s = gq_ld_sc<XH_Q4_K>(tail, (size_t)n / 2, i >> 5);
+            return fmaf(s.d, nib, s.m);
+        }
+        const GqSc6 s = gq_ld_sc<XH_Q6_K>(tail, (size_t)n / 2, i >> 5);
+        return ((i & 16) ? s.d1 : s.d0) * (nib + (float)(int)(kq6_hi(s.qa, s.qb, i & 31) * 16u) - 32.f);
     }
     const float d = (float)__builtin_bit_cast(_Float16, *(const uint16_t*)(r + gq_d_off(dtype, n) + (i >> 5) * 2));
     if (dtype == XH_Q8_0) return d * (float)(int8_t)r[i];

@@ -26,15 +26,15 @@ inline bool matrix_dtype_ok(int dt) {
            gq_dt(dt);
 }
 // bytes of one [n]-element row: in the device layout (gguf blocks: planar, gq_pitch) and in
-// the .xalm file / host upload (gguf blocks: n/32 blocks of gq_block_bytes)
+// the .xalm file / host upload (gguf blocks: n/32 blocks, or n/256 super-blocks, of gq_block_bytes)
 inline size_t dev_row_bytes(int dt, size_t n) { return gq_dt(dt) ? gq_pitch(dt, n) : n * dtype_size(dt); }
-inline size_t file_row_bytes(int dt, size_t n) { return gq_dt(dt) ? n / 32 * gq_block_bytes(dt) : n * dtype_size(dt); }
+inline size_t file_row_bytes(int dt, size_t n) { return gq_dt(dt) ? n / gq_group(dt) * gq_block_bytes(dt) : n * dtype_size(dt); }
 inline int elems_per_16b(int dt) { return 16 / (int)dtype_size(dt); }
 // LDS bytes of the decode matvec's x image for an n-column matrix of dt (gemv_smem_bytes); the
 // f32 image is the smallest of any dtype
 inline size_t matrix_lds_bytes(int dt, int n) {
-    const bool nib = gq_dt(dt) && dt != XH_Q8_0 && !gq_mx(dt);  // gq4_image
-    return gemv_lds_bytes(nib || gq_mx(dt) ? 32 : gq_dt(dt) ? 16 : elems_per_16b(dt), nib, n);
+    const bool nib = gq_dt(dt) && dt != XH_Q8_0 && !gq_mx(dt) && dt != XH_Q6_K;  // gq4_image
+    return gemv_lds_bytes(nib || gq_mx(dt) || dt == XH_Q6_K ? 32 : gq_dt(dt) ? 16 : elems_per_16b(dt), nib, n);
 }
 // the kernel's decode form for a matrix: fp8 with NaN/Inf codes -> the exact bit decoder
 inline int kdt(int dt, bool special) {
@@ -359,6 +359,8 @@ int for_dt(int dt, const F& f) {
         case XH_Q5_0: return f.template run<XH_Q5_0>();
         case XH_Q5_1: return f.template run<XH_Q5_1>();
         case XH_MXFP4: return f.template run<XH_MXFP4>();
+        case XH_Q4_K: return f.template run<XH_Q4_K>();
+        case XH_Q6_K: return f.template run<XH_Q6_K>();
         default: return -1;
     }
 }

@@ -202,8 +202,10 @@ __device__ __forceinline__ float4 load_norm4_nb(const void* w, const int dtype, 
 // sum(x) times the factor their form needs: -8 (Q4_0), -16 (Q5_0: d * sum((q - 16) x)), 1 (affine:
 // the m * sum(x) term).  gq4_image: 0 = no such image, else the dtype (the factor's selector).
 // MXFP4 has none: its codes are signed values the converter decodes, so x is staged as it is.
+// Q4_K shares the affine image (factor 1); Q6_K has none: its codes go through the exact f16 form of
+// Q8_0 (gq_dot), which takes the bias with it.
 template <int DT>
-__device__ __host__ constexpr int gq4_image() { return gq_dt(DT) && DT != XH_Q8_0 && !gq_mx(DT) ? DT : 0; }
+__device__ __host__ constexpr int gq4_image() { return gq_dt(DT) && DT != XH_Q8_0 && !gq_mx(DT) && DT != XH_Q6_K ? DT : 0; }
 template <int GQ4>
 __device__ __host__ constexpr float gq4_factor() { return GQ4 == XH_Q4_0 ? -8.f : GQ4 == XH_Q5_0 ? -16.f : 1.f; }
 __device__ __forceinline__ const float* gq4_nxs(const float4* xs4, const int n) {
@@ -564,11 +566,42 @@ __device__ __forceinline__ float gq_dot(const u32x4 w, const float4* xv, const u
     return s;
 }
 
+// Q6_K: the sums of (q - 32) x over the chunk's two 16-element scale groups.  The fifth-bit idea of
+// the Q5 blocks widened to two bits, on Q8_0's magic-number form instead of the denormal one: per
+// word, the two high bits of its four low-nibble codes are (qa >> 2w) & 0x03030303 (the plane is laid
+// out for that at upload), one v_lshl_or_b32 sets them on the masked nibbles, and gq_pair turns the
+// bytes into packed f16 (1024 + q) - 1056 = q - 32, exact; the same for the high nibbles with qb.
+// 8 integer ops + 4 perm + 4 packed adds + 8 fma_mix per 8 elements: 3 VALU ops per element.
+__device__ __forceinline__ void gq_dot6(const u32x4 w, const float4* xv, const uint32_t qa, const uint32_t qb, float& s0,
+                                        float& s1) {
+    const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+    const h2_t c = __builtin_bit_cast(h2_t, 0xE420E420u);  // -(1024 + 32) twice
+    s0 = 0.f;
+    s1 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const uint32_t lo = (ww[i] & 0x0F0F0F0Fu) | (((qa >> (2 * i)) & 0x03030303u) << 4);
+        const uint32_t hi = ((ww[i] >> 4) & 0x0F0F0F0Fu) | (((qb >> (2 * i)) & 0x03030303u) << 4);
+        const uint32_t l01 = gq_pair(lo, 0x04010400u, c), l23 = gq_pair(lo, 0x04030402u, c);
+        const uint32_t h01 = gq_pair(hi, 0x04010400u, c), h23 = gq_pair(hi, 0x04030402u, c);
+        s0 = fma_mix_lo(l01, xv[i].x, s0);
+        s1 = fma_mix_lo(h01, xv[4 + i].x, s1);
+        s0 = fma_mix_hi(l01, xv[i].y, s0);
+        s1 = fma_mix_hi(h01, xv[4 + i].y, s1);
+        s0 = fma_mix_lo(l23, xv[i].z, s0);
+        s1 = fma_mix_lo(h23, xv[4 + i].z, s1);
+        s0 = fma_mix_hi(l23, xv[i].w, s0);
+        s1 = fma_mix_hi(h23, xv[4 + i].w, s1);
+    }
+}
+
 // acc[r] += d[r] * sum(q * x) for the ROWS rows of one chunk (Q4_0: nx = -8 sum(x) of the block).
 // Q5_0: d * (sum(q x) - 16 sum(x)), nx = -16 sum(x).  Affine (Q4_1 / Q5_1): the block's
 // sum((d q + m) x) as d * sum(q x) + m * sum(x), nx = sum(x): two products per block instead of a
 // fused multiply-add per element; each rounds relative to its own term, |d| sum|q x| and
 // |m| sum|x| (the tests' magnitude), not to their possibly cancelling sum.
+// Q4_K: the affine form with d = d*sc and m = -(dmin*mn) of the chunk's sub-block (gq_ld_sc).
+// Q6_K: one fma per 16-element group, each group's sum under its own d*sc.
 // MXFP4: d = 2^(e - 127), one exact-scale fma per block on the f32 block sum (e = 0: a subnormal
 // f32 operand, which v_fma_f32 takes as it is; the kernels run with f32 denormals on).
 template <int DT, int ROWS>
@@ -576,7 +609,11 @@ __device__ __forceinline__ void gq_rows(const u32x4 (&w)[ROWS], const typename G
                                         float* acc, const float nx) {
 #pragma unroll
     for (int r = 0; r < ROWS; r++) {
-        if constexpr (gq_has_m(DT))
+        if constexpr (DT == XH_Q6_K) {
+            float s0, s1;
+            gq_dot6(w[r], xv, d[r].qa, d[r].qb, s0, s1);
+            acc[r] = fmaf(d[r].d0, s0, fmaf(d[r].d1, s1, acc[r]));
+        } else if constexpr (gq_affine(DT))
             acc[r] = fmaf(d[r].d, gq_dot<DT>(w[r], xv, d[r].qh) * 0x1p24f, fmaf(d[r].m, nx, acc[r]));
         else if constexpr (DT == XH_Q5_0)
             acc[r] = fmaf(d[r].d, fmaf(gq_dot<DT>(w[r], xv, d[r].qh), 0x1p24f, nx), acc[r]);

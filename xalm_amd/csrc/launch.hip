@@ -41,6 +41,9 @@ using ShapeLong = GemvShape<512, ROWS, UNROLL, true, 4, false>;
 // MXFP4 on the staged shapes: 2 chunks in flight.  A chunk is 32 converted values against 32 x
 // floats per row; at 4 chunks x 2 rows the instantiation needs more than the 128 VGPRs of 4 waves
 // per SIMD (hipcc: 24 - 31 spilled), at 2 it takes 106 - 126 and spills none.
+// The K-quants (Q4_K / Q6_K) take it too: at 4 chunks hipcc spills 44 - 64 (Q4_K: the unpacked
+// {d*sc, -dmin*mn} per chunk and row) and 148 - 164 bytes per lane (Q6_K: two scales and two plane
+// words), at 2 chunks none (Q4_K 106 - 116 VGPRs, Q6_K 123 - 126).
 using ShapeStagedMx = GemvShape<512, ROWS, 2, true, 4, false>;
 using ShapePF2 = GemvShape<512, ROWS, UNROLL, true, 4, true, 2>;  // n <= 4096
 using ShapePF8 = GemvShape<512, ROWS, UNROLL, true, 4, true, 8>;  // n <= 16384 (W2 / Wo inputs)
@@ -173,9 +176,9 @@ bool launch_gemv_t(const GemvArgs& a, hipStream_t s, int max_waves) {
             if constexpr (Sel::HAS_PF8) return launch_gemv_s<DT, PRO, EPI, ShapePF8>(a, s, max_waves);
             break;
         case SH_SHORT:
-            if constexpr (Sel::HAS_SHORT) return launch_gemv_s<DT, PRO, EPI, std::conditional_t<gq_mx(DT), ShapeStagedMx, ShapeShort>>(a, s, max_waves);
+            if constexpr (Sel::HAS_SHORT) return launch_gemv_s<DT, PRO, EPI, std::conditional_t<gq_mx(DT) || gq_k(DT), ShapeStagedMx, ShapeShort>>(a, s, max_waves);
             break;
-        case SH_LONG: return launch_gemv_s<DT, PRO, EPI, std::conditional_t<gq_mx(DT), ShapeStagedMx, ShapeLong>>(a, s, max_waves);
+        case SH_LONG: return launch_gemv_s<DT, PRO, EPI, std::conditional_t<gq_mx(DT) || gq_k(DT), ShapeStagedMx, ShapeLong>>(a, s, max_waves);
     }
     return false;
 }

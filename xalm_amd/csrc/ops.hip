@@ -53,7 +53,7 @@ int xh_op_matmul(float* xout, const float* x, const void* w, int dtype, int n, i
     if (!matrix_dtype_ok(dtype)) return set_err(nullptr, XH_E_INVALID, "unsupported dtype %d", dtype);
     DevBuf bw, bx, bo;
     int rc;
-    if (gq_dt(dtype) && n % 32) return set_err(nullptr, XH_E_INVALID, "bad matmul args: n %% 32");
+    if (gq_dt(dtype) && n % gq_group(dtype)) return set_err(nullptr, XH_E_INVALID, "bad matmul args: n %% %d", gq_group(dtype));
     // gguf blocks: w in the file layout, repacked to the planar device rows
     std::vector<uint8_t> gq_tmp;
     if (gq_mx(dtype)) {
@@ -270,6 +270,7 @@ namespace {
 int op_weight_rows(const char* what, int dtype, const void* w, int rows, int K, std::vector<uint8_t>& tmp, const void** dev_rows,
                    int* dt, bool* wide) {
     *wide = false;
+    if (gq_k(dtype) && K % 256) return set_err(nullptr, XH_E_INVALID, "%s: K %d is not in whole 256-element super-blocks", what, K);
     if (gq_mx(dtype)) {
         uint8_t lo, hi;
         mx_e_range((const uint8_t*)w, (size_t)rows * (K / 32), &lo, &hi);

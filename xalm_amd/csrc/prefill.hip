@@ -175,7 +175,7 @@ bool pf_lay0(const PfGemmPlan& p) {
     }
     // gguf blocks: their exact f16 hi + lo images through gemm16.h (XH_OPT_PREFILL 1); the affine
     // blocks (fmaf(d, q, m): no exact f16 pair) always take the f32-input MFMA kernel
-    if (gq_has_m(dt)) return false;
+    if (gq_affine(dt) || gq_k(dt)) return false;  // the K-quants likewise (Q6_K: up to 24 significant bits)
     if (gq_dt(dt)) return p.mode == 1 && K % MM_KMULT == 0;
     if (!pf_f16w(dt)) return false;
     if (p.mode == 1) return K % MM_KMULT == 0;

@@ -47,7 +47,8 @@ int tensor_slot(xh_ctx* ctx, int kind, int layer, int dtype, Slot* out) {
     }
     if (is_norm ? !(dtype == XH_F32 || dtype == XH_BF16) : !matrix_dtype_ok(dtype))
         return set_err(ctx, XH_E_INVALID, "tensor kind %d: unsupported dtype %d", kind, dtype);
-    if (gq_dt(dtype) && cols % 32) return set_err(ctx, XH_E_INVALID, "tensor kind %d: %zu columns, not whole 32-element blocks", kind, cols);
+    if (gq_dt(dtype) && cols % gq_group(dtype))
+        return set_err(ctx, XH_E_INVALID, "tensor kind %d: %zu columns, not whole %d-element blocks", kind, cols, gq_group(dtype));
     // a matvec input: its x image must fit the CU's LDS (the embedding is one only when tied)
     if (!is_norm && (kind != XH_EMBED || c.tie_word_embeddings) && matrix_lds_bytes(dtype, (int)cols) > GEMV_LDS_MAX)
         return set_err(ctx, XH_E_INVALID, "tensor kind %d: the %zu-element input of dtype %d needs %zu bytes of LDS, over %zu",
@@ -256,6 +257,22 @@ uint16_t f8_e4m3_f16_bits(const uint8_t b) {
 // -> planar device rows ([codes][qh per block][d per block][m per block][zero pad], pitch
 // gq_pitch; common.h), on the host, split over threads
 void xalm::gq_repack(int dt, const uint8_t* src, size_t rows, size_t cols, uint8_t* dst) {
+    if (gq_k(dt)) {
+        const size_t nsb = cols / 256, bs = gq_block_bytes(dt), pitch = gq_pitch(dt, cols);
+        const size_t end = dt == XH_Q4_K ? pitch : kq6_d_off(cols) + 2 * nsb;
+        auto part = [&](size_t r0, size_t r1) {
+            for (size_t r = r0; r < r1; r++) {
+                for (size_t b = 0; b < nsb; b++) kq_repack_sb(dt, src + (r * nsb + b) * bs, dst + r * pitch, cols, b);
+                memset(dst + r * pitch + end, 0, pitch - end);
+            }
+        };
+        const size_t nt = std::min<size_t>(16, std::max<size_t>(1, rows / 256));
+        std::vector<std::thread> th;
+        for (size_t t = 1; t < nt; t++) th.emplace_back(part, rows * t / nt, rows * (t + 1) / nt);
+        part(0, rows / nt);
+        for (auto& x : th) x.join();
+        return;
+    }
     const size_t nb = cols / 32, bs = gq_block_bytes(dt);
     const size_t hm = gq_has_m(dt) ? 2 : 0, hq = gq_has_qh(dt) ? 4 : 0;  // header bytes behind d
     const size_t ds = gq_mx(dt) ? 1 : 2;                                 // d (MXFP4: the scale byte e)
@@ -321,6 +338,19 @@ __global__ void synth_gq_kernel(char* base, size_t pitch, size_t rows, size_t co
     }
 }
 
+// synthetic K-quant super-blocks (xs_superblock), one thread each, into the planar rows.  A row's
+// threads write disjoint bytes; the pad behind a Q6_K row's d plane is never read.
+__global__ void synth_kq_kernel(char* base, size_t pitch, size_t rows, size_t cols, int dtype, uint64_t seed, float mean,
+                                float std) {
+    const size_t nsb = cols / 256;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows * nsb; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / nsb, b = i - r * nsb;
+        uint8_t blk[210];
+        xs_superblock(blk, dtype, seed, r, cols, b, mean, std);
+        kq_repack_sb(dtype, blk, (uint8_t*)base + r * pitch, cols, b);
+    }
+}
+
 // the byte count of a tensor upload against the config (load_tensor's checks,
 // src/model.cpp:62-76), before the device layout is touched
 int check_bytes(xh_ctx* ctx, int kind, int dtype, size_t bytes) {
@@ -337,6 +367,8 @@ int check_bytes(xh_ctx* ctx, int kind, int dtype, size_t bytes) {
         default: return set_err(ctx, XH_E_INVALID, "unknown tensor kind %d", kind);
     }
     const size_t rb = file_row_bytes(dtype, cols);
+    if (gq_k(dtype) && cols % 256)
+        return set_err(ctx, XH_E_INVALID, "tensor kind %d: %zu columns, not whole 256-element super-blocks", kind, cols);
     if (rb == 0 || (gq_dt(dtype) && cols % 32) || bytes != rows * rb)
         return set_err(ctx, XH_E_INVALID, "tensor kind %d: %zu bytes, expected %zu ([%zu,%zu] of dtype %d)", kind,
                        bytes, rows * rb, rows, cols, dtype);
@@ -423,7 +455,10 @@ int xh_upload_synthetic(xh_ctx* ctx, int kind, int layer, int dtype, uint64_t se
     Slot s;
     int rc = tensor_slot(ctx, kind, layer, dtype, &s);
     if (rc) return rc;
-    if (gq_dt(dtype))
+    if (gq_k(dtype))
+        hipLaunchKernelGGL(synth_kq_kernel, dim3(1024), dim3(64), 0, ctx->stream, s.base, s.pitch, s.rows, s.cols, dtype,
+                           seed, mean, std);
+    else if (gq_dt(dtype))
         hipLaunchKernelGGL(synth_gq_kernel, dim3(4096), dim3(256), 0, ctx->stream, s.base, s.pitch, s.rows, s.cols, dtype,
                            seed, mean, std);
     else
@@ -438,9 +473,16 @@ int xh_upload_synthetic(xh_ctx* ctx, int kind, int layer, int dtype, uint64_t se
 int xh_quantize_blocks(int dtype, const float* values, size_t n_blocks, void* out) {
     if (!gq_dt(dtype) || !values || !out) return set_err(nullptr, XH_E_INVALID, "quantize_blocks: dtype %d is no block type, or a null pointer", dtype);
     const size_t bs = gq_block_bytes(dtype);
-    if (gq_mx(dtype))
-        for (size_t i = 0; i < 32 * n_blocks; i++)
+    if (gq_mx(dtype) || gq_k(dtype))
+        for (size_t i = 0; i < gq_group(dtype) * n_blocks; i++)
             if (!std::isfinite(values[i])) return set_err(nullptr, XH_E_INVALID, "quantize_blocks: value %zu is not finite", i);
+    if (gq_k(dtype)) {  // n_blocks super-blocks
+        for (size_t b = 0; b < n_blocks; b++) {
+            if (dtype == XH_Q4_K) xs_quant_q4_k(values + 256 * b, (uint8_t*)out + b * bs);
+            else xs_quant_q6_k(values + 256 * b, (uint8_t*)out + b * bs);
+        }
+        return 0;
+    }
     for (size_t b = 0; b < n_blocks; b++) xs_quant_block(dtype, values + 32 * b, (uint8_t*)out + b * bs);
     return 0;
 }
@@ -450,6 +492,13 @@ int xh_dequantize_blocks(int dtype, const void* blocks, size_t n_blocks, float* 
     static const float E2M1[8] = {0.f, 0.5f, 1.f, 1.5f, 2.f, 3.f, 4.f, 6.f};
     const size_t bs = gq_block_bytes(dtype);
     auto f16 = [](const uint8_t* p) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(p[0] | p[1] << 8)); };
+    if (gq_k(dtype)) {  // n_blocks super-blocks
+        for (size_t b = 0; b < n_blocks; b++) {
+            if (dtype == XH_Q4_K) xs_dequant_q4_k((const uint8_t*)blocks + b * bs, out + 256 * b);
+            else xs_dequant_q6_k((const uint8_t*)blocks + b * bs, out + 256 * b);
+        }
+        return 0;
+    }
     for (size_t b = 0; b < n_blocks; b++) {
         const uint8_t* in = (const uint8_t*)blocks + b * bs;
         float* o = out + 32 * b;

@@ -36,8 +36,8 @@ Model Model::from_xalm(const XalmFile& xalm, const int context, const Device dev
     auto load = [&](const std::string& name, int kind, int layer, std::vector<int> shape) {
         const TensorInfo& ti = xalm.tensors.at(name);
         // gguf blocks (convert.py:176-187): the header holds the byte shape, 32 elements per block
-        if (block_bytes(ti.type) && shape.size() == 2 && shape[1] % 32 == 0)
-            shape[1] = shape[1] / 32 * (int)block_bytes(ti.type);
+        if (block_bytes(ti.type) && shape.size() == 2 && shape[1] % (int)block_elems(ti.type) == 0)
+            shape[1] = shape[1] / (int)block_elems(ti.type) * (int)block_bytes(ti.type);
         if (ti.shape != shape) {
             std::string a, b;
             for (int v : ti.shape) a += std::to_string(v) + ",";

@@ -53,6 +53,7 @@ size_t type_size(int type);
 // bytes of one 32-element block of the converter's gguf block types (convert.py:176-187,
 // quants.py), 0 for any other type: the one table of their names and sizes (xalm_file.cpp)
 size_t block_bytes(int type);
+size_t block_elems(int type);  // elements per block of a block type (32; the K-quants 256), else 0
 
 // ---- model ------------------------------------------------------------------------------
 enum class Device { CPU, HIP };

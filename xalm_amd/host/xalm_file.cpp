@@ -12,12 +12,13 @@
 
 namespace xalm {
 
-// the block types: name, id, bytes per 32-element block (the converter's gguf blocks, quants.py;
-// MXFP4: OCP microscaling FP4, written by tools/xalm_requant.py)
-struct BlockType { const char* name; int type; size_t bytes; };
-const BlockType BLOCK_TYPES[] = {{"Q8_0", XH_Q8_0, 34}, {"Q4_0", XH_Q4_0, 18}, {"Q4_1", XH_Q4_1, 20},
-                                 {"Q5_0", XH_Q5_0, 22}, {"Q5_1", XH_Q5_1, 24},
-                                 {"MXFP4", XH_MXFP4, 17}};
+// the block types: name, id, bytes and elements per block (the converter's gguf blocks, quants.py;
+// MXFP4 and the K-quants' 256-element super-blocks: written by tools/xalm_requant.py)
+struct BlockType { const char* name; int type; size_t bytes; size_t elems; };
+const BlockType BLOCK_TYPES[] = {{"Q8_0", XH_Q8_0, 34, 32}, {"Q4_0", XH_Q4_0, 18, 32}, {"Q4_1", XH_Q4_1, 20, 32},
+                                 {"Q5_0", XH_Q5_0, 22, 32}, {"Q5_1", XH_Q5_1, 24, 32},
+                                 {"MXFP4", XH_MXFP4, 17, 32},
+                                 {"Q4_K", XH_Q4_K, 144, 256}, {"Q6_K", XH_Q6_K, 210, 256}};
 
 // Type::parse, src/types.h:468-499 (case-insensitive names)
 int parse_type(const std::string& s) {
@@ -39,6 +40,12 @@ int parse_type(const std::string& s) {
 size_t block_bytes(int type) {
     for (const BlockType& b : BLOCK_TYPES)
         if (type == b.type) return b.bytes;
+    return 0;
+}
+
+size_t block_elems(int type) {
+    for (const BlockType& b : BLOCK_TYPES)
+        if (type == b.type) return b.elems;
     return 0;
 }
 
