@@ -152,9 +152,11 @@ int xh_create(const xh_config* cfg, int device_ordinal, xh_ctx** out);
  *   decode:  every layer takes the two-launch route (attention, then Wo), as a layer with a
  *            block-type Wo does; the fused attention + Wo launch has no fp8 instantiation.
  *   prompts: the GEMMs as ever; the attention as under XH_OPT_PREFILL_ATTN 0 (the per-token
- *            split kernel); no ring passes: a prompt that reaches past the ring is batched
- *            below max_seq_len and takes the per-token loop from the cut (xh_prefill_route
- *            answers accordingly). */
+ *            split kernel) unless XH_OPT_PREFILL_ATTN_KV8 is 1, under which it follows
+ *            XH_OPT_PREFILL_ATTN and XH_OPT_PREFILL_ATTN_SPLIT as on an fp16 context (the MFMA
+ *            kernels' fp8 form); either way no ring passes: a prompt that reaches past the ring
+ *            is batched below max_seq_len and takes the per-token loop from the cut
+ *            (xh_prefill_route answers accordingly, the same under both values). */
 int xh_create_kv(const xh_config* cfg, int device_ordinal, int kv_dtype, xh_ctx** out);
 /* The context's KV element type: XH_F16 or XH_F8_E4M3. */
 int xh_kv_dtype(const xh_ctx* ctx);
@@ -726,13 +728,22 @@ int xh_set_graphs(xh_ctx* ctx, int enable);
  * tokens (alone or left over by the passes) keep the per-token loop there.  0 = any prompt that reaches
  * past the ring takes the per-token loop as a whole.  Same math up to f32 rounding; the sink
  * K rows come out bit-identical on both routes. */
+/* XH_OPT_PREFILL_ATTN_KV8 (default 0): on an fp8 (e4m3) KV ring (xh_create_kv) 1 = the batched
+ * path's attention follows XH_OPT_PREFILL_ATTN (1 / 2 / 0) and XH_OPT_PREFILL_ATTN_SPLIT as on an
+ * fp16 context, on the MFMA kernels' fp8 form: K/V tiles loaded as codes, decoded by the gfx950
+ * converter to their exact f16 image and multiplied as the fp16 kernels multiply (bit-identical to
+ * the fp16 attention over that image); 0 = the attention is forced to the per-token split kernel
+ * (XH_OPT_PREFILL_ATTN 0).  The pass plan (xh_prefill_route) and the K/V the passes write do not
+ * depend on it.  On an fp16 context the value is stored and read back and has no effect.  Values
+ * other than 0 / 1 are XH_E_INVALID. */
 enum xh_option {
     XH_OPT_FUSE_ATTN_WO = 1,
     XH_OPT_PREFILL = 2,
     XH_OPT_PREFILL_GLU_SPLIT = 3,
     XH_OPT_PREFILL_ATTN = 5,
     XH_OPT_PREFILL_ATTN_SPLIT = 6,
-    XH_OPT_PREFILL_RING = 7
+    XH_OPT_PREFILL_RING = 7,
+    XH_OPT_PREFILL_ATTN_KV8 = 8
 };
 int xh_set_option(xh_ctx* ctx, int option, int value);
 int xh_get_option(const xh_ctx* ctx, int option, int* value);
@@ -770,6 +781,13 @@ int xh_op_prompt_gemm(float* y, const uint16_t* w, const uint16_t* xh, const uin
  * 4 or 8 q heads per KV head, head_dim 16 with 2; anything else is XH_E_INVALID before any launch. */
 int xh_op_prompt_attn(float* out, const float* q, const uint16_t* k, const uint16_t* v, int n, int pos0, int head_dim,
                       int n_heads, int n_kv_heads, int mode, int nsplit);
+/* The same over fp8 K/V (an fp8 context under XH_OPT_PREFILL_ATTN_KV8 1), through the same launch
+ * code: k and v [pos0 + n][n_kv_heads * head_dim] e4m3 codes, every other argument and the head
+ * shapes as xh_op_prompt_attn.  By definition the result is xh_op_prompt_attn's over the codes' f16
+ * image, bit for bit.  A NaN code (0x7F, 0xFF) in k or v is XH_E_INVALID before any launch, as in
+ * xh_kv_write8. */
+int xh_op_prompt_attn8(float* out, const float* q, const uint8_t* k, const uint8_t* v, int n, int pos0,
+                       int head_dim, int n_heads, int n_kv_heads, int mode, int nsplit);
 /* The attention of a ring pass (XH_OPT_PREFILL_RING; src/infer.cpp:608-613) at head_dim 128 on host
  * buffers: m tokens at positions p0.. >= max_seq_len, 3 <= m <= W = max_seq_len - 2.  k_ring / v_ring
  * [max_seq_len][kv_dim] fp16 bits: the ring as the pass finds it, and on return as the pass leaves

@@ -52,6 +52,7 @@ OPT_PREFILL_GLU_SPLIT = 3
 OPT_PREFILL_ATTN = 5
 OPT_PREFILL_ATTN_SPLIT = 6
 OPT_PREFILL_RING = 7
+OPT_PREFILL_ATTN_KV8 = 8
 
 # enum xh_tensor_kind
 EMBED, ATTN_NORM, FFN_NORM, WQ, WK, WV, WO, W1, W2, W3, FINAL_NORM, WCLS = range(12)
@@ -272,6 +273,7 @@ _SIGNATURES = {
     "xh_op_mha": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I]),
     "xh_op_prompt_gemm": (_I, [_P, _P, _P, _P, _I, _I, _I, _I]),
     "xh_op_prompt_attn": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I]),
+    "xh_op_prompt_attn8": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I]),
     "xh_op_prompt_attn_ring": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I]),
     "xh_op_prompt_matmul": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, ctypes.POINTER(_I)]),
     "xh_op_prompt_weight_image": (_I, [_I, _P, _I, _I, _P, _P, _I]),
@@ -673,6 +675,21 @@ def op_prompt_attn(q: np.ndarray, k: np.ndarray, v: np.ndarray, pos0: int, head_
     assert k.shape == (pos0 + n, n_kv_heads * head_dim) and v.shape == k.shape
     out = np.empty_like(q)
     check(lib().xh_op_prompt_attn(ptr(out), ptr(q), ptr(k), ptr(v), n, pos0, head_dim, n_heads, n_kv_heads, mode, nsplit))
+    return out
+
+
+def op_prompt_attn8(q: np.ndarray, k: np.ndarray, v: np.ndarray, pos0: int, head_dim: int, n_heads: int, n_kv_heads: int,
+                    mode: int = 1, nsplit: int = 0) -> np.ndarray:
+    """op_prompt_attn over fp8 K/V (xh_op_prompt_attn8): k, v e4m3 codes (uint8)
+    [pos0 + n][n_kv_heads * head_dim]; everything else as op_prompt_attn."""
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    k = np.ascontiguousarray(k, dtype=np.uint8)
+    v = np.ascontiguousarray(v, dtype=np.uint8)
+    n = q.shape[0]
+    assert q.shape == (n, n_heads * head_dim)
+    assert k.shape == (pos0 + n, n_kv_heads * head_dim) and v.shape == k.shape
+    out = np.empty_like(q)
+    check(lib().xh_op_prompt_attn8(ptr(out), ptr(q), ptr(k), ptr(v), n, pos0, head_dim, n_heads, n_kv_heads, mode, nsplit))
     return out
 
 

@@ -256,6 +256,7 @@ struct xh_ctx {
     int pf_attn_mode = 1;                        // XH_OPT_PREFILL_ATTN: 1 shared-tile MFMA (v1 for head_dim != 128),
                                                  // 2 per-wave MFMA tiles, 0 per-token split kernel
     bool pf_ring = true;                         // XH_OPT_PREFILL_RING: ring passes at positions >= max_seq_len
+    bool pf_attn_kv8 = false;                    // XH_OPT_PREFILL_ATTN_KV8: an fp8 KV ring follows pf_attn_mode too
     xalm::PfBufs pf;                             // the pass buffers
     // xh_perplexity: targets and probabilities of the whole run (allocated on first use)
     int* ppl_tgt = nullptr;                      // [ppl_cap] targets (per-token path)
@@ -418,10 +419,11 @@ bool pf_attn_shape_ok(int hd, int qpk);
 // n_cu CUs within part_floats of partials
 int pf_fa_split_max(int pos0);
 int pf_fa_pick_nsplit(const PfAttnDims& d, int n_cu, int n, int pos0, size_t part_floats);
-// causal rows [pos0, pos0 + n) over kc / vc; shared: the shared-tile kernel (head_dim 128) over
-// nsplit >= 1 splits, part (pf_fa_part_floats) when nsplit > 1; else the per-wave kernel
-int pf_fa_launch(const PfAttnDims& d, bool shared, const float* q, const uint16_t* kc, const uint16_t* vc, float* out,
-                 int n, int pos0, int nsplit, float* part, hipStream_t s);
+// causal rows [pos0, pos0 + n) over kc / vc of element type kv_dt (XH_F16; XH_F8_E4M3: one code per
+// element); shared: the shared-tile kernel (head_dim 128) over nsplit >= 1 splits, part
+// (pf_fa_part_floats) when nsplit > 1; else the per-wave kernel
+int pf_fa_launch(const PfAttnDims& d, int kv_dt, bool shared, const float* q, const uint16_t* kc, const uint16_t* vc,
+                 float* out, int n, int pos0, int nsplit, float* part, hipStream_t s);
 // a ring pass's walk, merge with the sinks (sinkv [m][2][kv_dim]) and commit; part always
 int pf_ring_launch(const PfAttnDims& d, const float* q, uint16_t* kc, uint16_t* vc, const uint16_t* ks, const uint16_t* vs,
                    const uint16_t* sinkv, float* out, int m, int p0, int max_seq_len, int nsplit, float* part,

@@ -197,10 +197,10 @@ int op_n_cu(int* n_cu) {
 // a forced split count against the bound the passes obey over pos0 slots of history
 // (and the grid's z extent)
 bool op_split_ok(int nsplit, int pos0) { return nsplit <= std::min(pf_fa_split_max(pos0), 65535); }
-}  // namespace
 
-int xh_op_prompt_attn(float* out, const float* q, const uint16_t* k, const uint16_t* v, int n, int pos0, int head_dim,
-                      int n_heads, int n_kv_heads, int mode, int nsplit) {
+// xh_op_prompt_attn / xh_op_prompt_attn8: k / v of element type kv_dt (fp16 bits, or one e4m3 code each)
+int op_prompt_attn_any(float* out, const float* q, const void* k, const void* v, int n, int pos0, int head_dim, int n_heads,
+                       int n_kv_heads, int mode, int nsplit, int kv_dt) {
     if (!out || !q || !k || !v || n <= 0 || pos0 < 0 || pos0 > (1 << 28) || n > (1 << 20) || nsplit < 0)
         return set_err(nullptr, XH_E_INVALID, "bad prompt_attn args");
     if (n_kv_heads <= 0 || n_heads <= 0 || n_heads > 1024 || n_heads % n_kv_heads ||
@@ -220,13 +220,28 @@ int xh_op_prompt_attn(float* out, const float* q, const uint16_t* k, const uint1
     if (nsplit == 0) nsplit = shared ? pf_fa_pick_nsplit(d, n_cu, n, pos0, SIZE_MAX) : 1;
     DevBuf bq, bk, bv, bo, bp;
     const size_t qe = (size_t)n * n_heads * head_dim, kve = (size_t)(pos0 + n) * n_kv_heads * head_dim;
-    if ((rc = op_alloc(bq, qe * 4, q)) || (rc = op_alloc(bk, kve * 2, k)) || (rc = op_alloc(bv, kve * 2, v)) ||
+    const size_t esz = kv_dt == XH_F8_E4M3 ? 1 : 2;
+    if (kv_dt == XH_F8_E4M3)
+        for (size_t i = 0; i < kve; i++)
+            if (f8_special(((const uint8_t*)k)[i], false) || f8_special(((const uint8_t*)v)[i], false))
+                return set_err(nullptr, XH_E_INVALID, "prompt_attn8: element %zu of k or v is the NaN code", i);
+    if ((rc = op_alloc(bq, qe * 4, q)) || (rc = op_alloc(bk, kve * esz, k)) || (rc = op_alloc(bv, kve * esz, v)) ||
         (rc = op_alloc(bo, qe * 4, nullptr)) || (rc = op_alloc(bp, nsplit > 1 ? pf_fa_part_floats(d, nsplit, n) * 4 : 0, nullptr)))
         return rc;
-    if (pf_fa_launch(d, shared, (const float*)bq.p, (const uint16_t*)bk.p, (const uint16_t*)bv.p, (float*)bo.p, n, pos0, nsplit,
+    if (pf_fa_launch(d, kv_dt, shared, (const float*)bq.p, (const uint16_t*)bk.p, (const uint16_t*)bv.p, (float*)bo.p, n, pos0, nsplit,
                      (float*)bp.p, nullptr) < 0)
         return set_err(nullptr, XH_E_INVALID, "prompt_attn: head shape not instantiated");
     return op_finish(out, bo, qe * 4);
+}
+}  // namespace
+
+int xh_op_prompt_attn(float* out, const float* q, const uint16_t* k, const uint16_t* v, int n, int pos0, int head_dim,
+                      int n_heads, int n_kv_heads, int mode, int nsplit) {
+    return op_prompt_attn_any(out, q, k, v, n, pos0, head_dim, n_heads, n_kv_heads, mode, nsplit, XH_F16);
+}
+int xh_op_prompt_attn8(float* out, const float* q, const uint8_t* k, const uint8_t* v, int n, int pos0, int head_dim,
+                       int n_heads, int n_kv_heads, int mode, int nsplit) {
+    return op_prompt_attn_any(out, q, k, v, n, pos0, head_dim, n_heads, n_kv_heads, mode, nsplit, XH_F8_E4M3);
 }
 
 int xh_op_prompt_attn_ring(float* out, uint16_t* k_ring, uint16_t* v_ring, const float* q, const uint16_t* ks,

@@ -706,9 +706,37 @@ __device__ __forceinline__ void fa_softmax_tile(const f32x16& st, const int b, c
 //         A = V^T fragments from a transposed LDS copy of the V tile; the k index of MFMA step
 //         s, lane half h, element e is slot 16 s + 8 (e >> 2) + 4 h + (e & 3) on both sides.
 // grid (n_kv_heads, ceil(n / (32/QPK))), 64 threads; no ring wrap inside a pass (pf_supported)
-template <int HD, int QPK>
+//
+// KV = XH_F8_E4M3 (an fp8 KV ring under XH_OPT_PREFILL_ATTN_KV8; both kernels): kc / vc hold one
+// e4m3 code per element, [slot][kv_dim] bytes.  Every finite e4m3 value is an f16 (|v| <= 448, a
+// multiple of 2^-9, 4 significant bits), so the attention over the codes is by definition the
+// fp16 attention over their f16 image: 8 codes are loaded as 8 bytes, decoded by v_cvt_pk_f32_fp8
+// (as attn_block) and packed to the 8 f16 the fp16 kernel would have loaded (the pack's
+// round-toward-zero never rounds).  Everything after the operands is the fp16 kernel's code, so
+// the outputs are bit-identical to it on the image.  The ring holds no NaN code (kv8_pack clamps).
+__device__ __forceinline__ u32x4 fa_image8(const uint2 c) {
+    const f2_t a = __builtin_amdgcn_cvt_pk_f32_fp8(c.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8(c.x, true);
+    const f2_t d = __builtin_amdgcn_cvt_pk_f32_fp8(c.y, false), e = __builtin_amdgcn_cvt_pk_f32_fp8(c.y, true);
+    return u32x4{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(a.x, a.y)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(b.x, b.y)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(d.x, d.y)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(e.x, e.y))};
+}
+// element `off` of a K / V ring of element type KV, and the 8 elements there as f16 bits
+template <int KV>
+__device__ __forceinline__ const uint16_t* fa_at(const uint16_t* p, const size_t off) {
+    if constexpr (KV == XH_F16) return p + off;
+    else return (const uint16_t*)((const uint8_t*)p + off);
+}
+template <int KV>
+__device__ __forceinline__ u32x4 fa_load8(const uint16_t* p) {
+    if constexpr (KV == XH_F16) return *(const u32x4*)p;
+    else return fa_image8(*(const uint2*)p);
+}
+template <int HD, int QPK, int KV = XH_F16>
 __global__ __launch_bounds__(64) void prefill_fa_kernel(const float* q, const uint16_t* kc, const uint16_t* vc,
                                                          float* out, int n, int pos0, int q_stride, int kv_dim) {
+    static_assert(KV == XH_F16 || KV == XH_F8_E4M3, "prefill_fa_kernel: KV element type");
     constexpr int TPW = 32 / QPK;        // tokens per wave
     constexpr int KS = HD / 16;          // k steps of q . k
     constexpr int NDT = (HD + 31) / 32;  // 32-row d tiles of O^T
@@ -761,8 +789,8 @@ __global__ __launch_bounds__(64) void prefill_fa_kernel(const float* q, const ui
 #pragma unroll
     for (int dt = 0; dt < NDT; dt++) o[dt] = f32x16{};
     float m = -INFINITY, lsum = 0.f;
-    const uint16_t* kg = kc + (size_t)g * HD;
-    const uint16_t* vg = vc + (size_t)g * HD;
+    const uint16_t* kg = fa_at<KV>(kc, (size_t)g * HD);
+    const uint16_t* vg = fa_at<KV>(vc, (size_t)g * HD);
     constexpr int VCH = 16 * HD / 8;  // (slot pair, 8 d) chunks of a V tile
     constexpr int VIT = (VCH + 63) / 64;
     for (int b = 0; b <= last; b += 32) {
@@ -774,17 +802,17 @@ __global__ __launch_bounds__(64) void prefill_fa_kernel(const float* q, const ui
             const int s0 = b + 2 * sp;
             va[it] = vb[it] = u32x4{0u, 0u, 0u, 0u};
             if (c < VCH) {
-                if (s0 <= last) va[it] = *(const u32x4*)(vg + (size_t)s0 * kv_dim + 8 * d8);
-                if (s0 + 1 <= last) vb[it] = *(const u32x4*)(vg + (size_t)(s0 + 1) * kv_dim + 8 * d8);
+                if (s0 <= last) va[it] = fa_load8<KV>(fa_at<KV>(vg, (size_t)s0 * kv_dim + 8 * d8));
+                if (s0 + 1 <= last) vb[it] = fa_load8<KV>(fa_at<KV>(vg, (size_t)(s0 + 1) * kv_dim + 8 * d8));
             }
         }
         // S^T = K Q^T (K rows clamped to the wave's range; masked below)
         f32x16 st = f32x16{};
         {
-            const uint16_t* kr = kg + (size_t)min(b + j32, last) * kv_dim + 8 * h;
+            const uint16_t* kr = fa_at<KV>(kg, (size_t)min(b + j32, last) * kv_dim + 8 * h);
 #pragma unroll
             for (int ks = 0; ks < KS; ks++) {
-                const f16x8 kf = __builtin_bit_cast(f16x8, *(const u32x4*)(kr + 16 * ks));
+                const f16x8 kf = __builtin_bit_cast(f16x8, fa_load8<KV>(fa_at<KV>(kr, 16 * ks)));
                 st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qh[ks], st, 0, 0, 0);
                 st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, ql[ks], st, 0, 0, 0);
             }
@@ -894,10 +922,24 @@ struct FaRing {
     int W;               // max_seq_len - 2
     int hoff;            // kv_pos(first position of the pass) - 2
 };
-template <int QPK, int NW, bool RING>
+// KV = XH_F8_E4M3 (RING = false only; the element type as at prefill_fa_kernel): the LDS image, its
+// reads and all arithmetic are the fp16 kernel's; only the loader differs.  The lane that issues
+// the DMA of chunk dch[k] of row drow[k] loads the same 8 elements as 8 bytes of codes into
+// registers instead (code8), and writes their f16 image (fa_image8) by ds_write_b128 to the
+// address the DMA would have written (image8: stage base + 1024 i + 16 lane).  Pipeline: a wave's
+// IPW instructions of a stage go in FA_TPS parts of HP = IPW / FA_TPS, one part (2 HP VGPRs of
+// codes) in registers at a time.  In step ks, after the barrier that publishes stage ks, the
+// other LDS stage is free (last read in step ks - 1, which every wave has left): ahead of tile
+// `sub` of the step the wave decodes part `sub` of stage ks + 1 into it — loaded one tile's MFMAs
+// ago — and issues the loads of the next part (of stage ks + 1, or part 0 of stage ks + 2), to land
+// under this tile's MFMAs.  A wave past its own rows still runs its loader parts.  The barrier's
+// lgkmcnt(0) now also retires this wave's ds_writes of the stage it publishes; the loads' waits are
+// the compiler's own.  (A whole stage ahead in registers, 16 VGPRs, spills: 240 are taken.)
+template <int QPK, int NW, bool RING, int KV = XH_F16>
 __device__ __forceinline__ void fa2_body(const float* q, const uint16_t* kc, const uint16_t* vc, float* out, const int n,
                                          const int pos0, const int q_stride, const int kv_dim, float* part_o,
                                          float2* part_ml, const FaRing rg) {
+    static_assert(KV == XH_F16 || (KV == XH_F8_E4M3 && !RING), "prefill_fa2_kernel: KV element type");
     constexpr int HD = 128;
     constexpr int TPW = 32 / QPK;        // tokens per wave
     constexpr int KS = HD / 16;          // k steps of q . k
@@ -971,6 +1013,19 @@ __device__ __forceinline__ void fa2_body(const float* q, const uint16_t* kc, con
                                              (__attribute__((address_space(3))) void*)(base + i * 1024), 16, 0, 0);
         }
     };
+    // the fp8 loader: instruction k's codes of stage st, and codes as f16 into a stage's image
+    constexpr int HP = IPW / FA_TPS;  // instructions per loader part
+    static_assert(KV == XH_F16 || IPW % FA_TPS == 0, "prefill_fa2_kernel: fp8 loader parts");
+    [[maybe_unused]] uint2 cr[HP];
+    [[maybe_unused]] auto code8 = [&](const int st, const int k) {
+        const int i = wv * IPW + k;
+        const uint8_t* src = (const uint8_t*)(((i >> 3) & 1) ? vc : kc) +
+                             (size_t)min(32 * FA_TPS * (st0 + st) + drow[k], last_wg) * kv_dim + (size_t)g * HD + 8 * dch[k];
+        return *(const uint2*)src;
+    };
+    [[maybe_unused]] auto image8 = [&](const int stage, const int k, const uint2 c) {
+        *(u32x4*)(fa_smem + stage * FA_STAGE_BYTES + (wv * IPW + k) * 1024 + 16 * lane) = fa_image8(c);
+    };
     // q row, split: this lane's k = 16 ks + 8 h + e (loads before the ring's first DMA)
     f16x8 qh[KS], ql[KS];
     float inv_s;
@@ -1003,10 +1058,24 @@ __device__ __forceinline__ void fa2_body(const float* q, const uint16_t* kc, con
                 ql[ks][e] = (_Float16)(u - (float)qh[ks][e]);
             }
     }
-    mm_wait_vm<0>();
+    if constexpr (KV == XH_F16) {
+        mm_wait_vm<0>();
 #pragma unroll
-    for (int d = 0; d < FA_NS - 1; d++)
-        if (d < nst) issue(d, d);
+        for (int d = 0; d < FA_NS - 1; d++)
+            if (d < nst) issue(d, d);
+    } else {
+        if (nst > 0) {  // stage 0 whole, through registers that are free before the walk
+            uint2 c0[IPW];
+#pragma unroll
+            for (int k = 0; k < IPW; k++) c0[k] = code8(0, k);
+#pragma unroll
+            for (int k = 0; k < IPW; k++) image8(0, k, c0[k]);
+        }
+        if (nst > 1) {
+#pragma unroll
+            for (int k = 0; k < HP; k++) cr[k] = code8(1, k);
+        }
+    }
 
     f32x16 o[NDT];
 #pragma unroll
@@ -1015,14 +1084,29 @@ __device__ __forceinline__ void fa2_body(const float* q, const uint16_t* kc, con
     // tr-read addresses of this lane inside a V image (block rows r0 + q, d columns of dt)
     const int grp = lane >> 4, qq = (lane >> 2) & 3, pp = lane & 3;
     for (int ks = 0; ks < nst; ks++) {
-        mm_wait_ahead<IPW, FA_NS>(min(FA_NS - 2, nst - 1 - ks));  // this wave's DMA of stage ks landed
+        if constexpr (KV == XH_F16)
+            mm_wait_ahead<IPW, FA_NS>(min(FA_NS - 2, nst - 1 - ks));  // this wave's DMA of stage ks landed
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // own ds_reads of the refilled stage retired
         __builtin_amdgcn_s_barrier();                              // ... every wave's; stage ks - 1 read
         asm volatile("" ::: "memory");
-        if (ks + FA_NS - 1 < nst) issue((ks + FA_NS - 1) % FA_NS, ks + FA_NS - 1);
+        if constexpr (KV == XH_F16) {
+            if (ks + FA_NS - 1 < nst) issue((ks + FA_NS - 1) % FA_NS, ks + FA_NS - 1);
+        }
 #pragma unroll
         for (int sub = 0; sub < FA_TPS; sub++) {
         const int b = 32 * ((st0 + ks) * FA_TPS + sub);
+        if constexpr (KV != XH_F16) {
+            if (ks + 1 < nst) {
+#pragma unroll
+                for (int k = 0; k < HP; k++) image8((ks + 1) % FA_NS, sub * HP + k, cr[k]);
+            }
+            const int nxt = sub + 1 < FA_TPS ? ks + 1 : ks + 2, np = (sub + 1) % FA_TPS;
+            if (nxt < nst) {
+#pragma unroll
+                for (int k = 0; k < HP; k++) cr[k] = code8(nxt, np * HP + k);
+            }
+            if (b > last) continue;  // wave-uniform: past this wave's rows (its loader parts still run)
+        }
         if (b > last) break;  // wave-uniform: past this wave's rows (it still issues its DMA share)
         if constexpr (RING) {
             if (b + 31 <= t0) continue;  // wave-uniform: below the first visible row (t0 + 1) of every row
@@ -1078,11 +1162,11 @@ __device__ __forceinline__ void fa2_body(const float* q, const uint16_t* kc, con
                 float4{o[dt][r] * inv_l, o[dt][r + 1] * inv_l, o[dt][r + 2] * inv_l, o[dt][r + 3] * inv_l};
         }
 }
-template <int QPK, int NW>
+template <int QPK, int NW, int KV = XH_F16>
 __global__ __launch_bounds__(64 * NW, 2) void prefill_fa2_kernel(const float* q, const uint16_t* kc, const uint16_t* vc,
                                                                float* out, int n, int pos0, int q_stride, int kv_dim,
                                                                float* part_o, float2* part_ml) {
-    fa2_body<QPK, NW, false>(q, kc, vc, out, n, pos0, q_stride, kv_dim, part_o, part_ml, FaRing{});
+    fa2_body<QPK, NW, false, KV>(q, kc, vc, out, n, pos0, q_stride, kv_dim, part_o, part_ml, FaRing{});
 }
 // the ring pass: n <= W query rows over the ring (kc / vc, untouched) and the staging rows
 template <int QPK, int NW>

@@ -409,7 +409,8 @@ constexpr bool pf_attn_shape(int hd, int qpk) {
 // One causal prompt attention on device pointers, the launch body of the passes and of
 // xh_op_prompt_attn: the shared-tile kernel (shared: head_dim 128 only) over nsplit history splits
 // with the merge behind it when nsplit > 1 (partials in `part`), else the per-wave kernel.
-template <int HD, int QPK>
+// KV: the element type behind kc / vc (XH_F8_E4M3: one code per element).
+template <int HD, int QPK, int KV>
 void pf_fa_t(const PfAttnDims& d, bool shared, const float* q, const uint16_t* kc, const uint16_t* vc, float* out, int n,
              int pos0, int nsplit, float* part, hipStream_t s) {
     constexpr int TPW = 32 / QPK;
@@ -417,7 +418,7 @@ void pf_fa_t(const PfAttnDims& d, bool shared, const float* q, const uint16_t* k
     if constexpr (HD == 128) {
         if (shared) {
             constexpr int NW = PF_FA_WAVES;
-            auto k = prefill_fa2_kernel<QPK, NW>;
+            auto k = prefill_fa2_kernel<QPK, NW, KV>;
             ensure_lds((const void*)k);
             const int nqt = fa2_query_tiles(n, QPK);
             float* po = nsplit > 1 ? part : nullptr;
@@ -430,16 +431,17 @@ void pf_fa_t(const PfAttnDims& d, bool shared, const float* q, const uint16_t* k
             return;
         }
     }
-    hipLaunchKernelGGL((prefill_fa_kernel<HD, QPK>), dim3(d.n_kv_heads, (n + TPW - 1) / TPW), dim3(64), 0, s, q, kc, vc, out,
+    hipLaunchKernelGGL((prefill_fa_kernel<HD, QPK, KV>), dim3(d.n_kv_heads, (n + TPW - 1) / TPW), dim3(64), 0, s, q, kc, vc, out,
                        n, pos0, q_dim, kv_dim);
 }
 template <int HD>
-int pf_fa_hd(const PfAttnDims& d, bool shared, const float* q, const uint16_t* kc, const uint16_t* vc, float* out, int n,
+int pf_fa_hd(const PfAttnDims& d, int kv_dt, bool shared, const float* q, const uint16_t* kc, const uint16_t* vc, float* out, int n,
              int pos0, int nsplit, float* part, hipStream_t s) {
     return for_qpk(d.n_heads / d.n_kv_heads, [&](auto Q) {
         constexpr int QPK = decltype(Q)::value;
         if constexpr (pf_attn_shape(HD, QPK)) {
-            pf_fa_t<HD, QPK>(d, shared, q, kc, vc, out, n, pos0, nsplit, part, s);
+            if (kv_dt == XH_F8_E4M3) pf_fa_t<HD, QPK, XH_F8_E4M3>(d, shared, q, kc, vc, out, n, pos0, nsplit, part, s);
+            else pf_fa_t<HD, QPK, XH_F16>(d, shared, q, kc, vc, out, n, pos0, nsplit, part, s);
             return 0;
         }
         return -1;
@@ -643,12 +645,12 @@ int xalm::pf_fa_pick_nsplit(const PfAttnDims& d, int n_cu, int n, int pos0, size
     ns = (int)std::min<size_t>((size_t)ns, part_floats / pf_fa_part_floats(d, 1, n));
     return std::max(ns, 1);
 }
-int xalm::pf_fa_launch(const PfAttnDims& d, bool shared, const float* q, const uint16_t* kc, const uint16_t* vc, float* out,
-                       int n, int pos0, int nsplit, float* part, hipStream_t s) {
-    if (d.n_kv_heads <= 0 || d.n_heads % d.n_kv_heads) return -1;
-    return d.head_dim == 128  ? pf_fa_hd<128>(d, shared, q, kc, vc, out, n, pos0, nsplit, part, s)
-           : d.head_dim == 64 ? pf_fa_hd<64>(d, shared, q, kc, vc, out, n, pos0, nsplit, part, s)
-           : d.head_dim == 16 ? pf_fa_hd<16>(d, shared, q, kc, vc, out, n, pos0, nsplit, part, s)
+int xalm::pf_fa_launch(const PfAttnDims& d, int kv_dt, bool shared, const float* q, const uint16_t* kc, const uint16_t* vc,
+                       float* out, int n, int pos0, int nsplit, float* part, hipStream_t s) {
+    if (d.n_kv_heads <= 0 || d.n_heads % d.n_kv_heads || (kv_dt != XH_F16 && kv_dt != XH_F8_E4M3)) return -1;
+    return d.head_dim == 128  ? pf_fa_hd<128>(d, kv_dt, shared, q, kc, vc, out, n, pos0, nsplit, part, s)
+           : d.head_dim == 64 ? pf_fa_hd<64>(d, kv_dt, shared, q, kc, vc, out, n, pos0, nsplit, part, s)
+           : d.head_dim == 16 ? pf_fa_hd<16>(d, kv_dt, shared, q, kc, vc, out, n, pos0, nsplit, part, s)
                               : -1;
 }
 int xalm::pf_ring_launch(const PfAttnDims& d, const float* q, uint16_t* kc, uint16_t* vc, const uint16_t* ks,
@@ -664,8 +666,9 @@ namespace {
 
 PfAttnDims pf_dims(const xh_ctx* ctx) { return {ctx->c.head_dim, ctx->c.n_heads, ctx->c.n_kv_heads}; }
 // the prompt attention in force: XH_OPT_PREFILL_ATTN, but 0 (prefill_attn_kernel, the decode
-// blocks) on an fp8 KV ring, which the MFMA kernels have no tiles for; the stored option is untouched
-int pf_attn_mode_of(const xh_ctx* ctx) { return ctx->kv8() ? 0 : ctx->pf_attn_mode; }
+// blocks) on an fp8 KV ring unless XH_OPT_PREFILL_ATTN_KV8 asks for the MFMA kernels' fp8 form
+// (prefill.h, KV = XH_F8_E4M3); the stored options are untouched
+int pf_attn_mode_of(const xh_ctx* ctx) { return ctx->kv8() && !ctx->pf_attn_kv8 ? 0 : ctx->pf_attn_mode; }
 // the splits of a pass of n tokens over pos0 slots of history, within the partials buffer
 int pf_fa_nsplit(const xh_ctx* ctx, int n, int pos0) {
     if (!ctx->pf_fa_split) return 1;
@@ -676,8 +679,8 @@ int pf_attn_any(xh_ctx* ctx, const AttnArgs& a, int n, int pos0) {
     const int hd = ctx->c.head_dim;
     if (pf_attn_mode_of(ctx) != 0) {
         const bool shared = ctx->pf_attn_mode == 1 && hd == 128;
-        return pf_fa_launch(pf_dims(ctx), shared, a.q, a.kc, a.vc, a.out, n, pos0, shared ? pf_fa_nsplit(ctx, n, pos0) : 1,
-                            ctx->pf.part, ctx->stream);
+        return pf_fa_launch(pf_dims(ctx), ctx->kv_dt, shared, a.q, a.kc, a.vc, a.out, n, pos0,
+                            shared ? pf_fa_nsplit(ctx, n, pos0) : 1, ctx->pf.part, ctx->stream);
     }
     auto go = [&](auto H) {
         constexpr int HD = decltype(H)::value;

@@ -49,6 +49,15 @@ using namespace xalm;
 using clk = std::chrono::steady_clock;
 
 static int g_kv_dtype = XH_F16;  // -K: the KV rings' element type
+static int g_attn_kv8 = 0;       // -a: XH_OPT_PREFILL_ATTN_KV8
+
+// the model of a run: -K's rings, -a's prompt attention on them
+static Model load_model(const XalmFile& file, int context, Device dev) {
+    Model model = Model::from_xalm(file, context, dev, 0, g_kv_dtype);
+    if (g_attn_kv8 && xh_set_option(model.ctx(), XH_OPT_PREFILL_ATTN_KV8, g_attn_kv8) != 0)
+        throw std::runtime_error(std::string("-a: ") + xh_last_error(model.ctx()));
+    return model;
+}
 
 static void error_usage() {
     fprintf(stderr, "Usage:   xalm <checkpoint> [options]\n");
@@ -61,6 +70,7 @@ static void error_usage() {
     fprintf(stderr, "  -n <int> number of steps in completion mode, default 128. 0 = max_seq_len, -1 = infinite\n");
     fprintf(stderr, "  -g <0|1> decode loop on the device (default 0)\n");
     fprintf(stderr, "  -K [f16,f8] KV ring element type (default f16; f8 = e4m3, hip only)\n");
+    fprintf(stderr, "  -a <0|1> with -K f8: prompt attention on the MFMA kernels' fp8 tiles (default 0, hip only)\n");
     fprintf(stderr, "  -t <float> sampling temperature (default 0 - greedy)\n");
     fprintf(stderr, "  -k <int> top-k, 0 = off (default 0)\n");
     fprintf(stderr, "  -p <float> top-p in (0, 1], 1 = off (default 1)\n");
@@ -111,7 +121,7 @@ static void run_completion(const std::string& path, Device dev, const std::strin
                            bool device_loop, const xh_sampling& sampling, const xh_logit_ctl& ctl,
                            const xh_trunc_ctl& trunc, xh_seq_ctl seq, const std::string& regex, int top_n) {
     const XalmFile file = XalmFile::load(path);
-    const Model model = Model::from_xalm(file, context, dev, 0, g_kv_dtype);
+    const Model model = load_model(file, context, dev);
     InferenceState state(model.config);
     const Sampler sampler(model.config);
     const Tokenizer tokenizer(file);
@@ -215,7 +225,7 @@ static void run_completion(const std::string& path, Device dev, const std::strin
 // run_perplexity, src/main.cpp:198-268
 static void run_perplexity(const std::string& path, Device dev, const std::string& prompt, int context, int top_n) {
     const XalmFile file = XalmFile::load(path);
-    const Model model = Model::from_xalm(file, context, dev, 0, g_kv_dtype);
+    const Model model = load_model(file, context, dev);
     InferenceState state(model.config);
     const Tokenizer tokenizer(file);
     model.forward(state, 0, 0);
@@ -277,6 +287,7 @@ int main(int argc, char** argv) {
             else if (v == "f8") g_kv_dtype = XH_F8_E4M3;
             else error_usage();
         }
+        else if (f == 'a') g_attn_kv8 = std::stoi(v);
         else if (f == 't') sampling.temperature = std::stof(v);
         else if (f == 'k') sampling.top_k = std::stoi(v);
         else if (f == 'p') sampling.top_p = std::stof(v);
@@ -317,6 +328,7 @@ int main(int argc, char** argv) {
         return 1;
     }
     if (g_kv_dtype != XH_F16 && device == "cpu") error_usage();  // the fp8 KV ring is the HIP device's
+    if (g_attn_kv8 && device == "cpu") error_usage();
     const Device dev = device == "cpu" ? Device::CPU : Device::HIP;
     try {
         if (mode == "completion") run_completion(path, dev, prompt, context, num_steps, device_loop != 0, sampling, ctl, trunc, seq, regex, top_n);
