@@ -641,6 +641,26 @@ enum xh_gemv_shape_id {
 };
 int xh_gemv_shape(int role, int dtype, int n);
 
+/* Test hook, host only (no context, no device): the path the single-token attention takes at
+ * kv_len for a head shape, computed by the functions the launches themselves call (the split
+ * count, the split length and its floors, the rows per round, the merge selection).  fused = 0: the
+ * split launch (xh_op_mha / xh_op_mha8, and the decode step without the fused launch); fused = 1:
+ * the attention side of the fused attention + Wo launch, XH_E_INVALID when no such launch exists
+ * for the head shape or kv_dtype is XH_F8_E4M3.  kv_dtype: XH_F16 or XH_F8_E4M3.
+ *   nsplit, T, n_active  the grid's splits per KV head, slots per split, splits holding slots
+ *   step                 K/V rows per round of a split
+ *   rounds_full / _last  rounds of a whole split (min(T, kv_len) slots) and of the last active one
+ *   wph                  waves per q head in the softmax
+ *   merge_mb, merge_nc   the in-kernel merge: 0 none (one active split, or the Wo side merges),
+ *                        4 / 8 / 16 partial values per thread and round trip; (m, l) loads per lane
+ *   stage                fused only: 1..4 partials merged in registers by the Wo workgroups,
+ *                        5 = the heads arrive merged; 0 on the split launch */
+typedef struct xh_attn_plan_t {
+    int fused, nsplit, T, n_active, step, rounds_full, rounds_last, wph, merge_mb, merge_nc, stage;
+} xh_attn_plan_t;
+int xh_attn_plan(int head_dim, int n_heads, int n_kv_heads, int max_seq_len, int kv_dtype, int fused, int kv_len,
+                 xh_attn_plan_t* out);
+
 /* Copy the current device logits to the host. */
 int xh_get_logits(xh_ctx* ctx, float* logits_out);
 

@@ -22,12 +22,16 @@ sum |w| |input| of the row, plus |residual| where one is added (affine gguf type
     RoPE pair            the rotated bars, |c| b0 + |s| b1, plus 4e-6 max(|v0|, |v1|)   (test_rope)
     GLU                  1.13 |u| bg + |act(g)| bu + 2e-7 |hb|  (1.13 bounds |SiLU'| and |GELU'|)
     f16 ring rows        the f32 bar plus one f16 ulp, |ref| 2^-10 + 2^-24
-    attention into Wo    2e-5 sum|wo| + 2e-6 mag + 1e-7        (2e-5 per attention element: test_mha)
+    attention into Wo    |wo| @ min(bar_att, 2e-5) + 2e-6 mag + 1e-7   (bar_att per attention element:
+                         tests/attn_ref.py; 2e-5: test_mha's flat bar, so the term is never looser than it was)
 
 Oracle headroom.  tests/test_stages_cpu.py composes the same stages from the CPU oracle's f32 ops
 and requires them under every bar with at least 4x headroom (the GPU sums in another order).
 Worst err / bar of the f32 oracle over the whole sweep (252 cases), measured on the CPU:
-    q 0.094   x1 0.004   hb 0.084   x2 0.157   logits 0.085   (headroom 6x and more)
+    q 0.094   x1 0.007   hb 0.084   x2 0.157   logits 0.109   (headroom 6x and more)
+(x1: 0.004 under the flat 2e-5 sum|wo| this term replaces.  At this sweep's 41 slots bar_att is
+0.6 to 2.4 times smaller than 2e-5 by element: larger than 2e-5 for some elements at head_dim 128,
+where the scores are large, hence the minimum.)
     k 0.493   v 0.494
 k and v are the f16 rounding itself: up to half an ulp in every correct evaluation, half of the
 bar's one-ulp term whatever the summation order, so their ratio approaches 1/2 by construction;
@@ -42,6 +46,7 @@ import numpy as np
 from oracle import oracle as O
 from xalm_amd import _lib as L
 
+import attn_ref as AR
 import stage_cases as SC
 
 STAGES = ("q", "k", "v", "x1_fused", "x1_split", "hb", "x2", "logits")
@@ -235,15 +240,9 @@ def check_stages(c, wdt, W, obs, pos=SC.HIST):
     # attention over the observed ring (history + the new row) from the observed q, then Wo
     kb = np.concatenate([f16_to_64(history(c, 0)), f16_to_64(obs.k_row)[None]])
     vb = np.concatenate([f16_to_64(history(c, 1)), f16_to_64(obs.v_row)[None]])
-    att = np.empty(q_dim)
-    qpk = c.heads // c.kv_heads
-    for h in range(c.heads):
-        hs, ks = slice(h * c.head_dim, (h + 1) * c.head_dim), slice(h // qpk * c.head_dim, (h // qpk + 1) * c.head_dim)
-        s = kb[:, ks] @ obs.q[hs].astype(np.float64) / np.sqrt(c.head_dim)
-        p = np.exp(s - s.max())
-        att[hs] = (p / p.sum()) @ vb[:, ks]
+    att, bar_att, _ = AR.attention64(kb, vb, obs.q, c.head_dim, kb.shape[0], c.heads, c.kv_heads)
     x1, b = matvec(*dec[L.WO], att, x0)
-    b = b + 2e-5 * dec[L.WO][1].sum(axis=1)
+    b = b + dec[L.WO][1] @ np.minimum(bar_att, 2e-5)
     for fuse, name in ((1, "x1_fused"), (0, "x1_split")):
         if fuse in obs.x1:
             ratio[name] = float(np.max(np.abs(obs.x1[fuse] - x1) / b))

@@ -82,6 +82,12 @@ class XhSampling(ctypes.Structure):
                 ("seed", ctypes.c_uint64)]
 
 
+class XhAttnPlan(ctypes.Structure):
+    """xh_attn_plan_t (include/xalm_hip.h): the path the single-token attention takes at one kv_len."""
+    _fields_ = [(n, ctypes.c_int) for n in ("fused", "nsplit", "T", "n_active", "step", "rounds_full", "rounds_last",
+                                            "wph", "merge_mb", "merge_nc", "stage")]
+
+
 CTL_MAX_WINDOW, CTL_MAX_BIAS = 1024, 256
 
 
@@ -253,6 +259,7 @@ _SIGNATURES = {
     "xh_debug_trace": (_I, [_P, _I, _P, _I, ctypes.POINTER(_I)]),
     "xh_debug_read": (_I, [_P, _I, _P, _SZ]),
     "xh_gemv_shape": (_I, [_I, _I, _I]),
+    "xh_attn_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(XhAttnPlan)]),
     "xh_get_logits": (_I, [_P, _P]),
     "xh_reset": (_I, [_P]),
     "xh_kv_write": (_I, [_P, _I, _I, _I, _I, _P]),
@@ -326,6 +333,16 @@ def gemv_shape(role: int, dtype: int, n: int) -> int:
     """The launch shape the decode matvec of `role` takes at input length n (xh_gemv_shape): an
     index into SHAPE_NAMES, plus SHAPE_BIG_LDS above 64 KiB of LDS; -1 = none.  No device needed."""
     return int(lib().xh_gemv_shape(role, dtype, n))
+
+
+def attn_plan(head_dim: int, n_heads: int, n_kv_heads: int, max_seq_len: int, kv_dtype: int, fused: int,
+              kv_len: int) -> XhAttnPlan:
+    """The path the single-token attention takes at kv_len (xh_attn_plan): the split launch
+    (fused = 0) or the attention side of the fused attention + Wo launch (fused = 1; raises where
+    the shape has none).  No device needed."""
+    p = XhAttnPlan()
+    check(lib().xh_attn_plan(head_dim, n_heads, n_kv_heads, max_seq_len, kv_dtype, fused, kv_len, ctypes.byref(p)))
+    return p
 
 
 def quantize_blocks(dtype: int, values: np.ndarray) -> np.ndarray:

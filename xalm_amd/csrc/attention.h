@@ -112,6 +112,50 @@ template <> struct AttnKv<XH_F8_E4M3, 4> {
 // passes per round of a long split for a lane chunk of `bytes`: ATTN_PREF_LONG 16-byte chunks' worth
 __device__ __host__ constexpr int attn_pref_long(const int bytes) { return ATTN_PREF_LONG * 16 / bytes; }
 
+// The launch geometry of attn_block as functions of its template arguments and of n_active: the
+// kernel takes every one of them from here, and so does the plan query (xh_attn_plan), so the two
+// cannot drift.
+// K/V passes per round: short splits of the fused launch (PARTIALS) ATTN_PREF, long splits by
+// the lane chunk's bytes
+__device__ __host__ constexpr int attn_pref(const int kv, const int qpk, const bool partials) {
+    return partials ? ATTN_PREF : attn_pref_long(kv == XH_F16 ? 16 : attn_kv_elems(kv, qpk));
+}
+// the split floor attn_block takes: MINT where the caller names one, else the mode's default
+__device__ __host__ constexpr int attn_block_min_t(const int hd, const int kv, const int qpk, const int threads,
+                                                   const bool partials, const int mint) {
+    return mint ? mint : partials ? attn_min_t_partials(hd, threads, attn_kv_elems(kv, qpk)) : ATTN_MIN_T;
+}
+// K/V rows per round of a THREADS-thread block
+__device__ __host__ constexpr int attn_step(const int hd, const int kv, const int qpk, const int threads,
+                                            const bool partials) {
+    return attn_pref(kv, qpk, partials) * (threads / (hd / attn_kv_elems(kv, qpk)));
+}
+// waves per head in the softmax
+__device__ __host__ constexpr int attn_wph(const int qpk, const int threads, const bool partials) {
+    return partials ? 1 : (threads / 64 / qpk > 0 ? threads / 64 / qpk : 1);
+}
+// thread groups of the merge (each sums a contiguous range of splits) for a block of `no` outputs
+__device__ __host__ constexpr int attn_merge_groups(const int no, const int threads) {
+    return (threads / no < threads / 64 - 1 ? threads / no : threads / 64 - 1) > 0
+               ? (threads / no < threads / 64 - 1 ? threads / no : threads / 64 - 1) : 1;
+}
+#ifndef ATTN_MERGE_MB
+#define ATTN_MERGE_MB 1
+#endif
+// partial values per thread per round trip of the merge: 4 / 8 / 16 by the group's split count (a
+// fixed 16 requested clamped copies of the last split for short chunks).  More than 64 active
+// splits take 16 whatever the chunk: only that form loads two (m, l) pairs per lane
+// (attn_merge_nc), and a lane holds the pair of split `lane` and of split `lane + 64`.
+__device__ __host__ constexpr int attn_merge_mb(const int n_active, const int mg) {
+    return n_active > 64               ? 16
+           : !ATTN_MERGE_MB            ? 16
+           : (n_active + mg - 1) / mg <= 4 ? 4
+           : (n_active + mg - 1) / mg <= 8 ? 8
+                                           : 16;
+}
+// (m, l) loads per lane of the merge form mb: up to 64 * NC splits
+__device__ __host__ constexpr int attn_merge_nc(const int mb) { return mb >= 16 ? 2 : 1; }
+
 __device__ __forceinline__ float ld_sc1(const float* p) {
     return __builtin_bit_cast(float, __hip_atomic_load((const uint32_t*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
@@ -155,7 +199,7 @@ __device__ __forceinline__ void attn_block(const AttnArgs& a, const int g, const
 #define ATTN_STAMP(k) \
     do { if (dbg && threadIdx.x == 0) dbg[k] = __builtin_amdgcn_s_memrealtime(); } while (0)
     constexpr int WAVES = THREADS / 64;
-    constexpr int PREF = PARTIALS ? ATTN_PREF : attn_pref_long(KV == XH_F16 ? 16 : attn_kv_elems(KV, QPK));
+    constexpr int PREF = attn_pref(KV, QPK, PARTIALS);
     constexpr int E = attn_kv_elems(KV, QPK);  // K/V elements per lane
     typedef AttnKv<KV, E> Kv;
     typedef typename Kv::V kvec;
@@ -170,7 +214,7 @@ __device__ __forceinline__ void attn_block(const AttnArgs& a, const int g, const
     int* flag = (int*)(ml + 2 * QPK);
 
     const int kv_len = a.sp->kv_len;
-    constexpr int MIN_T = MINT ? MINT : PARTIALS ? attn_min_t_partials(HD, THREADS, E) : ATTN_MIN_T;
+    constexpr int MIN_T = attn_block_min_t(HD, KV, QPK, THREADS, PARTIALS, MINT);
     const int T = attn_split_len(kv_len, a.nsplit, MIN_T);
     const int t0 = s * T;
     if (t0 >= kv_len) return;
@@ -231,7 +275,8 @@ __device__ __forceinline__ void attn_block(const AttnArgs& a, const int g, const
     // behind a branch would merge into a vmcnt(0); the last round has its own block, so every
     // wait is counted.  (One round in flight per wave left the passes latency-bound at long
     // contexts.)
-    constexpr int STEP = PREF * RPP;
+    constexpr int STEP = attn_step(HD, KV, QPK, THREADS, PARTIALS);
+    static_assert(STEP == PREF * RPP, "a round is PREF passes of RPP rows");
     auto ld_round = [&](kvec (&v)[PREF], const uint16_t* base_p, const int base) {
 #pragma unroll
         for (int p = 0; p < PREF; p++) v[p] = ld_kv(base_p, min(base + rr + p * RPP, t1 - 1));
@@ -273,7 +318,7 @@ __device__ __forceinline__ void attn_block(const AttnArgs& a, const int g, const
     // wave order through xw.  sc rows start 16-B aligned (T % 16 == 0); reads past len stay
     // inside the row and are masked.
     // (short splits of the fused launch keep one wave per head: no barrier between the passes)
-    constexpr int WPH = PARTIALS ? 1 : (WAVES / QPK > 0 ? WAVES / QPK : 1);
+    constexpr int WPH = attn_wph(QPK, THREADS, PARTIALS);
     const int len = t1 - t0;
     const int sh = wid / WPH, sw = wid - sh * WPH;  // this wave's head and its share
     float* row = sc + sh * T;
@@ -468,13 +513,8 @@ __device__ __forceinline__ void attn_block(const AttnArgs& a, const int g, const
     // left to right; the group sums are added in group order).  Every thread requests its
     // first MB partial values right behind its wave's (m, l) loads, so the (m, l) -> weights
     // step and the partial loads share one round trip.
-    constexpr int MG = (THREADS / NO < WAVES - 1 ? THREADS / NO : WAVES - 1) > 0
-                           ? (THREADS / NO < WAVES - 1 ? THREADS / NO : WAVES - 1) : 1;
-    // partial values per thread per round trip: 4 / 8 / 16 by the group's split count (a fixed 16
-    // requested clamped copies of the last split for short chunks)
-#ifndef ATTN_MERGE_MB
-#define ATTN_MERGE_MB 1
-#endif
+    constexpr int MG = attn_merge_groups(NO, THREADS);
+    // partial values per thread per round trip: attn_merge_mb
     float* wts = sc;        // [QPK][n_active] weights (sc is free now)
     float* den_s = red + MG * NO;  // [QPK]; red[k * NO + idx]: group sums
     const int chunk = (n_active + MG - 1) / MG;
@@ -485,7 +525,7 @@ __device__ __forceinline__ void attn_block(const AttnArgs& a, const int g, const
     const size_t mstride = (size_t)a.n_heads * HD;
     auto merge = [&](auto mb_c) {
         constexpr int MB = decltype(mb_c)::value;
-        constexpr int NC = MB >= 16 ? 2 : 1;  // (m, l) loads per lane: up to 64 NC splits
+        constexpr int NC = attn_merge_nc(MB);  // (m, l) loads per lane: up to 64 NC splits
         // (m, l) of head min(wid, QPK - 1), up to 2 splits per lane (n_active <= 128);
         // clamped indices so every load sits in one basic block with the partial loads
         const int h = min(wid, QPK - 1);
@@ -540,8 +580,9 @@ __device__ __forceinline__ void attn_block(const AttnArgs& a, const int g, const
             }
         }
     };
-    if (ATTN_MERGE_MB && chunk <= 4) merge(std::integral_constant<int, 4>{});
-    else if (ATTN_MERGE_MB && chunk <= 8) merge(std::integral_constant<int, 8>{});
+    const int mb = attn_merge_mb(n_active, MG);
+    if (mb == 4) merge(std::integral_constant<int, 4>{});
+    else if (mb == 8) merge(std::integral_constant<int, 8>{});
     else merge(std::integral_constant<int, 16>{});
     __syncthreads();
     for (int idx = tid; idx < NO; idx += THREADS) {

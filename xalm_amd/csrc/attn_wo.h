@@ -50,11 +50,23 @@ constexpr int AW_MAXS = 4;
 #ifndef AW_EARLY_WAVE0
 #define AW_EARLY_WAVE0 1
 #endif
+// How the Wo side receives n_active partials: 1 .. AW_MAXS = it merges them in registers
+// (aw_stage_na<n>), AW_MAXS + 1 = the heads arrive merged.  The kernel and xh_attn_plan both ask here.
+__host__ __device__ constexpr int aw_stage_form(const int n_active) {
+    return n_active > AW_MAXS ? AW_MAXS + 1 : n_active;
+}
+// The attention side of the launch by stage form: up to AW_MAXS the splits publish partials
+// (attn_block PARTIALS, MINT 0: the mode's own floor), past them each head's last split merges
+// (attn_block SIGNAL with MINT = aw_min_t).  aw_min_t: the launch's split floor, the same in both
+// forms, from which the kernel, the context's t_max_aw and the plan all take T.
+__host__ __device__ constexpr bool aw_partials(const int stage) { return stage <= AW_MAXS; }
+__host__ __device__ constexpr int aw_min_t(const int hd) { return attn_min_t_partials(hd, AW_THREADS); }
+__host__ __device__ constexpr int aw_mint(const int hd, const int stage) { return aw_partials(stage) ? 0 : aw_min_t(hd); }
 template <int HD>
 __device__ __forceinline__ bool aw_long(const AttnArgs& aa) {
     const int kv_len = aa.sp->kv_len;
-    const int T = attn_split_len(kv_len, aa.nsplit, attn_min_t_partials(HD, AW_THREADS));
-    return (kv_len + T - 1) / T > AW_MAXS;
+    const int T = attn_split_len(kv_len, aa.nsplit, aw_min_t(HD));
+    return !aw_partials(aw_stage_form((kv_len + T - 1) / T));
 }
 template <int E>
 __host__ __device__ constexpr size_t aw_image_bytes(const int n) {
@@ -166,7 +178,7 @@ __device__ __forceinline__ void aw_stage_merged(const AttnArgs& aa, const int n,
 #if AW_STAGE_NA
     // the partial count as a constant: no clamped duplicate loads (n_active = 1 issued 4 o and
     // 8 (m, l) loads per thread for 1 and 2 it needs)
-    switch (n_active) {
+    switch (aw_stage_form(n_active)) {
         case 1: aw_stage_na<E, HD, 1, THREADS>(aa, n, xs4); return;
         case 2: aw_stage_na<E, HD, 2, THREADS>(aa, n, xs4); return;
         case 3: aw_stage_na<E, HD, 3, THREADS>(aa, n, xs4); return;
@@ -241,7 +253,7 @@ __global__ __launch_bounds__(AW_THREADS) void attn_wo_kernel(const AttnArgs aa, 
     const int b = blockIdx.x;
     if (trace && threadIdx.x == 0) trace[8 * b] = __builtin_amdgcn_s_memrealtime();
     const int kv_len = aa.sp->kv_len;
-    const int T = attn_split_len(kv_len, aa.nsplit, attn_min_t_partials(HD, AW_THREADS));
+    const int T = attn_split_len(kv_len, aa.nsplit, aw_min_t(HD));
     const int n_active = (kv_len + T - 1) / T;
     const bool merged = aw_long<HD>(aa);  // heads arrive merged (one arrival per KV head)
     const unsigned target = (unsigned)(merged ? n_kv_heads : n_kv_heads * n_active);
@@ -258,10 +270,10 @@ __global__ __launch_bounds__(AW_THREADS) void attn_wo_kernel(const AttnArgs aa, 
         };
         if (merged) {
             // long contexts: each KV head's last split merges (ticket) and signals the head
-            attn_block<HD, QPK, AW_THREADS, false, attn_min_t_partials(HD, AW_THREADS), NoWait,
+            attn_block<HD, QPK, AW_THREADS, aw_partials(AW_MAXS + 1), aw_mint(HD, AW_MAXS + 1), NoWait,
                        decltype(arrive), true>(aa, g, s, smem, sync, nullptr, NoWait(), arrive);
         } else {
-            attn_block<HD, QPK, AW_THREADS, true, 0, NoWait, decltype(arrive)>(
+            attn_block<HD, QPK, AW_THREADS, aw_partials(AW_MAXS), aw_mint(HD, AW_MAXS), NoWait, decltype(arrive)>(
                 aa, g, s, smem, sync, trace ? trace + 8 * b : nullptr, NoWait(), arrive);
         }
         if (trace && threadIdx.x == 0) trace[8 * b + 1] = __builtin_amdgcn_s_memrealtime();

@@ -119,7 +119,7 @@ int xh_create_kv(const xh_config* cfg, int device_ordinal, int kv_dtype, xh_ctx*
     ctx->kv_dt = kv_dtype;
     ctx->nsplit = attn_nsplit(c.n_kv_heads, c.max_seq_len);
     ctx->t_max = attn_split_len(c.max_seq_len, ctx->nsplit);
-    ctx->t_max_aw = attn_split_len(c.max_seq_len, ctx->nsplit, attn_min_t_partials(c.head_dim, AW_THREADS));
+    ctx->t_max_aw = attn_split_len(c.max_seq_len, ctx->nsplit, aw_min_t(c.head_dim));
     int rc = 0;
 #define CREATE_TRY(expr) do { rc = (expr); if (rc) { g_create_error = ctx->err; xh_destroy(ctx); return rc; } } while (0)
     if (hipSetDevice(device_ordinal) != hipSuccess) { delete ctx; return set_err(nullptr, XH_E_HIP, "hipSetDevice failed"); }
@@ -306,6 +306,46 @@ int xh_debug_read(xh_ctx* ctx, int which, float* out, size_t cap) {
 }
 
 int xh_gemv_shape(int role, int dtype, int n) { return gemv_shape(role, dtype, n); }
+
+// The values attn_block and attn_wo_kernel form on the device from kv_len, through the functions
+// they form them with (attention.h, attn_wo.h): the split launch is attn_block<HD, QPK,
+// ATTN_THREADS, false, 0>; the fused launch attn_block<.., AW_THREADS, aw_partials(stage),
+// aw_mint(hd, stage)> with T from aw_min_t, as attn_wo_kernel instantiates and computes them.
+int xh_attn_plan(int head_dim, int n_heads, int n_kv_heads, int max_seq_len, int kv_dtype, int fused, int kv_len,
+                 xh_attn_plan_t* out) {
+    if (!out || n_kv_heads <= 0 || n_heads <= 0 || n_heads % n_kv_heads || kv_len <= 0 || kv_len > max_seq_len)
+        return set_err(nullptr, XH_E_INVALID, "bad attn_plan args");
+    if (kv_dtype != XH_F16 && kv_dtype != XH_F8_E4M3) return set_err(nullptr, XH_E_INVALID, "attn_plan: bad kv_dtype %d", kv_dtype);
+    const int hd = head_dim, qpk = n_heads / n_kv_heads;
+    if (!(qpk == 1 || qpk == 2 || qpk == 4 || qpk == 8) || !(hd == 16 || hd == 32 || hd == 64 || hd == 128 || hd == 256))
+        return set_err(nullptr, XH_E_INVALID, "attn_plan: no attention kernel for head_dim %d x %d q heads per kv head", hd, qpk);
+    if (fused && (kv_dtype != XH_F16 || !aw_instantiated(hd, qpk)))
+        return set_err(nullptr, XH_E_INVALID, "attn_plan: no fused attention + Wo launch for head_dim %d x %d, kv dtype %d", hd,
+                       qpk, kv_dtype);
+    xh_attn_plan_t p{};
+    p.fused = fused ? 1 : 0;
+    p.nsplit = attn_nsplit(n_kv_heads, max_seq_len);
+    const int threads = fused ? AW_THREADS : ATTN_THREADS;
+    // T: the kernels take it from their block's floor (attn_block_min_t; the fused kernel from
+    // aw_min_t, which both of its forms' floors equal)
+    p.T = attn_split_len(kv_len, p.nsplit, fused ? aw_min_t(hd) : attn_block_min_t(hd, kv_dtype, qpk, threads, false, 0));
+    p.n_active = (kv_len + p.T - 1) / p.T;
+    p.stage = fused ? aw_stage_form(p.n_active) : 0;
+    const bool partials = fused && aw_partials(p.stage);
+    if (fused && attn_block_min_t(hd, kv_dtype, qpk, threads, partials, aw_mint(hd, p.stage)) != aw_min_t(hd))
+        return set_err(nullptr, XH_E_INVALID, "attn_plan: the fused launch's block floor differs from aw_min_t");
+    p.step = attn_step(hd, kv_dtype, qpk, threads, partials);
+    const int full = kv_len < p.T ? kv_len : p.T, last = kv_len - (p.n_active - 1) * p.T;
+    p.rounds_full = (full + p.step - 1) / p.step;
+    p.rounds_last = (last + p.step - 1) / p.step;
+    p.wph = attn_wph(qpk, threads, partials);
+    if (!partials && p.n_active > 1) {
+        p.merge_mb = attn_merge_mb(p.n_active, attn_merge_groups(qpk * hd, threads));
+        p.merge_nc = attn_merge_nc(p.merge_mb);
+    }
+    *out = p;
+    return 0;
+}
 
 int xh_get_option(const xh_ctx* ctx, int option, int* value) {
     if (!ctx || !value) return XH_E_INVALID;
