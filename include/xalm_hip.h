@@ -154,9 +154,10 @@ int xh_create(const xh_config* cfg, int device_ordinal, xh_ctx** out);
  *   prompts: the GEMMs as ever; the attention as under XH_OPT_PREFILL_ATTN 0 (the per-token
  *            split kernel) unless XH_OPT_PREFILL_ATTN_KV8 is 1, under which it follows
  *            XH_OPT_PREFILL_ATTN and XH_OPT_PREFILL_ATTN_SPLIT as on an fp16 context (the MFMA
- *            kernels' fp8 form); either way no ring passes: a prompt that reaches past the ring
- *            is batched below max_seq_len and takes the per-token loop from the cut
- *            (xh_prefill_route answers accordingly, the same under both values). */
+ *            kernels' fp8 form); either way no ring passes unless XH_OPT_PREFILL_RING_KV8: a
+ *            prompt that reaches past the ring is batched below max_seq_len and takes the
+ *            per-token loop from the cut (xh_prefill_route answers accordingly, the same under
+ *            both values). */
 int xh_create_kv(const xh_config* cfg, int device_ordinal, int kv_dtype, xh_ctx** out);
 /* The context's KV element type: XH_F16 or XH_F8_E4M3. */
 int xh_kv_dtype(const xh_ctx* ctx);
@@ -755,6 +756,17 @@ int xh_set_graphs(xh_ctx* ctx, int enable);
  * the fp16 attention over that image); 0 = the attention is forced to the per-token split kernel
  * (XH_OPT_PREFILL_ATTN 0).  The pass plan (xh_prefill_route) and the K/V the passes write do not
  * depend on it.  On an fp16 context the value is stored and read back and has no effect.  Values
+ * other than 0 / 1 are XH_E_INVALID.  No ring passes on an fp8 ring unless XH_OPT_PREFILL_RING_KV8. */
+/* XH_OPT_PREFILL_RING_KV8 (default 0): on an fp8 (e4m3) KV ring 1 = the part of a prompt from position
+ * max_seq_len on runs ring passes as on an fp16 context (XH_OPT_PREFILL_RING: the same cut, pass
+ * lengths and one-or-two-token rule; xh_prefill_route answers as for an fp16 context), on the ring
+ * kernels' fp8 form: the pass's K/V rows are staged as the codes the token loop would store, the
+ * sinks iterate in their fp16 master and token t scores them against f8(master after t + 1
+ * rotations), and the attention is the fp16 ring pass's over the f16 image of all those codes, bit
+ * for bit; after the pass the master holds its last version and ring K slot r is f8(master[r]).
+ * It has effect only when XH_OPT_PREFILL_ATTN_KV8, XH_OPT_PREFILL_RING and XH_OPT_PREFILL_ATTN are
+ * all 1, head_dim is 128 and max_seq_len - 2 >= 2; otherwise, and on an fp16 context, the value is
+ * stored and read back and has no effect.  0 = the per-token loop from the cut, as ever.  Values
  * other than 0 / 1 are XH_E_INVALID. */
 enum xh_option {
     XH_OPT_FUSE_ATTN_WO = 1,
@@ -763,7 +775,8 @@ enum xh_option {
     XH_OPT_PREFILL_ATTN = 5,
     XH_OPT_PREFILL_ATTN_SPLIT = 6,
     XH_OPT_PREFILL_RING = 7,
-    XH_OPT_PREFILL_ATTN_KV8 = 8
+    XH_OPT_PREFILL_ATTN_KV8 = 8,
+    XH_OPT_PREFILL_RING_KV8 = 9
 };
 int xh_set_option(xh_ctx* ctx, int option, int value);
 int xh_get_option(const xh_ctx* ctx, int option, int* value);
@@ -818,6 +831,17 @@ int xh_op_prompt_attn8(float* out, const float* q, const uint8_t* k, const uint8
 int xh_op_prompt_attn_ring(float* out, uint16_t* k_ring, uint16_t* v_ring, const float* q, const uint16_t* ks,
                            const uint16_t* vs, const uint16_t* sink_ver, int m, int p0, int max_seq_len, int n_heads,
                            int n_kv_heads, int nsplit);
+/* The same over fp8 K/V (an fp8 context under XH_OPT_PREFILL_RING_KV8 1), through the same launch
+ * code: k_ring / v_ring, ks / vs and sink_ver hold one e4m3 code per element in the same shapes
+ * (sink_ver [m][2][kv_dim] codes: f8 of the master's version token t scores against); every other
+ * argument as xh_op_prompt_attn_ring, and what it rejects is rejected likewise.  By definition `out`
+ * is xh_op_prompt_attn_ring's over the codes' f16 image, bit for bit, and the rings come back with
+ * staging row t in slot 2 + (p0 - 2 + t) % W and sink_ver[m - 1] in K rows 0 and 1 (the hook has no
+ * master).  A NaN code (0x7F, 0xFF) in any of the five code buffers is XH_E_INVALID before any
+ * launch: out and the rings are untouched. */
+int xh_op_prompt_attn_ring8(float* out, uint8_t* k_ring, uint8_t* v_ring, const float* q, const uint8_t* ks,
+                            const uint8_t* vs, const uint8_t* sink_ver, int m, int p0, int max_seq_len,
+                            int n_heads, int n_kv_heads, int nsplit);
 
 /* One GEMM of a prompt pass on host buffers, through the launch code of the passes: y[n][rows] = x . w^T
  * with x f32 [n][K] and w [rows][K] of `dtype` in the file layout (repacked as xh_op_matmul does).  mode =

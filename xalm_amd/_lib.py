@@ -53,6 +53,7 @@ OPT_PREFILL_ATTN = 5
 OPT_PREFILL_ATTN_SPLIT = 6
 OPT_PREFILL_RING = 7
 OPT_PREFILL_ATTN_KV8 = 8
+OPT_PREFILL_RING_KV8 = 9
 
 # enum xh_tensor_kind
 EMBED, ATTN_NORM, FFN_NORM, WQ, WK, WV, WO, W1, W2, W3, FINAL_NORM, WCLS = range(12)
@@ -282,6 +283,7 @@ _SIGNATURES = {
     "xh_op_prompt_attn": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I]),
     "xh_op_prompt_attn8": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I]),
     "xh_op_prompt_attn_ring": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I]),
+    "xh_op_prompt_attn_ring8": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I]),
     "xh_op_prompt_matmul": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, ctypes.POINTER(_I)]),
     "xh_op_prompt_weight_image": (_I, [_I, _P, _I, _I, _P, _P, _I]),
     "xh_op_prompt_stage": (_I, [_I, _P, _I, _P, _P, _I, _I, _P, _I, ctypes.c_float, _I, _I, _SZ, _P, _P, _P, _P,
@@ -790,4 +792,24 @@ def op_prompt_attn_ring(q: np.ndarray, k_ring: np.ndarray, v_ring: np.ndarray, k
     out = np.empty_like(q)
     check(lib().xh_op_prompt_attn_ring(ptr(out), ptr(kr), ptr(vr), ptr(q), ptr(ks), ptr(vs), ptr(sv), m, p0, L, n_heads,
                                        n_kv_heads, nsplit))
+    return out, kr, vr
+
+
+def op_prompt_attn_ring8(q: np.ndarray, k_ring: np.ndarray, v_ring: np.ndarray, ks: np.ndarray, vs: np.ndarray,
+                         sink_ver: np.ndarray, p0: int, n_heads: int, n_kv_heads: int, nsplit: int = 0):
+    """op_prompt_attn_ring over fp8 K/V (xh_op_prompt_attn_ring8): k_ring, v_ring, ks, vs and sink_ver e4m3
+    codes (uint8) in the same shapes; everything else, and the return, as op_prompt_attn_ring."""
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    kr = np.array(k_ring, dtype=np.uint8, order="C", copy=True)
+    vr = np.array(v_ring, dtype=np.uint8, order="C", copy=True)
+    ks = np.ascontiguousarray(ks, dtype=np.uint8)
+    vs = np.ascontiguousarray(vs, dtype=np.uint8)
+    sv = np.ascontiguousarray(sink_ver, dtype=np.uint8)
+    m, kv_dim = ks.shape
+    L = kr.shape[0]
+    assert kv_dim == n_kv_heads * 128 and q.shape == (m, n_heads * 128)
+    assert kr.shape == (L, kv_dim) and vr.shape == kr.shape and vs.shape == ks.shape and sv.shape == (m, 2, kv_dim)
+    out = np.empty_like(q)
+    check(lib().xh_op_prompt_attn_ring8(ptr(out), ptr(kr), ptr(vr), ptr(q), ptr(ks), ptr(vs), ptr(sv), m, p0, L, n_heads,
+                                        n_kv_heads, nsplit))
     return out, kr, vr

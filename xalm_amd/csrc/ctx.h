@@ -137,9 +137,11 @@ struct PfBufs {
     // ATTN0: the per-token split attention (XH_OPT_PREFILL_ATTN 0 only)
     float *po = nullptr, *pml = nullptr;   // [T][nsplit][q_dim], [T][nsplit][n_heads][2]
     int* cnt = nullptr;                    // [T][n_kv_heads] split tickets
-    // RING: ring passes (positions >= max_seq_len, XH_OPT_PREFILL_RING)
+    // RING: ring passes (positions >= max_seq_len, XH_OPT_PREFILL_RING); elements of the ring's type
+    // (an fp8 ring: one code each, rows of kv_dim bytes)
     uint16_t *ks = nullptr, *vs = nullptr; // [T][kv_dim] the pass's K / V rows until its attention ran
     uint16_t* sinkv = nullptr;             // [T][2][kv_dim] sink K rows after 1 .. T re-rotations (one layer's)
+    uint16_t* sinkm = nullptr;             // fp8 only: [2][kv_dim] fp16, the master after the pass's last rotation
     // LOGITS: xh_perplexity's per-token logits of a pass and their targets
     float* logits = nullptr;               // [T][vocab]
     int* tgt = nullptr;                    // [T]
@@ -150,7 +152,7 @@ struct PfBufs {
             case PASS: return {(void**)&xh, (void**)&xl, (void**)&xs, (void**)&tok, (void**)&x, (void**)&xn,
                                (void**)&q, (void**)&att, (void**)&h, (void**)&part, (void**)&sp};
             case ATTN0: return {(void**)&po, (void**)&pml, (void**)&cnt};
-            case RING: return {(void**)&ks, (void**)&vs, (void**)&sinkv};
+            case RING: return {(void**)&ks, (void**)&vs, (void**)&sinkv, (void**)&sinkm};
             case LOGITS: return {(void**)&logits, (void**)&tgt};
             default: return {};
         }
@@ -257,6 +259,7 @@ struct xh_ctx {
                                                  // 2 per-wave MFMA tiles, 0 per-token split kernel
     bool pf_ring = true;                         // XH_OPT_PREFILL_RING: ring passes at positions >= max_seq_len
     bool pf_attn_kv8 = false;                    // XH_OPT_PREFILL_ATTN_KV8: an fp8 KV ring follows pf_attn_mode too
+    bool pf_ring_kv8 = false;                    // XH_OPT_PREFILL_RING_KV8: ... and runs ring passes (under pf_attn_kv8)
     xalm::PfBufs pf;                             // the pass buffers
     // xh_perplexity: targets and probabilities of the whole run (allocated on first use)
     int* ppl_tgt = nullptr;                      // [ppl_cap] targets (per-token path)
@@ -424,10 +427,12 @@ int pf_fa_pick_nsplit(const PfAttnDims& d, int n_cu, int n, int pos0, size_t par
 // (pf_fa_part_floats) when nsplit > 1; else the per-wave kernel
 int pf_fa_launch(const PfAttnDims& d, int kv_dt, bool shared, const float* q, const uint16_t* kc, const uint16_t* vc,
                  float* out, int n, int pos0, int nsplit, float* part, hipStream_t s);
-// a ring pass's walk, merge with the sinks (sinkv [m][2][kv_dim]) and commit; part always
-int pf_ring_launch(const PfAttnDims& d, const float* q, uint16_t* kc, uint16_t* vc, const uint16_t* ks, const uint16_t* vs,
-                   const uint16_t* sinkv, float* out, int m, int p0, int max_seq_len, int nsplit, float* part,
-                   hipStream_t s);
+// a ring pass's walk, merge with the sinks (sinkv [m][2][kv_dim]) and commit; part always.  kv_dt: the
+// element type behind kc / vc / ks / vs / sinkv (XH_F8_E4M3: one code each); an fp8 commit also moves
+// the last master version sinkm [2][kv_dim] (fp16) to `master` when there is one (null: neither)
+int pf_ring_launch(const PfAttnDims& d, int kv_dt, const float* q, uint16_t* kc, uint16_t* vc, const uint16_t* ks,
+                   const uint16_t* vs, const uint16_t* sinkv, float* out, int m, int p0, int max_seq_len, int nsplit,
+                   float* part, hipStream_t s, const uint16_t* sinkm = nullptr, uint16_t* master = nullptr);
 
 // prefill.hip: the prompt GEMM's launch bodies on device pointers, shared by the passes (pf_gemm) and
 // by xh_op_prompt_matmul / xh_op_prompt_weight_image / xh_op_prompt_stage.  Nothing here reads a context.

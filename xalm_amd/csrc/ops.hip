@@ -244,9 +244,12 @@ int xh_op_prompt_attn8(float* out, const float* q, const uint8_t* k, const uint8
     return op_prompt_attn_any(out, q, k, v, n, pos0, head_dim, n_heads, n_kv_heads, mode, nsplit, XH_F8_E4M3);
 }
 
-int xh_op_prompt_attn_ring(float* out, uint16_t* k_ring, uint16_t* v_ring, const float* q, const uint16_t* ks,
-                           const uint16_t* vs, const uint16_t* sink_ver, int m, int p0, int max_seq_len, int n_heads,
-                           int n_kv_heads, int nsplit) {
+namespace {
+// xh_op_prompt_attn_ring / xh_op_prompt_attn_ring8: every K/V buffer of element type kv_dt (fp16 bits, or
+// one e4m3 code each)
+int op_prompt_attn_ring_any(float* out, void* k_ring, void* v_ring, const float* q, const void* ks, const void* vs,
+                            const void* sink_ver, int m, int p0, int max_seq_len, int n_heads, int n_kv_heads, int nsplit,
+                            int kv_dt) {
     if (!out || !k_ring || !v_ring || !q || !ks || !vs || !sink_ver || nsplit < 0)
         return set_err(nullptr, XH_E_INVALID, "bad prompt_attn_ring args");
     if (n_kv_heads <= 0 || n_heads <= 0 || n_heads > 1024 || n_heads % n_kv_heads || !pf_attn_shape_ok(128, n_heads / n_kv_heads))
@@ -259,24 +262,49 @@ int xh_op_prompt_attn_ring(float* out, uint16_t* k_ring, uint16_t* v_ring, const
         return set_err(nullptr, XH_E_INVALID, "prompt_attn_ring: %d splits over %d slots (at most %d)", nsplit, W,
                        pf_fa_split_max(W));
     const PfAttnDims d{128, n_heads, n_kv_heads};
+    const size_t kv_dim = (size_t)n_kv_heads * 128, qe = (size_t)m * n_heads * 128, ring = (size_t)max_seq_len * kv_dim;
+    const size_t esz = kv_dt == XH_F8_E4M3 ? 1 : 2;
+    if (kv_dt == XH_F8_E4M3) {
+        const struct { const char* what; const void* p; size_t n; } bufs[] = {
+            {"k_ring", k_ring, ring}, {"v_ring", v_ring, ring}, {"ks", ks, m * kv_dim}, {"vs", vs, m * kv_dim},
+            {"sink_ver", sink_ver, 2 * m * kv_dim}};
+        for (const auto& b : bufs)
+            for (size_t i = 0; i < b.n; i++)
+                if (f8_special(((const uint8_t*)b.p)[i], false))
+                    return set_err(nullptr, XH_E_INVALID, "prompt_attn_ring8: element %zu of %s is the NaN code", i, b.what);
+    }
     int rc, n_cu = 0;
     if ((rc = op_n_cu(&n_cu))) return rc;
     if (nsplit == 0) nsplit = pf_fa_pick_nsplit(d, n_cu, m, W, SIZE_MAX);
     DevBuf bq, bk, bv, bks, bvs, bsv, bo, bp;
-    const size_t kv_dim = (size_t)n_kv_heads * 128, qe = (size_t)m * n_heads * 128, ring = (size_t)max_seq_len * kv_dim;
-    if ((rc = op_alloc(bq, qe * 4, q)) || (rc = op_alloc(bk, ring * 2, k_ring)) || (rc = op_alloc(bv, ring * 2, v_ring)) ||
-        (rc = op_alloc(bks, m * kv_dim * 2, ks)) || (rc = op_alloc(bvs, m * kv_dim * 2, vs)) ||
-        (rc = op_alloc(bsv, 2 * m * kv_dim * 2, sink_ver)) || (rc = op_alloc(bo, qe * 4, nullptr)) ||
+    if ((rc = op_alloc(bq, qe * 4, q)) || (rc = op_alloc(bk, ring * esz, k_ring)) || (rc = op_alloc(bv, ring * esz, v_ring)) ||
+        (rc = op_alloc(bks, m * kv_dim * esz, ks)) || (rc = op_alloc(bvs, m * kv_dim * esz, vs)) ||
+        (rc = op_alloc(bsv, 2 * m * kv_dim * esz, sink_ver)) || (rc = op_alloc(bo, qe * 4, nullptr)) ||
         (rc = op_alloc(bp, pf_fa_part_floats(d, nsplit, m) * 4, nullptr)))
         return rc;
-    if (pf_ring_launch(d, (const float*)bq.p, (uint16_t*)bk.p, (uint16_t*)bv.p, (const uint16_t*)bks.p, (const uint16_t*)bvs.p,
-                       (const uint16_t*)bsv.p, (float*)bo.p, m, p0, max_seq_len, nsplit, (float*)bp.p, nullptr) < 0)
+    if (pf_ring_launch(d, kv_dt, (const float*)bq.p, (uint16_t*)bk.p, (uint16_t*)bv.p, (const uint16_t*)bks.p,
+                       (const uint16_t*)bvs.p, (const uint16_t*)bsv.p, (float*)bo.p, m, p0, max_seq_len, nsplit, (float*)bp.p,
+                       nullptr) < 0)
         return set_err(nullptr, XH_E_INVALID, "prompt_attn_ring: head shape not instantiated");
     if ((rc = op_finish(out, bo, qe * 4))) return rc;
-    if (hipMemcpy(k_ring, bk.p, ring * 2, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(v_ring, bv.p, ring * 2, hipMemcpyDeviceToHost) != hipSuccess)
+    if (hipMemcpy(k_ring, bk.p, ring * esz, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(v_ring, bv.p, ring * esz, hipMemcpyDeviceToHost) != hipSuccess)
         return set_err(nullptr, XH_E_HIP, "hipMemcpy D2H failed");
     return 0;
+}
+}  // namespace
+
+int xh_op_prompt_attn_ring(float* out, uint16_t* k_ring, uint16_t* v_ring, const float* q, const uint16_t* ks,
+                           const uint16_t* vs, const uint16_t* sink_ver, int m, int p0, int max_seq_len, int n_heads,
+                           int n_kv_heads, int nsplit) {
+    return op_prompt_attn_ring_any(out, k_ring, v_ring, q, ks, vs, sink_ver, m, p0, max_seq_len, n_heads, n_kv_heads, nsplit,
+                                   XH_F16);
+}
+int xh_op_prompt_attn_ring8(float* out, uint8_t* k_ring, uint8_t* v_ring, const float* q, const uint8_t* ks,
+                            const uint8_t* vs, const uint8_t* sink_ver, int m, int p0, int max_seq_len, int n_heads,
+                            int n_kv_heads, int nsplit) {
+    return op_prompt_attn_ring_any(out, k_ring, v_ring, q, ks, vs, sink_ver, m, p0, max_seq_len, n_heads, n_kv_heads, nsplit,
+                                   XH_F8_E4M3);
 }
 
 namespace {

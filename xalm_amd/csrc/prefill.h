@@ -539,8 +539,8 @@ struct PfEpiArgs {
     // [n][kv_dim] instead of the ring, which its attention still reads as it stood (null: the ring)
     uint16_t* kstage;
     uint16_t* vstage;
-    // EPI_QKV8 (an fp8 KV ring: kcache / vcache rows of kv_dim codes; no ring passes): the fp16
-    // master of K slots 0 and 1 [2][kv_dim]
+    // EPI_QKV8 (an fp8 KV ring: kcache / vcache — and kstage / vstage of a ring pass — rows of
+    // kv_dim codes): the fp16 master of K slots 0 and 1 [2][kv_dim]
     uint16_t* sink_master;
 };
 
@@ -586,6 +586,10 @@ __global__ __launch_bounds__(256) void prefill_epi_kernel(const PfEpiArgs a) {
             if (isk) rope_pair(v0, v1, kr, a.head_dim, pos, a.rope_freq);
             if (a.epi == EPI_QKV8) {  // two codes in one 2-byte store, as gemv_epilogue
                 const uint32_t pk8 = kv8_pack(v0, v1);
+                if (a.kstage) {  // a ring pass (pos >= max_seq_len: no master row): the same codes, staged
+                    *(uint16_t*)((uint8_t*)(isk ? a.kstage : a.vstage) + (size_t)t * a.kv_dim + kr) = (uint16_t)pk8;
+                    return;
+                }
                 *(uint16_t*)((uint8_t*)(isk ? a.kcache : a.vcache) + (size_t)pos * a.kv_dim + kr) = (uint16_t)pk8;
                 if (isk && pos < 2) *(uint32_t*)(a.sink_master + (size_t)pos * a.kv_dim + kr) = kv8_image_f16x2(pk8);
                 return;
@@ -917,12 +921,14 @@ typedef short fa_s16x4 __attribute__((ext_vector_type(4)));
 // the workgroup's own stage range evenly, so a split — or the whole walk — can be invisible
 // to a row; it then writes (m, l, O) = (-inf, 0, 0).
 struct FaRing {
-    const uint16_t* ks;  // [n][kv_dim] the pass's K rows (fp16, roped at their positions)
+    const uint16_t* ks;  // [n][kv_dim] the pass's K rows (fp16, roped at their positions; an fp8 ring: codes)
     const uint16_t* vs;
     int W;               // max_seq_len - 2
     int hoff;            // kv_pos(first position of the pass) - 2
 };
-// KV = XH_F8_E4M3 (RING = false only; the element type as at prefill_fa_kernel): the LDS image, its
+// KV = XH_F8_E4M3 (the element type as at prefill_fa_kernel; RING: the ring and the staging rows hold
+// codes, rows of kv_dim bytes, and code8's source row goes through the ring map as the DMA's does;
+// the masks, the walk's start stage, the splits and their partials are untouched): the LDS image, its
 // reads and all arithmetic are the fp16 kernel's; only the loader differs.  The lane that issues
 // the DMA of chunk dch[k] of row drow[k] loads the same 8 elements as 8 bytes of codes into
 // registers instead (code8), and writes their f16 image (fa_image8) by ds_write_b128 to the
@@ -939,7 +945,7 @@ template <int QPK, int NW, bool RING, int KV = XH_F16>
 __device__ __forceinline__ void fa2_body(const float* q, const uint16_t* kc, const uint16_t* vc, float* out, const int n,
                                          const int pos0, const int q_stride, const int kv_dim, float* part_o,
                                          float2* part_ml, const FaRing rg) {
-    static_assert(KV == XH_F16 || (KV == XH_F8_E4M3 && !RING), "prefill_fa2_kernel: KV element type");
+    static_assert(KV == XH_F16 || KV == XH_F8_E4M3, "prefill_fa2_kernel: KV element type");
     constexpr int HD = 128;
     constexpr int TPW = 32 / QPK;        // tokens per wave
     constexpr int KS = HD / 16;          // k steps of q . k
@@ -1019,8 +1025,19 @@ __device__ __forceinline__ void fa2_body(const float* q, const uint16_t* kc, con
     [[maybe_unused]] uint2 cr[HP];
     [[maybe_unused]] auto code8 = [&](const int st, const int k) {
         const int i = wv * IPW + k;
-        const uint8_t* src = (const uint8_t*)(((i >> 3) & 1) ? vc : kc) +
-                             (size_t)min(32 * FA_TPS * (st0 + st) + drow[k], last_wg) * kv_dim + (size_t)g * HD + 8 * dch[k];
+        const uint8_t* src;
+        if constexpr (RING) {  // issue()'s map, rows of kv_dim bytes
+            const int u = min(32 * FA_TPS * (st0 + st) + drow[k], last_wg);
+            const bool isv = (i >> 3) & 1;
+            int s = rg.hoff + u;
+            s = s >= rg.W ? s - rg.W : s;
+            src = u < rg.W ? (const uint8_t*)(isv ? vc : kc) + (size_t)(2 + s) * kv_dim
+                           : (const uint8_t*)(isv ? rg.vs : rg.ks) + (size_t)(u - rg.W) * kv_dim;
+            src += (size_t)g * HD + 8 * dch[k];
+        } else {
+            src = (const uint8_t*)(((i >> 3) & 1) ? vc : kc) +
+                  (size_t)min(32 * FA_TPS * (st0 + st) + drow[k], last_wg) * kv_dim + (size_t)g * HD + 8 * dch[k];
+        }
         return *(const uint2*)src;
     };
     [[maybe_unused]] auto image8 = [&](const int stage, const int k, const uint2 c) {
@@ -1169,12 +1186,12 @@ __global__ __launch_bounds__(64 * NW, 2) void prefill_fa2_kernel(const float* q,
     fa2_body<QPK, NW, false, KV>(q, kc, vc, out, n, pos0, q_stride, kv_dim, part_o, part_ml, FaRing{});
 }
 // the ring pass: n <= W query rows over the ring (kc / vc, untouched) and the staging rows
-template <int QPK, int NW>
+template <int QPK, int NW, int KV = XH_F16>
 __global__ __launch_bounds__(64 * NW, 2) void prefill_fa2_ring_kernel(const float* q, const uint16_t* kc,
                                                                     const uint16_t* vc, const FaRing rg, int n,
                                                                     int q_stride, int kv_dim, float* part_o,
                                                                     float2* part_ml) {
-    fa2_body<QPK, NW, true>(q, kc, vc, nullptr, n, rg.W, q_stride, kv_dim, part_o, part_ml, rg);
+    fa2_body<QPK, NW, true, KV>(q, kc, vc, nullptr, n, rg.W, q_stride, kv_dim, part_o, part_ml, rg);
 }
 
 // Every version of the two sink K rows a ring pass of m tokens goes through (src/infer.cpp:421-431:
@@ -1182,9 +1199,14 @@ __global__ __launch_bounds__(64 * NW, 2) void prefill_fa2_ring_kernel(const floa
 // attends): ver[t][r] = row r after t + 1 rotations of the ring's row, the K that token t scores
 // the sinks against; ver[m - 1] is what the pass leaves in the ring.  One thread per (row, pair),
 // sequential in t, on sink_rotate_pair — the decode step's arithmetic (gemv.h).
+// KV = XH_F8_E4M3 (rotate_sinks<THREADS, true>): kc is the layer's fp16 master [2][kv_dim], which
+// iterates exactly as above; ver holds codes, ver[t][r] = f8(master row r after t + 1 rotations)
+// (kv8_pack of the fp16 pair, as the decode step rewrites ring slot r), and the unrounded master
+// after the m-th rotation goes to mlast [2][kv_dim] for the commit.
+template <int KV = XH_F16>
 __global__ __launch_bounds__(256) void prefill_sink_versions_kernel(const uint16_t* kc, const float* sink_cos,
                                                                     const float* sink_sin, int kv_dim, int head_dim,
-                                                                    int m, uint16_t* ver) {
+                                                                    int m, uint16_t* ver, uint16_t* mlast) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= kv_dim) return;
     const int half = kv_dim >> 1;
@@ -1200,27 +1222,42 @@ __global__ __launch_bounds__(256) void prefill_sink_versions_kernel(const uint16
         asm volatile("" : "+v"(k0), "+v"(k1));
         b0 = f32_to_f16_bits(k0);
         b1 = f32_to_f16_bits(k1);
-        *(uint32_t*)(ver + ((size_t)2 * t + r) * kv_dim + i) = (uint32_t)b0 | ((uint32_t)b1 << 16);
+        if constexpr (KV == XH_F16)
+            *(uint32_t*)(ver + ((size_t)2 * t + r) * kv_dim + i) = (uint32_t)b0 | ((uint32_t)b1 << 16);
+        else
+            *(uint16_t*)((uint8_t*)ver + ((size_t)2 * t + r) * kv_dim + i) =
+                (uint16_t)kv8_pack(f16_bits_to_f32(b0), f16_bits_to_f32(b1));
     }
+    if constexpr (KV != XH_F16) *(uint32_t*)(mlast + (size_t)r * kv_dim + i) = (uint32_t)b0 | ((uint32_t)b1 << 16);
 }
 
 // After a layer's ring-pass attention: staging row t -> ring row 2 + (hoff + t) % W (K and V),
 // and the last sink version -> ring K rows 0 and 1.  grid m + 1 (the last block: the sinks);
 // kv_dim % 8 == 0 (head_dim 128).  m <= W: the rows are distinct.
+// KV = XH_F8_E4M3: rows of kv_dim codes (kv_dim % 128 == 0: whole 16-byte chunks); ver[m - 1] is
+// f8 of the last master version mlast, which goes to the layer's master (null: a ring without one),
+// so ring K slot r == f8(master[r]) again.
+template <int KV = XH_F16>
 __global__ __launch_bounds__(256) void prefill_ring_commit_kernel(const FaRing rg, const uint16_t* ver, uint16_t* kc,
-                                                                  uint16_t* vc, int m, int kv_dim) {
-    const int t = blockIdx.x, nch = kv_dim >> 3;
+                                                                  uint16_t* vc, int m, int kv_dim,
+                                                                  const uint16_t* mlast, uint16_t* master) {
+    constexpr int EPC = KV == XH_F16 ? 8 : 16;  // elements per 16-byte chunk
+    const int t = blockIdx.x, nch = kv_dim / EPC;
     if (t == m) {
-        const u32x4* src = (const u32x4*)(ver + (size_t)2 * (m - 1) * kv_dim);
+        const u32x4* src = (const u32x4*)fa_at<KV>(ver, (size_t)2 * (m - 1) * kv_dim);
         for (int i = threadIdx.x; i < 2 * nch; i += 256) ((u32x4*)kc)[i] = src[i];
+        if constexpr (KV != XH_F16) {
+            if (master)
+                for (int i = threadIdx.x; i < 2 * (kv_dim >> 3); i += 256) ((u32x4*)master)[i] = ((const u32x4*)mlast)[i];
+        }
         return;
     }
     int s = rg.hoff + t;
     s = s >= rg.W ? s - rg.W : s;
     const size_t dst = (size_t)(2 + s) * kv_dim, src = (size_t)t * kv_dim;
     for (int i = threadIdx.x; i < nch; i += 256) {
-        ((u32x4*)(kc + dst))[i] = ((const u32x4*)(rg.ks + src))[i];
-        ((u32x4*)(vc + dst))[i] = ((const u32x4*)(rg.vs + src))[i];
+        ((u32x4*)fa_at<KV>(kc, dst))[i] = ((const u32x4*)fa_at<KV>(rg.ks, src))[i];
+        ((u32x4*)fa_at<KV>(vc, dst))[i] = ((const u32x4*)fa_at<KV>(rg.vs, src))[i];
     }
 }
 
@@ -1235,11 +1272,14 @@ __global__ __launch_bounds__(256) void prefill_ring_commit_kernel(const FaRing r
 constexpr int FA_MERGE_GROUPS = 8;
 struct FaSinks {
     const float* q;       // [n][q_stride]
-    const uint16_t* ver;  // [n][2][kv_dim] (prefill_sink_versions_kernel)
-    const uint16_t* vc;   // the ring's V rows
+    const uint16_t* ver;  // [n][2][kv_dim] (prefill_sink_versions_kernel; KV = XH_F8_E4M3: codes)
+    const uint16_t* vc;   // the ring's V rows (likewise)
     int kv_dim, qpk;
 };
-template <bool SINKS>
+// KV = XH_F8_E4M3 (SINKS only): ver and the ring's V rows hold e4m3 codes, decoded to f32 exactly by
+// the gfx950 converter — the f32 the fp16 form gets from the codes' f16 image — so the sums are
+// the fp16 form's, operand for operand and in its order.
+template <bool SINKS, int KV = XH_F16>
 __global__ __launch_bounds__(256) void prefill_fa_merge_kernel(const float* part_o, const float2* part_ml, float* out,
                                                                int n, int nsplit, int q_stride, const FaSinks sk) {
     constexpr int G = FA_MERGE_GROUPS;
@@ -1254,8 +1294,14 @@ __global__ __launch_bounds__(256) void prefill_fa_merge_kernel(const float* part
         __shared__ float sdot[4];
         const int r = threadIdx.x >> 7, d = threadIdx.x & 127;
         const size_t koff = (size_t)(head / sk.qpk) * 128 + d;
-        float pr = sk.q[(size_t)t * q_stride + (size_t)head * 128 + d] *
-                   f16_bits_to_f32(sk.ver[((size_t)2 * t + r) * sk.kv_dim + koff]);
+        const size_t voff = ((size_t)2 * t + r) * sk.kv_dim + koff;
+        float kv;
+        if constexpr (KV == XH_F16) kv = f16_bits_to_f32(sk.ver[voff]);
+        else {
+            const f2_t c2 = __builtin_amdgcn_cvt_pk_f32_fp8((uint32_t)((const uint8_t*)sk.ver)[voff], false);
+            kv = c2.x;
+        }
+        float pr = sk.q[(size_t)t * q_stride + (size_t)head * 128 + d] * kv;
         pr = wave_sum(pr);
         if ((threadIdx.x & 63) == 0) sdot[threadIdx.x >> 6] = pr;
         __syncthreads();
@@ -1296,12 +1342,22 @@ __global__ __launch_bounds__(256) void prefill_fa_merge_kernel(const float* part
 #pragma unroll
             for (int r = 0; r < 2; r++) {
                 const float w = __expf(ss[r] - M);
-                const uint2 u = *(const uint2*)(sk.vc + (size_t)r * sk.kv_dim + (size_t)(head / sk.qpk) * 128 + 4 * c);
+                const size_t voff = (size_t)r * sk.kv_dim + (size_t)(head / sk.qpk) * 128 + 4 * c;
                 den += w;
-                s4.x += w * f16_bits_to_f32((uint16_t)(u.x & 0xffffu));
-                s4.y += w * f16_bits_to_f32((uint16_t)(u.x >> 16));
-                s4.z += w * f16_bits_to_f32((uint16_t)(u.y & 0xffffu));
-                s4.w += w * f16_bits_to_f32((uint16_t)(u.y >> 16));
+                if constexpr (KV == XH_F16) {
+                    const uint2 u = *(const uint2*)(sk.vc + voff);
+                    s4.x += w * f16_bits_to_f32((uint16_t)(u.x & 0xffffu));
+                    s4.y += w * f16_bits_to_f32((uint16_t)(u.x >> 16));
+                    s4.z += w * f16_bits_to_f32((uint16_t)(u.y & 0xffffu));
+                    s4.w += w * f16_bits_to_f32((uint16_t)(u.y >> 16));
+                } else {
+                    const uint32_t u = *(const uint32_t*)((const uint8_t*)sk.vc + voff);
+                    const f2_t a = __builtin_amdgcn_cvt_pk_f32_fp8(u, false), b = __builtin_amdgcn_cvt_pk_f32_fp8(u, true);
+                    s4.x += w * a.x;
+                    s4.y += w * a.y;
+                    s4.z += w * b.x;
+                    s4.w += w * b.y;
+                }
             }
         }
         const float inv_l = 1.f / den;

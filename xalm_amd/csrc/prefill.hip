@@ -83,9 +83,12 @@ int pf_alloc_group(xh_ctx* ctx, const int g) {
         get(&b.pml, t * ctx->nsplit * ctx->c.n_heads * 2);
         get(&b.cnt, t * ctx->c.n_kv_heads);
     } else if (g == PfBufs::RING) {
-        get(&b.ks, t * ctx->kv_dim);
-        get(&b.vs, t * ctx->kv_dim);
-        get(&b.sinkv, t * 2 * ctx->kv_dim);
+        // rows of the ring's element type (an fp8 ring: kv_dim codes, kv_dim / 2 uint16_t)
+        const size_t row = ctx->kv_dim * ctx->kv_esz() / 2;
+        get(&b.ks, t * row);
+        get(&b.vs, t * row);
+        get(&b.sinkv, t * 2 * row);
+        if (ctx->kv8()) get(&b.sinkm, (size_t)2 * ctx->kv_dim);
     } else {
         get(&b.logits, t * ctx->c.vocab_size);
         get(&b.tgt, t);
@@ -449,9 +452,12 @@ int pf_fa_hd(const PfAttnDims& d, int kv_dt, bool shared, const float* q, const 
 }
 // The attention of a ring pass after its sink versions, on device pointers (head_dim 128): the
 // window walk into split partials, the merge that adds the sinks, the commit to the ring.
-template <int QPK>
+// KV: the element type behind every K/V buffer (XH_F8_E4M3: one code per element; sinkm / master:
+// the fp16 master's last version and its home, both null for a ring without a master).
+template <int QPK, int KV>
 int pf_ring_t(const PfAttnDims& d, const float* q, uint16_t* kc, uint16_t* vc, const uint16_t* ks, const uint16_t* vs,
-              const uint16_t* sinkv, float* out, int m, int p0, int max_seq_len, int nsplit, float* part, hipStream_t s) {
+              const uint16_t* sinkv, float* out, int m, int p0, int max_seq_len, int nsplit, float* part, hipStream_t s,
+              const uint16_t* sinkm, uint16_t* master) {
     constexpr int NW = PF_FA_WAVES;
     const int W = max_seq_len - 2;
     const int q_dim = d.n_heads * 128, kv_dim = d.n_kv_heads * 128;
@@ -459,14 +465,15 @@ int pf_ring_t(const PfAttnDims& d, const float* q, uint16_t* kc, uint16_t* vc, c
     const int nqt = fa2_query_tiles(m, QPK);
     float* po = part;
     float2* pml = (float2*)(part + (size_t)nsplit * m * q_dim);
-    auto k = prefill_fa2_ring_kernel<QPK, NW>;
+    auto k = prefill_fa2_ring_kernel<QPK, NW, KV>;
     ensure_lds((const void*)k);
     hipLaunchKernelGGL(k, dim3(d.n_kv_heads, nqt, nsplit), dim3(64 * NW), fa_lds_bytes(), s, q, (const uint16_t*)kc,
                        (const uint16_t*)vc, rg, m, q_dim, kv_dim, po, pml);
     const FaSinks sk{q, sinkv, vc, kv_dim, QPK};
-    hipLaunchKernelGGL(prefill_fa_merge_kernel<true>, dim3(d.n_heads, m), dim3(256), 0, s, (const float*)po,
+    hipLaunchKernelGGL((prefill_fa_merge_kernel<true, KV>), dim3(d.n_heads, m), dim3(256), 0, s, (const float*)po,
                        (const float2*)pml, out, m, nsplit, q_dim, sk);
-    hipLaunchKernelGGL(prefill_ring_commit_kernel, dim3(m + 1), dim3(256), 0, s, rg, sinkv, kc, vc, m, kv_dim);
+    hipLaunchKernelGGL(prefill_ring_commit_kernel<KV>, dim3(m + 1), dim3(256), 0, s, rg, sinkv, kc, vc, m, kv_dim, sinkm,
+                       master);
     return 0;
 }
 
@@ -653,12 +660,17 @@ int xalm::pf_fa_launch(const PfAttnDims& d, int kv_dt, bool shared, const float*
            : d.head_dim == 16 ? pf_fa_hd<16>(d, kv_dt, shared, q, kc, vc, out, n, pos0, nsplit, part, s)
                               : -1;
 }
-int xalm::pf_ring_launch(const PfAttnDims& d, const float* q, uint16_t* kc, uint16_t* vc, const uint16_t* ks,
+int xalm::pf_ring_launch(const PfAttnDims& d, int kv_dt, const float* q, uint16_t* kc, uint16_t* vc, const uint16_t* ks,
                          const uint16_t* vs, const uint16_t* sinkv, float* out, int m, int p0, int max_seq_len, int nsplit,
-                         float* part, hipStream_t s) {
-    if (d.head_dim != 128 || d.n_kv_heads <= 0 || d.n_heads % d.n_kv_heads) return -1;
+                         float* part, hipStream_t s, const uint16_t* sinkm, uint16_t* master) {
+    if (d.head_dim != 128 || d.n_kv_heads <= 0 || d.n_heads % d.n_kv_heads || (kv_dt != XH_F16 && kv_dt != XH_F8_E4M3))
+        return -1;
     return for_qpk(d.n_heads / d.n_kv_heads, [&](auto Q) {
-        return pf_ring_t<decltype(Q)::value>(d, q, kc, vc, ks, vs, sinkv, out, m, p0, max_seq_len, nsplit, part, s);
+        constexpr int QPK = decltype(Q)::value;
+        if (kv_dt == XH_F8_E4M3)
+            return pf_ring_t<QPK, XH_F8_E4M3>(d, q, kc, vc, ks, vs, sinkv, out, m, p0, max_seq_len, nsplit, part, s, sinkm,
+                                              master);
+        return pf_ring_t<QPK, XH_F16>(d, q, kc, vc, ks, vs, sinkv, out, m, p0, max_seq_len, nsplit, part, s, nullptr, nullptr);
     });
 }
 
@@ -721,11 +733,18 @@ int pf_attn_ring(xh_ctx* ctx, int l, int m, int p0) {
     if (pf_fa_part_floats(d, nsplit, m) > pf_part_floats(ctx, ctx->pf.cap[PfBufs::PASS]))
         return set_err(ctx, XH_E_INVALID, "prefill: the ring pass's attention partials do not fit");
     uint16_t *kc = ctx->kcache(l), *vc = ctx->vcache(l);
-    hipLaunchKernelGGL(prefill_sink_versions_kernel, dim3((ctx->kv_dim + 255) / 256), dim3(256), 0, ctx->stream,
-                       (const uint16_t*)kc, (const float*)ctx->sink_cos, (const float*)ctx->sink_sin, ctx->kv_dim,
-                       ctx->c.head_dim, m, ctx->pf.sinkv);
-    const int rc = pf_ring_launch(d, ctx->pf.q, kc, vc, ctx->pf.ks, ctx->pf.vs, ctx->pf.sinkv, ctx->pf.att, m, p0,
-                                  ctx->c.max_seq_len, nsplit, ctx->pf.part, ctx->stream);
+    const dim3 vgrid((ctx->kv_dim + 255) / 256);
+    if (ctx->kv8())  // the sinks iterate in the layer's fp16 master; the versions are its codes
+        hipLaunchKernelGGL(prefill_sink_versions_kernel<XH_F8_E4M3>, vgrid, dim3(256), 0, ctx->stream,
+                           (const uint16_t*)ctx->master(l), (const float*)ctx->sink_cos, (const float*)ctx->sink_sin,
+                           ctx->kv_dim, ctx->c.head_dim, m, ctx->pf.sinkv, ctx->pf.sinkm);
+    else
+        hipLaunchKernelGGL(prefill_sink_versions_kernel<XH_F16>, vgrid, dim3(256), 0, ctx->stream, (const uint16_t*)kc,
+                           (const float*)ctx->sink_cos, (const float*)ctx->sink_sin, ctx->kv_dim, ctx->c.head_dim, m,
+                           ctx->pf.sinkv, (uint16_t*)nullptr);
+    const int rc = pf_ring_launch(d, ctx->kv_dt, ctx->pf.q, kc, vc, ctx->pf.ks, ctx->pf.vs, ctx->pf.sinkv, ctx->pf.att, m, p0,
+                                  ctx->c.max_seq_len, nsplit, ctx->pf.part, ctx->stream, ctx->pf.sinkm,
+                                  ctx->kv8() ? ctx->master(l) : nullptr);
     return rc < 0 ? set_err(ctx, XH_E_INVALID, "prefill: head shape not instantiated") : rc;
 }
 
@@ -741,9 +760,11 @@ bool pf_supported(const xh_ctx* ctx) {
 }
 // Ring passes (positions >= max_seq_len): the shared-tile attention's head shape only
 // (prefill_fa2_ring_kernel is head_dim 128), and a ring with at least two slots behind the sinks
-// An fp8 KV ring has none: the pass would need the sinks' master versions and fp8 staging rows.
+// An fp8 KV ring has them under XH_OPT_PREFILL_RING_KV8 on top of XH_OPT_PREFILL_ATTN_KV8 only (the
+// ring kernels' fp8 form: staged codes, the sinks' versions from their fp16 master).
 bool pf_ring_ok(const xh_ctx* ctx) {
-    return ctx->pf_ring && !ctx->kv8() && ctx->c.head_dim == 128 && ctx->pf_attn_mode == 1 && ctx->c.max_seq_len - 2 >= 2;
+    if (ctx->kv8() && !(ctx->pf_ring_kv8 && ctx->pf_attn_kv8)) return false;
+    return ctx->pf_ring && ctx->c.head_dim == 128 && ctx->pf_attn_mode == 1 && ctx->c.max_seq_len - 2 >= 2;
 }
 
 // How a prompt of n tokens at pos0 runs: pieces in order, each batched (PF_RING: ring passes of at
@@ -762,7 +783,7 @@ void pf_plan(const xh_ctx* ctx, int n, int pos0, int min_n, std::vector<PfPiece>
     const int L = ctx->c.max_seq_len;
     out.clear();
     const bool wraps = pos0 > L - n;  // pos0 + n > L
-    // an fp8 KV ring batches the part below L and takes the loop from the cut
+    // an fp8 KV ring without ring passes batches the part below L and takes the loop from the cut
     if (!pf_supported(ctx) || (wraps && !pf_ring_ok(ctx) && !ctx->kv8())) {
         out.push_back({0, n, PF_LOOP, 0});
         return;

@@ -357,6 +357,7 @@ int xh_get_option(const xh_ctx* ctx, int option, int* value) {
         case XH_OPT_PREFILL_ATTN_SPLIT: *value = ctx->pf_fa_split; return 0;
         case XH_OPT_PREFILL_RING: *value = ctx->pf_ring ? 1 : 0; return 0;
         case XH_OPT_PREFILL_ATTN_KV8: *value = ctx->pf_attn_kv8 ? 1 : 0; return 0;
+        case XH_OPT_PREFILL_RING_KV8: *value = ctx->pf_ring_kv8 ? 1 : 0; return 0;
         default: return XH_E_INVALID;
     }
 }
@@ -394,6 +395,10 @@ int xh_set_option(xh_ctx* ctx, int option, int value) {
         case XH_OPT_PREFILL_ATTN_KV8:
             if (value < 0 || value > 1) return set_err(ctx, XH_E_INVALID, "XH_OPT_PREFILL_ATTN_KV8: 0 or 1");
             ctx->pf_attn_kv8 = value != 0;
+            return 0;
+        case XH_OPT_PREFILL_RING_KV8:
+            if (value < 0 || value > 1) return set_err(ctx, XH_E_INVALID, "XH_OPT_PREFILL_RING_KV8: 0 or 1");
+            ctx->pf_ring_kv8 = value != 0;
             return 0;
         default: return set_err(ctx, XH_E_INVALID, "unknown option %d", option);
     }

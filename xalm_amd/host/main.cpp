@@ -49,12 +49,14 @@ using namespace xalm;
 using clk = std::chrono::steady_clock;
 
 static int g_kv_dtype = XH_F16;  // -K: the KV rings' element type
-static int g_attn_kv8 = 0;       // -a: XH_OPT_PREFILL_ATTN_KV8
+static int g_attn_kv8 = 0;       // -a: 1 = XH_OPT_PREFILL_ATTN_KV8, 2 = that and XH_OPT_PREFILL_RING_KV8
 
-// the model of a run: -K's rings, -a's prompt attention on them
+// the model of a run: -K's rings, -a's prompt attention (and ring passes) on them
 static Model load_model(const XalmFile& file, int context, Device dev) {
     Model model = Model::from_xalm(file, context, dev, 0, g_kv_dtype);
-    if (g_attn_kv8 && xh_set_option(model.ctx(), XH_OPT_PREFILL_ATTN_KV8, g_attn_kv8) != 0)
+    const bool ring = g_attn_kv8 == 2;
+    if (g_attn_kv8 && (xh_set_option(model.ctx(), XH_OPT_PREFILL_ATTN_KV8, ring ? 1 : g_attn_kv8) != 0 ||
+                       (ring && xh_set_option(model.ctx(), XH_OPT_PREFILL_RING_KV8, 1) != 0)))
         throw std::runtime_error(std::string("-a: ") + xh_last_error(model.ctx()));
     return model;
 }
@@ -70,7 +72,8 @@ static void error_usage() {
     fprintf(stderr, "  -n <int> number of steps in completion mode, default 128. 0 = max_seq_len, -1 = infinite\n");
     fprintf(stderr, "  -g <0|1> decode loop on the device (default 0)\n");
     fprintf(stderr, "  -K [f16,f8] KV ring element type (default f16; f8 = e4m3, hip only)\n");
-    fprintf(stderr, "  -a <0|1> with -K f8: prompt attention on the MFMA kernels' fp8 tiles (default 0, hip only)\n");
+    fprintf(stderr, "  -a <0|1|2> with -K f8: 1 = prompt attention on the MFMA kernels' fp8 tiles, 2 = that and batched\n");
+    fprintf(stderr, "     ring passes past the context length (default 0, hip only)\n");
     fprintf(stderr, "  -t <float> sampling temperature (default 0 - greedy)\n");
     fprintf(stderr, "  -k <int> top-k, 0 = off (default 0)\n");
     fprintf(stderr, "  -p <float> top-p in (0, 1], 1 = off (default 1)\n");
