@@ -118,6 +118,14 @@ struct SeqTail {
 
 constexpr int ARGMAX_CANDS = 1024;  // the lm_head workgroups' argmax keys (argmax_embed_kernel's block size)
 
+// The kinds of per-token step (decode.hip).  A kind names the step's head, the launch that puts its
+// token in place, and with it the captured graph in xh_ctx::g_step: STEP_LOGITS and STEP_HYDRATE run a
+// token the host gave, with and without the lm_head; the others are the decode loop's steps, the token
+// chosen on the device under the greedy, sampled, extended, constrained, adaptive or sequence-aware
+// head.  The sampled heads are cumulative: each takes the parameter blocks of the one before it.
+enum StepKind { STEP_LOGITS, STEP_HYDRATE, STEP_GREEDY, STEP_SAMPLE, STEP_SAMPLE_EXT, STEP_SAMPLE_DFA, STEP_SAMPLE_ADAPT,
+                STEP_SAMPLE_SEQ, N_STEP_KINDS };
+
 // The batched prefill's device buffers (prefill.hip), in growth groups.  T = cap[PASS] tokens, the
 // pass length in use: a longer pass frees every group and reallocates PASS; the others are
 // allocated on their first use and sized to T.
@@ -267,8 +275,7 @@ struct xh_ctx {
     int ppl_cap = 0;
     int t_max_aw = 16;
     bool use_graphs = true;
-    hipGraphExec_t g_logits = nullptr, g_hydrate = nullptr, g_decode = nullptr, g_sample = nullptr,
-                   g_sample_ext = nullptr, g_sample_dfa = nullptr, g_sample_adapt = nullptr, g_sample_seq = nullptr;
+    hipGraphExec_t g_step[xalm::N_STEP_KINDS] = {};  // the captured step of each kind (null: not captured yet)
     int max_gemv_waves = 4096;  // 16 waves per CU
     // the qkv launch: its whole matrix is one round at 16 waves per CU (every wave one group,
     // requested at once); at 8 waves per CU each wave streams two groups back to back
@@ -392,11 +399,7 @@ int check_aw(xh_ctx* ctx);
 void drop_graphs(xh_ctx* ctx);
 int host_step_params(xh_ctx* ctx, int token, int pos);
 int run_step(xh_ctx* ctx, bool with_logits);
-void time_sample_head(xh_ctx* ctx);  // one sample_embed_kernel launch on ctx->stream (xh_time_kernel 6)
-void time_sample_ext_head(xh_ctx* ctx);  // one sample_ext_embed_kernel launch (xh_time_kernel 7)
-void time_sample_dfa_head(xh_ctx* ctx);  // one sample_dfa_embed_kernel launch (xh_time_kernel 8)
-void time_sample_adapt_head(xh_ctx* ctx);  // one sample_adapt_embed_kernel launch (xh_time_kernel 10)
-void time_sample_seq_head(xh_ctx* ctx);    // one sample_seq_embed_kernel launch (xh_time_kernel 11)
+void time_head(xh_ctx* ctx, StepKind head);  // one launch of the head's kernel on ctx->stream (xh_time_kernel 6 .. 8, 10, 11)
 // top_logprobs_kernel (top_logprobs.h; defined in decode.hip) over n_rows rows on stream s: the
 // kernel's arguments in its order
 void launch_top_logprobs(const float* logits, int vocab, size_t stride, int n_rows, const int* n_top_dev, int n_top,

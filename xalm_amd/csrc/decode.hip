@@ -1,5 +1,8 @@
-// decode.hip — the per-token step: argument builders, the fused attention + Wo launch, graph
-// capture and replay, and the ABI entries that run it (xh_forward, xh_decode_greedy, xh_get_logits).
+// decode.hip — the per-token step: its kernels, argument builders, the fused attention + Wo launch,
+// and one graph per StepKind (ctx.h), captured on first use and replayed.  The decode ABI entries
+// (xh_decode_greedy, xh_decode_sample, _ext, _dfa, _adapt, _seq) fill a DecodeCall and run the one
+// driver, decode_run; the xh_op_sample* entries share their argument checks, device staging and
+// copy-back.  Also here: xh_forward, xh_get_logits, the constraint and top-logprobs entries.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -285,37 +288,6 @@ namespace {
 // ---------------------------------------------------------------------------------------
 bool layer_traced(const xh_ctx* ctx, int l) { return ctx->layer_trace_on && l == ctx->c.n_layers - 1; }
 
-__global__ void argmax_advance_kernel(const float* logits, int vocab, StepParams* sp, int* tokens, int cap) {
-    // Sampler::sample_argmax (src/sampler.cpp:19-30): max starts at FLT_MIN, strict '>',
-    // so the first index of the maximum wins and all-tiny logits give token 0.
-    __shared__ float bv[1024];
-    __shared__ int bi[1024];
-    const int tid = threadIdx.x;
-    float best = FLT_MIN;
-    int idx = 0;
-    for (int i = tid; i < vocab; i += blockDim.x)
-        if (logits[i] > best) { best = logits[i]; idx = i; }
-    bv[tid] = best;
-    bi[tid] = idx;
-    __syncthreads();
-    for (int o = blockDim.x / 2; o > 0; o >>= 1) {
-        if (tid < o) {
-            const float v2 = bv[tid + o];
-            const int i2 = bi[tid + o];
-            if (v2 > bv[tid] || (v2 == bv[tid] && i2 < bi[tid])) { bv[tid] = v2; bi[tid] = i2; }
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const int tok = bi[0];
-        if (sp->step < cap) tokens[sp->step] = tok;
-        sp->step += 1;
-        sp->token = tok;
-        step_positions(sp, sp->pos_next);
-        sp->pos_next += 1;
-    }
-}
-
 bool use_attn_wo(const xh_ctx* ctx, int l) {
     const int dt = ctx->L[l].wo_dt;
     if (ctx->L[l].wo_x) return false;  // exact fp8 decode: the separate launches
@@ -342,44 +314,74 @@ int launch_attn_wo(xh_ctx* ctx, int l, hipStream_t s) {
     }
 }
 
-// head: HEAD_GREEDY = the token is the argmax of the previous step's logits (argmax_embed_kernel),
-// HEAD_SAMPLE = drawn from them under ctx->samp (sample_embed_kernel), HEAD_SAMPLE_EXT = drawn from
-// their adjusted copy under ctx->ext (sample_ext_embed_kernel)
-// HEAD_SAMPLE_DFA = drawn from their adjusted and masked copy under ctx->ext and ctx->dfa
-// (sample_dfa_embed_kernel), HEAD_SAMPLE_ADAPT = the same under ctx->adapt's truncation stages
-// (sample_adapt_embed_kernel), HEAD_SAMPLE_SEQ = the same with ctx->seq's sequence stage and XTC
-// (sample_seq_embed_kernel)
-enum StepHead { HEAD_GIVEN = 0, HEAD_GREEDY = 1, HEAD_SAMPLE = 2, HEAD_SAMPLE_EXT = 3, HEAD_SAMPLE_DFA = 4, HEAD_SAMPLE_ADAPT = 5,
-                HEAD_SAMPLE_SEQ = 6 };
-void launch_sample_head(xh_ctx* ctx, hipStream_t s);
-void launch_sample_ext_head(xh_ctx* ctx, hipStream_t s);
-void launch_sample_dfa_head(xh_ctx* ctx, hipStream_t s);
-void launch_sample_adapt_head(xh_ctx* ctx, hipStream_t s);
-void launch_sample_seq_head(xh_ctx* ctx, hipStream_t s);
-int enqueue_step(xh_ctx* ctx, hipStream_t s, bool with_logits, int head = HEAD_GIVEN) {
+// The head of a step of `kind` (StepKind, ctx.h), the launch that puts the step's token, positions and
+// x = embed[token] in place:
+//   STEP_LOGITS, STEP_HYDRATE  the token host_step_params gave (embed_kernel)
+//   STEP_GREEDY                the argmax of the previous step's logits (argmax_embed_kernel)
+//   STEP_SAMPLE                drawn from them under ctx->samp (sample_embed_kernel)
+//   STEP_SAMPLE_EXT            drawn from their adjusted copy under ctx->ext (sample_ext_embed_kernel)
+//   STEP_SAMPLE_DFA            ... adjusted and masked under ctx->ext and ctx->dfa (sample_dfa_embed_kernel)
+//   STEP_SAMPLE_ADAPT          the same under ctx->adapt's truncation stages (sample_adapt_embed_kernel)
+//   STEP_SAMPLE_SEQ            the same with ctx->seq's sequence stage and XTC (sample_seq_embed_kernel)
+void launch_head(xh_ctx* ctx, StepKind kind, hipStream_t s) {
+    const xh_config& c = ctx->c;
+    const float* logits = ctx->logits;
+    const void* emb = ctx->embed;
+    const float* rope_freq = ctx->rope_freq;
+    const int* btok = ctx->ext_btok;
+    const float* bval = ctx->ext_bval;
+    const int half = c.head_dim / 2;
+    switch (kind) {
+        case STEP_LOGITS:
+        case STEP_HYDRATE:
+            hipLaunchKernelGGL(embed_kernel, dim3((c.dim + 255) / 256), dim3(256), 0, s, emb, ctx->embed_dt, c.dim, ctx->x,
+                               (const StepParams*)ctx->sp, rope_freq, ctx->rope_cs, half);
+            break;
+        case STEP_GREEDY:
+            hipLaunchKernelGGL(argmax_embed_kernel, dim3(1), dim3(ARGMAX_CANDS), 0, s, (const unsigned long long*)ctx->cand,
+                               ctx->sp, ctx->dec_tokens, ctx->dec_cap, emb, ctx->embed_dt, c.dim, ctx->x, rope_freq,
+                               ctx->rope_cs, half);
+            break;
+        case STEP_SAMPLE:
+            hipLaunchKernelGGL(sample_embed_kernel, dim3(1), dim3(SMP_THREADS), 0, s, logits, c.vocab_size,
+                               (const xh_sampling*)ctx->samp, ctx->sp, ctx->dec_tokens, ctx->dec_cap, emb, ctx->embed_dt,
+                               c.dim, ctx->x, rope_freq, ctx->rope_cs, half);
+            break;
+        case STEP_SAMPLE_EXT:
+            hipLaunchKernelGGL(sample_ext_embed_kernel, dim3(1), dim3(SMP_THREADS), 0, s, logits, c.vocab_size, ctx->ext,
+                               ctx->ext_ring, btok, bval, ctx->ext_adj, ctx->sp, ctx->dec_tokens, ctx->dec_logprobs,
+                               ctx->dec_cap, emb, ctx->embed_dt, c.dim, ctx->x, rope_freq, ctx->rope_cs, half);
+            break;
+        case STEP_SAMPLE_DFA:
+            hipLaunchKernelGGL(sample_dfa_embed_kernel, dim3(1), dim3(SMP_THREADS), 0, s, logits, c.vocab_size, ctx->ext,
+                               ctx->dfa, ctx->ext_ring, btok, bval, ctx->ext_adj, ctx->sp, ctx->dec_tokens,
+                               ctx->dec_logprobs, ctx->dec_states, ctx->dec_cap, emb, ctx->embed_dt, c.dim, ctx->x,
+                               rope_freq, ctx->rope_cs, half);
+            break;
+        case STEP_SAMPLE_ADAPT:
+            hipLaunchKernelGGL(sample_adapt_embed_kernel, dim3(1), dim3(SMP_THREADS), 0, s, logits, c.vocab_size, ctx->ext,
+                               ctx->dfa, ctx->adapt, ctx->ext_ring, btok, bval, ctx->ext_adj, ctx->adapt_negd, ctx->sp,
+                               ctx->dec_tokens, ctx->dec_logprobs, ctx->dec_states, ctx->dec_cap, emb, ctx->embed_dt, c.dim,
+                               ctx->x, rope_freq, ctx->rope_cs, half);
+            break;
+        case STEP_SAMPLE_SEQ:
+            hipLaunchKernelGGL(sample_seq_embed_kernel, dim3(1), dim3(SMP_THREADS), 0, s, logits, c.vocab_size, ctx->ext,
+                               ctx->dfa, ctx->adapt, (const SeqCtl*)ctx->seq, ctx->ext_ring, btok, bval,
+                               (const int*)ctx->seq_brk, ctx->ext_adj, ctx->adapt_negd, ctx->sp,
+                               (const SeqTail*)ctx->seq_tail);
+            break;
+        case N_STEP_KINDS: break;
+    }
+}
+
+// one step of `kind`: its head, the layers, and the lm_head unless the step only hydrates the KV ring
+int enqueue_step(xh_ctx* ctx, hipStream_t s, StepKind kind) {
     const xh_config& c = ctx->c;
     const int mb = ctx->max_gemv_waves;
-    if (head == HEAD_SAMPLE_SEQ)
-        launch_sample_seq_head(ctx, s);
-    else if (head == HEAD_SAMPLE_ADAPT)
-        launch_sample_adapt_head(ctx, s);
-    else if (head == HEAD_SAMPLE_DFA)
-        launch_sample_dfa_head(ctx, s);
-    else if (head == HEAD_SAMPLE_EXT)
-        launch_sample_ext_head(ctx, s);
-    else if (head == HEAD_SAMPLE)
-        launch_sample_head(ctx, s);
-    else if (head == HEAD_GREEDY)
-        hipLaunchKernelGGL(argmax_embed_kernel, dim3(1), dim3(ARGMAX_CANDS), 0, s, (const unsigned long long*)ctx->cand,
-                           ctx->sp, ctx->dec_tokens, ctx->dec_cap, (const void*)ctx->embed, ctx->embed_dt, c.dim,
-                           ctx->x, (const float*)ctx->rope_freq, ctx->rope_cs, c.head_dim / 2);
-    else
-        hipLaunchKernelGGL(embed_kernel, dim3((c.dim + 255) / 256), dim3(256), 0, s, (const void*)ctx->embed,
-                           ctx->embed_dt, c.dim, ctx->x, (const StepParams*)ctx->sp, (const float*)ctx->rope_freq,
-                           ctx->rope_cs, c.head_dim / 2);
-    // xh_set_top_logprobs: the row kernel on the raw logits the head chose from (the lm_head at the
-    // end of this step is their next writer), as row sp->step - 1 with the head's token as target
-    if (head != HEAD_GIVEN && ctx->top_n > 0)
+    launch_head(ctx, kind, s);
+    // xh_set_top_logprobs: the row kernel on the raw logits a decode head chose from (the lm_head at
+    // the end of this step is their next writer), as row sp->step - 1 with the head's token as target
+    if (kind >= STEP_GREEDY && ctx->top_n > 0)
         launch_top_logprobs(ctx->logits, c.vocab_size, 0, 1, ctx->top_n_dev, 0, ctx->sp, ctx->dec_cap, ctx->dec_tokens,
                             XH_TOP_MAX, ctx->top_ids, ctx->top_lps, ctx->top_tlp, ctx->top_rank, s);
     for (int l = 0; l < c.n_layers; l++) {
@@ -403,7 +405,7 @@ int enqueue_step(xh_ctx* ctx, hipStream_t s, bool with_logits, int head = HEAD_G
         if (!launch_gemv(GEMV_RESID, kdt(w.w2_dt, w.w2_x), w2_args(ctx, l), s, mb))
             return set_err(ctx, XH_E_INVALID, "layer %d: unsupported w2 dtype", l);
     }
-    if (with_logits) {
+    if (kind != STEP_HYDRATE) {
         if (!launch_gemv(GEMV_LOGITS, kdt(ctx->wcls_dt, ctx->wcls_x), cls_args(ctx), s, mb))
             return set_err(ctx, XH_E_INVALID, "unsupported wcls dtype");
     }
@@ -411,57 +413,15 @@ int enqueue_step(xh_ctx* ctx, hipStream_t s, bool with_logits, int head = HEAD_G
     return 0;
 }
 
-void launch_sample_head(xh_ctx* ctx, hipStream_t s) {
-    const xh_config& c = ctx->c;
-    hipLaunchKernelGGL(sample_embed_kernel, dim3(1), dim3(SMP_THREADS), 0, s, (const float*)ctx->logits, c.vocab_size,
-                       (const xh_sampling*)ctx->samp, ctx->sp, ctx->dec_tokens, ctx->dec_cap, (const void*)ctx->embed,
-                       ctx->embed_dt, c.dim, ctx->x, (const float*)ctx->rope_freq, ctx->rope_cs, c.head_dim / 2);
-}
-
-void launch_sample_ext_head(xh_ctx* ctx, hipStream_t s) {
-    const xh_config& c = ctx->c;
-    hipLaunchKernelGGL(sample_ext_embed_kernel, dim3(1), dim3(SMP_THREADS), 0, s, (const float*)ctx->logits, c.vocab_size,
-                       ctx->ext, ctx->ext_ring, (const int*)ctx->ext_btok, (const float*)ctx->ext_bval, ctx->ext_adj,
-                       ctx->sp, ctx->dec_tokens, ctx->dec_logprobs, ctx->dec_cap, (const void*)ctx->embed, ctx->embed_dt,
-                       c.dim, ctx->x, (const float*)ctx->rope_freq, ctx->rope_cs, c.head_dim / 2);
-}
-
-void launch_sample_dfa_head(xh_ctx* ctx, hipStream_t s) {
-    const xh_config& c = ctx->c;
-    hipLaunchKernelGGL(sample_dfa_embed_kernel, dim3(1), dim3(SMP_THREADS), 0, s, (const float*)ctx->logits, c.vocab_size,
-                       ctx->ext, ctx->dfa, ctx->ext_ring, (const int*)ctx->ext_btok, (const float*)ctx->ext_bval,
-                       ctx->ext_adj, ctx->sp, ctx->dec_tokens, ctx->dec_logprobs, ctx->dec_states, ctx->dec_cap,
-                       (const void*)ctx->embed, ctx->embed_dt, c.dim, ctx->x, (const float*)ctx->rope_freq, ctx->rope_cs,
-                       c.head_dim / 2);
-}
-
-void launch_sample_adapt_head(xh_ctx* ctx, hipStream_t s) {
-    const xh_config& c = ctx->c;
-    hipLaunchKernelGGL(sample_adapt_embed_kernel, dim3(1), dim3(SMP_THREADS), 0, s, (const float*)ctx->logits, c.vocab_size,
-                       ctx->ext, ctx->dfa, ctx->adapt, ctx->ext_ring, (const int*)ctx->ext_btok,
-                       (const float*)ctx->ext_bval, ctx->ext_adj, ctx->adapt_negd, ctx->sp, ctx->dec_tokens,
-                       ctx->dec_logprobs, ctx->dec_states, ctx->dec_cap, (const void*)ctx->embed, ctx->embed_dt, c.dim,
-                       ctx->x, (const float*)ctx->rope_freq, ctx->rope_cs, c.head_dim / 2);
-}
-
-void launch_sample_seq_head(xh_ctx* ctx, hipStream_t s) {
-    const xh_config& c = ctx->c;
-    hipLaunchKernelGGL(sample_seq_embed_kernel, dim3(1), dim3(SMP_THREADS), 0, s, (const float*)ctx->logits, c.vocab_size,
-                       ctx->ext, ctx->dfa, ctx->adapt, (const SeqCtl*)ctx->seq, ctx->ext_ring, (const int*)ctx->ext_btok,
-                       (const float*)ctx->ext_bval, (const int*)ctx->seq_brk, ctx->ext_adj, ctx->adapt_negd, ctx->sp,
-                       (const SeqTail*)ctx->seq_tail);
-}
-
-// kind: 0 a step with logits, 1 without (hydrate), 2 .. 7 a decode step under the greedy, sampled,
-// extended, constrained, adaptive and sequence-aware head
-int capture(xh_ctx* ctx, int kind, hipGraphExec_t* out) {
+// the step of `kind` into its slot of ctx->g_step
+int capture(xh_ctx* ctx, StepKind kind) {
     hipGraph_t g = nullptr;
     HIP_TRY(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-    const int rc = enqueue_step(ctx, ctx->stream, kind != 1, kind == 2 ? HEAD_GREEDY : kind == 3 ? HEAD_SAMPLE : kind == 4 ? HEAD_SAMPLE_EXT : kind == 5 ? HEAD_SAMPLE_DFA : kind == 6 ? HEAD_SAMPLE_ADAPT : kind == 7 ? HEAD_SAMPLE_SEQ : HEAD_GIVEN);
+    const int rc = enqueue_step(ctx, ctx->stream, kind);
     hipError_t e = hipStreamEndCapture(ctx->stream, &g);
     if (rc) { if (g) hipGraphDestroy(g); return rc; }
     if (e != hipSuccess) return set_err(ctx, XH_E_HIP, "graph capture failed: %s", hipGetErrorString(e));
-    e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
+    e = hipGraphInstantiate(&ctx->g_step[kind], g, nullptr, nullptr, 0);
     hipGraphDestroy(g);
     if (e != hipSuccess) return set_err(ctx, XH_E_HIP, "graph instantiate failed: %s", hipGetErrorString(e));
     return 0;
@@ -469,8 +429,8 @@ int capture(xh_ctx* ctx, int kind, hipGraphExec_t* out) {
 
 // an eager step that failed part-way: the attention + Wo hand-off words may hold arrivals that
 // the layer's W1/W3 launch never zeroed
-int eager_step(xh_ctx* ctx, bool with_logits, int head) {
-    const int rc = enqueue_step(ctx, ctx->stream, with_logits, head);
+int eager_step(xh_ctx* ctx, StepKind kind) {
+    const int rc = enqueue_step(ctx, ctx->stream, kind);
     if (rc) hipMemsetAsync(ctx->aw_sync, 0, (size_t)ctx->c.n_layers * AW_SYNC_WORDS * 4, ctx->stream);
     return rc;
 }
@@ -567,11 +527,7 @@ int xalm::check_ready(xh_ctx* ctx) {
     return 0;
 }
 
-void xalm::time_sample_head(xh_ctx* ctx) { launch_sample_head(ctx, ctx->stream); }
-void xalm::time_sample_ext_head(xh_ctx* ctx) { launch_sample_ext_head(ctx, ctx->stream); }
-void xalm::time_sample_dfa_head(xh_ctx* ctx) { launch_sample_dfa_head(ctx, ctx->stream); }
-void xalm::time_sample_adapt_head(xh_ctx* ctx) { launch_sample_adapt_head(ctx, ctx->stream); }
-void xalm::time_sample_seq_head(xh_ctx* ctx) { launch_sample_seq_head(ctx, ctx->stream); }
+void xalm::time_head(xh_ctx* ctx, StepKind head) { launch_head(ctx, head, ctx->stream); }
 
 void xalm::launch_top_logprobs(const float* logits, int vocab, size_t stride, int n_rows, const int* n_top_dev, int n_top,
                                const StepParams* sp, int cap, const int* targets, int out_stride, int* ids, float* lps,
@@ -586,29 +542,22 @@ void xalm::time_top_logprobs(xh_ctx* ctx) {
 }
 
 void xalm::drop_graphs(xh_ctx* ctx) {
-    if (ctx->g_logits) hipGraphExecDestroy(ctx->g_logits);
-    if (ctx->g_hydrate) hipGraphExecDestroy(ctx->g_hydrate);
-    if (ctx->g_decode) hipGraphExecDestroy(ctx->g_decode);
-    if (ctx->g_sample) hipGraphExecDestroy(ctx->g_sample);
-    if (ctx->g_sample_ext) hipGraphExecDestroy(ctx->g_sample_ext);
-    if (ctx->g_sample_dfa) hipGraphExecDestroy(ctx->g_sample_dfa);
-    if (ctx->g_sample_adapt) hipGraphExecDestroy(ctx->g_sample_adapt);
-    ctx->g_logits = ctx->g_hydrate = ctx->g_decode = ctx->g_sample = ctx->g_sample_ext = ctx->g_sample_dfa = nullptr;
-    if (ctx->g_sample_seq) hipGraphExecDestroy(ctx->g_sample_seq);
-    ctx->g_sample_adapt = ctx->g_sample_seq = nullptr;
+    for (hipGraphExec_t& g : ctx->g_step) {
+        if (g) hipGraphExecDestroy(g);
+        g = nullptr;
+    }
 }
-
 
 // the step at host_step_params' position
 int xalm::run_step(xh_ctx* ctx, bool with_logits) {
+    const StepKind kind = with_logits ? STEP_LOGITS : STEP_HYDRATE;
     if (with_logits) ctx->cand_valid = true;  // the lm_head launch writes candidates
-    if (!ctx->use_graphs) return eager_step(ctx, with_logits, HEAD_GIVEN);
-    hipGraphExec_t* ge = with_logits ? &ctx->g_logits : &ctx->g_hydrate;
-    if (!*ge) {
-        int rc = capture(ctx, with_logits ? 0 : 1, ge);
+    if (!ctx->use_graphs) return eager_step(ctx, kind);
+    if (!ctx->g_step[kind]) {
+        int rc = capture(ctx, kind);
         if (rc) return rc;
     }
-    HIP_TRY(ctx, hipGraphLaunch(*ge, ctx->stream));
+    HIP_TRY(ctx, hipGraphLaunch(ctx->g_step[kind], ctx->stream));
     return 0;
 }
 
@@ -673,6 +622,265 @@ ExtCtl ext_block(const xh_sampling& s, const xh_logit_ctl& c, int count) {
     e.count = count;
     return e;
 }
+
+// the device block of a constraint's tables (device pointers) at `state`; a stop token that is off is -1
+DfaCtl dfa_block(const void* next, const void* accept, const void* bytes, const void* offsets, int n_states,
+                 uint32_t state, int stop_a, int stop_b) {
+    return DfaCtl{(const uint16_t*)next, (const uint8_t*)accept, (const uint8_t*)bytes, (const uint32_t*)offsets,
+                  n_states, state, stop_a < 0 ? -1 : stop_a, stop_b < 0 ? -1 : stop_b};
+}
+
+AdaptCtl adapt_block(const xh_trunc_ctl& t, float mu, bool constrain) {
+    return AdaptCtl{t.typical_p, t.top_n_sigma, t.mirostat_tau, t.mirostat_eta, mu, constrain ? 1 : 0};
+}
+
+// the device block of xh_seq_ctl and its breakers in ascending order (what the head's binary search needs)
+SeqCtl seq_block(const xh_seq_ctl& q, std::vector<int>* sorted) {
+    sorted->assign(q.breaker_token, q.breaker_token + q.n_breakers);
+    std::sort(sorted->begin(), sorted->end());
+    return SeqCtl{q.dry_multiplier, q.dry_base, q.dry_allowed_length, q.no_repeat_ngram, q.seq_last_n, q.n_breakers,
+                  q.xtc_probability, q.xtc_threshold};
+}
+
+// ---------------------------------------------------------------------------------------
+// the decode loop: one driver under the six xh_decode_* entries
+// ---------------------------------------------------------------------------------------
+// The union of the entries' arguments; an entry leaves what its head does not take at null / 0.
+// The heads are cumulative: each one from STEP_SAMPLE_EXT up takes what the one before it takes.
+struct DecodeCall {
+    StepKind head;  // STEP_GREEDY .. STEP_SAMPLE_SEQ
+    int pos, n_steps;
+    const xh_sampling* sampling;  // from STEP_SAMPLE
+    const xh_logit_ctl* ctl;      // from STEP_SAMPLE_EXT, with the history that fills the window ring
+    const xh_trunc_ctl* trunc;    // from STEP_SAMPLE_ADAPT
+    const xh_seq_ctl* seq;        // STEP_SAMPLE_SEQ
+    const int* history;
+    int n_history;
+    int constrain;  // the DFA mask runs: always under STEP_SAMPLE_DFA, the caller's choice above it
+    uint32_t state_in;
+    float mu_in;
+    int stop_a, stop_b;
+    int* tokens_out;
+    float* logprobs_out;
+    uint32_t* state_out;
+    float* mu_out;
+    int* n_done;
+};
+
+int decode_run(xh_ctx* ctx, const DecodeCall& k) {
+    const StepKind head = k.head;
+    const bool sampled = head >= STEP_SAMPLE, ext = head >= STEP_SAMPLE_EXT, adapt = head >= STEP_SAMPLE_ADAPT;
+    const bool seq = head == STEP_SAMPLE_SEQ, constrained = k.constrain != 0;
+    // the checks, every one before the first HIP call; those on the arguments alone come before
+    // those that need the context
+    if (k.n_done) *k.n_done = 0;
+    if (sampled && !sampling_ok(k.sampling)) return set_err(ctx, XH_E_INVALID, "bad sampling parameters");
+    const int vocab = ctx ? ctx->c.vocab_size : 0;
+    const char* why = nullptr;
+    if (ext) why = ctl_error(k.ctl, k.history, k.n_history, vocab);
+    if (!why && adapt) why = trunc_error(k.trunc, k.sampling, k.ctl ? k.ctl->min_p : 0.f, k.mu_in);
+    if (!why && seq) why = seq_error(k.seq, k.trunc, vocab);
+    if (why) return set_err(ctx, XH_E_INVALID, "%s", why);
+    if (!ctx || k.n_steps < 0) return XH_E_INVALID;
+    if (sampled) {
+        if (k.pos < 0) return set_err(ctx, XH_E_INVALID, "negative pos");
+        if (vocab > SMP_MAX_VOCAB) return set_err(ctx, XH_E_INVALID, "vocab_size > %d", SMP_MAX_VOCAB);
+    }
+    if (k.n_steps > ctx->dec_cap) return set_err(ctx, XH_E_INVALID, "n_steps > %d", ctx->dec_cap);
+    if (constrained) {
+        if (!ctx->dfa_vocab_set || !ctx->dfa_n_states)
+            return set_err(ctx, XH_E_INVALID, "constrained decode before xh_constraint_set_vocab and xh_constraint_set");
+        if (k.state_in != XH_DFA_DEAD && k.state_in >= (uint32_t)ctx->dfa_n_states)
+            return set_err(ctx, XH_E_INVALID, "state_in %u out of range", k.state_in);
+        // an end token is emitted in the stuck state, so it has to be a token
+        if (k.stop_a >= vocab || k.stop_b >= vocab) return set_err(ctx, XH_E_INVALID, "stop token out of range");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->dev));
+    int rc = check_ready(ctx);
+    if (rc) return rc;
+    // step counter 0, next position `pos`; the head sets the token and position fields
+    StepParams* h = ctx->sp_host;
+    h->step = 0;
+    h->pos_next = k.pos;
+    h->max_seq_len = ctx->c.max_seq_len;
+    HIP_TRY(ctx, hipMemcpyAsync(&ctx->sp->step, &h->step, 3 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    // The head's parameter blocks.  Every source is pageable, so a copy has left it when
+    // hipMemcpyAsync returns: the blocks may be locals and the caller's arrays may go after the call.
+    const hipStream_t s = ctx->stream;
+    if (head == STEP_SAMPLE) HIP_TRY(ctx, hipMemcpyAsync(ctx->samp, k.sampling, sizeof(xh_sampling), hipMemcpyHostToDevice, s));
+    if (ext) {
+        // the block, the bias table and the history's tail (ring slots 0 .. n_hist - 1)
+        const xh_logit_ctl& c = k.ctl ? *k.ctl : CTL_OFF;
+        const int n_hist = std::min(k.n_history, XH_CTL_MAX_WINDOW);
+        const ExtCtl blk = ext_block(*k.sampling, c, n_hist);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext, &blk, sizeof blk, hipMemcpyHostToDevice, s));
+        if (c.n_bias > 0) {
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_btok, c.bias_token, (size_t)c.n_bias * sizeof(int), hipMemcpyHostToDevice, s));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_bval, c.bias_value, (size_t)c.n_bias * sizeof(float), hipMemcpyHostToDevice, s));
+        }
+        if (n_hist > 0)
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_ring, k.history + (k.n_history - n_hist), (size_t)n_hist * sizeof(int),
+                                        hipMemcpyHostToDevice, s));
+    }
+    if (constrained) {
+        const DfaCtl blk = dfa_block(ctx->dfa_next, ctx->dfa_accept, ctx->dfa_bytes, ctx->dfa_offsets, ctx->dfa_n_states,
+                                     k.state_in, k.stop_a, k.stop_b);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->dfa, &blk, sizeof blk, hipMemcpyHostToDevice, s));
+        ctx->dfa_block_valid = true;
+    }
+    if (adapt) {
+        // mu lives in the block: the head reads and writes it every step
+        const AdaptCtl blk = adapt_block(*k.trunc, k.mu_in, k.constrain != 0);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->adapt, &blk, sizeof blk, hipMemcpyHostToDevice, s));
+        // the timing hooks of this head and of the ones above read ctx->adapt: it holds this call's parameters now
+        ctx->adapt_valid = true;
+        ctx->adapt_constrain = k.constrain != 0;
+    }
+    if (seq) {
+        std::vector<int> brk;
+        const SeqCtl blk = seq_block(*k.seq, &brk);
+        const SeqTail tail = {ctx->dec_tokens, ctx->dec_logprobs, ctx->dec_states, (const void*)ctx->embed, ctx->x,
+                              (const float*)ctx->rope_freq, ctx->rope_cs, ctx->dec_cap, ctx->embed_dt, ctx->c.dim,
+                              ctx->c.head_dim / 2};
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->seq, &blk, sizeof blk, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->seq_tail, &tail, sizeof tail, hipMemcpyHostToDevice, s));
+        if (!brk.empty())
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->seq_brk, brk.data(), brk.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        ctx->seq_valid = true;
+        ctx->seq_constrain = k.constrain != 0;
+    }
+    if (ext) HIP_TRY(ctx, hipStreamSynchronize(s));
+    if (ctx->use_graphs && k.n_steps > 0 && !ctx->g_step[head]) {
+        rc = capture(ctx, head);
+        if (rc) return rc;
+    }
+    if (head == STEP_GREEDY) {
+        // the first token is the argmax of the logits on the device: candidates from them if the
+        // launch that produced them left none (nothing yet)
+        if (!ctx->cand_valid)
+            hipLaunchKernelGGL(logits_cand_kernel, dim3(1), dim3(ARGMAX_CANDS), 0, s, (const float*)ctx->logits,
+                               ctx->c.vocab_size, ctx->cand);
+        ctx->cand_valid = true;
+    }
+    // A sampled head reads the logits themselves, so cand and cand_valid stay as they were until a
+    // step has run: every step's lm_head launch rewrites cand for the raw logits it leaves, and a
+    // greedy call may follow.
+    const bool stops = k.stop_a >= 0 || k.stop_b >= 0;
+    int done = 0;
+    for (int i = 0; i < k.n_steps; i++) {
+        if (ctx->use_graphs) {
+            HIP_TRY(ctx, hipGraphLaunch(ctx->g_step[head], s));
+        } else {
+            rc = eager_step(ctx, head);
+            if (rc) return rc;
+        }
+        ctx->cand_valid = true;
+        done = i + 1;
+        if (stops) {
+            int tok = -1;
+            HIP_TRY(ctx, hipMemcpyAsync(&tok, ctx->dec_tokens + i, sizeof(int), hipMemcpyDeviceToHost, s));
+            HIP_TRY(ctx, hipStreamSynchronize(s));
+            if (tok == k.stop_a || tok == k.stop_b) break;
+        }
+    }
+    if (k.tokens_out && done)
+        HIP_TRY(ctx, hipMemcpyAsync(k.tokens_out, ctx->dec_tokens, (size_t)done * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (ext && k.logprobs_out && done)
+        HIP_TRY(ctx, hipMemcpyAsync(k.logprobs_out, ctx->dec_logprobs, (size_t)done * sizeof(float), hipMemcpyDeviceToHost, s));
+    // no step runs past the last emitted token, so the per-step log holds the state and the block mu after it
+    uint32_t st = k.state_in;
+    float mu = k.mu_in;
+    if (constrained && done)
+        HIP_TRY(ctx, hipMemcpyAsync(&st, ctx->dec_states + (done - 1), sizeof st, hipMemcpyDeviceToHost, s));
+    if (adapt && done) HIP_TRY(ctx, hipMemcpyAsync(&mu, &ctx->adapt->mu, sizeof mu, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    if (k.state_out) *k.state_out = st;
+    if (k.mu_out) *k.mu_out = mu;
+    if (k.n_done) *k.n_done = done;
+    ctx->top_steps = ctx->top_n > 0 ? done : -1;
+    return check_aw(ctx);
+}
+
+// ---------------------------------------------------------------------------------------
+// the xh_op_* entries: the heads' device code on host arrays, without a context
+// ---------------------------------------------------------------------------------------
+// a device buffer of an op, freed with it: at least 16 bytes, the first src_bytes copied from src
+struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() { if (p) hipFree(p); }
+    bool alloc(size_t bytes, const void* src = nullptr, size_t src_bytes = 0) {
+        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return false;
+        return !src_bytes || hipMemcpy(p, src, src_bytes, hipMemcpyHostToDevice) == hipSuccess;
+    }
+};
+
+// The xh_op_sample* entries' argument checks in the order they report them; 0 = valid.  outs: the
+// entry's required outputs are all there.  ctl, trunc and seq are checked from the head that takes
+// them; STEP_SAMPLE_DFA demands the constraint, the heads above it take one or none (dfa null).
+int op_check(StepKind head, const float* logits, int vocab, const xh_sampling* sampling, int n_draws, bool outs,
+             const xh_logit_ctl* ctl = nullptr, const int* window = nullptr, int n_window = 0,
+             const xh_trunc_ctl* trunc = nullptr, float mu = 0.f, const xh_seq_ctl* seq = nullptr,
+             const xh_byte_dfa* dfa = nullptr, const uint8_t* bytes = nullptr, const uint32_t* offsets = nullptr,
+             uint32_t state = 0, int stop_a = -1, int stop_b = -1) {
+    if (!sampling_ok(sampling)) return set_err(nullptr, XH_E_INVALID, "bad sampling parameters");
+    if (!logits || !outs || vocab <= 0 || vocab > SMP_MAX_VOCAB || n_draws <= 0 || n_draws > 65536)
+        return set_err(nullptr, XH_E_INVALID, "bad sample args");
+    const char* why = nullptr;
+    if (head >= STEP_SAMPLE_EXT) why = ctl_error(ctl, window, n_window, vocab);
+    if (!why && head >= STEP_SAMPLE_ADAPT) why = trunc_error(trunc, sampling, ctl ? ctl->min_p : 0.f, mu);
+    if (!why && head == STEP_SAMPLE_SEQ) why = seq_error(seq, trunc, vocab);
+    if (!why && (head == STEP_SAMPLE_DFA || (head > STEP_SAMPLE_DFA && dfa))) {
+        why = dfa_error(dfa);
+        if (!why) why = pieces_error(bytes, offsets, vocab);
+        if (!why) why = dfa_state_error(dfa, state);
+        if (!why && (stop_a >= vocab || stop_b >= vocab)) why = "stop token out of range";
+    }
+    return why ? set_err(nullptr, XH_E_INVALID, "%s", why) : 0;
+}
+
+// what every op from xh_op_sample_ext up reads: the logits, room for l', the block of (sampling, ctl)
+// with the window's tail in the ring, and the bias table
+struct ExtStage {
+    DevBuf logits, adj, blk, ring, btok, bval;
+    bool stage(const float* h_logits, int vocab, const xh_sampling& s, const xh_logit_ctl* ctl, const int* window,
+               int n_window) {
+        const xh_logit_ctl& c = ctl ? *ctl : CTL_OFF;
+        const int n_win = std::min(n_window, XH_CTL_MAX_WINDOW);
+        const ExtCtl b = ext_block(s, c, n_win);
+        const size_t V = (size_t)vocab;
+        return logits.alloc(V * 4, h_logits, V * 4) && adj.alloc(V * 4) && blk.alloc(sizeof b, &b, sizeof b) &&
+               ring.alloc(XH_CTL_MAX_WINDOW * sizeof(int), n_win ? window + (n_window - n_win) : nullptr,
+                          (size_t)n_win * sizeof(int)) &&
+               btok.alloc(XH_CTL_MAX_BIAS * sizeof(int), c.bias_token, (size_t)c.n_bias * sizeof(int)) &&
+               bval.alloc(XH_CTL_MAX_BIAS * sizeof(float), c.bias_value, (size_t)c.n_bias * sizeof(float));
+    }
+};
+
+// a constraint's four tables and the block that points at them; dfa null: the block alone, its tables null
+struct DfaStage {
+    DevBuf next, acc, bytes, offs, blk;
+    bool stage(const xh_byte_dfa* dfa, const uint8_t* h_bytes, const uint32_t* offsets, int vocab, uint32_t state,
+               int stop_a, int stop_b) {
+        const size_t ns = dfa ? (size_t)dfa->n_states : 0, V = (size_t)vocab;
+        if (dfa && !(next.alloc(ns * 512, dfa->next, ns * 512) && acc.alloc(ns, dfa->accept, ns) &&
+                     bytes.alloc(offsets[vocab], h_bytes, offsets[vocab]) && offs.alloc((V + 1) * 4, offsets, (V + 1) * 4)))
+            return false;
+        const DfaCtl b = dfa_block(next.p, acc.p, bytes.p, offs.p, (int)ns, state, stop_a, stop_b);
+        return blk.alloc(sizeof b, &b, sizeof b);
+    }
+};
+
+int op_stage_failed() { return set_err(nullptr, XH_E_HIP, "hipMalloc / hipMemcpy failed"); }
+
+// behind an op's launches: wait for them ...
+hipError_t op_wait() {
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : hipDeviceSynchronize();
+}
+// ... and copy a result back: a null destination is skipped, the first error is carried forward
+void op_out(hipError_t& e, void* dst, const void* src, size_t bytes) {
+    if (e == hipSuccess && dst) e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
+}
 }  // namespace
 
 extern "C" {
@@ -695,135 +903,40 @@ int xh_forward(xh_ctx* ctx, int token, int pos, int mode, float* logits_out) {
     return check_aw(ctx);
 }
 
+// The six decode entries: a DecodeCall in its field order (head; pos, n_steps; sampling, ctl, trunc, seq;
+// history; constrain, state_in, mu_in; stops; the five outputs) for decode_run.
 int xh_decode_greedy(xh_ctx* ctx, int pos, int n_steps, int stop_a, int stop_b, int* tokens_out, int* n_done) {
-    if (!ctx || n_steps < 0) return XH_E_INVALID;
-    if (n_done) *n_done = 0;
-    if (n_steps > ctx->dec_cap) return set_err(ctx, XH_E_INVALID, "n_steps > %d", ctx->dec_cap);
-    HIP_TRY(ctx, hipSetDevice(ctx->dev));
-    int rc = check_ready(ctx);
-    if (rc) return rc;
-    // step counter 0, next position `pos`; token/pos fields are set by argmax_advance_kernel
-    StepParams* h = ctx->sp_host;
-    h->step = 0;
-    h->pos_next = pos;
-    h->max_seq_len = ctx->c.max_seq_len;
-    HIP_TRY(ctx, hipMemcpyAsync(&ctx->sp->step, &h->step, 3 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    if (ctx->use_graphs && n_steps > 0 && !ctx->g_decode) {
-        rc = capture(ctx, 2, &ctx->g_decode);
-        if (rc) return rc;
-    }
-    // the first token is the argmax of the logits on the device: candidates from them if the
-    // launch that produced them left none (nothing yet)
-    if (!ctx->cand_valid)
-        hipLaunchKernelGGL(logits_cand_kernel, dim3(1), dim3(ARGMAX_CANDS), 0, ctx->stream, (const float*)ctx->logits,
-                           ctx->c.vocab_size, ctx->cand);
-    ctx->cand_valid = true;
-    const bool stops = stop_a >= 0 || stop_b >= 0;
-    int done = 0;
-    for (int i = 0; i < n_steps; i++) {
-        if (ctx->use_graphs) {
-            HIP_TRY(ctx, hipGraphLaunch(ctx->g_decode, ctx->stream));
-        } else {
-            rc = eager_step(ctx, true, HEAD_GREEDY);
-            if (rc) return rc;
-        }
-        done = i + 1;
-        if (stops) {
-            int tok = -1;
-            HIP_TRY(ctx, hipMemcpyAsync(&tok, ctx->dec_tokens + i, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (tok == stop_a || tok == stop_b) break;
-        }
-    }
-    if (tokens_out && done)
-        HIP_TRY(ctx, hipMemcpyAsync(tokens_out, ctx->dec_tokens, (size_t)done * sizeof(int), hipMemcpyDeviceToHost,
-                                    ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (n_done) *n_done = done;
-    ctx->top_steps = ctx->top_n > 0 ? done : -1;
-    return check_aw(ctx);
+    if (!ctx || n_steps < 0) return XH_E_INVALID;  // this entry alone leaves *n_done as it was here
+    return decode_run(ctx, {STEP_GREEDY, pos, n_steps, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0.f, stop_a,
+                            stop_b, tokens_out, nullptr, nullptr, nullptr, n_done});
 }
 
 int xh_decode_sample(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* sampling, int stop_a, int stop_b,
                      int* tokens_out, int* n_done) {
-    if (n_done) *n_done = 0;
-    if (!sampling_ok(sampling)) return set_err(ctx, XH_E_INVALID, "bad sampling parameters");
-    if (!ctx || n_steps < 0) return XH_E_INVALID;
-    if (pos < 0) return set_err(ctx, XH_E_INVALID, "negative pos");
-    if (ctx->c.vocab_size > SMP_MAX_VOCAB) return set_err(ctx, XH_E_INVALID, "vocab_size > %d", SMP_MAX_VOCAB);
-    if (n_steps > ctx->dec_cap) return set_err(ctx, XH_E_INVALID, "n_steps > %d", ctx->dec_cap);
-    HIP_TRY(ctx, hipSetDevice(ctx->dev));
-    int rc = check_ready(ctx);
-    if (rc) return rc;
-    StepParams* h = ctx->sp_host;
-    h->step = 0;
-    h->pos_next = pos;
-    h->max_seq_len = ctx->c.max_seq_len;
-    HIP_TRY(ctx, hipMemcpyAsync(&ctx->sp->step, &h->step, 3 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    // the parameter block: a pageable source, so the copy has left `sampling` when the call returns
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->samp, sampling, sizeof(xh_sampling), hipMemcpyHostToDevice, ctx->stream));
-    if (ctx->use_graphs && n_steps > 0 && !ctx->g_sample) {
-        rc = capture(ctx, 3, &ctx->g_sample);
-        if (rc) return rc;
-    }
-    // the head reads the logits themselves: cand and cand_valid stay as the lm_head left them
-    // (every step's lm_head launch rewrites cand for the logits it leaves)
-    const bool stops = stop_a >= 0 || stop_b >= 0;
-    int done = 0;
-    for (int i = 0; i < n_steps; i++) {
-        if (ctx->use_graphs) {
-            HIP_TRY(ctx, hipGraphLaunch(ctx->g_sample, ctx->stream));
-        } else {
-            rc = eager_step(ctx, true, HEAD_SAMPLE);
-            if (rc) return rc;
-        }
-        ctx->cand_valid = true;
-        done = i + 1;
-        if (stops) {
-            int tok = -1;
-            HIP_TRY(ctx, hipMemcpyAsync(&tok, ctx->dec_tokens + i, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (tok == stop_a || tok == stop_b) break;
-        }
-    }
-    if (tokens_out && done)
-        HIP_TRY(ctx, hipMemcpyAsync(tokens_out, ctx->dec_tokens, (size_t)done * sizeof(int), hipMemcpyDeviceToHost,
-                                    ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (n_done) *n_done = done;
-    ctx->top_steps = ctx->top_n > 0 ? done : -1;
-    return check_aw(ctx);
+    return decode_run(ctx, {STEP_SAMPLE, pos, n_steps, sampling, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0.f, stop_a,
+                            stop_b, tokens_out, nullptr, nullptr, nullptr, n_done});
 }
 
 int xh_op_sample(const float* logits, int vocab, const xh_sampling* sampling, uint64_t pos0, int n_draws,
                  int* tokens_out, int* n_kept_out) {
-    if (!sampling_ok(sampling)) return set_err(nullptr, XH_E_INVALID, "bad sampling parameters");
-    if (!logits || !tokens_out || !n_kept_out || vocab <= 0 || vocab > SMP_MAX_VOCAB || n_draws <= 0 || n_draws > 65536)
-        return set_err(nullptr, XH_E_INVALID, "bad sample args");
-    float* d_logits = nullptr;
-    xh_sampling* d_samp = nullptr;
-    int* d_out = nullptr;
-    int rc = 0;
-    if (hipMalloc((void**)&d_logits, (size_t)vocab * 4) != hipSuccess || hipMalloc((void**)&d_samp, sizeof(xh_sampling)) != hipSuccess ||
-        hipMalloc((void**)&d_out, (size_t)2 * n_draws * sizeof(int)) != hipSuccess)
-        rc = set_err(nullptr, XH_E_HIP, "hipMalloc failed");
-    if (!rc && (hipMemcpy(d_logits, logits, (size_t)vocab * 4, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(d_samp, sampling, sizeof(xh_sampling), hipMemcpyHostToDevice) != hipSuccess))
-        rc = set_err(nullptr, XH_E_HIP, "hipMemcpy failed");
-    if (!rc) {
-        hipLaunchKernelGGL(sample_op_kernel, dim3(n_draws), dim3(SMP_THREADS), 0, nullptr, (const float*)d_logits, vocab,
-                           (const xh_sampling*)d_samp, (uint32_t)pos0, d_out, d_out + n_draws);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipMemcpy(tokens_out, d_out, (size_t)n_draws * sizeof(int), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(n_kept_out, d_out + n_draws, (size_t)n_draws * sizeof(int), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = set_err(nullptr, XH_E_HIP, "sample op failed: %s", hipGetErrorString(e));
-    }
-    hipFree(d_logits);
-    hipFree(d_samp);
-    hipFree(d_out);
-    return rc;
+    if (int rc = op_check(STEP_SAMPLE, logits, vocab, sampling, n_draws, tokens_out && n_kept_out)) return rc;
+    const size_t V = (size_t)vocab, nd = (size_t)n_draws;
+    DevBuf d_logits, d_samp, d_out;
+    if (!d_logits.alloc(V * 4) || !d_samp.alloc(sizeof(xh_sampling)) || !d_out.alloc(2 * nd * sizeof(int)))
+        return set_err(nullptr, XH_E_HIP, "hipMalloc failed");
+    if (hipMemcpy(d_logits.p, logits, V * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_samp.p, sampling, sizeof(xh_sampling), hipMemcpyHostToDevice) != hipSuccess)
+        return set_err(nullptr, XH_E_HIP, "hipMemcpy failed");
+    int* d_tok = (int*)d_out.p;
+    hipLaunchKernelGGL(sample_op_kernel, dim3(n_draws), dim3(SMP_THREADS), 0, nullptr, (const float*)d_logits.p, vocab,
+                       (const xh_sampling*)d_samp.p, (uint32_t)pos0, d_tok, d_tok + nd);
+    hipError_t e = op_wait();
+    op_out(e, tokens_out, d_tok, nd * sizeof(int));
+    op_out(e, n_kept_out, d_tok + nd, nd * sizeof(int));
+    if (e != hipSuccess) return set_err(nullptr, XH_E_HIP, "sample op failed: %s", hipGetErrorString(e));
+    return 0;
 }
+
 
 int xh_adjust_logits(const float* logits, int vocab, const xh_logit_ctl* ctl, const int* window, int n_window,
                      float* out) {
@@ -859,113 +972,37 @@ int xh_adjust_logits(const float* logits, int vocab, const xh_logit_ctl* ctl, co
 int xh_decode_sample_ext(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* sampling, const xh_logit_ctl* ctl,
                          const int* history, int n_history, int stop_a, int stop_b, int* tokens_out,
                          float* logprobs_out, int* n_done) {
-    if (n_done) *n_done = 0;
-    if (!sampling_ok(sampling)) return set_err(ctx, XH_E_INVALID, "bad sampling parameters");
-    if (const char* why = ctl_error(ctl, history, n_history, ctx ? ctx->c.vocab_size : 0))
-        return set_err(ctx, XH_E_INVALID, "%s", why);
-    if (!ctx || n_steps < 0) return XH_E_INVALID;
-    if (pos < 0) return set_err(ctx, XH_E_INVALID, "negative pos");
-    if (ctx->c.vocab_size > SMP_MAX_VOCAB) return set_err(ctx, XH_E_INVALID, "vocab_size > %d", SMP_MAX_VOCAB);
-    if (n_steps > ctx->dec_cap) return set_err(ctx, XH_E_INVALID, "n_steps > %d", ctx->dec_cap);
-    HIP_TRY(ctx, hipSetDevice(ctx->dev));
-    int rc = check_ready(ctx);
-    if (rc) return rc;
-    const xh_logit_ctl& c = ctl ? *ctl : CTL_OFF;
-    StepParams* h = ctx->sp_host;
-    h->step = 0;
-    h->pos_next = pos;
-    h->max_seq_len = ctx->c.max_seq_len;
-    HIP_TRY(ctx, hipMemcpyAsync(&ctx->sp->step, &h->step, 3 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    // the parameter block, the bias table and the history's tail (ring slots 0 .. n_hist - 1):
-    // pageable sources, so the copies have left them when the call returns
-    const int n_hist = std::min(n_history, XH_CTL_MAX_WINDOW);
-    const ExtCtl blk = ext_block(*sampling, c, n_hist);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ext, &blk, sizeof blk, hipMemcpyHostToDevice, ctx->stream));
-    if (c.n_bias > 0) {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_btok, c.bias_token, (size_t)c.n_bias * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_bval, c.bias_value, (size_t)c.n_bias * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (n_hist > 0)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_ring, history + (n_history - n_hist), (size_t)n_hist * sizeof(int),
-                                    hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->use_graphs && n_steps > 0 && !ctx->g_sample_ext) {
-        rc = capture(ctx, 4, &ctx->g_sample_ext);
-        if (rc) return rc;
-    }
-    // the head reads the logits themselves; every step's lm_head launch rewrites cand for the raw
-    // logits it leaves, so a greedy call may follow
-    const bool stops = stop_a >= 0 || stop_b >= 0;
-    int done = 0;
-    for (int i = 0; i < n_steps; i++) {
-        if (ctx->use_graphs) {
-            HIP_TRY(ctx, hipGraphLaunch(ctx->g_sample_ext, ctx->stream));
-        } else {
-            rc = eager_step(ctx, true, HEAD_SAMPLE_EXT);
-            if (rc) return rc;
-        }
-        ctx->cand_valid = true;
-        done = i + 1;
-        if (stops) {
-            int tok = -1;
-            HIP_TRY(ctx, hipMemcpyAsync(&tok, ctx->dec_tokens + i, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (tok == stop_a || tok == stop_b) break;
-        }
-    }
-    if (tokens_out && done)
-        HIP_TRY(ctx, hipMemcpyAsync(tokens_out, ctx->dec_tokens, (size_t)done * sizeof(int), hipMemcpyDeviceToHost,
-                                    ctx->stream));
-    if (logprobs_out && done)
-        HIP_TRY(ctx, hipMemcpyAsync(logprobs_out, ctx->dec_logprobs, (size_t)done * sizeof(float), hipMemcpyDeviceToHost,
-                                    ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (n_done) *n_done = done;
-    ctx->top_steps = ctx->top_n > 0 ? done : -1;
-    return check_aw(ctx);
+    return decode_run(ctx, {STEP_SAMPLE_EXT, pos, n_steps, sampling, ctl, nullptr, nullptr, history, n_history, 0, 0, 0.f,
+                            stop_a, stop_b, tokens_out, logprobs_out, nullptr, nullptr, n_done});
 }
 
 int xh_op_sample_ext(const float* logits, int vocab, const xh_sampling* sampling, const xh_logit_ctl* ctl,
                      const int* window, int n_window, uint64_t pos0, int n_draws, int* tokens_out, int* n_kept_out,
                      float* adjusted_out, float* logprob_out) {
-    if (!sampling_ok(sampling)) return set_err(nullptr, XH_E_INVALID, "bad sampling parameters");
-    if (!logits || !tokens_out || !n_kept_out || vocab <= 0 || vocab > SMP_MAX_VOCAB || n_draws <= 0 || n_draws > 65536)
-        return set_err(nullptr, XH_E_INVALID, "bad sample args");
-    if (const char* why = ctl_error(ctl, window, n_window, vocab)) return set_err(nullptr, XH_E_INVALID, "%s", why);
-    const xh_logit_ctl& c = ctl ? *ctl : CTL_OFF;
-    const int n_win = std::min(n_window, XH_CTL_MAX_WINDOW);
-    const ExtCtl blk = ext_block(*sampling, c, n_win);
-    struct Buf {
-        void* p = nullptr;
-        ~Buf() { if (p) hipFree(p); }
-        bool alloc(size_t bytes, const void* src, size_t src_bytes) {
-            if (hipMalloc(&p, bytes) != hipSuccess) return false;
-            return !src_bytes || hipMemcpy(p, src, src_bytes, hipMemcpyHostToDevice) == hipSuccess;
-        }
-    } d_logits, d_adj, d_blk, d_ring, d_btok, d_bval, d_prep, d_out, d_lp;
-    if (!d_logits.alloc((size_t)vocab * 4, logits, (size_t)vocab * 4) || !d_adj.alloc((size_t)vocab * 4, nullptr, 0) ||
-        !d_blk.alloc(sizeof blk, &blk, sizeof blk) ||
-        !d_ring.alloc(XH_CTL_MAX_WINDOW * sizeof(int), n_win ? window + (n_window - n_win) : nullptr, (size_t)n_win * sizeof(int)) ||
-        !d_btok.alloc(XH_CTL_MAX_BIAS * sizeof(int), c.bias_token, (size_t)c.n_bias * sizeof(int)) ||
-        !d_bval.alloc(XH_CTL_MAX_BIAS * sizeof(float), c.bias_value, (size_t)c.n_bias * sizeof(float)) ||
-        !d_prep.alloc(sizeof(ExtPrep), nullptr, 0) || !d_out.alloc((size_t)2 * n_draws * sizeof(int), nullptr, 0) ||
-        !d_lp.alloc((size_t)n_draws * sizeof(float), nullptr, 0))
-        return set_err(nullptr, XH_E_HIP, "hipMalloc / hipMemcpy failed");
-    hipLaunchKernelGGL(sample_ext_prep_kernel, dim3(1), dim3(SMP_THREADS), 0, nullptr, (const float*)d_logits.p, vocab,
-                       (const ExtCtl*)d_blk.p, (const int*)d_ring.p, (const int*)d_btok.p, (const float*)d_bval.p,
-                       (float*)d_adj.p, (ExtPrep*)d_prep.p);
-    hipLaunchKernelGGL(sample_ext_op_kernel, dim3(n_draws), dim3(SMP_THREADS), 0, nullptr, (const float*)d_logits.p,
-                       (const float*)d_adj.p, vocab, (const ExtCtl*)d_blk.p, (const ExtPrep*)d_prep.p, (uint32_t)pos0,
-                       (int*)d_out.p, (int*)d_out.p + n_draws, (float*)d_lp.p);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(tokens_out, d_out.p, (size_t)n_draws * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(n_kept_out, (int*)d_out.p + n_draws, (size_t)n_draws * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && adjusted_out) e = hipMemcpy(adjusted_out, d_adj.p, (size_t)vocab * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && logprob_out) e = hipMemcpy(logprob_out, d_lp.p, (size_t)n_draws * sizeof(float), hipMemcpyDeviceToHost);
+    if (int rc = op_check(STEP_SAMPLE_EXT, logits, vocab, sampling, n_draws, tokens_out && n_kept_out, ctl, window, n_window))
+        return rc;
+    const size_t V = (size_t)vocab, nd = (size_t)n_draws;
+    ExtStage x;
+    DevBuf d_prep, d_out, d_lp;
+    if (!x.stage(logits, vocab, *sampling, ctl, window, n_window) || !d_prep.alloc(sizeof(ExtPrep)) ||
+        !d_out.alloc(2 * nd * sizeof(int)) || !d_lp.alloc(nd * sizeof(float)))
+        return op_stage_failed();
+    int* d_tok = (int*)d_out.p;
+    hipLaunchKernelGGL(sample_ext_prep_kernel, dim3(1), dim3(SMP_THREADS), 0, nullptr, (const float*)x.logits.p, vocab,
+                       (const ExtCtl*)x.blk.p, (const int*)x.ring.p, (const int*)x.btok.p, (const float*)x.bval.p,
+                       (float*)x.adj.p, (ExtPrep*)d_prep.p);
+    hipLaunchKernelGGL(sample_ext_op_kernel, dim3(n_draws), dim3(SMP_THREADS), 0, nullptr, (const float*)x.logits.p,
+                       (const float*)x.adj.p, vocab, (const ExtCtl*)x.blk.p, (const ExtPrep*)d_prep.p, (uint32_t)pos0,
+                       d_tok, d_tok + nd, (float*)d_lp.p);
+    hipError_t e = op_wait();
+    op_out(e, tokens_out, d_tok, nd * sizeof(int));
+    op_out(e, n_kept_out, d_tok + nd, nd * sizeof(int));
+    op_out(e, adjusted_out, x.adj.p, V * 4);
+    op_out(e, logprob_out, d_lp.p, nd * sizeof(float));
     if (e != hipSuccess) return set_err(nullptr, XH_E_HIP, "sample_ext op failed: %s", hipGetErrorString(e));
     return 0;
 }
+
 
 int xh_constraint_set_vocab(xh_ctx* ctx, const uint8_t* bytes, const uint32_t* offsets) {
     if (!ctx) return XH_E_INVALID;
@@ -1030,137 +1067,39 @@ int xh_constraint_set(xh_ctx* ctx, const xh_byte_dfa* dfa) {
 int xh_decode_sample_dfa(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* sampling, const xh_logit_ctl* ctl,
                          const int* history, int n_history, uint32_t state_in, int stop_a, int stop_b, int* tokens_out,
                          float* logprobs_out, uint32_t* state_out, int* n_done) {
-    if (n_done) *n_done = 0;
-    if (!sampling_ok(sampling)) return set_err(ctx, XH_E_INVALID, "bad sampling parameters");
-    if (const char* why = ctl_error(ctl, history, n_history, ctx ? ctx->c.vocab_size : 0))
-        return set_err(ctx, XH_E_INVALID, "%s", why);
-    if (!ctx || n_steps < 0) return XH_E_INVALID;
-    if (pos < 0) return set_err(ctx, XH_E_INVALID, "negative pos");
-    if (ctx->c.vocab_size > SMP_MAX_VOCAB) return set_err(ctx, XH_E_INVALID, "vocab_size > %d", SMP_MAX_VOCAB);
-    if (n_steps > ctx->dec_cap) return set_err(ctx, XH_E_INVALID, "n_steps > %d", ctx->dec_cap);
-    if (!ctx->dfa_vocab_set || !ctx->dfa_n_states)
-        return set_err(ctx, XH_E_INVALID, "constrained decode before xh_constraint_set_vocab and xh_constraint_set");
-    if (state_in != XH_DFA_DEAD && state_in >= (uint32_t)ctx->dfa_n_states)
-        return set_err(ctx, XH_E_INVALID, "state_in %u out of range", state_in);
-    // an end token is emitted in the stuck state, so it has to be a token
-    if (stop_a >= ctx->c.vocab_size || stop_b >= ctx->c.vocab_size)
-        return set_err(ctx, XH_E_INVALID, "stop token out of range");
-    HIP_TRY(ctx, hipSetDevice(ctx->dev));
-    int rc = check_ready(ctx);
-    if (rc) return rc;
-    const xh_logit_ctl& c = ctl ? *ctl : CTL_OFF;
-    StepParams* h = ctx->sp_host;
-    h->step = 0;
-    h->pos_next = pos;
-    h->max_seq_len = ctx->c.max_seq_len;
-    HIP_TRY(ctx, hipMemcpyAsync(&ctx->sp->step, &h->step, 3 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    const int n_hist = std::min(n_history, XH_CTL_MAX_WINDOW);
-    const ExtCtl blk = ext_block(*sampling, c, n_hist);
-    const DfaCtl dblk = {ctx->dfa_next, ctx->dfa_accept, ctx->dfa_bytes, ctx->dfa_offsets, ctx->dfa_n_states, state_in,
-                         stop_a < 0 ? -1 : stop_a, stop_b < 0 ? -1 : stop_b};
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ext, &blk, sizeof blk, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->dfa, &dblk, sizeof dblk, hipMemcpyHostToDevice, ctx->stream));
-    ctx->dfa_block_valid = true;
-    if (c.n_bias > 0) {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_btok, c.bias_token, (size_t)c.n_bias * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_bval, c.bias_value, (size_t)c.n_bias * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (n_hist > 0)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_ring, history + (n_history - n_hist), (size_t)n_hist * sizeof(int),
-                                    hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->use_graphs && n_steps > 0 && !ctx->g_sample_dfa) {
-        rc = capture(ctx, 5, &ctx->g_sample_dfa);
-        if (rc) return rc;
-    }
-    const bool stops = stop_a >= 0 || stop_b >= 0;
-    int done = 0;
-    for (int i = 0; i < n_steps; i++) {
-        if (ctx->use_graphs) {
-            HIP_TRY(ctx, hipGraphLaunch(ctx->g_sample_dfa, ctx->stream));
-        } else {
-            rc = eager_step(ctx, true, HEAD_SAMPLE_DFA);
-            if (rc) return rc;
-        }
-        ctx->cand_valid = true;
-        done = i + 1;
-        if (stops) {
-            int tok = -1;
-            HIP_TRY(ctx, hipMemcpyAsync(&tok, ctx->dec_tokens + i, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (tok == stop_a || tok == stop_b) break;
-        }
-    }
-    if (tokens_out && done)
-        HIP_TRY(ctx, hipMemcpyAsync(tokens_out, ctx->dec_tokens, (size_t)done * sizeof(int), hipMemcpyDeviceToHost,
-                                    ctx->stream));
-    if (logprobs_out && done)
-        HIP_TRY(ctx, hipMemcpyAsync(logprobs_out, ctx->dec_logprobs, (size_t)done * sizeof(float), hipMemcpyDeviceToHost,
-                                    ctx->stream));
-    uint32_t st = state_in;
-    if (done)
-        HIP_TRY(ctx, hipMemcpyAsync(&st, ctx->dec_states + (done - 1), sizeof st, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (state_out) *state_out = st;
-    if (n_done) *n_done = done;
-    ctx->top_steps = ctx->top_n > 0 ? done : -1;
-    return check_aw(ctx);
+    return decode_run(ctx, {STEP_SAMPLE_DFA, pos, n_steps, sampling, ctl, nullptr, nullptr, history, n_history, 1, state_in,
+                            0.f, stop_a, stop_b, tokens_out, logprobs_out, state_out, nullptr, n_done});
 }
 
 int xh_op_sample_dfa(const float* logits, int vocab, const xh_sampling* sampling, const xh_logit_ctl* ctl,
                      const int* window, int n_window, const xh_byte_dfa* dfa, const uint8_t* bytes,
                      const uint32_t* offsets, uint32_t state, int stop_a, int stop_b, uint64_t pos0, int n_draws,
                      int* tokens_out, int* n_kept_out, float* masked_out, uint32_t* next_state_out, float* logprob_out) {
-    if (!sampling_ok(sampling)) return set_err(nullptr, XH_E_INVALID, "bad sampling parameters");
-    if (!logits || !tokens_out || !n_kept_out || !next_state_out || vocab <= 0 || vocab > SMP_MAX_VOCAB || n_draws <= 0 ||
-        n_draws > 65536)
-        return set_err(nullptr, XH_E_INVALID, "bad sample args");
-    if (const char* why = ctl_error(ctl, window, n_window, vocab)) return set_err(nullptr, XH_E_INVALID, "%s", why);
-    if (const char* why = dfa_error(dfa)) return set_err(nullptr, XH_E_INVALID, "%s", why);
-    if (const char* why = pieces_error(bytes, offsets, vocab)) return set_err(nullptr, XH_E_INVALID, "%s", why);
-    if (const char* why = dfa_state_error(dfa, state)) return set_err(nullptr, XH_E_INVALID, "%s", why);
-    if (stop_a >= vocab || stop_b >= vocab) return set_err(nullptr, XH_E_INVALID, "stop token out of range");
-    const xh_logit_ctl& c = ctl ? *ctl : CTL_OFF;
-    const int n_win = std::min(n_window, XH_CTL_MAX_WINDOW);
-    const ExtCtl blk = ext_block(*sampling, c, n_win);
-    struct Buf {
-        void* p = nullptr;
-        ~Buf() { if (p) hipFree(p); }
-        bool alloc(size_t bytes, const void* src, size_t src_bytes) {
-            if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return false;
-            return !src_bytes || hipMemcpy(p, src, src_bytes, hipMemcpyHostToDevice) == hipSuccess;
-        }
-    } d_logits, d_adj, d_blk, d_dfa, d_ring, d_btok, d_bval, d_prep, d_out, d_lp, d_next, d_acc, d_bytes, d_offs;
-    const size_t ns = (size_t)dfa->n_states;
-    if (!d_logits.alloc((size_t)vocab * 4, logits, (size_t)vocab * 4) || !d_adj.alloc((size_t)vocab * 4, nullptr, 0) ||
-        !d_blk.alloc(sizeof blk, &blk, sizeof blk) ||
-        !d_ring.alloc(XH_CTL_MAX_WINDOW * sizeof(int), n_win ? window + (n_window - n_win) : nullptr, (size_t)n_win * sizeof(int)) ||
-        !d_btok.alloc(XH_CTL_MAX_BIAS * sizeof(int), c.bias_token, (size_t)c.n_bias * sizeof(int)) ||
-        !d_bval.alloc(XH_CTL_MAX_BIAS * sizeof(float), c.bias_value, (size_t)c.n_bias * sizeof(float)) ||
-        !d_prep.alloc(sizeof(DfaPrep), nullptr, 0) || !d_out.alloc((size_t)3 * n_draws * sizeof(int), nullptr, 0) ||
-        !d_lp.alloc((size_t)n_draws * sizeof(float), nullptr, 0) ||
-        !d_next.alloc(ns * 512, dfa->next, ns * 512) || !d_acc.alloc(ns, dfa->accept, ns) ||
-        !d_bytes.alloc(offsets[vocab], bytes, offsets[vocab]) ||
-        !d_offs.alloc(((size_t)vocab + 1) * 4, offsets, ((size_t)vocab + 1) * 4))
-        return set_err(nullptr, XH_E_HIP, "hipMalloc / hipMemcpy failed");
-    const DfaCtl dblk = {(const uint16_t*)d_next.p, (const uint8_t*)d_acc.p, (const uint8_t*)d_bytes.p,
-                         (const uint32_t*)d_offs.p, dfa->n_states, state, stop_a < 0 ? -1 : stop_a, stop_b < 0 ? -1 : stop_b};
-    if (!d_dfa.alloc(sizeof dblk, &dblk, sizeof dblk)) return set_err(nullptr, XH_E_HIP, "hipMalloc / hipMemcpy failed");
-    hipLaunchKernelGGL(sample_dfa_prep_kernel, dim3(1), dim3(SMP_THREADS), 0, nullptr, (const float*)d_logits.p, vocab,
-                       (const ExtCtl*)d_blk.p, (const DfaCtl*)d_dfa.p, (const int*)d_ring.p, (const int*)d_btok.p,
-                       (const float*)d_bval.p, (float*)d_adj.p, (DfaPrep*)d_prep.p);
-    hipLaunchKernelGGL(sample_dfa_op_kernel, dim3(n_draws), dim3(SMP_THREADS), 0, nullptr, (const float*)d_logits.p,
-                       (const float*)d_adj.p, vocab, (const ExtCtl*)d_blk.p, (const DfaCtl*)d_dfa.p,
-                       (const DfaPrep*)d_prep.p, (uint32_t)pos0, (int*)d_out.p, (int*)d_out.p + n_draws,
-                       (uint32_t*)d_out.p + 2 * (size_t)n_draws, (float*)d_lp.p);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(tokens_out, d_out.p, (size_t)n_draws * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(n_kept_out, (int*)d_out.p + n_draws, (size_t)n_draws * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess)
-        e = hipMemcpy(next_state_out, (int*)d_out.p + 2 * (size_t)n_draws, (size_t)n_draws * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && masked_out) e = hipMemcpy(masked_out, d_adj.p, (size_t)vocab * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && logprob_out) e = hipMemcpy(logprob_out, d_lp.p, (size_t)n_draws * sizeof(float), hipMemcpyDeviceToHost);
+    if (int rc = op_check(STEP_SAMPLE_DFA, logits, vocab, sampling, n_draws, tokens_out && n_kept_out && next_state_out, ctl,
+                          window, n_window, nullptr, 0.f, nullptr, dfa, bytes, offsets, state, stop_a, stop_b))
+        return rc;
+    const size_t V = (size_t)vocab, nd = (size_t)n_draws;
+    ExtStage x;
+    DfaStage d;
+    DevBuf d_prep, d_out, d_lp;
+    if (!x.stage(logits, vocab, *sampling, ctl, window, n_window) || !d_prep.alloc(sizeof(DfaPrep)) ||
+        !d_out.alloc(3 * nd * sizeof(int)) || !d_lp.alloc(nd * sizeof(float)) ||
+        !d.stage(dfa, bytes, offsets, vocab, state, stop_a, stop_b))
+        return op_stage_failed();
+    int* d_tok = (int*)d_out.p;
+    hipLaunchKernelGGL(sample_dfa_prep_kernel, dim3(1), dim3(SMP_THREADS), 0, nullptr, (const float*)x.logits.p, vocab,
+                       (const ExtCtl*)x.blk.p, (const DfaCtl*)d.blk.p, (const int*)x.ring.p, (const int*)x.btok.p,
+                       (const float*)x.bval.p, (float*)x.adj.p, (DfaPrep*)d_prep.p);
+    hipLaunchKernelGGL(sample_dfa_op_kernel, dim3(n_draws), dim3(SMP_THREADS), 0, nullptr, (const float*)x.logits.p,
+                       (const float*)x.adj.p, vocab, (const ExtCtl*)x.blk.p, (const DfaCtl*)d.blk.p,
+                       (const DfaPrep*)d_prep.p, (uint32_t)pos0, d_tok, d_tok + nd, (uint32_t*)d_tok + 2 * nd,
+                       (float*)d_lp.p);
+    hipError_t e = op_wait();
+    op_out(e, tokens_out, d_tok, nd * sizeof(int));
+    op_out(e, n_kept_out, d_tok + nd, nd * sizeof(int));
+    op_out(e, next_state_out, d_tok + 2 * nd, nd * sizeof(uint32_t));
+    op_out(e, masked_out, x.adj.p, V * 4);
+    op_out(e, logprob_out, d_lp.p, nd * sizeof(float));
     if (e != hipSuccess) return set_err(nullptr, XH_E_HIP, "sample_dfa op failed: %s", hipGetErrorString(e));
     return 0;
 }
@@ -1169,96 +1108,8 @@ int xh_decode_sample_adapt(xh_ctx* ctx, int pos, int n_steps, const xh_sampling*
                            const xh_trunc_ctl* trunc, const int* history, int n_history, int constrain, uint32_t state_in,
                            float mu_in, int stop_a, int stop_b, int* tokens_out, float* logprobs_out, uint32_t* state_out,
                            float* mu_out, int* n_done) {
-    if (n_done) *n_done = 0;
-    if (!sampling_ok(sampling)) return set_err(ctx, XH_E_INVALID, "bad sampling parameters");
-    if (const char* why = ctl_error(ctl, history, n_history, ctx ? ctx->c.vocab_size : 0))
-        return set_err(ctx, XH_E_INVALID, "%s", why);
-    if (const char* why = trunc_error(trunc, sampling, ctl ? ctl->min_p : 0.f, mu_in))
-        return set_err(ctx, XH_E_INVALID, "%s", why);
-    if (!ctx || n_steps < 0) return XH_E_INVALID;
-    if (pos < 0) return set_err(ctx, XH_E_INVALID, "negative pos");
-    if (ctx->c.vocab_size > SMP_MAX_VOCAB) return set_err(ctx, XH_E_INVALID, "vocab_size > %d", SMP_MAX_VOCAB);
-    if (n_steps > ctx->dec_cap) return set_err(ctx, XH_E_INVALID, "n_steps > %d", ctx->dec_cap);
-    if (constrain) {
-        if (!ctx->dfa_vocab_set || !ctx->dfa_n_states)
-            return set_err(ctx, XH_E_INVALID, "constrained decode before xh_constraint_set_vocab and xh_constraint_set");
-        if (state_in != XH_DFA_DEAD && state_in >= (uint32_t)ctx->dfa_n_states)
-            return set_err(ctx, XH_E_INVALID, "state_in %u out of range", state_in);
-        if (stop_a >= ctx->c.vocab_size || stop_b >= ctx->c.vocab_size)
-            return set_err(ctx, XH_E_INVALID, "stop token out of range");
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->dev));
-    int rc = check_ready(ctx);
-    if (rc) return rc;
-    const xh_logit_ctl& c = ctl ? *ctl : CTL_OFF;
-    StepParams* h = ctx->sp_host;
-    h->step = 0;
-    h->pos_next = pos;
-    h->max_seq_len = ctx->c.max_seq_len;
-    HIP_TRY(ctx, hipMemcpyAsync(&ctx->sp->step, &h->step, 3 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    // the three blocks (mu and the state in them), the bias table and the history's tail
-    const int n_hist = std::min(n_history, XH_CTL_MAX_WINDOW);
-    const ExtCtl blk = ext_block(*sampling, c, n_hist);
-    const AdaptCtl ablk = {trunc->typical_p, trunc->top_n_sigma, trunc->mirostat_tau, trunc->mirostat_eta, mu_in,
-                           constrain ? 1 : 0};
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ext, &blk, sizeof blk, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->adapt, &ablk, sizeof ablk, hipMemcpyHostToDevice, ctx->stream));
-    if (constrain) {
-        const DfaCtl dblk = {ctx->dfa_next, ctx->dfa_accept, ctx->dfa_bytes, ctx->dfa_offsets, ctx->dfa_n_states, state_in,
-                             stop_a < 0 ? -1 : stop_a, stop_b < 0 ? -1 : stop_b};
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->dfa, &dblk, sizeof dblk, hipMemcpyHostToDevice, ctx->stream));
-        ctx->dfa_block_valid = true;
-    }
-    ctx->adapt_valid = true;
-    ctx->adapt_constrain = constrain != 0;
-    if (c.n_bias > 0) {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_btok, c.bias_token, (size_t)c.n_bias * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_bval, c.bias_value, (size_t)c.n_bias * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (n_hist > 0)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_ring, history + (n_history - n_hist), (size_t)n_hist * sizeof(int),
-                                    hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->use_graphs && n_steps > 0 && !ctx->g_sample_adapt) {
-        rc = capture(ctx, 6, &ctx->g_sample_adapt);
-        if (rc) return rc;
-    }
-    const bool stops = stop_a >= 0 || stop_b >= 0;
-    int done = 0;
-    for (int i = 0; i < n_steps; i++) {
-        if (ctx->use_graphs) {
-            HIP_TRY(ctx, hipGraphLaunch(ctx->g_sample_adapt, ctx->stream));
-        } else {
-            rc = eager_step(ctx, true, HEAD_SAMPLE_ADAPT);
-            if (rc) return rc;
-        }
-        ctx->cand_valid = true;
-        done = i + 1;
-        if (stops) {
-            int tok = -1;
-            HIP_TRY(ctx, hipMemcpyAsync(&tok, ctx->dec_tokens + i, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (tok == stop_a || tok == stop_b) break;
-        }
-    }
-    if (tokens_out && done)
-        HIP_TRY(ctx, hipMemcpyAsync(tokens_out, ctx->dec_tokens, (size_t)done * sizeof(int), hipMemcpyDeviceToHost,
-                                    ctx->stream));
-    if (logprobs_out && done)
-        HIP_TRY(ctx, hipMemcpyAsync(logprobs_out, ctx->dec_logprobs, (size_t)done * sizeof(float), hipMemcpyDeviceToHost,
-                                    ctx->stream));
-    // no step runs past the last emitted token, so the blocks hold the state and mu after it
-    uint32_t st = state_in;
-    float mu = mu_in;
-    if (done && constrain)
-        HIP_TRY(ctx, hipMemcpyAsync(&st, ctx->dec_states + (done - 1), sizeof st, hipMemcpyDeviceToHost, ctx->stream));
-    if (done) HIP_TRY(ctx, hipMemcpyAsync(&mu, &ctx->adapt->mu, sizeof mu, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (state_out) *state_out = st;
-    if (mu_out) *mu_out = mu;
-    if (n_done) *n_done = done;
-    ctx->top_steps = ctx->top_n > 0 ? done : -1;
-    return check_aw(ctx);
+    return decode_run(ctx, {STEP_SAMPLE_ADAPT, pos, n_steps, sampling, ctl, trunc, nullptr, history, n_history, constrain,
+                            state_in, mu_in, stop_a, stop_b, tokens_out, logprobs_out, state_out, mu_out, n_done});
 }
 
 int xh_op_sample_adapt(const float* logits, int vocab, const xh_sampling* sampling, const xh_logit_ctl* ctl,
@@ -1266,189 +1117,48 @@ int xh_op_sample_adapt(const float* logits, int vocab, const xh_sampling* sampli
                        const uint8_t* bytes, const uint32_t* offsets, uint32_t state, float mu, int stop_a, int stop_b,
                        uint64_t pos0, int n_draws, int* tokens_out, int* n_kept_out, uint32_t* next_state_out,
                        float* mu_out, uint8_t* kept_out, float* thr_out) {
-    if (!sampling_ok(sampling)) return set_err(nullptr, XH_E_INVALID, "bad sampling parameters");
-    if (!logits || !tokens_out || !n_kept_out || !next_state_out || !mu_out || vocab <= 0 || vocab > SMP_MAX_VOCAB ||
-        n_draws <= 0 || n_draws > 65536)
-        return set_err(nullptr, XH_E_INVALID, "bad sample args");
-    if (const char* why = ctl_error(ctl, window, n_window, vocab)) return set_err(nullptr, XH_E_INVALID, "%s", why);
-    if (const char* why = trunc_error(trunc, sampling, ctl ? ctl->min_p : 0.f, mu)) return set_err(nullptr, XH_E_INVALID, "%s", why);
-    if (dfa) {
-        if (const char* why = dfa_error(dfa)) return set_err(nullptr, XH_E_INVALID, "%s", why);
-        if (const char* why = pieces_error(bytes, offsets, vocab)) return set_err(nullptr, XH_E_INVALID, "%s", why);
-        if (const char* why = dfa_state_error(dfa, state)) return set_err(nullptr, XH_E_INVALID, "%s", why);
-        if (stop_a >= vocab || stop_b >= vocab) return set_err(nullptr, XH_E_INVALID, "stop token out of range");
-    }
-    const xh_logit_ctl& c = ctl ? *ctl : CTL_OFF;
-    const int n_win = std::min(n_window, XH_CTL_MAX_WINDOW);
-    const ExtCtl blk = ext_block(*sampling, c, n_win);
-    const AdaptCtl ablk = {trunc->typical_p, trunc->top_n_sigma, trunc->mirostat_tau, trunc->mirostat_eta, mu, dfa ? 1 : 0};
-    struct Buf {
-        void* p = nullptr;
-        ~Buf() { if (p) hipFree(p); }
-        bool alloc(size_t bytes, const void* src, size_t src_bytes) {
-            if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return false;
-            return !src_bytes || hipMemcpy(p, src, src_bytes, hipMemcpyHostToDevice) == hipSuccess;
-        }
-    } d_logits, d_adj, d_negd, d_kept, d_blk, d_ablk, d_dfa, d_ring, d_btok, d_bval, d_prep, d_out, d_mu, d_next, d_acc,
-        d_bytes, d_offs;
-    const size_t ns = dfa ? (size_t)dfa->n_states : 0;
-    if (!d_logits.alloc((size_t)vocab * 4, logits, (size_t)vocab * 4) || !d_adj.alloc((size_t)vocab * 4, nullptr, 0) ||
-        !d_negd.alloc((size_t)vocab * 4, nullptr, 0) || !d_kept.alloc((size_t)vocab, nullptr, 0) ||
-        !d_blk.alloc(sizeof blk, &blk, sizeof blk) || !d_ablk.alloc(sizeof ablk, &ablk, sizeof ablk) ||
-        !d_ring.alloc(XH_CTL_MAX_WINDOW * sizeof(int), n_win ? window + (n_window - n_win) : nullptr, (size_t)n_win * sizeof(int)) ||
-        !d_btok.alloc(XH_CTL_MAX_BIAS * sizeof(int), c.bias_token, (size_t)c.n_bias * sizeof(int)) ||
-        !d_bval.alloc(XH_CTL_MAX_BIAS * sizeof(float), c.bias_value, (size_t)c.n_bias * sizeof(float)) ||
-        !d_prep.alloc(sizeof(AdaptOpPrep), nullptr, 0) || !d_out.alloc((size_t)3 * n_draws * sizeof(int), nullptr, 0) ||
-        !d_mu.alloc((size_t)n_draws * sizeof(float), nullptr, 0) ||
-        (dfa && (!d_next.alloc(ns * 512, dfa->next, ns * 512) || !d_acc.alloc(ns, dfa->accept, ns) ||
-                 !d_bytes.alloc(offsets[vocab], bytes, offsets[vocab]) ||
-                 !d_offs.alloc(((size_t)vocab + 1) * 4, offsets, ((size_t)vocab + 1) * 4))))
-        return set_err(nullptr, XH_E_HIP, "hipMalloc / hipMemcpy failed");
-    const DfaCtl dblk = {(const uint16_t*)d_next.p, (const uint8_t*)d_acc.p, (const uint8_t*)d_bytes.p,
-                         (const uint32_t*)d_offs.p, dfa ? dfa->n_states : 0, state, stop_a < 0 ? -1 : stop_a,
-                         stop_b < 0 ? -1 : stop_b};
-    if (!d_dfa.alloc(sizeof dblk, &dblk, sizeof dblk)) return set_err(nullptr, XH_E_HIP, "hipMalloc / hipMemcpy failed");
-    hipLaunchKernelGGL(sample_adapt_prep_kernel, dim3(1), dim3(SMP_THREADS), 0, nullptr, (const float*)d_logits.p, vocab,
-                       (const ExtCtl*)d_blk.p, (const DfaCtl*)d_dfa.p, (const AdaptCtl*)d_ablk.p, (const int*)d_ring.p,
-                       (const int*)d_btok.p, (const float*)d_bval.p, (float*)d_adj.p, (float*)d_negd.p, (uint8_t*)d_kept.p,
+    if (int rc = op_check(STEP_SAMPLE_ADAPT, logits, vocab, sampling, n_draws,
+                          tokens_out && n_kept_out && next_state_out && mu_out, ctl, window, n_window, trunc, mu, nullptr, dfa,
+                          bytes, offsets, state, stop_a, stop_b))
+        return rc;
+    const AdaptCtl ablk = adapt_block(*trunc, mu, dfa != nullptr);
+    const size_t V = (size_t)vocab, nd = (size_t)n_draws;
+    ExtStage x;
+    DfaStage d;
+    DevBuf d_negd, d_kept, d_ablk, d_prep, d_out, d_mu;
+    if (!x.stage(logits, vocab, *sampling, ctl, window, n_window) || !d_negd.alloc(V * 4) || !d_kept.alloc(V) ||
+        !d_ablk.alloc(sizeof ablk, &ablk, sizeof ablk) || !d_prep.alloc(sizeof(AdaptOpPrep)) ||
+        !d_out.alloc(3 * nd * sizeof(int)) || !d_mu.alloc(nd * sizeof(float)) ||
+        !d.stage(dfa, bytes, offsets, vocab, state, stop_a, stop_b))
+        return op_stage_failed();
+    int* d_tok = (int*)d_out.p;
+    hipLaunchKernelGGL(sample_adapt_prep_kernel, dim3(1), dim3(SMP_THREADS), 0, nullptr, (const float*)x.logits.p, vocab,
+                       (const ExtCtl*)x.blk.p, (const DfaCtl*)d.blk.p, (const AdaptCtl*)d_ablk.p, (const int*)x.ring.p,
+                       (const int*)x.btok.p, (const float*)x.bval.p, (float*)x.adj.p, (float*)d_negd.p, (uint8_t*)d_kept.p,
                        (AdaptOpPrep*)d_prep.p);
-    hipLaunchKernelGGL(sample_adapt_op_kernel, dim3(n_draws), dim3(SMP_THREADS), 0, nullptr, (const float*)d_adj.p, vocab,
-                       (const ExtCtl*)d_blk.p, (const DfaCtl*)d_dfa.p, (const AdaptCtl*)d_ablk.p,
-                       (const AdaptOpPrep*)d_prep.p, (uint32_t)pos0, (int*)d_out.p, (int*)d_out.p + n_draws,
-                       (uint32_t*)d_out.p + 2 * (size_t)n_draws, (float*)d_mu.p);
+    hipLaunchKernelGGL(sample_adapt_op_kernel, dim3(n_draws), dim3(SMP_THREADS), 0, nullptr, (const float*)x.adj.p, vocab,
+                       (const ExtCtl*)x.blk.p, (const DfaCtl*)d.blk.p, (const AdaptCtl*)d_ablk.p,
+                       (const AdaptOpPrep*)d_prep.p, (uint32_t)pos0, d_tok, d_tok + nd, (uint32_t*)d_tok + 2 * nd,
+                       (float*)d_mu.p);
     AdaptOpPrep hp;
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(tokens_out, d_out.p, (size_t)n_draws * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(n_kept_out, (int*)d_out.p + n_draws, (size_t)n_draws * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess)
-        e = hipMemcpy(next_state_out, (int*)d_out.p + 2 * (size_t)n_draws, (size_t)n_draws * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(mu_out, d_mu.p, (size_t)n_draws * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && kept_out) e = hipMemcpy(kept_out, d_kept.p, (size_t)vocab, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && thr_out) {
-        e = hipMemcpy(&hp, d_prep.p, sizeof hp, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) *thr_out = hp.ap.thr;
-    }
+    hipError_t e = op_wait();
+    op_out(e, tokens_out, d_tok, nd * sizeof(int));
+    op_out(e, n_kept_out, d_tok + nd, nd * sizeof(int));
+    op_out(e, next_state_out, d_tok + 2 * nd, nd * sizeof(uint32_t));
+    op_out(e, mu_out, d_mu.p, nd * sizeof(float));
+    op_out(e, kept_out, d_kept.p, V);
+    op_out(e, thr_out ? &hp : nullptr, d_prep.p, sizeof hp);
     if (e != hipSuccess) return set_err(nullptr, XH_E_HIP, "sample_adapt op failed: %s", hipGetErrorString(e));
+    if (thr_out) *thr_out = hp.ap.thr;
     return 0;
 }
-
-namespace {
-// the device block of xh_seq_ctl and its breakers in ascending order (what the head's binary search needs)
-SeqCtl seq_block(const xh_seq_ctl& q, std::vector<int>* sorted) {
-    sorted->assign(q.breaker_token, q.breaker_token + q.n_breakers);
-    std::sort(sorted->begin(), sorted->end());
-    return SeqCtl{q.dry_multiplier, q.dry_base, q.dry_allowed_length, q.no_repeat_ngram, q.seq_last_n, q.n_breakers,
-                  q.xtc_probability, q.xtc_threshold};
-}
-}  // namespace
 
 int xh_decode_sample_seq(xh_ctx* ctx, int pos, int n_steps, const xh_sampling* sampling, const xh_logit_ctl* ctl,
                          const xh_trunc_ctl* trunc, const xh_seq_ctl* seq, const int* history, int n_history, int constrain,
                          uint32_t state_in, float mu_in, int stop_a, int stop_b, int* tokens_out, float* logprobs_out,
                          uint32_t* state_out, float* mu_out, int* n_done) {
-    if (n_done) *n_done = 0;
-    if (!sampling_ok(sampling)) return set_err(ctx, XH_E_INVALID, "bad sampling parameters");
-    if (const char* why = ctl_error(ctl, history, n_history, ctx ? ctx->c.vocab_size : 0))
-        return set_err(ctx, XH_E_INVALID, "%s", why);
-    if (const char* why = trunc_error(trunc, sampling, ctl ? ctl->min_p : 0.f, mu_in))
-        return set_err(ctx, XH_E_INVALID, "%s", why);
-    if (const char* why = seq_error(seq, trunc, ctx ? ctx->c.vocab_size : 0)) return set_err(ctx, XH_E_INVALID, "%s", why);
-    if (!ctx || n_steps < 0) return XH_E_INVALID;
-    if (pos < 0) return set_err(ctx, XH_E_INVALID, "negative pos");
-    if (ctx->c.vocab_size > SMP_MAX_VOCAB) return set_err(ctx, XH_E_INVALID, "vocab_size > %d", SMP_MAX_VOCAB);
-    if (n_steps > ctx->dec_cap) return set_err(ctx, XH_E_INVALID, "n_steps > %d", ctx->dec_cap);
-    if (constrain) {
-        if (!ctx->dfa_vocab_set || !ctx->dfa_n_states)
-            return set_err(ctx, XH_E_INVALID, "constrained decode before xh_constraint_set_vocab and xh_constraint_set");
-        if (state_in != XH_DFA_DEAD && state_in >= (uint32_t)ctx->dfa_n_states)
-            return set_err(ctx, XH_E_INVALID, "state_in %u out of range", state_in);
-        if (stop_a >= ctx->c.vocab_size || stop_b >= ctx->c.vocab_size)
-            return set_err(ctx, XH_E_INVALID, "stop token out of range");
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->dev));
-    int rc = check_ready(ctx);
-    if (rc) return rc;
-    const xh_logit_ctl& c = ctl ? *ctl : CTL_OFF;
-    StepParams* h = ctx->sp_host;
-    h->step = 0;
-    h->pos_next = pos;
-    h->max_seq_len = ctx->c.max_seq_len;
-    HIP_TRY(ctx, hipMemcpyAsync(&ctx->sp->step, &h->step, 3 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    // the four blocks (mu and the state in them), the bias table, the breakers and the history's tail
-    const int n_hist = std::min(n_history, XH_CTL_MAX_WINDOW);
-    const ExtCtl blk = ext_block(*sampling, c, n_hist);
-    const AdaptCtl ablk = {trunc->typical_p, trunc->top_n_sigma, trunc->mirostat_tau, trunc->mirostat_eta, mu_in,
-                           constrain ? 1 : 0};
-    std::vector<int> brk;
-    const SeqCtl sblk = seq_block(*seq, &brk);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ext, &blk, sizeof blk, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->adapt, &ablk, sizeof ablk, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->seq, &sblk, sizeof sblk, hipMemcpyHostToDevice, ctx->stream));
-    const SeqTail tblk = {ctx->dec_tokens, ctx->dec_logprobs, ctx->dec_states, (const void*)ctx->embed, ctx->x,
-                          (const float*)ctx->rope_freq, ctx->rope_cs, ctx->dec_cap, ctx->embed_dt, ctx->c.dim,
-                          ctx->c.head_dim / 2};
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->seq_tail, &tblk, sizeof tblk, hipMemcpyHostToDevice, ctx->stream));
-    if (!brk.empty())
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->seq_brk, brk.data(), brk.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    if (constrain) {
-        const DfaCtl dblk = {ctx->dfa_next, ctx->dfa_accept, ctx->dfa_bytes, ctx->dfa_offsets, ctx->dfa_n_states, state_in,
-                             stop_a < 0 ? -1 : stop_a, stop_b < 0 ? -1 : stop_b};
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->dfa, &dblk, sizeof dblk, hipMemcpyHostToDevice, ctx->stream));
-        ctx->dfa_block_valid = true;
-    }
-    // the adaptive head's timing hook reads ctx->adapt too: it holds this call's parameters now
-    ctx->adapt_valid = true;
-    ctx->adapt_constrain = constrain != 0;
-    ctx->seq_valid = true;
-    ctx->seq_constrain = constrain != 0;
-    if (c.n_bias > 0) {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_btok, c.bias_token, (size_t)c.n_bias * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_bval, c.bias_value, (size_t)c.n_bias * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (n_hist > 0)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_ring, history + (n_history - n_hist), (size_t)n_hist * sizeof(int),
-                                    hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->use_graphs && n_steps > 0 && !ctx->g_sample_seq) {
-        rc = capture(ctx, 7, &ctx->g_sample_seq);
-        if (rc) return rc;
-    }
-    const bool stops = stop_a >= 0 || stop_b >= 0;
-    int done = 0;
-    for (int i = 0; i < n_steps; i++) {
-        if (ctx->use_graphs) {
-            HIP_TRY(ctx, hipGraphLaunch(ctx->g_sample_seq, ctx->stream));
-        } else {
-            rc = eager_step(ctx, true, HEAD_SAMPLE_SEQ);
-            if (rc) return rc;
-        }
-        ctx->cand_valid = true;
-        done = i + 1;
-        if (stops) {
-            int tok = -1;
-            HIP_TRY(ctx, hipMemcpyAsync(&tok, ctx->dec_tokens + i, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (tok == stop_a || tok == stop_b) break;
-        }
-    }
-    if (tokens_out && done)
-        HIP_TRY(ctx, hipMemcpyAsync(tokens_out, ctx->dec_tokens, (size_t)done * sizeof(int), hipMemcpyDeviceToHost,
-                                    ctx->stream));
-    if (logprobs_out && done)
-        HIP_TRY(ctx, hipMemcpyAsync(logprobs_out, ctx->dec_logprobs, (size_t)done * sizeof(float), hipMemcpyDeviceToHost,
-                                    ctx->stream));
-    uint32_t st = state_in;
-    float mu = mu_in;
-    if (done && constrain)
-        HIP_TRY(ctx, hipMemcpyAsync(&st, ctx->dec_states + (done - 1), sizeof st, hipMemcpyDeviceToHost, ctx->stream));
-    if (done) HIP_TRY(ctx, hipMemcpyAsync(&mu, &ctx->adapt->mu, sizeof mu, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (state_out) *state_out = st;
-    if (mu_out) *mu_out = mu;
-    if (n_done) *n_done = done;
-    ctx->top_steps = ctx->top_n > 0 ? done : -1;
-    return check_aw(ctx);
+    return decode_run(ctx, {STEP_SAMPLE_SEQ, pos, n_steps, sampling, ctl, trunc, seq, history, n_history, constrain, state_in,
+                            mu_in, stop_a, stop_b, tokens_out, logprobs_out, state_out, mu_out, n_done});
 }
 
 int xh_op_sample_seq(const float* logits, int vocab, const xh_sampling* sampling, const xh_logit_ctl* ctl,
@@ -1457,111 +1167,74 @@ int xh_op_sample_seq(const float* logits, int vocab, const xh_sampling* sampling
                      int stop_a, int stop_b, uint64_t pos0, int n_draws, int* tokens_out, int* n_kept_out,
                      uint32_t* next_state_out, float* mu_out, float* adjusted_out, int* rep_out, int* ng_out,
                      uint8_t* kept_out, int* xtc_fired_out) {
-    if (!sampling_ok(sampling)) return set_err(nullptr, XH_E_INVALID, "bad sampling parameters");
-    if (!logits || !tokens_out || !n_kept_out || !next_state_out || !mu_out || vocab <= 0 || vocab > SMP_MAX_VOCAB ||
-        n_draws <= 0 || n_draws > 65536)
-        return set_err(nullptr, XH_E_INVALID, "bad sample args");
-    if (const char* why = ctl_error(ctl, window, n_window, vocab)) return set_err(nullptr, XH_E_INVALID, "%s", why);
-    if (const char* why = trunc_error(trunc, sampling, ctl ? ctl->min_p : 0.f, mu)) return set_err(nullptr, XH_E_INVALID, "%s", why);
-    if (const char* why = seq_error(seq, trunc, vocab)) return set_err(nullptr, XH_E_INVALID, "%s", why);
-    if (dfa) {
-        if (const char* why = dfa_error(dfa)) return set_err(nullptr, XH_E_INVALID, "%s", why);
-        if (const char* why = pieces_error(bytes, offsets, vocab)) return set_err(nullptr, XH_E_INVALID, "%s", why);
-        if (const char* why = dfa_state_error(dfa, state)) return set_err(nullptr, XH_E_INVALID, "%s", why);
-        if (stop_a >= vocab || stop_b >= vocab) return set_err(nullptr, XH_E_INVALID, "stop token out of range");
-    }
-    const xh_logit_ctl& c = ctl ? *ctl : CTL_OFF;
-    const int n_win = std::min(n_window, XH_CTL_MAX_WINDOW);
-    const ExtCtl blk = ext_block(*sampling, c, n_win);
-    const AdaptCtl ablk = {trunc->typical_p, trunc->top_n_sigma, trunc->mirostat_tau, trunc->mirostat_eta, mu, dfa ? 1 : 0};
+    if (int rc = op_check(STEP_SAMPLE_SEQ, logits, vocab, sampling, n_draws,
+                          tokens_out && n_kept_out && next_state_out && mu_out, ctl, window, n_window, trunc, mu, seq, dfa,
+                          bytes, offsets, state, stop_a, stop_b))
+        return rc;
+    const AdaptCtl ablk = adapt_block(*trunc, mu, dfa != nullptr);
     std::vector<int> brk;
     const SeqCtl sblk = seq_block(*seq, &brk);
-    struct Buf {
-        void* p = nullptr;
-        ~Buf() { if (p) hipFree(p); }
-        bool alloc(size_t bytes, const void* src, size_t src_bytes) {
-            if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return false;
-            return !src_bytes || hipMemcpy(p, src, src_bytes, hipMemcpyHostToDevice) == hipSuccess;
-        }
-    } d_logits, d_adj, d_negd, d_snap, d_rep, d_kept, d_rows, d_krows, d_blk, d_ablk, d_sblk, d_brk, d_dfa, d_ring, d_btok,
-        d_bval, d_prep, d_out, d_mu, d_next, d_acc, d_bytes, d_offs;
-    const size_t ns = dfa ? (size_t)dfa->n_states : 0, V = (size_t)vocab, nd = (size_t)n_draws;
-    if (!d_logits.alloc(V * 4, logits, V * 4) || !d_adj.alloc(V * 4, nullptr, 0) || !d_negd.alloc(V * 4, nullptr, 0) ||
-        !d_snap.alloc(V * 4, nullptr, 0) || !d_rep.alloc(2 * V * sizeof(int), nullptr, 0) || !d_kept.alloc(V, nullptr, 0) ||
-        !d_rows.alloc(nd * V * 4, nullptr, 0) || !d_krows.alloc(nd * V, nullptr, 0) ||
-        !d_blk.alloc(sizeof blk, &blk, sizeof blk) || !d_ablk.alloc(sizeof ablk, &ablk, sizeof ablk) ||
-        !d_sblk.alloc(sizeof sblk, &sblk, sizeof sblk) ||
+    const size_t V = (size_t)vocab, nd = (size_t)n_draws;
+    ExtStage x;
+    DfaStage d;
+    DevBuf d_negd, d_snap, d_rep, d_kept, d_rows, d_krows, d_ablk, d_sblk, d_brk, d_prep, d_out, d_mu;
+    if (!x.stage(logits, vocab, *sampling, ctl, window, n_window) || !d_negd.alloc(V * 4) || !d_snap.alloc(V * 4) ||
+        !d_rep.alloc(2 * V * sizeof(int)) || !d_kept.alloc(V) || !d_rows.alloc(nd * V * 4) || !d_krows.alloc(nd * V) ||
+        !d_ablk.alloc(sizeof ablk, &ablk, sizeof ablk) || !d_sblk.alloc(sizeof sblk, &sblk, sizeof sblk) ||
         !d_brk.alloc(XH_SEQ_MAX_BREAKERS * sizeof(int), brk.data(), brk.size() * sizeof(int)) ||
-        !d_ring.alloc(XH_CTL_MAX_WINDOW * sizeof(int), n_win ? window + (n_window - n_win) : nullptr, (size_t)n_win * sizeof(int)) ||
-        !d_btok.alloc(XH_CTL_MAX_BIAS * sizeof(int), c.bias_token, (size_t)c.n_bias * sizeof(int)) ||
-        !d_bval.alloc(XH_CTL_MAX_BIAS * sizeof(float), c.bias_value, (size_t)c.n_bias * sizeof(float)) ||
-        !d_prep.alloc(sizeof(AdaptOpPrep), nullptr, 0) || !d_out.alloc(4 * nd * sizeof(int), nullptr, 0) ||
-        !d_mu.alloc(nd * sizeof(float), nullptr, 0) ||
-        (dfa && (!d_next.alloc(ns * 512, dfa->next, ns * 512) || !d_acc.alloc(ns, dfa->accept, ns) ||
-                 !d_bytes.alloc(offsets[vocab], bytes, offsets[vocab]) ||
-                 !d_offs.alloc((V + 1) * 4, offsets, (V + 1) * 4))))
-        return set_err(nullptr, XH_E_HIP, "hipMalloc / hipMemcpy failed");
+        !d_prep.alloc(sizeof(AdaptOpPrep)) || !d_out.alloc(4 * nd * sizeof(int)) || !d_mu.alloc(nd * sizeof(float)) ||
+        !d.stage(dfa, bytes, offsets, vocab, state, stop_a, stop_b))
+        return op_stage_failed();
     if (hipMemset(d_rep.p, 0, 2 * V * sizeof(int)) != hipSuccess) return set_err(nullptr, XH_E_HIP, "hipMemset failed");
-    const DfaCtl dblk = {(const uint16_t*)d_next.p, (const uint8_t*)d_acc.p, (const uint8_t*)d_bytes.p,
-                         (const uint32_t*)d_offs.p, dfa ? dfa->n_states : 0, state, stop_a < 0 ? -1 : stop_a,
-                         stop_b < 0 ? -1 : stop_b};
-    if (!d_dfa.alloc(sizeof dblk, &dblk, sizeof dblk)) return set_err(nullptr, XH_E_HIP, "hipMalloc / hipMemcpy failed");
     int* d_tok = (int*)d_out.p;
-    hipLaunchKernelGGL(sample_seq_prep_kernel, dim3(1), dim3(SMP_THREADS), 0, nullptr, (const float*)d_logits.p, vocab,
-                       (const ExtCtl*)d_blk.p, (const DfaCtl*)d_dfa.p, (const AdaptCtl*)d_ablk.p, (const SeqCtl*)d_sblk.p,
-                       (const int*)d_ring.p, (const int*)d_btok.p, (const float*)d_bval.p, (const int*)d_brk.p,
-                       (float*)d_adj.p, (float*)d_negd.p, (float*)d_snap.p, (int*)d_rep.p, (int*)d_rep.p + V,
+    hipLaunchKernelGGL(sample_seq_prep_kernel, dim3(1), dim3(SMP_THREADS), 0, nullptr, (const float*)x.logits.p, vocab,
+                       (const ExtCtl*)x.blk.p, (const DfaCtl*)d.blk.p, (const AdaptCtl*)d_ablk.p, (const SeqCtl*)d_sblk.p,
+                       (const int*)x.ring.p, (const int*)x.btok.p, (const float*)x.bval.p, (const int*)d_brk.p,
+                       (float*)x.adj.p, (float*)d_negd.p, (float*)d_snap.p, (int*)d_rep.p, (int*)d_rep.p + V,
                        (uint8_t*)d_kept.p, (AdaptOpPrep*)d_prep.p);
-    hipLaunchKernelGGL(sample_seq_op_kernel, dim3(n_draws), dim3(SMP_THREADS), 0, nullptr, (const float*)d_adj.p,
-                       (const uint8_t*)d_kept.p, (float*)d_rows.p, (uint8_t*)d_krows.p, vocab, (const ExtCtl*)d_blk.p,
-                       (const DfaCtl*)d_dfa.p, (const AdaptCtl*)d_ablk.p, (const SeqCtl*)d_sblk.p,
+    hipLaunchKernelGGL(sample_seq_op_kernel, dim3(n_draws), dim3(SMP_THREADS), 0, nullptr, (const float*)x.adj.p,
+                       (const uint8_t*)d_kept.p, (float*)d_rows.p, (uint8_t*)d_krows.p, vocab, (const ExtCtl*)x.blk.p,
+                       (const DfaCtl*)d.blk.p, (const AdaptCtl*)d_ablk.p, (const SeqCtl*)d_sblk.p,
                        (const AdaptOpPrep*)d_prep.p, (uint32_t)pos0, d_tok, d_tok + nd, (uint32_t*)d_tok + 2 * nd,
                        (float*)d_mu.p, d_tok + 3 * nd);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(tokens_out, d_tok, nd * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(n_kept_out, d_tok + nd, nd * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(next_state_out, d_tok + 2 * nd, nd * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(mu_out, d_mu.p, nd * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && xtc_fired_out) e = hipMemcpy(xtc_fired_out, d_tok + 3 * nd, nd * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && adjusted_out) e = hipMemcpy(adjusted_out, d_snap.p, V * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rep_out) e = hipMemcpy(rep_out, d_rep.p, V * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && ng_out) e = hipMemcpy(ng_out, (int*)d_rep.p + V, V * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && kept_out) e = hipMemcpy(kept_out, d_krows.p, nd * V, hipMemcpyDeviceToHost);
+    hipError_t e = op_wait();
+    op_out(e, tokens_out, d_tok, nd * sizeof(int));
+    op_out(e, n_kept_out, d_tok + nd, nd * sizeof(int));
+    op_out(e, next_state_out, d_tok + 2 * nd, nd * sizeof(uint32_t));
+    op_out(e, mu_out, d_mu.p, nd * sizeof(float));
+    op_out(e, xtc_fired_out, d_tok + 3 * nd, nd * sizeof(int));
+    op_out(e, adjusted_out, d_snap.p, V * 4);
+    op_out(e, rep_out, d_rep.p, V * sizeof(int));
+    op_out(e, ng_out, (int*)d_rep.p + V, V * sizeof(int));
+    op_out(e, kept_out, d_krows.p, nd * V);
     if (e != hipSuccess) return set_err(nullptr, XH_E_HIP, "sample_seq op failed: %s", hipGetErrorString(e));
     return 0;
 }
+
 
 int xh_op_top_logprobs(const float* logits, int vocab, int n_rows, int n_top, const int* targets, int* ids_out,
                        float* lps_out, float* target_lp_out, int* target_rank_out) {
     if (const char* why = top_args_error(logits, vocab, n_rows, n_top, 1, targets, ids_out, lps_out, target_lp_out,
                                          target_rank_out))
         return set_err(nullptr, XH_E_INVALID, "%s", why);
-    struct Buf {
-        void* p = nullptr;
-        ~Buf() { if (p) hipFree(p); }
-        bool alloc(size_t bytes, const void* src) {
-            if (hipMalloc(&p, bytes) != hipSuccess) return false;
-            return !src || hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-        }
-    } d_logits, d_tgt, d_ids, d_lps, d_tlp, d_rank;
+    DevBuf d_logits, d_tgt, d_ids, d_lps, d_tlp, d_rank;
     const size_t rows = (size_t)n_rows, top = rows * (size_t)n_top;
-    if (!d_logits.alloc(rows * vocab * 4, logits) || !d_ids.alloc(top * sizeof(int), nullptr) ||
-        !d_lps.alloc(top * sizeof(float), nullptr) ||
-        (targets && (!d_tgt.alloc(rows * sizeof(int), targets) || !d_tlp.alloc(rows * sizeof(float), nullptr) ||
-                     !d_rank.alloc(rows * sizeof(int), nullptr))))
-        return set_err(nullptr, XH_E_HIP, "hipMalloc / hipMemcpy failed");
+    if (!d_logits.alloc(rows * vocab * 4, logits, rows * vocab * 4) || !d_ids.alloc(top * sizeof(int)) ||
+        !d_lps.alloc(top * sizeof(float)) ||
+        (targets && (!d_tgt.alloc(rows * sizeof(int), targets, rows * sizeof(int)) || !d_tlp.alloc(rows * sizeof(float)) ||
+                     !d_rank.alloc(rows * sizeof(int)))))
+        return op_stage_failed();
     launch_top_logprobs((const float*)d_logits.p, vocab, (size_t)vocab, n_rows, nullptr, n_top, nullptr, 0,
                         (const int*)d_tgt.p, n_top, (int*)d_ids.p, (float*)d_lps.p, (float*)d_tlp.p, (int*)d_rank.p, nullptr);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(ids_out, d_ids.p, top * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(lps_out, d_lps.p, top * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && targets) e = hipMemcpy(target_lp_out, d_tlp.p, rows * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && targets) e = hipMemcpy(target_rank_out, d_rank.p, rows * sizeof(int), hipMemcpyDeviceToHost);
+    hipError_t e = op_wait();
+    op_out(e, ids_out, d_ids.p, top * sizeof(int));
+    op_out(e, lps_out, d_lps.p, top * sizeof(float));
+    op_out(e, targets ? target_lp_out : nullptr, d_tlp.p, rows * sizeof(float));
+    op_out(e, targets ? target_rank_out : nullptr, d_rank.p, rows * sizeof(int));
     if (e != hipSuccess) return set_err(nullptr, XH_E_HIP, "top_logprobs op failed: %s", hipGetErrorString(e));
     return 0;
 }
+
 
 int xh_set_top_logprobs(xh_ctx* ctx, int n_top) {
     if (!ctx) return XH_E_INVALID;

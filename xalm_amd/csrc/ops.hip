@@ -539,12 +539,12 @@ int xh_time_kernel(xh_ctx* ctx, int which, int iters, float* avg_us) {
             case 2: return launch_gemv(GEMV_RESID, kdt(ctx->L[l].wo_dt, ctx->L[l].wo_x), wo_args(ctx, l), ctx->stream, mb);
             case 3: return launch_gemv(GEMV_RESID, kdt(ctx->L[l].w2_dt, ctx->L[l].w2_x), w2_args(ctx, l), ctx->stream, mb);
             case 4: return launch_gemv(GEMV_LOGITS, kdt(ctx->wcls_dt, ctx->wcls_x), cls_args(ctx), ctx->stream, mb);
-            case 6: time_sample_head(ctx); return true;
-            case 7: time_sample_ext_head(ctx); return true;
-            case 8: time_sample_dfa_head(ctx); return true;
+            case 6: time_head(ctx, STEP_SAMPLE); return true;
+            case 7: time_head(ctx, STEP_SAMPLE_EXT); return true;
+            case 8: time_head(ctx, STEP_SAMPLE_DFA); return true;
             case 9: time_top_logprobs(ctx); return true;
-            case 10: time_sample_adapt_head(ctx); return true;
-            case 11: time_sample_seq_head(ctx); return true;
+            case 10: time_head(ctx, STEP_SAMPLE_ADAPT); return true;
+            case 11: time_head(ctx, STEP_SAMPLE_SEQ); return true;
             default:
                 return launch_attn(attn_args(ctx, l), ctx->c.head_dim, ctx->qpk, ctx->c.n_kv_heads, ctx->t_max,
                                    ctx->stream, ctx->kv_dt);
