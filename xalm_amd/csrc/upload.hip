@@ -436,8 +436,11 @@ int xh_upload_file(xh_ctx* ctx, int kind, int layer, int dtype, const char* path
         if (e != hipSuccess) rc = set_err(ctx, XH_E_HIP, "%s: copy to the device: %s", path, hipGetErrorString(e));
     } else if (!rc) {
         const size_t row_bytes = s.cols * dtype_size(dtype);
-        // unregistered (e.g. a mapping the driver cannot pin) the same copy runs pageable
+        // unregistered (e.g. a mapping the driver cannot pin) the same copy runs pageable; the
+        // refusal is taken off the thread's last-error slot, where the next launch's
+        // hipGetLastError check would find it
         const bool reg = hipHostRegister(map, len, hipHostRegisterReadOnly) == hipSuccess;
+        if (!reg) (void)hipGetLastError();
         const hipError_t e = copy2d_sync(ctx, s.base, s.pitch, (const char*)map + (offset - a0), row_bytes,
                                          row_bytes, s.rows);
         if (reg) hipHostUnregister(map);
