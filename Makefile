@@ -11,7 +11,7 @@ HOSTFLAGS := -O2 -std=c++17 -fPIC -Wall -Wextra
 
 LIB := xalm_amd/lib
 BIN := xalm_amd/bin
-HIP_UNITS := xalm_hip launch decode prefill prefill_blas upload ops
+HIP_UNITS := xalm_hip launch decode prefill prefill_blas gemm_bf16 upload ops
 HOST_SRC := $(wildcard xalm_amd/host/*.cpp)
 HOST_HDR := $(wildcard xalm_amd/host/*.h) include/xalm_hip.h include/xalm_host.h
 
@@ -33,6 +33,9 @@ HIP_OBJS := $(patsubst %,$(OBJ)/%.o,$(HIP_UNITS)) $(patsubst %,$(OBJ)/dt_launch_
 $(OBJ)/%.o: xalm_amd/csrc/%.hip
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -MMD -MP -c -o $@ $<
+# the bf16 prompt GEMM and its producers: a unit of its own, compiled without packed-f32 VALU
+# instructions (its f32 arithmetic is the producers' x * scale * w; the older units keep their code)
+$(OBJ)/gemm_bf16.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 $(OBJ)/dt_launch_dt%.o: xalm_amd/csrc/dt_launch.hip
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -MMD -MP -DPK_DT=$* -c -o $@ $<

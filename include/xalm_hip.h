@@ -768,6 +768,19 @@ int xh_set_graphs(xh_ctx* ctx, int enable);
  * all 1, head_dim is 128 and max_seq_len - 2 >= 2; otherwise, and on an fp16 context, the value is
  * stored and read back and has no effect.  0 = the per-token loop from the cut, as ever.  Values
  * other than 0 / 1 are XH_E_INVALID. */
+/* XH_OPT_PREFILL_BF16 (default 0): 1 = under XH_OPT_PREFILL 1 a bf16 weight matrix with K % 64 == 0 (the
+ * layer GEMMs, and the lm_head GEMM of xh_perplexity / xh_score) runs on the LDS-tiled bf16 MFMA GEMM
+ * (gemm_bf16.h) instead of the f32-input MFMA kernel: the weights as stored (no image, no range rule:
+ * bf16 has f32's exponent range), the activations as three bf16 pieces b0 = bf16(x), b1 = bf16(x - b0),
+ * b2 = bf16(x - b0 - b1), each rounded to nearest even, b0 + b1 + b2 == x exactly for x = 0 or
+ * 2^-100 <= |x| < 2^127 (outside that range a piece can be a subnormal bf16, which this contract does
+ * not cover); products exact, one f32 accumulator for the three pieces, no row scale, an order fixed by
+ * the tiling (the same bits on every run).  A model whose layer GEMMs all take row-major or bf16-piece
+ * input then plans passes of up to 2048 tokens instead of 64 (xh_prefill_route plans by the same rule).
+ * A GEMM over at most 64 tokens (a short prompt, the last pass of a long one) keeps the f32-input kernel,
+ * which covers them in one launch bound by the weight stream.  Under XH_OPT_PREFILL 0 / 2 / 3 / 4, for every non-bf16 matrix and for a bf16 matrix with another K the
+ * value is stored and read back and has no effect.  0 = bf16 matrices on the f32-input MFMA kernel, as
+ * ever.  Values other than 0 / 1 are XH_E_INVALID.  Same math per token up to f32 rounding. */
 enum xh_option {
     XH_OPT_FUSE_ATTN_WO = 1,
     XH_OPT_PREFILL = 2,
@@ -776,7 +789,8 @@ enum xh_option {
     XH_OPT_PREFILL_ATTN_SPLIT = 6,
     XH_OPT_PREFILL_RING = 7,
     XH_OPT_PREFILL_ATTN_KV8 = 8,
-    XH_OPT_PREFILL_RING_KV8 = 9
+    XH_OPT_PREFILL_RING_KV8 = 9,
+    XH_OPT_PREFILL_BF16 = 10
 };
 int xh_set_option(xh_ctx* ctx, int option, int value);
 int xh_get_option(const xh_ctx* ctx, int option, int* value);
@@ -859,6 +873,14 @@ int xh_op_prompt_attn_ring8(float* out, uint8_t* k_ring, uint8_t* v_ring, const 
  * tokens at once). */
 int xh_op_prompt_matmul(float* y, const float* x, const void* w, int dtype, int rows, int K, int n, int mode, int ks,
                         int* route_out);
+/* One GEMM of a prompt pass on the bf16 route (XH_OPT_PREFILL_BF16 1; gemm_bf16.h) on host buffers, through
+ * the launch code of the passes: y[n][rows] = x . w^T with x f32 [n][K] and w [rows][K] bf16 bits.  Launches:
+ * prefill_split_bf16_kernel, the GEMM, prefill_epi_kernel with EPI_STORE (no row scale).  pieces_out (may be
+ * NULL) receives the producer's three bf16 pieces of x, [3][n][K] bits.  ks 0: the passes' K slicing; k >= 1
+ * forces k slices and is XH_E_INVALID unless k is a power of two, k <= 8 and K % (64 k) == 0.  XH_E_INVALID
+ * before any launch also for K % 64 != 0, n < 1 or n > 2048, rows < 1 and a NULL y, x or w. */
+int xh_op_prompt_matmul_bf16(float* y, const float* x, const uint16_t* w, int rows, int K, int n, int ks,
+                             uint16_t* pieces_out);
 /* The exact f16 image(s) the row-major route multiplies, by the passes' image kernels: hi_out [rows][K]
  * f16 bits for e4m3 / e5m2 (finite codes) / MXFP4 (scales in 114 .. 140) with lo_out NULL; hi_out and
  * lo_out for Q8_0 / Q4_0 / Q5_0 (w = hi + lo exactly).  w in the file layout, K % 32 == 0.  max_groups 0:

@@ -54,6 +54,7 @@ OPT_PREFILL_ATTN_SPLIT = 6
 OPT_PREFILL_RING = 7
 OPT_PREFILL_ATTN_KV8 = 8
 OPT_PREFILL_RING_KV8 = 9
+OPT_PREFILL_BF16 = 10
 
 # enum xh_tensor_kind
 EMBED, ATTN_NORM, FFN_NORM, WQ, WK, WV, WO, W1, W2, W3, FINAL_NORM, WCLS = range(12)
@@ -285,6 +286,7 @@ _SIGNATURES = {
     "xh_op_prompt_attn_ring": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I]),
     "xh_op_prompt_attn_ring8": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I]),
     "xh_op_prompt_matmul": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, ctypes.POINTER(_I)]),
+    "xh_op_prompt_matmul_bf16": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "xh_op_prompt_weight_image": (_I, [_I, _P, _I, _I, _P, _P, _I]),
     "xh_op_prompt_stage": (_I, [_I, _P, _I, _P, _P, _I, _I, _P, _I, ctypes.c_float, _I, _I, _SZ, _P, _P, _P, _P,
                                 ctypes.POINTER(_I)]),
@@ -717,6 +719,7 @@ def op_prompt_attn8(q: np.ndarray, k: np.ndarray, v: np.ndarray, pos0: int, head
  STAGE_GLU_THEN_SPLIT, STAGE_STORE) = range(7)
 # xh_op_prompt_matmul's route_out
 ROUTE_ROWMAJOR, ROUTE_F32 = 0, -1
+ROUTE_BF16 = -2  # the bf16 route of XH_OPT_PREFILL_BF16 (xh_prompt_gemm_tile's argument for it)
 
 
 def prompt_gemm_tile(route: int) -> int:
@@ -735,6 +738,19 @@ def op_prompt_matmul(x: np.ndarray, w: np.ndarray, dtype: int, rows: int, mode: 
     route = ctypes.c_int(-99)
     check(lib().xh_op_prompt_matmul(ptr(out), ptr(x), ptr(w), dtype, rows, K, n, mode, ks, ctypes.byref(route)))
     return out, route.value
+
+
+def op_prompt_matmul_bf16(x: np.ndarray, w: np.ndarray, ks: int = 0):
+    """One GEMM of a prompt pass on the bf16 route (xh_op_prompt_matmul_bf16): x f32 [n][K], w bf16 bits
+    uint16 [rows][K].  Returns (y f32 [n][rows], the producer's pieces uint16 [3][n][K])."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    w = np.ascontiguousarray(w, dtype=np.uint16)
+    (n, K), rows = x.shape, w.shape[0]
+    assert w.shape == (rows, K)
+    out = np.empty((n, rows), dtype=np.float32)
+    pieces = np.empty((3, n, K), dtype=np.uint16)
+    check(lib().xh_op_prompt_matmul_bf16(ptr(out), ptr(x), ptr(w), rows, K, n, ks, ptr(pieces)))
+    return out, pieces
 
 
 def op_prompt_weight_image(dtype: int, w: np.ndarray, rows: int, K: int, max_groups: int = 0):

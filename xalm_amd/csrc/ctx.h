@@ -133,7 +133,8 @@ struct PfBufs {
     enum Group { PASS, ATTN0, RING, LOGITS, N_GROUPS };
     int cap[N_GROUPS] = {};                // tokens each group holds
     // PASS
-    uint16_t* xh = nullptr;                // [2T][max K] f16 halves of a GEMM input
+    uint16_t* xh = nullptr;                // [2T][max K] f16 halves of a GEMM input ([3T]: bf16 pieces, xh_planes 3)
+    int xh_planes = 0;                     // token-row planes xh holds: 2, or 3 under XH_OPT_PREFILL_BF16
     uint16_t* xl = nullptr;                // [PF_TOK][max K] the split kernel's lo fragments
     float* xs = nullptr;                   // [T] 1 / row scale
     int* tok = nullptr;                    // [T]
@@ -268,6 +269,7 @@ struct xh_ctx {
     bool pf_ring = true;                         // XH_OPT_PREFILL_RING: ring passes at positions >= max_seq_len
     bool pf_attn_kv8 = false;                    // XH_OPT_PREFILL_ATTN_KV8: an fp8 KV ring follows pf_attn_mode too
     bool pf_ring_kv8 = false;                    // XH_OPT_PREFILL_RING_KV8: ... and runs ring passes (under pf_attn_kv8)
+    bool pf_bf16 = false;                        // XH_OPT_PREFILL_BF16: bf16 matrices on gemm_bf16.h (under prefill_gemm 1)
     xalm::PfBufs pf;                             // the pass buffers
     // xh_perplexity: targets and probabilities of the whole run (allocated on first use)
     int* ppl_tgt = nullptr;                      // [ppl_cap] targets (per-token path)
@@ -450,6 +452,7 @@ struct PfGemmPlan {
     int n, n_cu;
     size_t part_floats;  // capacity of `part`
     int ks, max_groups;
+    bool bf16;           // XH_OPT_PREFILL_BF16
 };
 struct PfGemmIo {
     const void* w;        // device rows of dt
@@ -463,7 +466,9 @@ struct PfGemmIo {
 enum { PF_GEMM_OK = 0, PF_GEMM_E_IMAGE = -1, PF_GEMM_E_FIT = -2, PF_GEMM_E_SHAPE = -3, PF_GEMM_E_DTYPE = -4 };
 // weights per 16-byte chunk of the f32-input kernel's decoder of dt (WDec<DT>::E)
 int pf_elems(int dt);
-// the route: 0 = row-major split input (gemm16.h or hipBLASLt), E > 0 = the fragment kernel, -1 = f32 input
+// the route: 0 = row-major split input (gemm16.h or hipBLASLt), E > 0 = the fragment kernel, -1 = f32 input,
+// PF_ROUTE_BF16 = bf16 weights as stored against three row-major bf16 pieces of x (gemm_bf16.h)
+constexpr int PF_ROUTE_BF16 = -2;
 int pf_gemm_route(const PfGemmPlan& p);
 // rows per wave (routes -1 and E > 0) or per workgroup (route 0): the launch's row tile
 int pf_gemm_row_tile(int route);
@@ -491,6 +496,12 @@ void pf_glu_split_launch(const float* part, int ks, const float* part_s, int n, 
 // prefill_epi_kernel with EPI_STORE / EPI_RESID / EPI_GLU (no K/V arguments)
 void pf_epi_plain_launch(const float* part, const float* part_s, int ks, int n, int rows, int epi, float* out,
                          size_t out_stride, int act, hipStream_t s);
+
+// gemm_bf16.hip: the route PF_ROUTE_BF16.  x3: the pieces [3][n][K] bf16 bits, plane after plane (io.xh of
+// pf_gemm_bf16, which reads neither io.xl nor io.xs: its partials are unscaled)
+void pf_split_bf16_launch(const float* x, int K, int n, uint16_t* x3, hipStream_t s);
+void pf_norm_split_bf16_launch(const float* x, int dim, const void* nw, int ndt, float eps, int n, uint16_t* x3, hipStream_t s);
+int pf_gemm_bf16(const PfGemmPlan& p, const PfGemmIo& io, int* ks_out, hipStream_t s);
 
 // prefill_blas.hip (XH_OPT_PREFILL 4).  blas_ok: 0 unprobed, 1 every GEMM shape of the model has
 // an f16 plan, -1 not.  blas_has_plan: *have = hipBLASLt has an algorithm for the shape.

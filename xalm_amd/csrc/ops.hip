@@ -386,6 +386,36 @@ int xh_op_prompt_matmul(float* y, const float* x, const void* w, int dtype, int 
     return op_finish(y, bo, (size_t)n * rows * 4);
 }
 
+int xh_op_prompt_matmul_bf16(float* y, const float* x, const uint16_t* w, int rows, int K, int n, int ks, uint16_t* pieces_out) {
+    if (!y || !x || !w) return set_err(nullptr, XH_E_INVALID, "prompt_matmul_bf16: y, x or w is NULL");
+    if (rows < 1 || rows > (1 << 20) || K < 1 || K > (1 << 20) || K % 64 || n < 1 || n > 2048)
+        return set_err(nullptr, XH_E_INVALID, "prompt_matmul_bf16: %d rows, K %d (whole 64s), %d tokens (1 .. 2048)", rows, K, n);
+    PfGemmPlan p{};
+    p.mode = 1; p.bf16 = true; p.dt = XH_BF16; p.K = K; p.rows = rows; p.n = n; p.ks = ks;
+    p.part_floats = (size_t)8 * n * rows;  // room for any slicing the picker may take
+    if (ks < 0 || (ks > 0 && !pf_gemm_ks_ok(p, PF_ROUTE_BF16)))
+        return set_err(nullptr, XH_E_INVALID, "prompt_matmul_bf16: %d slices of K %d", ks, K);
+    int rc;
+    if ((rc = op_n_cu(&p.n_cu))) return rc;
+    const size_t xe = (size_t)n * K;
+    DevBuf bw, bx, b3, bp, bo;
+    if ((rc = op_alloc(bw, (size_t)rows * K * 2, w)) || (rc = op_alloc(bx, xe * 4, x)) || (rc = op_alloc(b3, 3 * xe * 2, nullptr)) ||
+        (rc = op_alloc(bp, p.part_floats * 4, nullptr)) || (rc = op_alloc(bo, (size_t)n * rows * 4, nullptr)))
+        return rc;
+    const PfGemmIo io{bw.p, (const float*)bx.p, (uint16_t*)b3.p, nullptr, nullptr, nullptr, 0, (float*)bp.p};
+    int nks = 0;
+    pf_split_bf16_launch(io.x, K, n, io.xh, nullptr);
+    if ((rc = pf_gemm_bf16(p, io, &nks, nullptr))) {
+        hipDeviceSynchronize();
+        return set_err(nullptr, XH_E_INVALID, "prompt_matmul_bf16: the launch code refused the GEMM (%d)", rc);
+    }
+    pf_epi_plain_launch(io.part, nullptr, nks, n, rows, EPI_STORE, (float*)bo.p, 0, 0, nullptr);
+    if ((rc = op_finish(y, bo, (size_t)n * rows * 4))) return rc;
+    if (pieces_out && hipMemcpy(pieces_out, b3.p, 3 * xe * 2, hipMemcpyDeviceToHost) != hipSuccess)
+        return set_err(nullptr, XH_E_HIP, "hipMemcpy D2H failed");
+    return 0;
+}
+
 int xh_op_prompt_weight_image(int dtype, const void* w, int rows, int K, uint16_t* hi_out, uint16_t* lo_out, int max_groups) {
     const bool one = dtype == XH_F8_E4M3 || dtype == XH_F8_E5M2 || dtype == XH_MXFP4;
     const bool two = dtype == XH_Q8_0 || dtype == XH_Q4_0 || dtype == XH_Q5_0;

@@ -45,7 +45,8 @@ namespace {
 // pass buffers for T tokens (kept while later passes fit; a longer pass length reallocates)
 int pf_alloc(xh_ctx* ctx, const int T) {
     PfBufs& b = ctx->pf;
-    if (b.cap[PfBufs::PASS] >= T) return 0;
+    const int planes = ctx->pf_bf16 ? 3 : 2;  // the bf16 route's three pieces, only when the option is on
+    if (b.cap[PfBufs::PASS] >= T && b.xh_planes >= planes) return 0;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     pf_free(ctx);
     const xh_config& c = ctx->c;
@@ -59,9 +60,10 @@ int pf_alloc(xh_ctx* ctx, const int T) {
     // xh: the split-kernel fragments of <= 64 tokens, or hi rows then lo rows of a row-major
     // pass input (gemm16.h / hipBLASLt); xl: the split kernel's lo fragments
     const size_t kmax = std::max({(size_t)c.dim, (size_t)c.hidden_dim, (size_t)ctx->q_dim});
-    if ((rc = dmalloc(ctx, &b.xh, 2 * std::max(t, (size_t)PF_TOK) * kmax)) ||
+    if ((rc = dmalloc(ctx, &b.xh, planes * std::max(t, (size_t)PF_TOK) * kmax)) ||
         (rc = dmalloc(ctx, &b.xl, PF_TOK * kmax)) || (rc = dmalloc(ctx, &b.xs, std::max(t, (size_t)PF_TOK))))
         return rc;
+    b.xh_planes = planes;
     b.cap[PfBufs::PASS] = T;
     return 0;
 }
@@ -185,16 +187,30 @@ bool pf_lay0(const PfGemmPlan& p) {
     if (p.mode == 4) return p.blas;
     return false;
 }
+// XH_OPT_PREFILL_BF16 under XH_OPT_PREFILL 1: a bf16 matrix with K in whole 64-deep steps runs as
+// stored on gemm_bf16.h, against three row-major bf16 pieces of x.  A GEMM over at most PF_TOK tokens
+// (p.n; 0 = the plan of a whole pass) keeps the f32-input kernel: it covers them in one launch bound
+// by the weight stream, where a 128-token tile would spend three quarters of its MFMA work on rows
+// past the end (32 tokens, 8 Mistral-7B layers: 1.97 ms against 2.36 on gemm_bf16.h).
+bool pf_bf16_route(const PfGemmPlan& p) {
+    return p.bf16 && p.mode == 1 && p.dt == XH_BF16 && p.K % MM_KMULT == 0 && (p.n == 0 || p.n > PF_TOK);
+}
 // the plan of a GEMM of this context (n, the partials and a forced slicing left to the caller)
 PfGemmPlan pf_plan_of(const xh_ctx* ctx, int dt, int K, int rows, bool wide) {
     PfGemmPlan p{};
     p.mode = ctx->prefill_gemm;
+    p.bf16 = ctx->pf_bf16;
     p.blas = p.mode == 4 && blas_ok(ctx) > 0;
     p.dt = dt; p.K = K; p.rows = rows; p.wide = wide;
     p.n_cu = ctx->n_cu;
     return p;
 }
 bool pf_lay0(const xh_ctx* ctx, int dt, int K, bool wide) { return pf_lay0(pf_plan_of(ctx, dt, K, 0, wide)); }
+// Does the GEMM take the rows of a whole pass (row-major halves or bf16 pieces), or 64-token slices?
+bool pf_whole_pass(const xh_ctx* ctx, int dt, int K, bool wide) {
+    const PfGemmPlan p = pf_plan_of(ctx, dt, K, 0, wide);
+    return pf_lay0(p) || pf_bf16_route(p);
+}
 // Once per prefill: (XH_OPT_PREFILL 4, once per context) does hipBLASLt have an f16 plan for every
 // full-pass GEMM of the model (if not, every dtype keeps the MFMA kernels); and the f16 image
 // buffer of the largest fp8 matrix that goes to the f16 GEMMs.
@@ -226,23 +242,25 @@ int pf_prepare(xh_ctx* ctx) {
     }
     return 0;
 }
-// Layout of the split-f16 input of the GEMM over W (dtype dt, [rows][K]): pf_gemm_route of its plan
-int pf_layout(const xh_ctx* ctx, int dt, int K, int rows, bool wide) {
-    return pf_gemm_route(pf_plan_of(ctx, dt, K, rows, wide));
+// Layout of the split-f16 input of the GEMM over W (dtype dt, [rows][K]) and n tokens: pf_gemm_route of its plan
+int pf_layout(const xh_ctx* ctx, int dt, int K, int rows, bool wide, int n) {
+    PfGemmPlan p = pf_plan_of(ctx, dt, K, rows, wide);
+    p.n = n;
+    return pf_gemm_route(p);
 }
 // split-f16 halves of a pass's rows: hi into pf.xh; lo into pf.xl (fragments) or right after
 // the hi rows (row-major)
 uint16_t* pf_lo(xh_ctx* ctx, int layout, int n, int K) { return pf_split_lo(layout, n, K, ctx->pf.xh, ctx->pf.xl); }
 // grid of the split kernels: one workgroup per token row, fragments padded to 32-token tiles
 int pf_split_grid(int layout, int n) { return layout ? 32 * ((n + 31) / 32) : n; }
-int pf_layout(const xh_ctx* ctx, const PfMat& g) { return pf_layout(ctx, g.dt, g.K, g.rows, g.wide); }
-// Tokens per pass: PF_TOK_MM (gemm16.h) / PF_TOK_BLAS (hipBLASLt) when every layer GEMM takes the
-// row-major input (the lm_head of a perplexity pass aside: it runs on 64-token slices when it
-// cannot), else 64 (the register-streaming MFMA kernels' two token tiles)
+int pf_layout(const xh_ctx* ctx, const PfMat& g, int n) { return pf_layout(ctx, g.dt, g.K, g.rows, g.wide, n); }
+// Tokens per pass: PF_TOK_MM (gemm16.h, gemm_bf16.h) / PF_TOK_BLAS (hipBLASLt) when every layer GEMM
+// takes the row-major input or the bf16 pieces (the lm_head of a perplexity pass aside: it runs on
+// 64-token slices when it cannot), else 64 (the register-streaming MFMA kernels' two token tiles)
 int pf_pass_tokens(const xh_ctx* ctx) {
     for (int l = 0; l < (int)ctx->L.size(); l++)
         for (const PfMat& g : pf_layer_mats(ctx, l))
-            if (!pf_lay0(ctx, g.dt, g.K, g.wide)) return PF_TOK;
+            if (!pf_whole_pass(ctx, g.dt, g.K, g.wide)) return PF_TOK;
     return ctx->prefill_gemm == 4 ? PF_TOK_BLAS : PF_TOK_MM;
 }
 // One pass of prefill_batched: m tokens at positions p0.. (ring: all >= max_seq_len), and what one
@@ -254,8 +272,11 @@ struct PfPass { int m, p0; bool ring; bool scaled; bool split_ready; };
 void pf_norm(xh_ctx* ctx, PfPass& ps, const void* nw, int ndt, const PfMat& g) {
     const xh_config& c = ctx->c;
     PfBufs& b = ctx->pf;
-    const int lay = pf_layout(ctx, g);
-    if (lay >= 0) {
+    const int lay = pf_layout(ctx, g, ps.m);
+    if (lay == PF_ROUTE_BF16) {
+        pf_norm_split_bf16_launch(b.x, c.dim, nw, ndt, c.norm_eps, ps.m, b.xh, ctx->stream);
+        ps.split_ready = true;
+    } else if (lay >= 0) {
         pf_norm_split_launch(b.x, c.dim, nw, ndt, c.norm_eps, ps.m, lay, b.xh, pf_lo(ctx, lay, ps.m, c.dim), b.xs,
                              ctx->stream);
         ps.split_ready = true;
@@ -305,7 +326,13 @@ int pf_gemm(xh_ctx* ctx, PfPass& ps, const PfMat& g, const float* x, int n, int&
         ps.split_ready = false;
     }
     int rc;
-    if (lay == 0) {
+    if (lay == PF_ROUTE_BF16) {
+        // three bf16 pieces of x (its GLU and residual inputs arrive as f32: the two-launch producers);
+        // no row scale
+        if (!ps.split_ready) pf_split_bf16_launch(x, g.K, n, b.xh, ctx->stream);
+        ps.split_ready = false;
+        rc = pf_gemm_bf16(p, io, &ks, ctx->stream);
+    } else if (lay == 0) {
         // row-major hi rows then lo rows; partials unscaled, the epilogue multiplies by 1 / s_t
         const uint16_t *w_hi = nullptr, *w_lo = nullptr;
         if ((rc = pf_gemm_images(p, io, &w_hi, &w_lo, ctx->stream))) return pf_gemm_err(ctx, rc, g, n);
@@ -346,7 +373,7 @@ void pf_epi(xh_ctx* ctx, const PfPass& ps, PfEpiArgs e) {
 int pf_resid_norm(xh_ctx* ctx, PfPass& ps, int ks, const void* nw, int ndt, const PfMat& g) {
     const xh_config& c = ctx->c;
     PfBufs& b = ctx->pf;
-    const int lay = pf_layout(ctx, g);
+    const int lay = pf_layout(ctx, g, ps.m);
     const size_t lds = (size_t)c.dim * sizeof(float);  // + the kernel's static red[4]
     if (lay >= 0 && ctx->pf_resid_norm && c.dim % 8 == 0 && lds + 4 * sizeof(float) <= 64 * 1024) {
         HIP_TRY(ctx, hipGetLastError());  // an earlier launch's error is reported as such
@@ -368,7 +395,7 @@ int pf_resid_norm(xh_ctx* ctx, PfPass& ps, int ks, const void* nw, int ndt, cons
 int pf_glu(xh_ctx* ctx, PfPass& ps, int ks, const PfMat& w2) {
     const xh_config& c = ctx->c;
     PfBufs& b = ctx->pf;
-    const int lay = pf_layout(ctx, w2);
+    const int lay = pf_layout(ctx, w2, ps.m);
     // dynamic LDS = one f32 row of h; the kernel adds a static 16-float reduction array
     const size_t lds = (size_t)c.hidden_dim * sizeof(float);
     if (lay >= 0 && ctx->pf_glu_split && lds + 16 * sizeof(float) <= 64 * 1024) {
@@ -491,6 +518,7 @@ int xalm::pf_elems(int dt) {
 // split.  The split kernel also needs a K slicing.
 int xalm::pf_gemm_route(const PfGemmPlan& p) {
     if (pf_lay0(p)) return 0;
+    if (pf_bf16_route(p)) return PF_ROUTE_BF16;
     const bool f8 = pf_f8(p.dt);
     const int m = p.mode;
     if (!(m == 2 || ((m == 1 || m == 4) && f8))) return -1;
@@ -498,11 +526,13 @@ int xalm::pf_gemm_route(const PfGemmPlan& p) {
     const int E = elems_per_16b(p.dt);
     return pf_ks16(p.rows, p.K, E) ? E : -1;
 }
-int xalm::pf_gemm_row_tile(int route) { return route == 0 ? MM_BR : 32 * (route > 0 ? PF_RT16 : PF_RT); }
+int xalm::pf_gemm_row_tile(int route) {
+    return route == 0 || route == PF_ROUTE_BF16 ? MM_BR : 32 * (route > 0 ? PF_RT16 : PF_RT);  // MB_BR == MM_BR
+}
 bool xalm::pf_gemm_ks_ok(const PfGemmPlan& p, int route) {
     const int ks = p.ks, K = p.K;
     if (ks <= 0 || (ks & (ks - 1))) return false;  // every picker doubles
-    if (route == 0) {                              // mm_pick_ks
+    if (route == 0 || route == PF_ROUTE_BF16) {    // mm_pick_ks
         const int images = gq_dt(p.dt) && !gq_mx(p.dt) ? 2 : 1;
         return ks <= 8 && K % (ks * MM_KMULT) == 0 && (size_t)images * ks * p.n * p.rows <= p.part_floats;
     }
@@ -902,7 +932,7 @@ int pf_logits_probs(xh_ctx* ctx, PfPass& ps, const int* targets, float* probs, c
     const PfMat cls = pf_cls_mat(ctx);
     const size_t cls_rb = dev_row_bytes(ctx->wcls_dt, c.dim);
     // lm_head weights off the hipBLASLt path (bf16 on the fp8 checkpoints): 64-token slices
-    const int tstep = pf_lay0(ctx, cls.dt, c.dim, cls.wide) ? m : PF_TOK;
+    const int tstep = pf_whole_pass(ctx, cls.dt, c.dim, cls.wide) ? m : PF_TOK;
     for (int r0 = 0; r0 < c.vocab_size; r0 += PF_CLS_CHUNK) {
         PfMat g = cls;
         g.w = (const char*)cls.w + (size_t)r0 * cls_rb;

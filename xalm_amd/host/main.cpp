@@ -50,14 +50,17 @@ using clk = std::chrono::steady_clock;
 
 static int g_kv_dtype = XH_F16;  // -K: the KV rings' element type
 static int g_attn_kv8 = 0;       // -a: 1 = XH_OPT_PREFILL_ATTN_KV8, 2 = that and XH_OPT_PREFILL_RING_KV8
+static int g_prefill_bf16 = 0;   // -b: XH_OPT_PREFILL_BF16
 
-// the model of a run: -K's rings, -a's prompt attention (and ring passes) on them
+// the model of a run: -K's rings, -a's prompt attention (and ring passes) on them, -b's bf16 prompt GEMM
 static Model load_model(const XalmFile& file, int context, Device dev) {
     Model model = Model::from_xalm(file, context, dev, 0, g_kv_dtype);
     const bool ring = g_attn_kv8 == 2;
     if (g_attn_kv8 && (xh_set_option(model.ctx(), XH_OPT_PREFILL_ATTN_KV8, ring ? 1 : g_attn_kv8) != 0 ||
                        (ring && xh_set_option(model.ctx(), XH_OPT_PREFILL_RING_KV8, 1) != 0)))
         throw std::runtime_error(std::string("-a: ") + xh_last_error(model.ctx()));
+    if (g_prefill_bf16 && xh_set_option(model.ctx(), XH_OPT_PREFILL_BF16, g_prefill_bf16) != 0)
+        throw std::runtime_error(std::string("-b: ") + xh_last_error(model.ctx()));
     return model;
 }
 
@@ -74,6 +77,8 @@ static void error_usage() {
     fprintf(stderr, "  -K [f16,f8] KV ring element type (default f16; f8 = e4m3, hip only)\n");
     fprintf(stderr, "  -a <0|1|2> with -K f8: 1 = prompt attention on the MFMA kernels' fp8 tiles, 2 = that and batched\n");
     fprintf(stderr, "     ring passes past the context length (default 0, hip only)\n");
+    fprintf(stderr, "  -b <0|1> 1 = bf16 weight matrices of the prompt passes on the bf16 MFMA GEMM, passes of up to\n");
+    fprintf(stderr, "     2048 tokens instead of 64 (default 0, hip only)\n");
     fprintf(stderr, "  -t <float> sampling temperature (default 0 - greedy)\n");
     fprintf(stderr, "  -k <int> top-k, 0 = off (default 0)\n");
     fprintf(stderr, "  -p <float> top-p in (0, 1], 1 = off (default 1)\n");
@@ -291,6 +296,7 @@ int main(int argc, char** argv) {
             else error_usage();
         }
         else if (f == 'a') g_attn_kv8 = std::stoi(v);
+        else if (f == 'b') g_prefill_bf16 = std::stoi(v);
         else if (f == 't') sampling.temperature = std::stof(v);
         else if (f == 'k') sampling.top_k = std::stoi(v);
         else if (f == 'p') sampling.top_p = std::stof(v);
@@ -331,7 +337,7 @@ int main(int argc, char** argv) {
         return 1;
     }
     if (g_kv_dtype != XH_F16 && device == "cpu") error_usage();  // the fp8 KV ring is the HIP device's
-    if (g_attn_kv8 && device == "cpu") error_usage();
+    if ((g_attn_kv8 || g_prefill_bf16) && device == "cpu") error_usage();
     const Device dev = device == "cpu" ? Device::CPU : Device::HIP;
     try {
         if (mode == "completion") run_completion(path, dev, prompt, context, num_steps, device_loop != 0, sampling, ctl, trunc, seq, regex, top_n);
