@@ -781,6 +781,19 @@ int xh_set_graphs(xh_ctx* ctx, int enable);
  * which covers them in one launch bound by the weight stream.  Under XH_OPT_PREFILL 0 / 2 / 3 / 4, for every non-bf16 matrix and for a bf16 matrix with another K the
  * value is stored and read back and has no effect.  0 = bf16 matrices on the f32-input MFMA kernel, as
  * ever.  Values other than 0 / 1 are XH_E_INVALID.  Same math per token up to f32 rounding. */
+/* XH_OPT_PREFILL_KQ (default 0): 1 = under XH_OPT_PREFILL 1 a Q4_K / Q6_K weight matrix with K % 256 == 0 (the
+ * layer GEMMs, and the lm_head GEMM of xh_perplexity / xh_score) runs on the LDS-tiled K-quant MFMA GEMM
+ * (gemm_kq.h) instead of the f32-input MFMA kernel.  The kernel multiplies the codes (exact in f16) by the
+ * row-major f16 hi + lo halves of the activations (the f16 GEMM's input and row scale) and applies the scales
+ * to the sums: per 32-element sub-block (d*sc) * sum(q x) - (dmin*mn) * sum(x) for Q4_K, per 16-element group
+ * (d*sc) * sum((q - 32) x) for Q6_K, as the decode matvec evaluates them; an order fixed by the tiling (the same
+ * bits on every run).  A model whose layer GEMMs all take row-major, bf16-piece or K-quant input then plans
+ * passes of up to 2048 tokens instead of 64 (xh_prefill_route plans by the same rule; a q4_k_m file needs both
+ * formats served, which this option does).  A GEMM over at most 64 tokens (a short prompt, the last pass of a
+ * long one) keeps the f32-input kernel, which covers them in one launch bound by the weight stream.  Under
+ * XH_OPT_PREFILL 0 / 2 / 3 / 4 and for every other dtype the value is stored and read back and has no effect.
+ * 0 = K-quant matrices on the f32-input MFMA kernel, as ever.  Values other than 0 / 1 are XH_E_INVALID.  Same
+ * math per token up to f32 rounding. */
 enum xh_option {
     XH_OPT_FUSE_ATTN_WO = 1,
     XH_OPT_PREFILL = 2,
@@ -790,7 +803,8 @@ enum xh_option {
     XH_OPT_PREFILL_RING = 7,
     XH_OPT_PREFILL_ATTN_KV8 = 8,
     XH_OPT_PREFILL_RING_KV8 = 9,
-    XH_OPT_PREFILL_BF16 = 10
+    XH_OPT_PREFILL_BF16 = 10,
+    XH_OPT_PREFILL_KQ = 11
 };
 int xh_set_option(xh_ctx* ctx, int option, int value);
 int xh_get_option(const xh_ctx* ctx, int option, int* value);
@@ -881,6 +895,13 @@ int xh_op_prompt_matmul(float* y, const float* x, const void* w, int dtype, int 
  * before any launch also for K % 64 != 0, n < 1 or n > 2048, rows < 1 and a NULL y, x or w. */
 int xh_op_prompt_matmul_bf16(float* y, const float* x, const uint16_t* w, int rows, int K, int n, int ks,
                              uint16_t* pieces_out);
+/* One GEMM of a prompt pass on the K-quant route (XH_OPT_PREFILL_KQ 1; gemm_kq.h) on host buffers, through the
+ * launch code of the passes: y[n][rows] = x . w^T with x f32 [n][K] and w [rows][K] of dtype XH_Q4_K or XH_Q6_K
+ * in the FILE layout (repacked to the device rows as xh_op_matmul does).  Launches: prefill_split_kernel
+ * (layout 0), the GEMM, prefill_epi_kernel with EPI_STORE and 1 / s_t.  ks 0: the passes' K slicing; k >= 1
+ * forces k slices and is XH_E_INVALID unless k is a power of two, k <= 8 and K % (256 k) == 0.  XH_E_INVALID
+ * before any launch also for another dtype, K % 256 != 0, n < 1 or n > 2048, rows < 1 and a NULL y, x or w. */
+int xh_op_prompt_matmul_kq(float* y, const float* x, const void* w, int dtype, int rows, int K, int n, int ks);
 /* The exact f16 image(s) the row-major route multiplies, by the passes' image kernels: hi_out [rows][K]
  * f16 bits for e4m3 / e5m2 (finite codes) / MXFP4 (scales in 114 .. 140) with lo_out NULL; hi_out and
  * lo_out for Q8_0 / Q4_0 / Q5_0 (w = hi + lo exactly).  w in the file layout, K % 32 == 0.  max_groups 0:

@@ -55,6 +55,7 @@ OPT_PREFILL_RING = 7
 OPT_PREFILL_ATTN_KV8 = 8
 OPT_PREFILL_RING_KV8 = 9
 OPT_PREFILL_BF16 = 10
+OPT_PREFILL_KQ = 11
 
 # enum xh_tensor_kind
 EMBED, ATTN_NORM, FFN_NORM, WQ, WK, WV, WO, W1, W2, W3, FINAL_NORM, WCLS = range(12)
@@ -287,6 +288,7 @@ _SIGNATURES = {
     "xh_op_prompt_attn_ring8": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I]),
     "xh_op_prompt_matmul": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, ctypes.POINTER(_I)]),
     "xh_op_prompt_matmul_bf16": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "xh_op_prompt_matmul_kq": (_I, [_P, _P, _P, _I, _I, _I, _I, _I]),
     "xh_op_prompt_weight_image": (_I, [_I, _P, _I, _I, _P, _P, _I]),
     "xh_op_prompt_stage": (_I, [_I, _P, _I, _P, _P, _I, _I, _P, _I, ctypes.c_float, _I, _I, _SZ, _P, _P, _P, _P,
                                 ctypes.POINTER(_I)]),
@@ -720,6 +722,7 @@ def op_prompt_attn8(q: np.ndarray, k: np.ndarray, v: np.ndarray, pos0: int, head
 # xh_op_prompt_matmul's route_out
 ROUTE_ROWMAJOR, ROUTE_F32 = 0, -1
 ROUTE_BF16 = -2  # the bf16 route of XH_OPT_PREFILL_BF16 (xh_prompt_gemm_tile's argument for it)
+ROUTE_KQ = -3  # the K-quant route of XH_OPT_PREFILL_KQ
 
 
 def prompt_gemm_tile(route: int) -> int:
@@ -751,6 +754,17 @@ def op_prompt_matmul_bf16(x: np.ndarray, w: np.ndarray, ks: int = 0):
     pieces = np.empty((3, n, K), dtype=np.uint16)
     check(lib().xh_op_prompt_matmul_bf16(ptr(out), ptr(x), ptr(w), rows, K, n, ks, ptr(pieces)))
     return out, pieces
+
+
+def op_prompt_matmul_kq(x: np.ndarray, w: np.ndarray, dtype: int, rows: int, ks: int = 0) -> np.ndarray:
+    """One GEMM of a prompt pass on the K-quant route (xh_op_prompt_matmul_kq): x f32 [n][K], w the Q4_K / Q6_K
+    blocks of [rows][K] in the file layout (uint8).  Returns y f32 [n][rows]."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    w = np.ascontiguousarray(w, dtype=np.uint8)
+    n, K = x.shape
+    out = np.empty((n, rows), dtype=np.float32)
+    check(lib().xh_op_prompt_matmul_kq(ptr(out), ptr(x), ptr(w), dtype, rows, K, n, ks))
+    return out
 
 
 def op_prompt_weight_image(dtype: int, w: np.ndarray, rows: int, K: int, max_groups: int = 0):

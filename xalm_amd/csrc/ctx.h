@@ -270,6 +270,7 @@ struct xh_ctx {
     bool pf_attn_kv8 = false;                    // XH_OPT_PREFILL_ATTN_KV8: an fp8 KV ring follows pf_attn_mode too
     bool pf_ring_kv8 = false;                    // XH_OPT_PREFILL_RING_KV8: ... and runs ring passes (under pf_attn_kv8)
     bool pf_bf16 = false;                        // XH_OPT_PREFILL_BF16: bf16 matrices on gemm_bf16.h (under prefill_gemm 1)
+    bool pf_kq = false;                          // XH_OPT_PREFILL_KQ: Q4_K / Q6_K matrices on gemm_kq.h (under prefill_gemm 1)
     xalm::PfBufs pf;                             // the pass buffers
     // xh_perplexity: targets and probabilities of the whole run (allocated on first use)
     int* ppl_tgt = nullptr;                      // [ppl_cap] targets (per-token path)
@@ -453,6 +454,7 @@ struct PfGemmPlan {
     size_t part_floats;  // capacity of `part`
     int ks, max_groups;
     bool bf16;           // XH_OPT_PREFILL_BF16
+    bool kq;             // XH_OPT_PREFILL_KQ
 };
 struct PfGemmIo {
     const void* w;        // device rows of dt
@@ -469,6 +471,10 @@ int pf_elems(int dt);
 // the route: 0 = row-major split input (gemm16.h or hipBLASLt), E > 0 = the fragment kernel, -1 = f32 input,
 // PF_ROUTE_BF16 = bf16 weights as stored against three row-major bf16 pieces of x (gemm_bf16.h)
 constexpr int PF_ROUTE_BF16 = -2;
+// PF_ROUTE_KQ = Q4_K / Q6_K device rows against route 0's row-major split input (gemm_kq.h): on the
+// activation side it IS layout 0 (pf_act_layout)
+constexpr int PF_ROUTE_KQ = -3;
+inline int pf_act_layout(int route) { return route == PF_ROUTE_KQ ? 0 : route; }
 int pf_gemm_route(const PfGemmPlan& p);
 // rows per wave (routes -1 and E > 0) or per workgroup (route 0): the launch's row tile
 int pf_gemm_row_tile(int route);
@@ -502,6 +508,10 @@ void pf_epi_plain_launch(const float* part, const float* part_s, int ks, int n, 
 void pf_split_bf16_launch(const float* x, int K, int n, uint16_t* x3, hipStream_t s);
 void pf_norm_split_bf16_launch(const float* x, int dim, const void* nw, int ndt, float eps, int n, uint16_t* x3, hipStream_t s);
 int pf_gemm_bf16(const PfGemmPlan& p, const PfGemmIo& io, int* ks_out, hipStream_t s);
+
+// gemm_kq.hip: the route PF_ROUTE_KQ over io.w (planar device rows of p.dt) and io.xh (hi rows then lo rows, as
+// route 0); unscaled partials, the epilogue multiplies by 1 / s_t (io.xs)
+int pf_gemm_kq(const PfGemmPlan& p, const PfGemmIo& io, int* ks_out, hipStream_t s);
 
 // prefill_blas.hip (XH_OPT_PREFILL 4).  blas_ok: 0 unprobed, 1 every GEMM shape of the model has
 // an f16 plan, -1 not.  blas_has_plan: *have = hipBLASLt has an algorithm for the shape.

@@ -195,21 +195,29 @@ bool pf_lay0(const PfGemmPlan& p) {
 bool pf_bf16_route(const PfGemmPlan& p) {
     return p.bf16 && p.mode == 1 && p.dt == XH_BF16 && p.K % MM_KMULT == 0 && (p.n == 0 || p.n > PF_TOK);
 }
+// XH_OPT_PREFILL_KQ under XH_OPT_PREFILL 1: a Q4_K / Q6_K matrix with K in whole super-blocks runs on
+// gemm_kq.h, which multiplies the codes against route 0's row-major halves and applies the scales to the
+// sums.  A GEMM over at most PF_TOK tokens keeps the f32-input kernel, as on the bf16 route and for its
+// reason (one launch bound by the weight stream against a 128-token tile that is mostly padding).
+bool pf_kq_route(const PfGemmPlan& p) {
+    return p.kq && p.mode == 1 && gq_k(p.dt) && p.K % 256 == 0 && (p.n == 0 || p.n > PF_TOK);
+}
 // the plan of a GEMM of this context (n, the partials and a forced slicing left to the caller)
 PfGemmPlan pf_plan_of(const xh_ctx* ctx, int dt, int K, int rows, bool wide) {
     PfGemmPlan p{};
     p.mode = ctx->prefill_gemm;
     p.bf16 = ctx->pf_bf16;
+    p.kq = ctx->pf_kq;
     p.blas = p.mode == 4 && blas_ok(ctx) > 0;
     p.dt = dt; p.K = K; p.rows = rows; p.wide = wide;
     p.n_cu = ctx->n_cu;
     return p;
 }
 bool pf_lay0(const xh_ctx* ctx, int dt, int K, bool wide) { return pf_lay0(pf_plan_of(ctx, dt, K, 0, wide)); }
-// Does the GEMM take the rows of a whole pass (row-major halves or bf16 pieces), or 64-token slices?
+// Does the GEMM take the rows of a whole pass (row-major halves, bf16 pieces or K-quant codes), or 64-token slices?
 bool pf_whole_pass(const xh_ctx* ctx, int dt, int K, bool wide) {
     const PfGemmPlan p = pf_plan_of(ctx, dt, K, 0, wide);
-    return pf_lay0(p) || pf_bf16_route(p);
+    return pf_lay0(p) || pf_bf16_route(p) || pf_kq_route(p);
 }
 // Once per prefill: (XH_OPT_PREFILL 4, once per context) does hipBLASLt have an f16 plan for every
 // full-pass GEMM of the model (if not, every dtype keeps the MFMA kernels); and the f16 image
@@ -254,8 +262,8 @@ uint16_t* pf_lo(xh_ctx* ctx, int layout, int n, int K) { return pf_split_lo(layo
 // grid of the split kernels: one workgroup per token row, fragments padded to 32-token tiles
 int pf_split_grid(int layout, int n) { return layout ? 32 * ((n + 31) / 32) : n; }
 int pf_layout(const xh_ctx* ctx, const PfMat& g, int n) { return pf_layout(ctx, g.dt, g.K, g.rows, g.wide, n); }
-// Tokens per pass: PF_TOK_MM (gemm16.h, gemm_bf16.h) / PF_TOK_BLAS (hipBLASLt) when every layer GEMM
-// takes the row-major input or the bf16 pieces (the lm_head of a perplexity pass aside: it runs on
+// Tokens per pass: PF_TOK_MM (gemm16.h, gemm_bf16.h, gemm_kq.h) / PF_TOK_BLAS (hipBLASLt) when every layer GEMM
+// takes the row-major input (gemm_kq.h's too) or the bf16 pieces (the lm_head of a perplexity pass aside: it runs on
 // 64-token slices when it cannot), else 64 (the register-streaming MFMA kernels' two token tiles)
 int pf_pass_tokens(const xh_ctx* ctx) {
     for (int l = 0; l < (int)ctx->L.size(); l++)
@@ -272,7 +280,7 @@ struct PfPass { int m, p0; bool ring; bool scaled; bool split_ready; };
 void pf_norm(xh_ctx* ctx, PfPass& ps, const void* nw, int ndt, const PfMat& g) {
     const xh_config& c = ctx->c;
     PfBufs& b = ctx->pf;
-    const int lay = pf_layout(ctx, g, ps.m);
+    const int lay = pf_act_layout(pf_layout(ctx, g, ps.m));
     if (lay == PF_ROUTE_BF16) {
         pf_norm_split_bf16_launch(b.x, c.dim, nw, ndt, c.norm_eps, ps.m, b.xh, ctx->stream);
         ps.split_ready = true;
@@ -319,13 +327,19 @@ int pf_gemm(xh_ctx* ctx, PfPass& ps, const PfMat& g, const float* x, int n, int&
     p.n = n;
     p.part_floats = pf_part_floats(ctx, b.cap[PfBufs::PASS]);
     const PfGemmIo io{g.w, x, b.xh, b.xl, b.xs, ctx->pf_wdq, ctx->pf_wdq_elems, b.part};
-    const int lay = pf_gemm_route(p);
+    const int lay = pf_gemm_route(p), xlay = pf_act_layout(lay);
     ps.scaled = false;
-    if (lay >= 0) {
-        if (!ps.split_ready) pf_split_launch(x, g.K, n, lay, b.xh, pf_lo(ctx, lay, n, g.K), b.xs, ctx->stream);
+    if (xlay >= 0) {
+        if (!ps.split_ready) pf_split_launch(x, g.K, n, xlay, b.xh, pf_lo(ctx, xlay, n, g.K), b.xs, ctx->stream);
         ps.split_ready = false;
     }
     int rc;
+    if (lay == PF_ROUTE_KQ) {
+        // route 0's input, the codes as stored; partials unscaled, the epilogue multiplies by 1 / s_t
+        ps.scaled = true;
+        rc = pf_gemm_kq(p, io, &ks, ctx->stream);
+        return rc ? pf_gemm_err(ctx, rc, g, n) : 0;
+    }
     if (lay == PF_ROUTE_BF16) {
         // three bf16 pieces of x (its GLU and residual inputs arrive as f32: the two-launch producers);
         // no row scale
@@ -373,7 +387,7 @@ void pf_epi(xh_ctx* ctx, const PfPass& ps, PfEpiArgs e) {
 int pf_resid_norm(xh_ctx* ctx, PfPass& ps, int ks, const void* nw, int ndt, const PfMat& g) {
     const xh_config& c = ctx->c;
     PfBufs& b = ctx->pf;
-    const int lay = pf_layout(ctx, g, ps.m);
+    const int lay = pf_act_layout(pf_layout(ctx, g, ps.m));
     const size_t lds = (size_t)c.dim * sizeof(float);  // + the kernel's static red[4]
     if (lay >= 0 && ctx->pf_resid_norm && c.dim % 8 == 0 && lds + 4 * sizeof(float) <= 64 * 1024) {
         HIP_TRY(ctx, hipGetLastError());  // an earlier launch's error is reported as such
@@ -395,7 +409,7 @@ int pf_resid_norm(xh_ctx* ctx, PfPass& ps, int ks, const void* nw, int ndt, cons
 int pf_glu(xh_ctx* ctx, PfPass& ps, int ks, const PfMat& w2) {
     const xh_config& c = ctx->c;
     PfBufs& b = ctx->pf;
-    const int lay = pf_layout(ctx, w2, ps.m);
+    const int lay = pf_act_layout(pf_layout(ctx, w2, ps.m));
     // dynamic LDS = one f32 row of h; the kernel adds a static 16-float reduction array
     const size_t lds = (size_t)c.hidden_dim * sizeof(float);
     if (lay >= 0 && ctx->pf_glu_split && lds + 16 * sizeof(float) <= 64 * 1024) {
@@ -519,6 +533,7 @@ int xalm::pf_elems(int dt) {
 int xalm::pf_gemm_route(const PfGemmPlan& p) {
     if (pf_lay0(p)) return 0;
     if (pf_bf16_route(p)) return PF_ROUTE_BF16;
+    if (pf_kq_route(p)) return PF_ROUTE_KQ;
     const bool f8 = pf_f8(p.dt);
     const int m = p.mode;
     if (!(m == 2 || ((m == 1 || m == 4) && f8))) return -1;
@@ -527,11 +542,14 @@ int xalm::pf_gemm_route(const PfGemmPlan& p) {
     return pf_ks16(p.rows, p.K, E) ? E : -1;
 }
 int xalm::pf_gemm_row_tile(int route) {
-    return route == 0 || route == PF_ROUTE_BF16 ? MM_BR : 32 * (route > 0 ? PF_RT16 : PF_RT);  // MB_BR == MM_BR
+    const bool wg = route == 0 || route == PF_ROUTE_BF16 || route == PF_ROUTE_KQ;  // MB_BR == MK_BR == MM_BR
+    return wg ? MM_BR : 32 * (route > 0 ? PF_RT16 : PF_RT);
 }
 bool xalm::pf_gemm_ks_ok(const PfGemmPlan& p, int route) {
     const int ks = p.ks, K = p.K;
     if (ks <= 0 || (ks & (ks - 1))) return false;  // every picker doubles
+    if (route == PF_ROUTE_KQ)                      // mk_pick_ks (gemm_kq.h): slices of whole super-blocks
+        return ks <= 8 && K % (ks * 256) == 0 && (size_t)ks * p.n * p.rows <= p.part_floats;
     if (route == 0 || route == PF_ROUTE_BF16) {    // mm_pick_ks
         const int images = gq_dt(p.dt) && !gq_mx(p.dt) ? 2 : 1;
         return ks <= 8 && K % (ks * MM_KMULT) == 0 && (size_t)images * ks * p.n * p.rows <= p.part_floats;
