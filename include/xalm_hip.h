@@ -794,6 +794,19 @@ int xh_set_graphs(xh_ctx* ctx, int enable);
  * XH_OPT_PREFILL 0 / 2 / 3 / 4 and for every other dtype the value is stored and read back and has no effect.
  * 0 = K-quant matrices on the f32-input MFMA kernel, as ever.  Values other than 0 / 1 are XH_E_INVALID.  Same
  * math per token up to f32 rounding. */
+/* XH_OPT_PREFILL_GQ (default 0): 1 = under XH_OPT_PREFILL 1 a Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 weight matrix with
+ * K % 64 == 0 (the layer GEMMs, and the lm_head GEMM of xh_perplexity / xh_score) runs its prompt GEMMs over more
+ * than 64 tokens on the LDS-tiled block-code MFMA GEMM (gemm_gq.h) instead of gemm16.h over two f16 weight images
+ * (Q8_0 / Q4_0 / Q5_0) or the f32-input MFMA kernel (Q4_1 / Q5_1).  The kernel multiplies the codes (exact in
+ * f16) by the row-major f16 hi + lo halves of the activations (the f16 GEMM's input and row scale) and applies
+ * the scales to the sums of each 32-element block: acc = fmaf(d, sum((q - bias) x), acc) for Q8_0 / Q4_0 / Q5_0
+ * (bias 0 / 8 / 16), acc = fmaf(d, sum(q x), fmaf(m, sum(x), acc)) for Q4_1 / Q5_1; an order fixed by the tiling
+ * (the same bits on every run).  No weight image is built or sized for such a matrix unless a pass of the call
+ * is short enough to keep the old route, and a Q4_1 / Q5_1 model plans passes of up to 2048 tokens instead of 64
+ * (xh_prefill_route plans by the same rule).  A GEMM over at most 64 tokens (a short prompt, the last pass of a
+ * long one) keeps its old route.  Under XH_OPT_PREFILL 0 / 2 / 3 / 4, for every other dtype (MXFP4 and the
+ * K-quants included) and for K % 64 != 0 the value is stored and read back and has no effect.  0 = as ever.
+ * Values other than 0 / 1 are XH_E_INVALID and leave the stored value.  Same math per token up to f32 rounding. */
 enum xh_option {
     XH_OPT_FUSE_ATTN_WO = 1,
     XH_OPT_PREFILL = 2,
@@ -804,7 +817,8 @@ enum xh_option {
     XH_OPT_PREFILL_ATTN_KV8 = 8,
     XH_OPT_PREFILL_RING_KV8 = 9,
     XH_OPT_PREFILL_BF16 = 10,
-    XH_OPT_PREFILL_KQ = 11
+    XH_OPT_PREFILL_KQ = 11,
+    XH_OPT_PREFILL_GQ = 12
 };
 int xh_set_option(xh_ctx* ctx, int option, int value);
 int xh_get_option(const xh_ctx* ctx, int option, int* value);
@@ -902,6 +916,14 @@ int xh_op_prompt_matmul_bf16(float* y, const float* x, const uint16_t* w, int ro
  * forces k slices and is XH_E_INVALID unless k is a power of two, k <= 8 and K % (256 k) == 0.  XH_E_INVALID
  * before any launch also for another dtype, K % 256 != 0, n < 1 or n > 2048, rows < 1 and a NULL y, x or w. */
 int xh_op_prompt_matmul_kq(float* y, const float* x, const void* w, int dtype, int rows, int K, int n, int ks);
+/* One GEMM of a prompt pass on the block-code route (XH_OPT_PREFILL_GQ 1; gemm_gq.h) on host buffers, through the
+ * launch code of the passes: y[n][rows] = x . w^T with x f32 [n][K] and w [rows][K] of dtype XH_Q8_0, XH_Q4_0,
+ * XH_Q4_1, XH_Q5_0 or XH_Q5_1 in the FILE layout (repacked to the device rows as xh_op_matmul does).  Launches:
+ * prefill_split_kernel (layout 0), the GEMM, prefill_epi_kernel with EPI_STORE and 1 / s_t.  ks 0: the passes' K
+ * slicing; k >= 1 forces k slices and is XH_E_INVALID unless k is a power of two, k <= 8 and K % (64 k) == 0.
+ * XH_E_INVALID before any launch (no device touched, y untouched) also for another dtype, K % 64 != 0, n < 1 or
+ * n > 2048, rows < 1 and a NULL y, x or w. */
+int xh_op_prompt_matmul_gq(float* y, const float* x, const void* w, int dtype, int rows, int K, int n, int ks);
 /* The exact f16 image(s) the row-major route multiplies, by the passes' image kernels: hi_out [rows][K]
  * f16 bits for e4m3 / e5m2 (finite codes) / MXFP4 (scales in 114 .. 140) with lo_out NULL; hi_out and
  * lo_out for Q8_0 / Q4_0 / Q5_0 (w = hi + lo exactly).  w in the file layout, K % 32 == 0.  max_groups 0:

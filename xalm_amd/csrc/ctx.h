@@ -271,6 +271,7 @@ struct xh_ctx {
     bool pf_ring_kv8 = false;                    // XH_OPT_PREFILL_RING_KV8: ... and runs ring passes (under pf_attn_kv8)
     bool pf_bf16 = false;                        // XH_OPT_PREFILL_BF16: bf16 matrices on gemm_bf16.h (under prefill_gemm 1)
     bool pf_kq = false;                          // XH_OPT_PREFILL_KQ: Q4_K / Q6_K matrices on gemm_kq.h (under prefill_gemm 1)
+    bool pf_gq = false;                          // XH_OPT_PREFILL_GQ: the 32-element gguf blocks on gemm_gq.h (under prefill_gemm 1)
     xalm::PfBufs pf;                             // the pass buffers
     // xh_perplexity: targets and probabilities of the whole run (allocated on first use)
     int* ppl_tgt = nullptr;                      // [ppl_cap] targets (per-token path)
@@ -455,6 +456,7 @@ struct PfGemmPlan {
     int ks, max_groups;
     bool bf16;           // XH_OPT_PREFILL_BF16
     bool kq;             // XH_OPT_PREFILL_KQ
+    bool gq;             // XH_OPT_PREFILL_GQ
 };
 struct PfGemmIo {
     const void* w;        // device rows of dt
@@ -474,7 +476,9 @@ constexpr int PF_ROUTE_BF16 = -2;
 // PF_ROUTE_KQ = Q4_K / Q6_K device rows against route 0's row-major split input (gemm_kq.h): on the
 // activation side it IS layout 0 (pf_act_layout)
 constexpr int PF_ROUTE_KQ = -3;
-inline int pf_act_layout(int route) { return route == PF_ROUTE_KQ ? 0 : route; }
+// PF_ROUTE_GQ = Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 device rows against the same input (gemm_gq.h): layout 0 likewise
+constexpr int PF_ROUTE_GQ = -4;
+inline int pf_act_layout(int route) { return route == PF_ROUTE_KQ || route == PF_ROUTE_GQ ? 0 : route; }
 int pf_gemm_route(const PfGemmPlan& p);
 // rows per wave (routes -1 and E > 0) or per workgroup (route 0): the launch's row tile
 int pf_gemm_row_tile(int route);
@@ -512,6 +516,9 @@ int pf_gemm_bf16(const PfGemmPlan& p, const PfGemmIo& io, int* ks_out, hipStream
 // gemm_kq.hip: the route PF_ROUTE_KQ over io.w (planar device rows of p.dt) and io.xh (hi rows then lo rows, as
 // route 0); unscaled partials, the epilogue multiplies by 1 / s_t (io.xs)
 int pf_gemm_kq(const PfGemmPlan& p, const PfGemmIo& io, int* ks_out, hipStream_t s);
+
+// gemm_gq.hip: the route PF_ROUTE_GQ, same operands and partials as pf_gemm_kq
+int pf_gemm_gq(const PfGemmPlan& p, const PfGemmIo& io, int* ks_out, hipStream_t s);
 
 // prefill_blas.hip (XH_OPT_PREFILL 4).  blas_ok: 0 unprobed, 1 every GEMM shape of the model has
 // an f16 plan, -1 not.  blas_has_plan: *have = hipBLASLt has an algorithm for the shape.

@@ -202,27 +202,39 @@ bool pf_bf16_route(const PfGemmPlan& p) {
 bool pf_kq_route(const PfGemmPlan& p) {
     return p.kq && p.mode == 1 && gq_k(p.dt) && p.K % 256 == 0 && (p.n == 0 || p.n > PF_TOK);
 }
+// XH_OPT_PREFILL_GQ under XH_OPT_PREFILL 1: a Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 matrix with K in whole 64s runs on
+// gemm_gq.h (the codes against route 0's row-major halves, the scales applied to the block sums) in place of
+// the hi + lo f16 images on gemm16.h (Q8_0 / Q4_0 / Q5_0) or the f32-input kernel (Q4_1 / Q5_1).  It comes
+// before pf_lay0 in pf_gemm_route.  A GEMM over at most PF_TOK tokens keeps its old route, as on the bf16 and
+// K-quant routes and for their reason.
+bool pf_gq_route(const PfGemmPlan& p) {
+    return p.gq && p.mode == 1 && gq_dt(p.dt) && !gq_mx(p.dt) && !gq_k(p.dt) && p.K % MM_KMULT == 0 && (p.n == 0 || p.n > PF_TOK);
+}
 // the plan of a GEMM of this context (n, the partials and a forced slicing left to the caller)
 PfGemmPlan pf_plan_of(const xh_ctx* ctx, int dt, int K, int rows, bool wide) {
     PfGemmPlan p{};
     p.mode = ctx->prefill_gemm;
     p.bf16 = ctx->pf_bf16;
     p.kq = ctx->pf_kq;
+    p.gq = ctx->pf_gq;
     p.blas = p.mode == 4 && blas_ok(ctx) > 0;
     p.dt = dt; p.K = K; p.rows = rows; p.wide = wide;
     p.n_cu = ctx->n_cu;
     return p;
 }
 bool pf_lay0(const xh_ctx* ctx, int dt, int K, bool wide) { return pf_lay0(pf_plan_of(ctx, dt, K, 0, wide)); }
-// Does the GEMM take the rows of a whole pass (row-major halves, bf16 pieces or K-quant codes), or 64-token slices?
+// Does the GEMM take the rows of a whole pass (row-major halves, bf16 pieces, K-quant or block codes), or 64-token slices?
 bool pf_whole_pass(const xh_ctx* ctx, int dt, int K, bool wide) {
     const PfGemmPlan p = pf_plan_of(ctx, dt, K, 0, wide);
-    return pf_lay0(p) || pf_bf16_route(p) || pf_kq_route(p);
+    return pf_lay0(p) || pf_bf16_route(p) || pf_kq_route(p) || pf_gq_route(p);
 }
 // Once per prefill: (XH_OPT_PREFILL 4, once per context) does hipBLASLt have an f16 plan for every
 // full-pass GEMM of the model (if not, every dtype keeps the MFMA kernels); and the f16 image
-// buffer of the largest fp8 matrix that goes to the f16 GEMMs.
-int pf_prepare(xh_ctx* ctx) {
+// buffer of the largest fp8 matrix that goes to the f16 GEMMs.  n: the tokens of the batched call (0: unknown),
+// pass_cap: a ring pass's bound on the pass length; a matrix whose GEMMs all take gemm_gq.h
+// (XH_OPT_PREFILL_GQ: the call's shortest pass, its last, has more than PF_TOK tokens) needs no image.
+int pf_pass_tokens(const xh_ctx* ctx);
+int pf_prepare(xh_ctx* ctx, int n = 0, int pass_cap = 0) {
     const std::vector<PfMat> gs = pf_all_mats(ctx);
     if (ctx->prefill_gemm == 4 && !blas_ok(ctx)) {
         int ok = 1;
@@ -236,9 +248,13 @@ int pf_prepare(xh_ctx* ctx) {
         blas_set_ok(ctx, ok);
     }
     size_t wdq = 0;  // fp8: one f16 image; gguf blocks: hi and lo images
-    for (const PfMat& g : gs)
-        if ((pf_f8(g.dt) || gq_dt(g.dt)) && pf_lay0(ctx, g.dt, g.K, g.wide))
+    const int pass = pass_cap > 0 ? std::min(pf_pass_tokens(ctx), pass_cap) : pf_pass_tokens(ctx);
+    for (const PfMat& g : gs) {
+        PfGemmPlan p = pf_plan_of(ctx, g.dt, g.K, g.rows, g.wide);
+        p.n = n > 0 ? n - (n - 1) / pass * pass : 1;
+        if ((pf_f8(g.dt) || gq_dt(g.dt)) && pf_lay0(p) && !pf_gq_route(p))
             wdq = std::max(wdq, (size_t)g.rows * g.K * (gq_dt(g.dt) && !gq_mx(g.dt) ? 2 : 1));
+    }
     if (wdq > ctx->pf_wdq_elems) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         hipFree(ctx->pf_wdq);
@@ -262,8 +278,8 @@ uint16_t* pf_lo(xh_ctx* ctx, int layout, int n, int K) { return pf_split_lo(layo
 // grid of the split kernels: one workgroup per token row, fragments padded to 32-token tiles
 int pf_split_grid(int layout, int n) { return layout ? 32 * ((n + 31) / 32) : n; }
 int pf_layout(const xh_ctx* ctx, const PfMat& g, int n) { return pf_layout(ctx, g.dt, g.K, g.rows, g.wide, n); }
-// Tokens per pass: PF_TOK_MM (gemm16.h, gemm_bf16.h, gemm_kq.h) / PF_TOK_BLAS (hipBLASLt) when every layer GEMM
-// takes the row-major input (gemm_kq.h's too) or the bf16 pieces (the lm_head of a perplexity pass aside: it runs on
+// Tokens per pass: PF_TOK_MM (gemm16.h, gemm_bf16.h, gemm_kq.h, gemm_gq.h) / PF_TOK_BLAS (hipBLASLt) when every layer GEMM
+// takes the row-major input (gemm_kq.h's and gemm_gq.h's too) or the bf16 pieces (the lm_head of a perplexity pass aside: it runs on
 // 64-token slices when it cannot), else 64 (the register-streaming MFMA kernels' two token tiles)
 int pf_pass_tokens(const xh_ctx* ctx) {
     for (int l = 0; l < (int)ctx->L.size(); l++)
@@ -334,10 +350,10 @@ int pf_gemm(xh_ctx* ctx, PfPass& ps, const PfMat& g, const float* x, int n, int&
         ps.split_ready = false;
     }
     int rc;
-    if (lay == PF_ROUTE_KQ) {
+    if (lay == PF_ROUTE_KQ || lay == PF_ROUTE_GQ) {
         // route 0's input, the codes as stored; partials unscaled, the epilogue multiplies by 1 / s_t
         ps.scaled = true;
-        rc = pf_gemm_kq(p, io, &ks, ctx->stream);
+        rc = lay == PF_ROUTE_KQ ? pf_gemm_kq(p, io, &ks, ctx->stream) : pf_gemm_gq(p, io, &ks, ctx->stream);
         return rc ? pf_gemm_err(ctx, rc, g, n) : 0;
     }
     if (lay == PF_ROUTE_BF16) {
@@ -531,6 +547,7 @@ int xalm::pf_elems(int dt) {
 // where the GEMM fits, else the split kernel for fp8; 2: the split kernel for f16 and fp8; 3: never
 // split.  The split kernel also needs a K slicing.
 int xalm::pf_gemm_route(const PfGemmPlan& p) {
+    if (pf_gq_route(p)) return PF_ROUTE_GQ;  // before route 0: Q8_0 / Q4_0 / Q5_0 would take it with their images
     if (pf_lay0(p)) return 0;
     if (pf_bf16_route(p)) return PF_ROUTE_BF16;
     if (pf_kq_route(p)) return PF_ROUTE_KQ;
@@ -542,7 +559,7 @@ int xalm::pf_gemm_route(const PfGemmPlan& p) {
     return pf_ks16(p.rows, p.K, E) ? E : -1;
 }
 int xalm::pf_gemm_row_tile(int route) {
-    const bool wg = route == 0 || route == PF_ROUTE_BF16 || route == PF_ROUTE_KQ;  // MB_BR == MK_BR == MM_BR
+    const bool wg = route == 0 || route == PF_ROUTE_BF16 || route == PF_ROUTE_KQ || route == PF_ROUTE_GQ;  // MB_BR == MK_BR == MM_BR
     return wg ? MM_BR : 32 * (route > 0 ? PF_RT16 : PF_RT);
 }
 bool xalm::pf_gemm_ks_ok(const PfGemmPlan& p, int route) {
@@ -550,8 +567,8 @@ bool xalm::pf_gemm_ks_ok(const PfGemmPlan& p, int route) {
     if (ks <= 0 || (ks & (ks - 1))) return false;  // every picker doubles
     if (route == PF_ROUTE_KQ)                      // mk_pick_ks (gemm_kq.h): slices of whole super-blocks
         return ks <= 8 && K % (ks * 256) == 0 && (size_t)ks * p.n * p.rows <= p.part_floats;
-    if (route == 0 || route == PF_ROUTE_BF16) {    // mm_pick_ks
-        const int images = gq_dt(p.dt) && !gq_mx(p.dt) ? 2 : 1;
+    if (route == 0 || route == PF_ROUTE_BF16 || route == PF_ROUTE_GQ) {  // mm_pick_ks (gemm_gq.h: one set of partials)
+        const int images = route == 0 && gq_dt(p.dt) && !gq_mx(p.dt) ? 2 : 1;
         return ks <= 8 && K % (ks * MM_KMULT) == 0 && (size_t)images * ks * p.n * p.rows <= p.part_floats;
     }
     const int E = route > 0 ? route : pf_elems(p.dt);
@@ -979,7 +996,7 @@ int pf_logits_probs(xh_ctx* ctx, PfPass& ps, const int* targets, float* probs, c
 int prefill_batched(xh_ctx* ctx, const int* tokens, int n, int pos0, int want_logits, const int* targets = nullptr,
                     float* probs = nullptr, bool ring = false, const ScoreTail* sc = nullptr) {
     const xh_config& c = ctx->c;
-    int rc = pf_prepare(ctx);
+    int rc = pf_prepare(ctx, n, ring ? c.max_seq_len - 2 : 0);
     if (rc) return rc;
     const int pass = ring ? std::min(pf_pass_tokens(ctx), c.max_seq_len - 2) : pf_pass_tokens(ctx);
     if ((rc = pf_alloc(ctx, std::min(pass, std::max(n, PF_TOK))))) return rc;

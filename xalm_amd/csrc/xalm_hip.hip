@@ -360,6 +360,7 @@ int xh_get_option(const xh_ctx* ctx, int option, int* value) {
         case XH_OPT_PREFILL_RING_KV8: *value = ctx->pf_ring_kv8 ? 1 : 0; return 0;
         case XH_OPT_PREFILL_BF16: *value = ctx->pf_bf16 ? 1 : 0; return 0;
         case XH_OPT_PREFILL_KQ: *value = ctx->pf_kq ? 1 : 0; return 0;
+        case XH_OPT_PREFILL_GQ: *value = ctx->pf_gq ? 1 : 0; return 0;
         default: return XH_E_INVALID;
     }
 }
@@ -409,6 +410,10 @@ int xh_set_option(xh_ctx* ctx, int option, int value) {
         case XH_OPT_PREFILL_KQ:
             if (value < 0 || value > 1) return set_err(ctx, XH_E_INVALID, "XH_OPT_PREFILL_KQ: 0 or 1");
             ctx->pf_kq = value != 0;
+            return 0;
+        case XH_OPT_PREFILL_GQ:
+            if (value < 0 || value > 1) return set_err(ctx, XH_E_INVALID, "XH_OPT_PREFILL_GQ: 0 or 1");
+            ctx->pf_gq = value != 0;
             return 0;
         default: return set_err(ctx, XH_E_INVALID, "unknown option %d", option);
     }

@@ -52,6 +52,7 @@ static int g_kv_dtype = XH_F16;  // -K: the KV rings' element type
 static int g_attn_kv8 = 0;       // -a: 1 = XH_OPT_PREFILL_ATTN_KV8, 2 = that and XH_OPT_PREFILL_RING_KV8
 static int g_prefill_bf16 = 0;   // -b: XH_OPT_PREFILL_BF16
 static int g_prefill_kq = 0;     // -Q: XH_OPT_PREFILL_KQ
+static int g_prefill_gq = 0;     // -G: XH_OPT_PREFILL_GQ
 
 // the model of a run: -K's rings, -a's prompt attention (and ring passes) on them, -b's bf16 prompt GEMM
 static Model load_model(const XalmFile& file, int context, Device dev) {
@@ -64,6 +65,8 @@ static Model load_model(const XalmFile& file, int context, Device dev) {
         throw std::runtime_error(std::string("-b: ") + xh_last_error(model.ctx()));
     if (g_prefill_kq && xh_set_option(model.ctx(), XH_OPT_PREFILL_KQ, g_prefill_kq) != 0)
         throw std::runtime_error(std::string("-Q: ") + xh_last_error(model.ctx()));
+    if (g_prefill_gq && xh_set_option(model.ctx(), XH_OPT_PREFILL_GQ, g_prefill_gq) != 0)
+        throw std::runtime_error(std::string("-G: ") + xh_last_error(model.ctx()));
     return model;
 }
 
@@ -84,6 +87,8 @@ static void error_usage() {
     fprintf(stderr, "     2048 tokens instead of 64 (default 0, hip only)\n");
     fprintf(stderr, "  -Q <0|1> 1 = Q4_K / Q6_K weight matrices of the prompt passes on the K-quant MFMA GEMM, passes of up\n");
     fprintf(stderr, "     to 2048 tokens instead of 64 (default 0, hip only)\n");
+    fprintf(stderr, "  -G <0|1> 1 = Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 weight matrices of the prompt passes on the block-code\n");
+    fprintf(stderr, "     MFMA GEMM, no f16 weight images (default 0, hip only)\n");
     fprintf(stderr, "  -t <float> sampling temperature (default 0 - greedy)\n");
     fprintf(stderr, "  -k <int> top-k, 0 = off (default 0)\n");
     fprintf(stderr, "  -p <float> top-p in (0, 1], 1 = off (default 1)\n");
@@ -303,6 +308,7 @@ int main(int argc, char** argv) {
         else if (f == 'a') g_attn_kv8 = std::stoi(v);
         else if (f == 'b') g_prefill_bf16 = std::stoi(v);
         else if (f == 'Q') g_prefill_kq = std::stoi(v);
+        else if (f == 'G') g_prefill_gq = std::stoi(v);
         else if (f == 't') sampling.temperature = std::stof(v);
         else if (f == 'k') sampling.top_k = std::stoi(v);
         else if (f == 'p') sampling.top_p = std::stof(v);
@@ -343,7 +349,7 @@ int main(int argc, char** argv) {
         return 1;
     }
     if (g_kv_dtype != XH_F16 && device == "cpu") error_usage();  // the fp8 KV ring is the HIP device's
-    if ((g_attn_kv8 || g_prefill_bf16 || g_prefill_kq) && device == "cpu") error_usage();
+    if ((g_attn_kv8 || g_prefill_bf16 || g_prefill_kq || g_prefill_gq) && device == "cpu") error_usage();
     const Device dev = device == "cpu" ? Device::CPU : Device::HIP;
     try {
         if (mode == "completion") run_completion(path, dev, prompt, context, num_steps, device_loop != 0, sampling, ctl, trunc, seq, regex, top_n);
