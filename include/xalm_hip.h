@@ -807,6 +807,18 @@ int xh_set_graphs(xh_ctx* ctx, int enable);
  * long one) keeps its old route.  Under XH_OPT_PREFILL 0 / 2 / 3 / 4, for every other dtype (MXFP4 and the
  * K-quants included) and for K % 64 != 0 the value is stored and read back and has no effect.  0 = as ever.
  * Values other than 0 / 1 are XH_E_INVALID and leave the stored value.  Same math per token up to f32 rounding. */
+/* XH_OPT_PREFILL_SHORT (default 0): 1 = under XH_OPT_PREFILL 1 every prompt GEMM over 1 .. 64 tokens (a short
+ * prompt, the last pass of a long one, every 64-token pass of a model whose long route is off, and the lm_head
+ * GEMM of xh_perplexity / xh_score over such a pass) of a Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 weight matrix with
+ * K % 64 == 0 or a Q4_K / Q6_K one with K % 256 == 0 runs on the weight-streaming code GEMM (gemm_sk.h) instead
+ * of gemm16.h over two f16 weight images (Q8_0 / Q4_0 / Q5_0) or the f32-input MFMA kernel (the others).  The
+ * arithmetic is that of XH_OPT_PREFILL_GQ / XH_OPT_PREFILL_KQ (codes times the row-major f16 hi + lo halves,
+ * the scales applied to each scale group's sums, an order fixed by the tiling); the weights go from memory
+ * through registers into the matrix instruction.  Pass planning is unchanged (xh_prefill_route answers as
+ * with 0); no weight image is sized for a matrix none of whose passes in a call keeps route 0.  Under
+ * XH_OPT_PREFILL 0 / 2 / 3 / 4 and for every other dtype the value is stored and read back and has no effect.
+ * 0 = as ever.  Values other than 0 / 1 are XH_E_INVALID and leave the stored value.  Same math per token up
+ * to f32 rounding. */
 enum xh_option {
     XH_OPT_FUSE_ATTN_WO = 1,
     XH_OPT_PREFILL = 2,
@@ -818,7 +830,8 @@ enum xh_option {
     XH_OPT_PREFILL_RING_KV8 = 9,
     XH_OPT_PREFILL_BF16 = 10,
     XH_OPT_PREFILL_KQ = 11,
-    XH_OPT_PREFILL_GQ = 12
+    XH_OPT_PREFILL_GQ = 12,
+    XH_OPT_PREFILL_SHORT = 13
 };
 int xh_set_option(xh_ctx* ctx, int option, int value);
 int xh_get_option(const xh_ctx* ctx, int option, int* value);
@@ -924,6 +937,15 @@ int xh_op_prompt_matmul_kq(float* y, const float* x, const void* w, int dtype, i
  * XH_E_INVALID before any launch (no device touched, y untouched) also for another dtype, K % 64 != 0, n < 1 or
  * n > 2048, rows < 1 and a NULL y, x or w. */
 int xh_op_prompt_matmul_gq(float* y, const float* x, const void* w, int dtype, int rows, int K, int n, int ks);
+/* One GEMM of a short prompt pass on the weight-streaming route (XH_OPT_PREFILL_SHORT 1; gemm_sk.h) on host
+ * buffers, through the launch code of the passes: y[n][rows] = x . w^T with x f32 [n][K], 1 <= n <= 64, and w
+ * [rows][K] of dtype XH_Q8_0, XH_Q4_0, XH_Q4_1, XH_Q5_0, XH_Q5_1, XH_Q4_K or XH_Q6_K in the FILE layout (repacked
+ * to the device rows as xh_op_matmul does).  Launches: prefill_split_kernel (layout 0), the GEMM,
+ * prefill_epi_kernel with EPI_STORE and 1 / s_t.  ks 0: the passes' K slicing; k >= 1 forces k slices and is
+ * XH_E_INVALID unless k is a power of two, k <= 16 and K % (64 k) == 0 (K-quants: K % (256 k) == 0).
+ * XH_E_INVALID before any launch (no device touched, y untouched) also for another dtype, K % 64 != 0 (K-quants:
+ * K % 256 != 0), n < 1 or n > 64, rows < 1 and a NULL y, x or w. */
+int xh_op_prompt_matmul_sk(float* y, const float* x, const void* w, int dtype, int rows, int K, int n, int ks);
 /* The exact f16 image(s) the row-major route multiplies, by the passes' image kernels: hi_out [rows][K]
  * f16 bits for e4m3 / e5m2 (finite codes) / MXFP4 (scales in 114 .. 140) with lo_out NULL; hi_out and
  * lo_out for Q8_0 / Q4_0 / Q5_0 (w = hi + lo exactly).  w in the file layout, K % 32 == 0.  max_groups 0:

@@ -57,6 +57,7 @@ OPT_PREFILL_RING_KV8 = 9
 OPT_PREFILL_BF16 = 10
 OPT_PREFILL_KQ = 11
 OPT_PREFILL_GQ = 12
+OPT_PREFILL_SHORT = 13
 
 # enum xh_tensor_kind
 EMBED, ATTN_NORM, FFN_NORM, WQ, WK, WV, WO, W1, W2, W3, FINAL_NORM, WCLS = range(12)
@@ -291,6 +292,7 @@ _SIGNATURES = {
     "xh_op_prompt_matmul_bf16": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "xh_op_prompt_matmul_kq": (_I, [_P, _P, _P, _I, _I, _I, _I, _I]),
     "xh_op_prompt_matmul_gq": (_I, [_P, _P, _P, _I, _I, _I, _I, _I]),
+    "xh_op_prompt_matmul_sk": (_I, [_P, _P, _P, _I, _I, _I, _I, _I]),
     "xh_op_prompt_weight_image": (_I, [_I, _P, _I, _I, _P, _P, _I]),
     "xh_op_prompt_stage": (_I, [_I, _P, _I, _P, _P, _I, _I, _P, _I, ctypes.c_float, _I, _I, _SZ, _P, _P, _P, _P,
                                 ctypes.POINTER(_I)]),
@@ -726,6 +728,7 @@ ROUTE_ROWMAJOR, ROUTE_F32 = 0, -1
 ROUTE_BF16 = -2  # the bf16 route of XH_OPT_PREFILL_BF16 (xh_prompt_gemm_tile's argument for it)
 ROUTE_KQ = -3  # the K-quant route of XH_OPT_PREFILL_KQ
 ROUTE_GQ = -4  # the block-code route of XH_OPT_PREFILL_GQ
+ROUTE_SK = -5  # the short-pass route of XH_OPT_PREFILL_SHORT
 
 
 def prompt_gemm_tile(route: int) -> int:
@@ -778,6 +781,18 @@ def op_prompt_matmul_gq(x: np.ndarray, w: np.ndarray, dtype: int, rows: int, ks:
     n, K = x.shape
     out = np.empty((n, rows), dtype=np.float32)
     check(lib().xh_op_prompt_matmul_gq(ptr(out), ptr(x), ptr(w), dtype, rows, K, n, ks))
+    return out
+
+
+def op_prompt_matmul_sk(x: np.ndarray, w: np.ndarray, dtype: int, rows: int, ks: int = 0) -> np.ndarray:
+    """One GEMM of a short prompt pass on the weight-streaming route (xh_op_prompt_matmul_sk): x f32 [n][K] with
+    n <= 64, w the Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q4_K / Q6_K blocks of [rows][K] in the file layout (uint8).
+    Returns y f32 [n][rows]."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    w = np.ascontiguousarray(w, dtype=np.uint8)
+    n, K = x.shape
+    out = np.empty((n, rows), dtype=np.float32)
+    check(lib().xh_op_prompt_matmul_sk(ptr(out), ptr(x), ptr(w), dtype, rows, K, n, ks))
     return out
 
 

@@ -272,6 +272,7 @@ struct xh_ctx {
     bool pf_bf16 = false;                        // XH_OPT_PREFILL_BF16: bf16 matrices on gemm_bf16.h (under prefill_gemm 1)
     bool pf_kq = false;                          // XH_OPT_PREFILL_KQ: Q4_K / Q6_K matrices on gemm_kq.h (under prefill_gemm 1)
     bool pf_gq = false;                          // XH_OPT_PREFILL_GQ: the 32-element gguf blocks on gemm_gq.h (under prefill_gemm 1)
+    bool pf_sk = false;                          // XH_OPT_PREFILL_SHORT: GEMMs over <= 64 tokens of the gguf blocks and K-quants on gemm_sk.h
     xalm::PfBufs pf;                             // the pass buffers
     // xh_perplexity: targets and probabilities of the whole run (allocated on first use)
     int* ppl_tgt = nullptr;                      // [ppl_cap] targets (per-token path)
@@ -457,6 +458,7 @@ struct PfGemmPlan {
     bool bf16;           // XH_OPT_PREFILL_BF16
     bool kq;             // XH_OPT_PREFILL_KQ
     bool gq;             // XH_OPT_PREFILL_GQ
+    bool sk;             // XH_OPT_PREFILL_SHORT
 };
 struct PfGemmIo {
     const void* w;        // device rows of dt
@@ -478,7 +480,10 @@ constexpr int PF_ROUTE_BF16 = -2;
 constexpr int PF_ROUTE_KQ = -3;
 // PF_ROUTE_GQ = Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 device rows against the same input (gemm_gq.h): layout 0 likewise
 constexpr int PF_ROUTE_GQ = -4;
-inline int pf_act_layout(int route) { return route == PF_ROUTE_KQ || route == PF_ROUTE_GQ ? 0 : route; }
+// PF_ROUTE_SK = the device rows of either family against the same input over at most PF_TOK tokens (gemm_sk.h):
+// layout 0 likewise
+constexpr int PF_ROUTE_SK = -5;
+inline int pf_act_layout(int route) { return route == PF_ROUTE_KQ || route == PF_ROUTE_GQ || route == PF_ROUTE_SK ? 0 : route; }
 int pf_gemm_route(const PfGemmPlan& p);
 // rows per wave (routes -1 and E > 0) or per workgroup (route 0): the launch's row tile
 int pf_gemm_row_tile(int route);
@@ -519,6 +524,12 @@ int pf_gemm_kq(const PfGemmPlan& p, const PfGemmIo& io, int* ks_out, hipStream_t
 
 // gemm_gq.hip: the route PF_ROUTE_GQ, same operands and partials as pf_gemm_kq
 int pf_gemm_gq(const PfGemmPlan& p, const PfGemmIo& io, int* ks_out, hipStream_t s);
+
+// gemm_sk.hip: the route PF_ROUTE_SK (1 .. PF_TOK tokens), same operands and partials as pf_gemm_kq; its
+// workgroup's row tile, and whether ks slices of K are ones its picker could take for dt
+int pf_gemm_sk(const PfGemmPlan& p, const PfGemmIo& io, int* ks_out, hipStream_t s);
+int sk_row_tile();
+bool sk_ks_ok(int dt, int K, int ks);
 
 // prefill_blas.hip (XH_OPT_PREFILL 4).  blas_ok: 0 unprobed, 1 every GEMM shape of the model has
 // an f16 plan, -1 not.  blas_has_plan: *have = hipBLASLt has an algorithm for the shape.

@@ -210,6 +210,16 @@ bool pf_kq_route(const PfGemmPlan& p) {
 bool pf_gq_route(const PfGemmPlan& p) {
     return p.gq && p.mode == 1 && gq_dt(p.dt) && !gq_mx(p.dt) && !gq_k(p.dt) && p.K % MM_KMULT == 0 && (p.n == 0 || p.n > PF_TOK);
 }
+// XH_OPT_PREFILL_SHORT under XH_OPT_PREFILL 1: the GEMMs the three routes above leave behind, over 1 .. PF_TOK
+// tokens of a Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 matrix (K in whole 64s) or a Q4_K / Q6_K one (whole 256s), run on
+// gemm_sk.h: the same code arithmetic against route 0's row-major halves, the weights streamed through registers.
+// The plan of a whole pass (p.n == 0) never takes it, so pass planning is untouched; it comes first in
+// pf_gemm_route.
+bool pf_sk_route(const PfGemmPlan& p) {
+    if (!p.sk || p.mode != 1 || p.n < 1 || p.n > PF_TOK) return false;
+    if (gq_k(p.dt)) return p.K % 256 == 0;
+    return gq_dt(p.dt) && !gq_mx(p.dt) && p.K % MM_KMULT == 0;
+}
 // the plan of a GEMM of this context (n, the partials and a forced slicing left to the caller)
 PfGemmPlan pf_plan_of(const xh_ctx* ctx, int dt, int K, int rows, bool wide) {
     PfGemmPlan p{};
@@ -217,6 +227,7 @@ PfGemmPlan pf_plan_of(const xh_ctx* ctx, int dt, int K, int rows, bool wide) {
     p.bf16 = ctx->pf_bf16;
     p.kq = ctx->pf_kq;
     p.gq = ctx->pf_gq;
+    p.sk = ctx->pf_sk;
     p.blas = p.mode == 4 && blas_ok(ctx) > 0;
     p.dt = dt; p.K = K; p.rows = rows; p.wide = wide;
     p.n_cu = ctx->n_cu;
@@ -250,9 +261,16 @@ int pf_prepare(xh_ctx* ctx, int n = 0, int pass_cap = 0) {
     size_t wdq = 0;  // fp8: one f16 image; gguf blocks: hi and lo images
     const int pass = pass_cap > 0 ? std::min(pf_pass_tokens(ctx), pass_cap) : pf_pass_tokens(ctx);
     for (const PfMat& g : gs) {
+        // the call's last pass and, if it has one (or n is unknown), a full pass: an image only for a matrix
+        // with a pass on route 0 (gemm_sk.h takes the short ones under XH_OPT_PREFILL_SHORT)
         PfGemmPlan p = pf_plan_of(ctx, g.dt, g.K, g.rows, g.wide);
         p.n = n > 0 ? n - (n - 1) / pass * pass : 1;
-        if ((pf_f8(g.dt) || gq_dt(g.dt)) && pf_lay0(p) && !pf_gq_route(p))
+        bool on0 = pf_gemm_route(p) == 0;
+        if (!on0 && (n == 0 || n > pass)) {
+            p.n = pass;
+            on0 = pf_gemm_route(p) == 0;
+        }
+        if ((pf_f8(g.dt) || gq_dt(g.dt)) && on0)
             wdq = std::max(wdq, (size_t)g.rows * g.K * (gq_dt(g.dt) && !gq_mx(g.dt) ? 2 : 1));
     }
     if (wdq > ctx->pf_wdq_elems) {
@@ -350,10 +368,12 @@ int pf_gemm(xh_ctx* ctx, PfPass& ps, const PfMat& g, const float* x, int n, int&
         ps.split_ready = false;
     }
     int rc;
-    if (lay == PF_ROUTE_KQ || lay == PF_ROUTE_GQ) {
+    if (lay == PF_ROUTE_KQ || lay == PF_ROUTE_GQ || lay == PF_ROUTE_SK) {
         // route 0's input, the codes as stored; partials unscaled, the epilogue multiplies by 1 / s_t
         ps.scaled = true;
-        rc = lay == PF_ROUTE_KQ ? pf_gemm_kq(p, io, &ks, ctx->stream) : pf_gemm_gq(p, io, &ks, ctx->stream);
+        rc = lay == PF_ROUTE_KQ   ? pf_gemm_kq(p, io, &ks, ctx->stream)
+             : lay == PF_ROUTE_GQ ? pf_gemm_gq(p, io, &ks, ctx->stream)
+                                  : pf_gemm_sk(p, io, &ks, ctx->stream);
         return rc ? pf_gemm_err(ctx, rc, g, n) : 0;
     }
     if (lay == PF_ROUTE_BF16) {
@@ -547,6 +567,7 @@ int xalm::pf_elems(int dt) {
 // where the GEMM fits, else the split kernel for fp8; 2: the split kernel for f16 and fp8; 3: never
 // split.  The split kernel also needs a K slicing.
 int xalm::pf_gemm_route(const PfGemmPlan& p) {
+    if (pf_sk_route(p)) return PF_ROUTE_SK;  // first: the short GEMMs of every route below
     if (pf_gq_route(p)) return PF_ROUTE_GQ;  // before route 0: Q8_0 / Q4_0 / Q5_0 would take it with their images
     if (pf_lay0(p)) return 0;
     if (pf_bf16_route(p)) return PF_ROUTE_BF16;
@@ -559,12 +580,15 @@ int xalm::pf_gemm_route(const PfGemmPlan& p) {
     return pf_ks16(p.rows, p.K, E) ? E : -1;
 }
 int xalm::pf_gemm_row_tile(int route) {
+    if (route == PF_ROUTE_SK) return sk_row_tile();
     const bool wg = route == 0 || route == PF_ROUTE_BF16 || route == PF_ROUTE_KQ || route == PF_ROUTE_GQ;  // MB_BR == MK_BR == MM_BR
     return wg ? MM_BR : 32 * (route > 0 ? PF_RT16 : PF_RT);
 }
 bool xalm::pf_gemm_ks_ok(const PfGemmPlan& p, int route) {
     const int ks = p.ks, K = p.K;
     if (ks <= 0 || (ks & (ks - 1))) return false;  // every picker doubles
+    if (route == PF_ROUTE_SK)                      // sk_pick_ks (gemm_sk.h): slices of whole 64s / super-blocks
+        return sk_ks_ok(p.dt, K, ks) && (size_t)ks * p.n * p.rows <= p.part_floats;
     if (route == PF_ROUTE_KQ)                      // mk_pick_ks (gemm_kq.h): slices of whole super-blocks
         return ks <= 8 && K % (ks * 256) == 0 && (size_t)ks * p.n * p.rows <= p.part_floats;
     if (route == 0 || route == PF_ROUTE_BF16 || route == PF_ROUTE_GQ) {  // mm_pick_ks (gemm_gq.h: one set of partials)
