@@ -11,7 +11,7 @@ HOSTFLAGS := -O2 -std=c++17 -fPIC -Wall -Wextra
 
 LIB := xalm_amd/lib
 BIN := xalm_amd/bin
-HIP_UNITS := xalm_hip launch decode prefill prefill_blas gemm_bf16 gemm_kq gemm_gq gemm_sk upload ops
+HIP_UNITS := xalm_hip launch decode prefill prefill_blas gemm_bf16 gemm_kq gemm_gq gemm_sk gemm_i8 upload ops
 HOST_SRC := $(wildcard xalm_amd/host/*.cpp)
 HOST_HDR := $(wildcard xalm_amd/host/*.h) include/xalm_hip.h include/xalm_host.h
 

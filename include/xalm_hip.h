@@ -819,6 +819,30 @@ int xh_set_graphs(xh_ctx* ctx, int enable);
  * XH_OPT_PREFILL 0 / 2 / 3 / 4 and for every other dtype the value is stored and read back and has no effect.
  * 0 = as ever.  Values other than 0 / 1 are XH_E_INVALID and leave the stored value.  Same math per token up
  * to f32 rounding. */
+/* XH_OPT_PREFILL_I8 (default 0): 1 = under XH_OPT_PREFILL 1 a Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 weight matrix with
+ * K % 64 == 0 (the layer GEMMs, and the lm_head GEMM of xh_perplexity / xh_score) runs its prompt GEMMs over more
+ * than 64 tokens in INTEGERS on gemm_i8.h: the weight codes against the activations rounded to 8 bits per
+ * 32-element block (ggml's Q8_1), one v_mfma_i32_16x16x32_i8 per block.  Unlike the options above this changes
+ * the math beyond f32 rounding.  Input: the row-major f16 halves xh, xl [n][K] of the layout-0 producers under
+ * the power-of-two row scale s_t.  Quantiser, per token t and block b (elements 32 b .. 32 b + 31), every
+ * operation one IEEE f32 operation, none contracted:
+ *     v_k = xh + xl (exact)        amax = max |v_k|        inv = amax > 0 ? 127.0f / amax : 0
+ *     qx_k = (int8) rintf(v_k * inv), clamped to +-127     dx = amax / 127.0f
+ *     sx = dx * (float) sum_k qx_k   (the integer sum is exact)
+ * stored per token row as the int8 codes [K], then {dx, sx} as f32 per block.  GEMM, per weight row r, token t
+ * and K slice, blocks in ascending order, from acc = 0:
+ *     Q8_0 / Q4_0 / Q5_0   acc = fmaf(d_w * dx, (float) sum_k (q_k - bias) qx_k, acc)      bias 0 / 8 / 16
+ *     Q4_1 / Q5_1          acc = fmaf(d_w * dx, (float) sum_k q_k qx_k, fmaf(m_w, sx, acc))
+ * with the integer sum exact (|sum| <= 32 * 128 * 127 < 2^19) and d_w * dx one rounded product.  The slices are
+ * summed in slice order, times 1 / s_t, by the epilogue of the other routes; the order is fixed by the tiling (no
+ * atomics, the same bits on every run).  The quantiser runs once per GEMM input of a pass (qkv, Wo, W1/W3, W2)
+ * into a buffer sized only when the option is on and a matrix takes the route.  With XH_OPT_PREFILL_GQ also 1,
+ * int8 takes these GEMMs.  A GEMM over at most 64 tokens keeps what it has (gemm_sk.h under
+ * XH_OPT_PREFILL_SHORT included).  Planning as under XH_OPT_PREFILL_GQ: a Q4_1 / Q5_1 model plans passes of up to
+ * 2048 tokens (xh_prefill_route likewise), and no f16 weight image is sized for a matrix whose passes all leave
+ * route 0.  Under XH_OPT_PREFILL 0 / 2 / 3 / 4, for every other dtype (MXFP4 and the K-quants included) and for
+ * K % 64 != 0 the value is stored and read back and has no effect.  0 = as ever.  Values other than 0 / 1 are
+ * XH_E_INVALID and leave the stored value. */
 enum xh_option {
     XH_OPT_FUSE_ATTN_WO = 1,
     XH_OPT_PREFILL = 2,
@@ -831,7 +855,8 @@ enum xh_option {
     XH_OPT_PREFILL_BF16 = 10,
     XH_OPT_PREFILL_KQ = 11,
     XH_OPT_PREFILL_GQ = 12,
-    XH_OPT_PREFILL_SHORT = 13
+    XH_OPT_PREFILL_SHORT = 13,
+    XH_OPT_PREFILL_I8 = 14
 };
 int xh_set_option(xh_ctx* ctx, int option, int value);
 int xh_get_option(const xh_ctx* ctx, int option, int* value);
@@ -946,6 +971,15 @@ int xh_op_prompt_matmul_gq(float* y, const float* x, const void* w, int dtype, i
  * XH_E_INVALID before any launch (no device touched, y untouched) also for another dtype, K % 64 != 0 (K-quants:
  * K % 256 != 0), n < 1 or n > 64, rows < 1 and a NULL y, x or w. */
 int xh_op_prompt_matmul_sk(float* y, const float* x, const void* w, int dtype, int rows, int K, int n, int ks);
+/* One GEMM of a prompt pass on the int8 route (XH_OPT_PREFILL_I8 1; gemm_i8.h) on host buffers, through the launch
+ * code of the passes: y[n][rows] = x . w^T with x f32 [n][K] and w [rows][K] of dtype XH_Q8_0, XH_Q4_0, XH_Q4_1,
+ * XH_Q5_0 or XH_Q5_1 in the FILE layout.  Launches: prefill_split_kernel (layout 0), prefill_quant_q8_kernel, the
+ * GEMM, prefill_epi_kernel with EPI_STORE and 1 / s_t.  codes_out [n][K] and scales_out [n][K / 32][2] ({dx, sx})
+ * return the quantiser's output; either may be NULL.  1 <= n <= 2048 (the passes route only n > 64).  ks as
+ * xh_op_prompt_matmul_gq's.  XH_E_INVALID before any launch (no device touched, y untouched) for another dtype,
+ * K % 64 != 0, n < 1 or n > 2048, rows < 1, a bad ks and a NULL y, x or w. */
+int xh_op_prompt_matmul_i8(float* y, const float* x, const void* w, int dtype, int rows, int K, int n, int ks,
+                           int8_t* codes_out, float* scales_out);
 /* The exact f16 image(s) the row-major route multiplies, by the passes' image kernels: hi_out [rows][K]
  * f16 bits for e4m3 / e5m2 (finite codes) / MXFP4 (scales in 114 .. 140) with lo_out NULL; hi_out and
  * lo_out for Q8_0 / Q4_0 / Q5_0 (w = hi + lo exactly).  w in the file layout, K % 32 == 0.  max_groups 0:

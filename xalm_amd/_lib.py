@@ -58,6 +58,7 @@ OPT_PREFILL_BF16 = 10
 OPT_PREFILL_KQ = 11
 OPT_PREFILL_GQ = 12
 OPT_PREFILL_SHORT = 13
+OPT_PREFILL_I8 = 14
 
 # enum xh_tensor_kind
 EMBED, ATTN_NORM, FFN_NORM, WQ, WK, WV, WO, W1, W2, W3, FINAL_NORM, WCLS = range(12)
@@ -293,6 +294,7 @@ _SIGNATURES = {
     "xh_op_prompt_matmul_kq": (_I, [_P, _P, _P, _I, _I, _I, _I, _I]),
     "xh_op_prompt_matmul_gq": (_I, [_P, _P, _P, _I, _I, _I, _I, _I]),
     "xh_op_prompt_matmul_sk": (_I, [_P, _P, _P, _I, _I, _I, _I, _I]),
+    "xh_op_prompt_matmul_i8": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "xh_op_prompt_weight_image": (_I, [_I, _P, _I, _I, _P, _P, _I]),
     "xh_op_prompt_stage": (_I, [_I, _P, _I, _P, _P, _I, _I, _P, _I, ctypes.c_float, _I, _I, _SZ, _P, _P, _P, _P,
                                 ctypes.POINTER(_I)]),
@@ -729,6 +731,7 @@ ROUTE_BF16 = -2  # the bf16 route of XH_OPT_PREFILL_BF16 (xh_prompt_gemm_tile's 
 ROUTE_KQ = -3  # the K-quant route of XH_OPT_PREFILL_KQ
 ROUTE_GQ = -4  # the block-code route of XH_OPT_PREFILL_GQ
 ROUTE_SK = -5  # the short-pass route of XH_OPT_PREFILL_SHORT
+ROUTE_I8 = -6  # the int8 route of XH_OPT_PREFILL_I8
 
 
 def prompt_gemm_tile(route: int) -> int:
@@ -794,6 +797,21 @@ def op_prompt_matmul_sk(x: np.ndarray, w: np.ndarray, dtype: int, rows: int, ks:
     out = np.empty((n, rows), dtype=np.float32)
     check(lib().xh_op_prompt_matmul_sk(ptr(out), ptr(x), ptr(w), dtype, rows, K, n, ks))
     return out
+
+
+def op_prompt_matmul_i8(x: np.ndarray, w: np.ndarray, dtype: int, rows: int, ks: int = 0, want_quant: bool = False):
+    """One GEMM of a prompt pass on the int8 route (xh_op_prompt_matmul_i8): x f32 [n][K], w the Q8_0 / Q4_0 / Q4_1 /
+    Q5_0 / Q5_1 blocks of [rows][K] in the file layout (uint8).  Returns y f32 [n][rows]; with want_quant
+    (y, codes int8 [n][K], scales f32 [n][K / 32][2] = {dx, sx}), the quantiser's output."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    w = np.ascontiguousarray(w, dtype=np.uint8)
+    n, K = x.shape
+    out = np.empty((n, rows), dtype=np.float32)
+    codes = np.empty((n, K), dtype=np.int8) if want_quant else None
+    scales = np.empty((n, K // 32, 2), dtype=np.float32) if want_quant else None
+    check(lib().xh_op_prompt_matmul_i8(ptr(out), ptr(x), ptr(w), dtype, rows, K, n, ks,
+                                       ptr(codes) if want_quant else None, ptr(scales) if want_quant else None))
+    return (out, codes, scales) if want_quant else out
 
 
 def op_prompt_weight_image(dtype: int, w: np.ndarray, rows: int, K: int, max_groups: int = 0):

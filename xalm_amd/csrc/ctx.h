@@ -143,6 +143,8 @@ struct PfBufs {
     float* h = nullptr;                    // [T][hidden]
     float* part = nullptr;                 // split-K partials [ks][n][rows] (pf_part_floats)
     StepParams* sp = nullptr;              // [T] per-token attention scalars
+    int8_t* q8 = nullptr;                  // [T] rows of pf_i8_row_bytes(max K): a GEMM input quantised per block
+                                           // (XH_OPT_PREFILL_I8; null unless a matrix takes the route)
     // ATTN0: the per-token split attention (XH_OPT_PREFILL_ATTN 0 only)
     float *po = nullptr, *pml = nullptr;   // [T][nsplit][q_dim], [T][nsplit][n_heads][2]
     int* cnt = nullptr;                    // [T][n_kv_heads] split tickets
@@ -159,7 +161,7 @@ struct PfBufs {
     std::vector<void**> owned(int g) {
         switch (g) {
             case PASS: return {(void**)&xh, (void**)&xl, (void**)&xs, (void**)&tok, (void**)&x, (void**)&xn,
-                               (void**)&q, (void**)&att, (void**)&h, (void**)&part, (void**)&sp};
+                               (void**)&q, (void**)&att, (void**)&h, (void**)&part, (void**)&sp, (void**)&q8};
             case ATTN0: return {(void**)&po, (void**)&pml, (void**)&cnt};
             case RING: return {(void**)&ks, (void**)&vs, (void**)&sinkv, (void**)&sinkm};
             case LOGITS: return {(void**)&logits, (void**)&tgt};
@@ -273,6 +275,7 @@ struct xh_ctx {
     bool pf_kq = false;                          // XH_OPT_PREFILL_KQ: Q4_K / Q6_K matrices on gemm_kq.h (under prefill_gemm 1)
     bool pf_gq = false;                          // XH_OPT_PREFILL_GQ: the 32-element gguf blocks on gemm_gq.h (under prefill_gemm 1)
     bool pf_sk = false;                          // XH_OPT_PREFILL_SHORT: GEMMs over <= 64 tokens of the gguf blocks and K-quants on gemm_sk.h
+    bool pf_i8 = false;                          // XH_OPT_PREFILL_I8: the 32-element gguf blocks on gemm_i8.h against int8 activations (under prefill_gemm 1)
     xalm::PfBufs pf;                             // the pass buffers
     // xh_perplexity: targets and probabilities of the whole run (allocated on first use)
     int* ppl_tgt = nullptr;                      // [ppl_cap] targets (per-token path)
@@ -459,6 +462,7 @@ struct PfGemmPlan {
     bool kq;             // XH_OPT_PREFILL_KQ
     bool gq;             // XH_OPT_PREFILL_GQ
     bool sk;             // XH_OPT_PREFILL_SHORT
+    bool i8;             // XH_OPT_PREFILL_I8
 };
 struct PfGemmIo {
     const void* w;        // device rows of dt
@@ -483,7 +487,12 @@ constexpr int PF_ROUTE_GQ = -4;
 // PF_ROUTE_SK = the device rows of either family against the same input over at most PF_TOK tokens (gemm_sk.h):
 // layout 0 likewise
 constexpr int PF_ROUTE_SK = -5;
-inline int pf_act_layout(int route) { return route == PF_ROUTE_KQ || route == PF_ROUTE_GQ || route == PF_ROUTE_SK ? 0 : route; }
+// PF_ROUTE_I8 = the device rows of PF_ROUTE_GQ's dtypes against the same input quantised per block to int8
+// (gemm_i8.h): layout 0 likewise, the quantiser reads its halves
+constexpr int PF_ROUTE_I8 = -6;
+inline int pf_act_layout(int route) {
+    return route == PF_ROUTE_KQ || route == PF_ROUTE_GQ || route == PF_ROUTE_SK || route == PF_ROUTE_I8 ? 0 : route;
+}
 int pf_gemm_route(const PfGemmPlan& p);
 // rows per wave (routes -1 and E > 0) or per workgroup (route 0): the launch's row tile
 int pf_gemm_row_tile(int route);
@@ -530,6 +539,13 @@ int pf_gemm_gq(const PfGemmPlan& p, const PfGemmIo& io, int* ks_out, hipStream_t
 int pf_gemm_sk(const PfGemmPlan& p, const PfGemmIo& io, int* ks_out, hipStream_t s);
 int sk_row_tile();
 bool sk_ks_ok(int dt, int K, int ks);
+
+// gemm_i8.hip: the route PF_ROUTE_I8.  pf_quant_q8_launch: the layout-0 halves xh, xl [n][K] to n rows of
+// pf_i8_row_bytes(K) (int8 codes [K], then {dx, sx} f32 per block); pf_gemm_i8: io.w against those rows, partials as
+// pf_gemm_kq's
+size_t pf_i8_row_bytes(int K);
+void pf_quant_q8_launch(const uint16_t* xh, const uint16_t* xl, int K, int n, int8_t* xq, hipStream_t s);
+int pf_gemm_i8(const PfGemmPlan& p, const PfGemmIo& io, const int8_t* xq, int* ks_out, hipStream_t s);
 
 // prefill_blas.hip (XH_OPT_PREFILL 4).  blas_ok: 0 unprobed, 1 every GEMM shape of the model has
 // an f16 plan, -1 not.  blas_has_plan: *have = hipBLASLt has an algorithm for the shape.

@@ -513,6 +513,46 @@ int xh_op_prompt_matmul_sk(float* y, const float* x, const void* w, int dtype, i
     return op_finish(y, bo, (size_t)n * rows * 4);
 }
 
+int xh_op_prompt_matmul_i8(float* y, const float* x, const void* w, int dtype, int rows, int K, int n, int ks,
+                           int8_t* codes_out, float* scales_out) {
+    if (!y || !x || !w) return set_err(nullptr, XH_E_INVALID, "prompt_matmul_i8: y, x or w is NULL");
+    if (dtype != XH_Q8_0 && dtype != XH_Q4_0 && dtype != XH_Q4_1 && dtype != XH_Q5_0 && dtype != XH_Q5_1)
+        return set_err(nullptr, XH_E_INVALID, "prompt_matmul_i8: dtype %d (Q8_0, Q4_0, Q4_1, Q5_0 or Q5_1)", dtype);
+    if (rows < 1 || rows > (1 << 20) || K < 1 || K > (1 << 20) || K % 64 || n < 1 || n > 2048)
+        return set_err(nullptr, XH_E_INVALID, "prompt_matmul_i8: %d rows, K %d (whole 64s), %d tokens (1 .. 2048)", rows, K, n);
+    PfGemmPlan p{};
+    p.mode = 1; p.i8 = true; p.dt = dtype; p.K = K; p.rows = rows; p.n = n; p.ks = ks;
+    p.part_floats = (size_t)8 * n * rows;  // room for any slicing the picker may take
+    if (ks < 0 || (ks > 0 && !pf_gemm_ks_ok(p, PF_ROUTE_I8)))
+        return set_err(nullptr, XH_E_INVALID, "prompt_matmul_i8: %d slices of K %d", ks, K);
+    int rc;
+    if ((rc = op_n_cu(&p.n_cu))) return rc;
+    std::vector<uint8_t> tmp((size_t)rows * dev_row_bytes(dtype, K));
+    gq_repack(dtype, (const uint8_t*)w, rows, K, tmp.data());
+    const size_t xe = (size_t)n * K, qrow = pf_i8_row_bytes(K);
+    DevBuf bw, bx, bxh, bxs, bq, bp, bo;
+    if ((rc = op_alloc(bw, tmp.size(), tmp.data())) || (rc = op_alloc(bx, xe * 4, x)) || (rc = op_alloc(bxh, 2 * xe * 2, nullptr)) ||
+        (rc = op_alloc(bxs, (size_t)n * 4, nullptr)) || (rc = op_alloc(bq, (size_t)n * qrow, nullptr)) ||
+        (rc = op_alloc(bp, p.part_floats * 4, nullptr)) || (rc = op_alloc(bo, (size_t)n * rows * 4, nullptr)))
+        return rc;
+    const PfGemmIo io{bw.p, (const float*)bx.p, (uint16_t*)bxh.p, nullptr, (float*)bxs.p, nullptr, 0, (float*)bp.p};
+    int nks = 0;
+    pf_split_launch(io.x, K, n, 0, io.xh, pf_split_lo(0, n, K, io.xh, nullptr), io.xs, nullptr);
+    pf_quant_q8_launch(io.xh, pf_split_lo(0, n, K, io.xh, nullptr), K, n, (int8_t*)bq.p, nullptr);
+    if ((rc = pf_gemm_i8(p, io, (const int8_t*)bq.p, &nks, nullptr))) {
+        hipDeviceSynchronize();
+        return set_err(nullptr, XH_E_INVALID, "prompt_matmul_i8: the launch code refused the GEMM (%d)", rc);
+    }
+    pf_epi_plain_launch(io.part, io.xs, nks, n, rows, EPI_STORE, (float*)bo.p, 0, 0, nullptr);
+    if ((rc = op_finish(y, bo, (size_t)n * rows * 4))) return rc;
+    // the quantiser's rows: the codes, then {dx, sx} per block
+    if (codes_out && hipMemcpy2D(codes_out, K, bq.p, qrow, K, n, hipMemcpyDeviceToHost) != hipSuccess)
+        return set_err(nullptr, XH_E_HIP, "hipMemcpy D2H failed");
+    if (scales_out && hipMemcpy2D(scales_out, K / 4, (const char*)bq.p + K, qrow, K / 4, n, hipMemcpyDeviceToHost) != hipSuccess)
+        return set_err(nullptr, XH_E_HIP, "hipMemcpy D2H failed");
+    return 0;
+}
+
 int xh_op_prompt_weight_image(int dtype, const void* w, int rows, int K, uint16_t* hi_out, uint16_t* lo_out, int max_groups) {
     const bool one = dtype == XH_F8_E4M3 || dtype == XH_F8_E5M2 || dtype == XH_MXFP4;
     const bool two = dtype == XH_Q8_0 || dtype == XH_Q4_0 || dtype == XH_Q5_0;

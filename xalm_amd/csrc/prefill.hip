@@ -42,11 +42,13 @@ void xalm::pf_free(xh_ctx* ctx) {
 
 namespace {
 
+bool pf_i8_any(const xh_ctx* ctx);
 // pass buffers for T tokens (kept while later passes fit; a longer pass length reallocates)
 int pf_alloc(xh_ctx* ctx, const int T) {
     PfBufs& b = ctx->pf;
     const int planes = ctx->pf_bf16 ? 3 : 2;  // the bf16 route's three pieces, only when the option is on
-    if (b.cap[PfBufs::PASS] >= T && b.xh_planes >= planes) return 0;
+    const bool q8 = pf_i8_any(ctx);           // the int8 route's quantised rows, only when a matrix takes it
+    if (b.cap[PfBufs::PASS] >= T && b.xh_planes >= planes && (!q8 || b.q8)) return 0;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     pf_free(ctx);
     const xh_config& c = ctx->c;
@@ -63,6 +65,7 @@ int pf_alloc(xh_ctx* ctx, const int T) {
     if ((rc = dmalloc(ctx, &b.xh, planes * std::max(t, (size_t)PF_TOK) * kmax)) ||
         (rc = dmalloc(ctx, &b.xl, PF_TOK * kmax)) || (rc = dmalloc(ctx, &b.xs, std::max(t, (size_t)PF_TOK))))
         return rc;
+    if (q8 && (rc = dmalloc(ctx, &b.q8, std::max(t, (size_t)PF_TOK) * pf_i8_row_bytes((int)kmax)))) return rc;
     b.xh_planes = planes;
     b.cap[PfBufs::PASS] = T;
     return 0;
@@ -210,7 +213,13 @@ bool pf_kq_route(const PfGemmPlan& p) {
 bool pf_gq_route(const PfGemmPlan& p) {
     return p.gq && p.mode == 1 && gq_dt(p.dt) && !gq_mx(p.dt) && !gq_k(p.dt) && p.K % MM_KMULT == 0 && (p.n == 0 || p.n > PF_TOK);
 }
-// XH_OPT_PREFILL_SHORT under XH_OPT_PREFILL 1: the GEMMs the three routes above leave behind, over 1 .. PF_TOK
+// XH_OPT_PREFILL_I8 under XH_OPT_PREFILL 1: the same matrices and GEMMs as pf_gq_route on gemm_i8.h: the codes in
+// integers against route 0's halves quantised per 32-element block to int8 (prefill_quant_q8_kernel, once per
+// GEMM input).  It comes before pf_gq_route in pf_gemm_route: with both options on, int8 takes the long GEMMs.
+bool pf_i8_route(const PfGemmPlan& p) {
+    return p.i8 && p.mode == 1 && gq_dt(p.dt) && !gq_mx(p.dt) && !gq_k(p.dt) && p.K % MM_KMULT == 0 && (p.n == 0 || p.n > PF_TOK);
+}
+// XH_OPT_PREFILL_SHORT under XH_OPT_PREFILL 1: the GEMMs the routes above leave behind, over 1 .. PF_TOK
 // tokens of a Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 matrix (K in whole 64s) or a Q4_K / Q6_K one (whole 256s), run on
 // gemm_sk.h: the same code arithmetic against route 0's row-major halves, the weights streamed through registers.
 // The plan of a whole pass (p.n == 0) never takes it, so pass planning is untouched; it comes first in
@@ -228,6 +237,7 @@ PfGemmPlan pf_plan_of(const xh_ctx* ctx, int dt, int K, int rows, bool wide) {
     p.kq = ctx->pf_kq;
     p.gq = ctx->pf_gq;
     p.sk = ctx->pf_sk;
+    p.i8 = ctx->pf_i8;
     p.blas = p.mode == 4 && blas_ok(ctx) > 0;
     p.dt = dt; p.K = K; p.rows = rows; p.wide = wide;
     p.n_cu = ctx->n_cu;
@@ -237,7 +247,14 @@ bool pf_lay0(const xh_ctx* ctx, int dt, int K, bool wide) { return pf_lay0(pf_pl
 // Does the GEMM take the rows of a whole pass (row-major halves, bf16 pieces, K-quant or block codes), or 64-token slices?
 bool pf_whole_pass(const xh_ctx* ctx, int dt, int K, bool wide) {
     const PfGemmPlan p = pf_plan_of(ctx, dt, K, 0, wide);
-    return pf_lay0(p) || pf_bf16_route(p) || pf_kq_route(p) || pf_gq_route(p);
+    return pf_lay0(p) || pf_bf16_route(p) || pf_kq_route(p) || pf_gq_route(p) || pf_i8_route(p);
+}
+// does a matrix of the model take the int8 route in a whole pass (pf_alloc: the quantised rows' buffer)
+bool pf_i8_any(const xh_ctx* ctx) {
+    if (!ctx->pf_i8) return false;
+    for (const PfMat& g : pf_all_mats(ctx))
+        if (pf_i8_route(pf_plan_of(ctx, g.dt, g.K, g.rows, g.wide))) return true;
+    return false;
 }
 // Once per prefill: (XH_OPT_PREFILL 4, once per context) does hipBLASLt have an f16 plan for every
 // full-pass GEMM of the model (if not, every dtype keeps the MFMA kernels); and the f16 image
@@ -368,6 +385,14 @@ int pf_gemm(xh_ctx* ctx, PfPass& ps, const PfMat& g, const float* x, int n, int&
         ps.split_ready = false;
     }
     int rc;
+    if (lay == PF_ROUTE_I8) {
+        // route 0's input quantised per block (once per GEMM input: qkv and W1/W3 are one matrix each), then the
+        // integer GEMM; partials unscaled, the epilogue multiplies by 1 / s_t
+        ps.scaled = true;
+        pf_quant_q8_launch(b.xh, pf_lo(ctx, 0, n, g.K), g.K, n, b.q8, ctx->stream);
+        rc = pf_gemm_i8(p, io, b.q8, &ks, ctx->stream);
+        return rc ? pf_gemm_err(ctx, rc, g, n) : 0;
+    }
     if (lay == PF_ROUTE_KQ || lay == PF_ROUTE_GQ || lay == PF_ROUTE_SK) {
         // route 0's input, the codes as stored; partials unscaled, the epilogue multiplies by 1 / s_t
         ps.scaled = true;
@@ -568,6 +593,7 @@ int xalm::pf_elems(int dt) {
 // split.  The split kernel also needs a K slicing.
 int xalm::pf_gemm_route(const PfGemmPlan& p) {
     if (pf_sk_route(p)) return PF_ROUTE_SK;  // first: the short GEMMs of every route below
+    if (pf_i8_route(p)) return PF_ROUTE_I8;  // before gemm_gq.h: with both options on, int8 takes the long GEMMs
     if (pf_gq_route(p)) return PF_ROUTE_GQ;  // before route 0: Q8_0 / Q4_0 / Q5_0 would take it with their images
     if (pf_lay0(p)) return 0;
     if (pf_bf16_route(p)) return PF_ROUTE_BF16;
@@ -581,7 +607,8 @@ int xalm::pf_gemm_route(const PfGemmPlan& p) {
 }
 int xalm::pf_gemm_row_tile(int route) {
     if (route == PF_ROUTE_SK) return sk_row_tile();
-    const bool wg = route == 0 || route == PF_ROUTE_BF16 || route == PF_ROUTE_KQ || route == PF_ROUTE_GQ;  // MB_BR == MK_BR == MM_BR
+    const bool wg = route == 0 || route == PF_ROUTE_BF16 || route == PF_ROUTE_KQ || route == PF_ROUTE_GQ ||
+                    route == PF_ROUTE_I8;  // MB_BR == MK_BR == MI_BR == MM_BR
     return wg ? MM_BR : 32 * (route > 0 ? PF_RT16 : PF_RT);
 }
 bool xalm::pf_gemm_ks_ok(const PfGemmPlan& p, int route) {
@@ -591,7 +618,7 @@ bool xalm::pf_gemm_ks_ok(const PfGemmPlan& p, int route) {
         return sk_ks_ok(p.dt, K, ks) && (size_t)ks * p.n * p.rows <= p.part_floats;
     if (route == PF_ROUTE_KQ)                      // mk_pick_ks (gemm_kq.h): slices of whole super-blocks
         return ks <= 8 && K % (ks * 256) == 0 && (size_t)ks * p.n * p.rows <= p.part_floats;
-    if (route == 0 || route == PF_ROUTE_BF16 || route == PF_ROUTE_GQ) {  // mm_pick_ks (gemm_gq.h: one set of partials)
+    if (route == 0 || route == PF_ROUTE_BF16 || route == PF_ROUTE_GQ || route == PF_ROUTE_I8) {  // mm_pick_ks (gemm_gq.h, gemm_i8.h: one set of partials)
         const int images = route == 0 && gq_dt(p.dt) && !gq_mx(p.dt) ? 2 : 1;
         return ks <= 8 && K % (ks * MM_KMULT) == 0 && (size_t)images * ks * p.n * p.rows <= p.part_floats;
     }

@@ -362,6 +362,7 @@ int xh_get_option(const xh_ctx* ctx, int option, int* value) {
         case XH_OPT_PREFILL_KQ: *value = ctx->pf_kq ? 1 : 0; return 0;
         case XH_OPT_PREFILL_GQ: *value = ctx->pf_gq ? 1 : 0; return 0;
         case XH_OPT_PREFILL_SHORT: *value = ctx->pf_sk ? 1 : 0; return 0;
+        case XH_OPT_PREFILL_I8: *value = ctx->pf_i8 ? 1 : 0; return 0;
         default: return XH_E_INVALID;
     }
 }
@@ -419,6 +420,10 @@ int xh_set_option(xh_ctx* ctx, int option, int value) {
         case XH_OPT_PREFILL_SHORT:
             if (value < 0 || value > 1) return set_err(ctx, XH_E_INVALID, "XH_OPT_PREFILL_SHORT: 0 or 1");
             ctx->pf_sk = value != 0;
+            return 0;
+        case XH_OPT_PREFILL_I8:
+            if (value < 0 || value > 1) return set_err(ctx, XH_E_INVALID, "XH_OPT_PREFILL_I8: 0 or 1");
+            ctx->pf_i8 = value != 0;
             return 0;
         default: return set_err(ctx, XH_E_INVALID, "unknown option %d", option);
     }

@@ -54,6 +54,7 @@ static int g_prefill_bf16 = 0;   // -b: XH_OPT_PREFILL_BF16
 static int g_prefill_kq = 0;     // -Q: XH_OPT_PREFILL_KQ
 static int g_prefill_gq = 0;     // -G: XH_OPT_PREFILL_GQ
 static int g_prefill_sk = 0;     // -j: XH_OPT_PREFILL_SHORT
+static int g_prefill_i8 = 0;     // -I: XH_OPT_PREFILL_I8
 
 // the model of a run: -K's rings, -a's prompt attention (and ring passes) on them, -b's bf16 prompt GEMM
 static Model load_model(const XalmFile& file, int context, Device dev) {
@@ -70,6 +71,8 @@ static Model load_model(const XalmFile& file, int context, Device dev) {
         throw std::runtime_error(std::string("-G: ") + xh_last_error(model.ctx()));
     if (g_prefill_sk && xh_set_option(model.ctx(), XH_OPT_PREFILL_SHORT, g_prefill_sk) != 0)
         throw std::runtime_error(std::string("-j: ") + xh_last_error(model.ctx()));
+    if (g_prefill_i8 && xh_set_option(model.ctx(), XH_OPT_PREFILL_I8, g_prefill_i8) != 0)
+        throw std::runtime_error(std::string("-I: ") + xh_last_error(model.ctx()));
     return model;
 }
 
@@ -92,6 +95,8 @@ static void error_usage() {
     fprintf(stderr, "     to 2048 tokens instead of 64 (default 0, hip only)\n");
     fprintf(stderr, "  -G <0|1> 1 = Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 weight matrices of the prompt passes on the block-code\n");
     fprintf(stderr, "     MFMA GEMM, no f16 weight images (default 0, hip only)\n");
+    fprintf(stderr, "  -I <0|1> 1 = the same matrices over more than 64 tokens on the int8 MFMA GEMM against activations rounded to\n");
+    fprintf(stderr, "     8 bits per 32-element block (changes the math beyond f32 rounding; wins over -G; default 0, hip only)\n");
     fprintf(stderr, "  -j <0|1> 1 = prompt GEMMs over at most 64 tokens of the gguf block and Q4_K / Q6_K weight matrices on the\n");
     fprintf(stderr, "     weight-streaming code GEMM (default 0, hip only)\n");
     fprintf(stderr, "  -t <float> sampling temperature (default 0 - greedy)\n");
@@ -315,6 +320,7 @@ int main(int argc, char** argv) {
         else if (f == 'Q') g_prefill_kq = std::stoi(v);
         else if (f == 'G') g_prefill_gq = std::stoi(v);
         else if (f == 'j') g_prefill_sk = std::stoi(v);
+        else if (f == 'I') g_prefill_i8 = std::stoi(v);
         else if (f == 't') sampling.temperature = std::stof(v);
         else if (f == 'k') sampling.top_k = std::stoi(v);
         else if (f == 'p') sampling.top_p = std::stof(v);
@@ -355,7 +361,7 @@ int main(int argc, char** argv) {
         return 1;
     }
     if (g_kv_dtype != XH_F16 && device == "cpu") error_usage();  // the fp8 KV ring is the HIP device's
-    if ((g_attn_kv8 || g_prefill_bf16 || g_prefill_kq || g_prefill_gq || g_prefill_sk) && device == "cpu") error_usage();
+    if ((g_attn_kv8 || g_prefill_bf16 || g_prefill_kq || g_prefill_gq || g_prefill_sk || g_prefill_i8) && device == "cpu") error_usage();
     const Device dev = device == "cpu" ? Device::CPU : Device::HIP;
     try {
         if (mode == "completion") run_completion(path, dev, prompt, context, num_steps, device_loop != 0, sampling, ctl, trunc, seq, regex, top_n);
